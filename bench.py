@@ -7,6 +7,12 @@ A "step" on a rank = one synthetic clip (T=30, 240x320, BASELINE.json configs[1]
 (batched), the mask loss, one backward, gradient all-reduce (RCCL, overlapped with backward), grad-clip 0.3 and
 an AdamW step -- mirroring pipeline.py:134-174 + train.py:89-102.  value = world_size * clips_per_rank / step time.
 Prints ONE JSON line on rank 0.
+
+A plain run only sets up, warms up, times the K steps and prints the line.  --full adds everything else the line can carry: the
+per-kernel roofline pass, host enqueue time, the CPU baseline, the other precision modes with their parity check and the
+BASELINE configs[3] / [4] legs (--no-cpu-baseline / --no-parity / --no-config-legs drop single legs of a --full run).
+--dump-outputs DIR writes what the last timed step computed on rank 0 as DIR/<name>.npy (float32): loss, grad_norm, sel_occl_fracs
+and fixed seeded samples of output_mask, target_mask, query_mask and of the updated parameters (flattened in net.parameters() order).
 """
 import argparse
 import json
@@ -36,6 +42,8 @@ def parse():
     ap.add_argument('--depth', type=int, default=12)
     ap.add_argument('--grad-dtype', default='f32', choices=['f32', 'bf16'], help='dtype of the all-reduced gradient buckets (N > 1)')
     ap.add_argument('--launch-selftest', action='store_true', help='only start the ranks, all-reduce one number and print the rank count (CPU-runnable check of the N > 1 launch path)')
+    ap.add_argument('--full', action='store_true', help='also run the roofline pass, host enqueue timing, CPU baseline, precision / parity legs and config legs')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the outputs of the last timed step as DIR/<name>.npy (float32)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-parity', action='store_true', help='skip the fp32 parity-mode timing and the live max|d| check against the oracle')
     ap.add_argument('--no-config-legs', action='store_true', help='skip the configs[3] long-clip forward and configs[4] batched-eval legs')
@@ -359,6 +367,24 @@ def parity_leg(make_trainer, bf16_net, ref_mask, args, bf16_rate=None):
     return out
 
 
+def dump_outputs(path, net, last):
+    """--dump-outputs: what the last timed step handed its caller (the pipeline's dict, the loss, the gradient norm) and the parameters
+    the optimizer left, as float32 DIR/<name>.npy (36 MB in all).  An output larger than its sample size is reduced to a fixed sample:
+    sorted flat indices drawn with numpy seed 0, the same in every run with the same arguments."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    params = torch.cat([p.detach().reshape(-1).float() for p in net.parameters()])
+    arrays = dict(loss=(last['loss'], None), grad_norm=(last['grad_norm'], None), sel_occl_fracs=(last['sel_occl_fracs'], None),
+                  output_mask=(last['output_mask'], 1 << 22), target_mask=(last['target_mask'], 1 << 21),
+                  query_mask=(last['seeker_query_mask'], 1 << 20), params=(params, 1 << 21))
+    for name, (t, n) in arrays.items():
+        a = t.detach().float()
+        if n is not None and a.numel() > n:
+            idx = np.sort(np.random.default_rng(0).choice(a.numel(), n, replace=False))
+            a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+        np.save(os.path.join(path, name + '.npy'), a.cpu().numpy().astype(np.float32))
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without a launcher around it: start the N ranks ourselves (one process per GPU, RCCL) as a CHILD
     process -- never exec: a process that may have touched the GPU must not replace itself -- relay its output and return its exit
@@ -481,6 +507,7 @@ def run(args):
     from tcow_amd.pipeline import SeekerPipeline
     from tcow_amd.tcow_loss import default_args
     Qs = args.queries
+    torch.manual_seed(ddp.shard_seed(900, rank))          # the step's drop-path draws: the same arguments compute the same steps in every run (--dump-outputs)
     # synthetic Kubric-shaped batch for this rank: 1 clip, Qs queries chosen by desirability, query_time 0 (README.md:42)
     data = synth.to_torch_tree(synth.make_kubric_batch(1, args.frames, args.height, args.width, seed=ddp.shard_seed(900, rank), n_objects=5), dev,
                                host_keys=synth.HOST_KEYS)   # control-flow metadata stays on the host, as in the reference's DataLoader batch
@@ -499,19 +526,19 @@ def run(args):
                               rng=__import__('numpy').random.default_rng(ddp.shard_seed(900, rank)))
         state = {'step': 0}
 
-        def step():
+        def step(keep=None):
             model_retval = pipe.forward_kubric(data)                        # query sampling, query/target masks, ONE batched Seeker call (pipeline.py:85-200); persistent gradient buckets are overwritten, no zero_grad
             progress = state['step'] / 1000.0
             loss = pipe.step_losses(data, model_retval, progress)['total_seeker']   # loss.py:238-421: weighted BCE + bootstrapped BCE + soft Jaccard
             loss.backward()                                                # train.py:98 (bucketed RCCL all-reduce runs inside, overlapped)
             opt.step()                                                     # grad-clip 0.3 + AdamW in three launches
             state['step'] += 1
+            if keep is not None:                                           # (--dump-outputs: the last timed step's results)
+                keep.update(model_retval, loss=loss, grad_norm=opt.grad_norm())
             return loss
         return net, step
 
     net, step = make_trainer(args.precision)
-    timer = KernelTimer('fp16' if args.precision == 'fp16' else 'bf16')
-    atimer = AttnTimer('fp16' if args.precision == 'fp16' else 'bf16')
 
     for _ in range(args.warmup):
         step()
@@ -519,28 +546,35 @@ def run(args):
         torch.distributed.barrier()
     torch.cuda.synchronize()
     net.seeker.grad_hook.reset_stats()
+    last = {}
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = step()
+    for i in range(args.steps):
+        loss = step(last if args.dump_outputs and i == args.steps - 1 else None)
     torch.cuda.synchronize()
     if world > 1:
         torch.distributed.barrier()
     dt = time.perf_counter() - t0
     ddp_stats = net.seeker.grad_hook.stats() if world > 1 else None
-    # second, untimed pass of the same step count: per-launch HIP events around every NT GEMM (roofline.achieved)
-    timer.begin(400 * args.steps)
-    atimer.begin(120 * args.steps)
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    timer.end()
-    atimer.end(args.steps, {'bf16': PEAK_BF16_TFLOPS, 'fp16': PEAK_BF16_TFLOPS, 'fp32': PEAK_F32_TFLOPS, 'bf16x3': PEAK_BF16_TFLOPS / 3.0}[args.precision])
-    # host time to enqueue ONE step into an empty stream (the loop above is throttled by the queue depth: the host runs ahead of the GPU)
-    enq = []
-    for _ in range(3):
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, net, last)
+    del last
+    if args.full:
+        timer = KernelTimer('fp16' if args.precision == 'fp16' else 'bf16')
+        atimer = AttnTimer('fp16' if args.precision == 'fp16' else 'bf16')
+        # second, untimed pass of the same step count: per-launch HIP events around every NT GEMM (roofline.achieved)
+        timer.begin(400 * args.steps)
+        atimer.begin(120 * args.steps)
+        for _ in range(args.steps):
+            step()
         torch.cuda.synchronize()
-        te = time.perf_counter(); step(); enq.append((time.perf_counter() - te) * 1e3)
-    torch.cuda.synchronize()
+        timer.end()
+        atimer.end(args.steps, {'bf16': PEAK_BF16_TFLOPS, 'fp16': PEAK_BF16_TFLOPS, 'fp32': PEAK_F32_TFLOPS, 'bf16x3': PEAK_BF16_TFLOPS / 3.0}[args.precision])
+        # host time to enqueue ONE step into an empty stream (the loop above is throttled by the queue depth: the host runs ahead of the GPU)
+        enq = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            te = time.perf_counter(); step(); enq.append((time.perf_counter() - te) * 1e3)
+        torch.cuda.synchronize()
     if world > 1:
         torch.distributed.barrier()
     rank_ms = None
@@ -556,13 +590,7 @@ def run(args):
     if rank == 0:
         g = net.seeker.geometry(Qs)
         fl = flops.seeker_forward_flops(1, g['T'], g['Hp'], g['Wp'], g['D'], g['heads'], args.depth)
-        ks = timer.summary()
         peak = {'bf16': PEAK_BF16_TFLOPS, 'fp16': PEAK_BF16_TFLOPS, 'fp32': PEAK_F32_TFLOPS, 'bf16x3': PEAK_BF16_TFLOPS / 3.0}[args.precision]   # (dense f16 = dense bf16 peak)   # bf16x3: three MFMAs per product
-        traffic = pmc_traffic() if args.precision in ('bf16', 'fp16') else None        # (same kernels, same bytes in both 16-bit builds)
-        roof = dict(bound='mfma', kernel={'bf16': 'gemm_nt_bf16_320_kernel (+ gemm_nt_bf16_c2_kernel, gemm_nt_bf16_256_kernel, gemm_nt_bf16_kernel)', 'fp16': 'gemm_nt_bf16_320_kernel built for binary16 (libtcow_hip_fp16.so)',
-                            'fp32': 'gemm_f32_kernel', 'bf16x3': 'gemm_x3_kernel'}[args.precision],
-                    achieved=ks['tflops'], peak=peak, unit='TFLOP/s', frac=ks['tflops'] / peak, traffic=traffic,
-                    launches_per_step=ks['launches'] / args.steps, avg_launch_us=ks['avg_us'], flops_per_launch=ks['flops_per_launch'])
         step_tflops = 3.0 * Qs * fl['total'] / (ms_per_step * 1e-3) / 1e12
         res = dict(metric='train clips/sec (T=30, 240x320)', value=clips_per_s, unit='clips/s', n_gpus=world, ranks_seen=(torch.distributed.get_world_size() if world > 1 else 1), steps=args.steps,
                    warmup=args.warmup, ms_per_step=ms_per_step, higher_is_better=True, scaling='weak', vs_baseline=None,
@@ -572,7 +600,15 @@ def run(args):
                                clips_per_gpu=1, num_queries=Qs, parallelism=f'dp{world}', optimizer='AdamW lr 1e-4, clip 0.3',
                                loss='TCOW mask losses (loss.py:238-421): class-balanced BCE + bootstrapped BCE + soft Jaccard on 3 channels'),
                    query_forwards_per_s=clips_per_s * Qs, step_model_tflops=step_tflops, step_mfma_frac=step_tflops / peak,
-                   final_loss=float(loss.detach()), host_enqueue_ms=round(sorted(enq)[1], 2), roofline=roof, roofline_attention=atimer.result)
+                   final_loss=float(loss.detach()))
+        if args.full:
+            ks = timer.summary()
+            traffic = pmc_traffic() if args.precision in ('bf16', 'fp16') else None        # (same kernels, same bytes in both 16-bit builds)
+            roof = dict(bound='mfma', kernel={'bf16': 'gemm_nt_bf16_320_kernel (+ gemm_nt_bf16_c2_kernel, gemm_nt_bf16_256_kernel, gemm_nt_bf16_kernel)', 'fp16': 'gemm_nt_bf16_320_kernel built for binary16 (libtcow_hip_fp16.so)',
+                                'fp32': 'gemm_f32_kernel', 'bf16x3': 'gemm_x3_kernel'}[args.precision],
+                        achieved=ks['tflops'], peak=peak, unit='TFLOP/s', frac=ks['tflops'] / peak, traffic=traffic,
+                        launches_per_step=ks['launches'] / args.steps, avg_launch_us=ks['avg_us'], flops_per_launch=ks['flops_per_launch'])
+            res.update(host_enqueue_ms=round(sorted(enq)[1], 2), roofline=roof, roofline_attention=atimer.result)
         if world > 1:
             # what the scaling curve needs to explain itself: how long the compute stream stood still for the gradient all-reduce (rank 0),
             # how much went over xGMI per step in how many collectives, and the spread of the per-rank step times
@@ -581,14 +617,14 @@ def run(args):
                               rccl=rccl_knobs(), rccl_version=contact.get('rccl_version'), backend=contact.get('backend'), first_contact_ms=round(contact.get('ms', 0.0), 1),
                               cpu_baseline='reported at N = 1 only (rank 0 of a single-GPU run)')
         ref_mask = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 ref_mask, res['cpu_baseline'] = cpu_baseline(cfg, args.cpu_budget_s)
             except Exception as e:  # the baseline is a reported aside; never fail the bench line over it
                 res['cpu_baseline'] = dict(value=None, unit='clips/s', cores=os.cpu_count(), kind='port', sample=f'failed: {e}')
-        if world == 1 and args.precision == 'bf16' and not args.no_parity:
+        if args.full and world == 1 and args.precision == 'bf16' and not args.no_parity:
             res.update(parity_leg(make_trainer, net, ref_mask, args, bf16_rate=clips_per_s))
-        if world == 1 and not args.no_config_legs:
+        if args.full and world == 1 and not args.no_config_legs:
             try:
                 res.update(config_legs(args, dev))
             except Exception as e:  # reported asides; never lose the headline over them

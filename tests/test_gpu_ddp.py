@@ -149,7 +149,7 @@ def test_full_size_two_rank_bench_line_on_one_gpu(cuda):
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'TCOW_DDP_GROUP'):
         env.pop(k, None)
     env['TCOW_DIST_BACKEND'] = 'gloo'
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-parity'],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-parity'],
                          env=env, capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
     res = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][-1])

@@ -37,7 +37,7 @@ for k, (v, c) in fetch.items():
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sha = hashlib.sha256(b''.join(open(os.path.join(root, 'tcow_amd', 'csrc', f), 'rb').read() for f in ('gemm_bf16.hip', 'gemm_nt_common.h'))).hexdigest()     # (as bench.py pmc_traffic)
 rec = dict(kernel='gemm_nt_bf16_*_kernel (every NT-GEMM launch of the timed steps at M = 27090, dispatch-weighted)',
-           command='rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE --kernel-trace -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-parity --no-config-legs (tools/pmc_bench.sh)',
+           command='rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE --kernel-trace -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-parity --no-config-legs (tools/pmc_bench.sh)',
            dispatches_fetch=n_f, dispatches_write=n_w, fetch_size_kib_mean=f_nt, write_size_kib_mean=w_nt,
            fetch_correction=corr, calibration=dict(scale_cast_fetch_kib=sc_f, ln_fwd_fetch_kib=ln_f, known_f32_read_kib=known_read, scale_cast_write_kib=sc_w, known_bf16_write_kib=known_write),
            traffic_bytes_per_launch=(f_nt * corr + w_nt) * 1024.0 if f_nt and w_nt else None, gemm_bf16_sha256=sha, per_kernel=per)

@@ -301,8 +301,8 @@ def _ref_attn(qkv, B, T, S, D, heads, ca, spatial):
     (True, 1, 3, 301, 5, 1), (True, 1, 3, 40, 3, 1), (True, 1, 5, 173, 5, 1), (True, 1, 2, 304, 2, 1), (True, 1, 2, 305, 3, 0), (True, 3, 9, 301, 1, 1),
     (True, 1, 2, 1201, 12, 1)])          # last: the spatial sequence of BASELINE configs[3] (480x640: 1200 patches + cls)
 def test_attention_fwd_bwd(ops, cuda, mname, tol, spatial, B, T, S, heads, ca):
-    """Empty / ragged cases included: S=2 (one patch), T not a multiple of 32, sequences longer than the MFMA limits
-    (T=70, S=333 take the f32-arithmetic kernels), causal windows 0 / 1 / look-ahead."""
+    """Empty / ragged cases included: S=2 (one patch), T not a multiple of 32, temporal sequences past the wave-private kernels' 64 frames
+    (T=70 takes the streaming kernels), causal windows 0 / 1 / look-ahead.  lse against the log-sum-exp of the reference's scaled, masked scores."""
     mode, dt = _mode(ops, mname)
     D = heads * 64; M = B * T * S
     g = torch.Generator(device='cuda').manual_seed(S * T)
@@ -314,6 +314,20 @@ def test_attention_fwd_bwd(ops, cuda, mname, tol, spatial, B, T, S, heads, ca):
     ref = _ref_attn(q32, B, T, S, D, heads, ca, spatial)
     assert torch.isfinite(out.float()).all()
     assert rel(out, ref) < tol
+    x = qkv.double().reshape(B, T, S, 3, heads, 64)
+    if spatial:
+        s0 = 0 if ca in (0, 1) else 1
+        qq, kk = x[:, :, s0:, 0].permute(0, 1, 3, 2, 4), x[:, :, s0:, 1].permute(0, 1, 3, 2, 4)
+        want_l = torch.logsumexp(qq @ kk.transpose(-1, -2) * 0.125, -1).permute(0, 1, 3, 2)
+        got_l = lse.reshape(B, T, S, heads)[:, :, s0:]
+    else:
+        qq, kk = x[:, :, 1:, 0].permute(0, 2, 3, 1, 4), x[:, :, 1:, 1].permute(0, 2, 3, 1, 4)
+        a = qq @ kk.transpose(-1, -2) * 0.125
+        if ca > 0:
+            a = a.masked_fill(~torch.ones(T, T, dtype=torch.bool, device=cuda).tril(0 if ca <= 2 else ca - 2), float('-inf'))
+        want_l = torch.logsumexp(a, -1).permute(0, 3, 1, 2)
+        got_l = lse.reshape(B, T, S, heads)[:, :, 1:]
+    assert float((got_l.double() - want_l).abs().max()) < (1e-4 if mname in ('f32', 'f32x3') else 0.05)     # N(0, 1) scores: |score| < ~6
     dout = torch.randn(M, D, device=cuda, generator=g).to(dt)
     (ref * dout.float()).sum().backward()
     dqkv = torch.full((M, 3 * D), float('nan'), device=cuda, dtype=dt)

@@ -57,7 +57,7 @@ extern "C" {
 
 /* ABI version (bumped on any signature change) and last error text of the calling thread.  A host compares tcow_version() with the TCOW_ABI_VERSION it
  * was built against before the first call (tcow_amd/_lib.py does, for both builds of the library). */
-#define TCOW_ABI_VERSION 10
+#define TCOW_ABI_VERSION 11
 int tcow_version(void);
 const char* tcow_last_error(void);
 
@@ -201,6 +201,23 @@ int tcow_attn_temporal_bwd(void* stream, const tcow_attn_shape* shape, const voi
                            const void* dout, const float* lse, void* dqkv, void* workspace, long workspace_bytes);
 int tcow_attn_spatial_bwd(void* stream, const tcow_attn_shape* shape, const void* qkv, const void* out,
                           const void* dout, const float* lse, void* dqkv, void* workspace, long workspace_bytes);
+
+/* ------------------------------------------------------------------------------------------- streaming inference (attention_stream.hip)
+ * A stream feeds the model c >= 1 new frames at a time (tcow_amd/stream.py).  With causal_attention 1 or 2 frame t depends on frames 0..t only
+ * (tril() of vit.py:93-99, frame-0 cls of vit.py:192-198), so each chunk runs the block schedule on its own rows and takes the temporal keys /
+ * values of earlier frames from a per-block cache.
+ * tcow_attn_temporal_cached_fwd: `chunk` = {B, T = c, S, D, heads, causal, dtype}; qkv [B*c*S, 3D], out [B*c*S, D] in the chunk's row order
+ *   (b*c + j)*S + s; k_cache / v_cache [B, S-1, heads, T_total, 64] (`dtype`: TCOW_BF16 = the build's 16-bit type, TCOW_F32; arithmetic f32).
+ *   For every b, slot s >= 1, head h, chunk frame j, t = t0 + j:  out = softmax_{t' <= t}(q_t . k_t' / 8) v_t', keys / values of t' < t0 from
+ *   the cache and of t' >= t0 from the chunk (replaces vit.py:88-109 of the temporal attention, vit.py:169-172); then the chunk's K / V are
+ *   the cache's rows t0 .. t0+c-1.  Slot-0 rows of out are zero.  t0 is read from device memory (*t0_dev), so one captured graph serves every
+ *   step; a t0 with t0 + c > T_total writes NaN to out and leaves the cache alone.  causal must be 1 or 2, T_total <= TCOW_STREAM_MAX_FRAMES.
+ * tcow_cls_stream: x [B*c*S, D] f32 after the spatial projection (causal_attention == 1; replaces tcow_cls_merge mode 1, vit.py:189-198,215):
+ *   t0 == 0: every frame's slot 0 <- frame 0's slot 0, and that row -> cls_cache [B, D]; t0 > 0: every frame's slot 0 <- cls_cache. */
+#define TCOW_STREAM_MAX_FRAMES 1024
+int tcow_attn_temporal_cached_fwd(void* stream, const tcow_attn_shape* chunk, int T_total, const int* t0_dev, const void* qkv, void* k_cache,
+                                  void* v_cache, void* out);
+int tcow_cls_stream(void* stream, int B, int c, int S, int D, float* x, float* cls_cache, const int* t0_dev);
 
 /* ------------------------------------------------------------------------------------------- token glue
  * tcow_im2col: cat([rgb (B,3,T,H,W), query (B,1,T,H,W)]) (mask_tracker.py:107-108), optional (rgb-0.45)/0.225

@@ -91,6 +91,8 @@ SIGNATURES = {
     'tcow_attn_bwd_workspace_bytes': (_l, [_ash]),
     'tcow_attn_temporal_bwd': (_i, [_vp, _ash, _vp, _vp, _vp, _vp, _vp, _vp, _l]),
     'tcow_attn_spatial_bwd': (_i, [_vp, _ash, _vp, _vp, _vp, _vp, _vp, _vp, _l]),
+    'tcow_attn_temporal_cached_fwd': (_i, [_vp, _ash, _i, _vp, _vp, _vp, _vp, _vp]),
+    'tcow_cls_stream': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'tcow_im2col': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     'tcow_gather_frames': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'tcow_resize_aa': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp]),
@@ -132,7 +134,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 10       # TCOW_ABI_VERSION of include/tcow_hip.h
+ABI_VERSION = 11       # TCOW_ABI_VERSION of include/tcow_hip.h
 
 
 def _declare(L, tolerant=False):

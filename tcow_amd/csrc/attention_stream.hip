@@ -1,0 +1,199 @@
+// Streaming inference (tcow_amd/stream.py): temporal attention of a chunk of c new frames against a per-block K/V cache of the frames before
+// it, and the cls-row bookkeeping of causal_attention == 1 across chunks.  Replaces, for a stream, the temporal core of Attention.forward
+// (vit.py:88-109 with the tril() mask of vit.py:93-99) and the frame-0 cls broadcast of vit.py:189-198,215.
+//
+// tcow_attn_temporal_cached_fwd: one wave per (clip b, slot s, head h); four waves per workgroup.  The head's 64 channels of a K / V row
+// are one 128-byte (16-bit) or 256-byte (f32) line: LPR lanes read it with one 16-byte load each, so a wave covers G = 64 / LPR key rows per
+// load (16-bit: 8 lanes x 8 elements, 8 rows; f32: 16 lanes x 4, 4 rows).  Lane group g walks keys g, g + G, ... with its own online
+// softmax (scores reduced over the group's lanes by xor shuffles), ST_U batches of G rows in flight per wave; the G partial states are merged
+// by xor shuffles at the end.  No LDS.  The cache of (b, s, h) is one contiguous [T_total, 64] block ([B, S-1, heads, T_total, 64]), so a
+// pass over it is a run of whole lines.  Keys of frames < t0 come from the cache, keys of the chunk's own frames from the chunk's qkv
+// rows; the same wave copies the chunk's K / V rows into cache positions t0 .. t0+c-1 (nothing reads them in this launch).
+#include <math.h>
+
+#include "attention_common.h"
+
+namespace {
+
+constexpr int ST_WAVES = 4;     // waves (items) per workgroup
+constexpr int ST_U = 4;         // batches of G key rows loaded before they are used
+
+template <typename T> struct StreamVec;
+template <> struct StreamVec<bf16_t> {
+    static constexpr int VEC = 8;
+    static __device__ __forceinline__ void ld(const bf16_t* p, float* v) {
+        const uint4 u = *reinterpret_cast<const uint4*>(p);
+        v[0] = bflo(u.x); v[1] = bfhi(u.x); v[2] = bflo(u.y); v[3] = bfhi(u.y);
+        v[4] = bflo(u.z); v[5] = bfhi(u.z); v[6] = bflo(u.w); v[7] = bfhi(u.w);
+    }
+    static __device__ __forceinline__ void st(bf16_t* p, const float* v) {
+        uint4 u;
+        u.x = pack_bf2(v[0], v[1]); u.y = pack_bf2(v[2], v[3]); u.z = pack_bf2(v[4], v[5]); u.w = pack_bf2(v[6], v[7]);
+        *reinterpret_cast<uint4*>(p) = u;
+    }
+};
+template <> struct StreamVec<float> {
+    static constexpr int VEC = 4;
+    static __device__ __forceinline__ void ld(const float* p, float* v) {
+        const float4 f = *reinterpret_cast<const float4*>(p);
+        v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
+    }
+    static __device__ __forceinline__ void st(float* p, const float* v) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
+};
+
+__device__ __forceinline__ void copy16(void* dst, const void* src) { *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src); }
+
+template <typename T>
+__global__ __launch_bounds__(64 * ST_WAVES) void temporal_cached_kernel(int B, int c, int S, int D, int heads, int T_total, const int* __restrict__ t0_dev,
+                                                                       const T* __restrict__ qkv, T* __restrict__ kc, T* __restrict__ vc, T* __restrict__ out) {
+    constexpr int VEC = StreamVec<T>::VEC, LPR = ATT_HD / VEC, G = 64 / LPR;
+    const int lane = threadIdx.x & 63, grp = lane / LPR, sub = lane - grp * LPR;
+    const long item = (long)blockIdx.x * ST_WAVES + (threadIdx.x >> 6);
+    if (item >= (long)B * S * heads) return;
+    const int h = (int)(item % heads);
+    const long bs = item / heads;
+    const int s = (int)(bs % S), b = (int)(bs / S);
+    const int t0 = *t0_dev;
+    const long ld3 = 3L * D;
+    const int col = h * ATT_HD + sub * VEC;
+    const bool bad_t0 = t0 < 0 || t0 + c > T_total;
+    if (s == 0 || bad_t0) {
+        // slot 0 takes no part in temporal attention: its rows are defined as zero (as in the clip path).  A t0 outside the stream (the host
+        // checks it before it writes t0) touches no cache row and writes NaN.
+        float z[VEC];
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) z[e] = bad_t0 ? __builtin_nanf("") : 0.f;
+        for (int j = grp; j < c; j += G) StreamVec<T>::st(out + ((long)(b * c + j) * S + s) * D + col, z);
+        return;
+    }
+    const size_t cbase = ((((size_t)b * (S - 1) + (s - 1)) * heads + h) * T_total) * ATT_HD + sub * VEC;
+    // append the chunk's keys / values: cache[t0 + j] = chunk row j (bit copies)
+    for (int j = grp; j < c; j += G) {
+        const T* src = qkv + ((long)(b * c + j) * S + s) * ld3 + col;
+        copy16(kc + cbase + (size_t)(t0 + j) * ATT_HD, src + D);
+        copy16(vc + cbase + (size_t)(t0 + j) * ATT_HD, src + 2 * D);
+    }
+    const float scale = 0.125f;      // head_dim ** -0.5 (vit.py:74)
+    for (int j = 0; j < c; ++j) {
+        const int t = t0 + j;            // query frame; keys 0 .. t (tril() of causal 1 and 2)
+        float q[VEC];
+        StreamVec<T>::ld(qkv + ((long)(b * c + j) * S + s) * ld3 + col, q);
+        float m = -INFINITY, l = 0.f, acc[VEC];
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc[e] = 0.f;
+        for (int k0 = 0; k0 <= t; k0 += G * ST_U) {
+            float kv[ST_U][VEC], vv[ST_U][VEC];
+#pragma unroll
+            for (int u = 0; u < ST_U; ++u) {
+                const int kt = k0 + u * G + grp;
+                if (kt <= t) {
+                    const T* kp = kt < t0 ? kc + cbase + (size_t)kt * ATT_HD : qkv + ((long)(b * c + kt - t0) * S + s) * ld3 + D + col;
+                    const T* vp = kt < t0 ? vc + cbase + (size_t)kt * ATT_HD : qkv + ((long)(b * c + kt - t0) * S + s) * ld3 + 2 * D + col;
+                    StreamVec<T>::ld(kp, kv[u]);
+                    StreamVec<T>::ld(vp, vv[u]);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < VEC; ++e) { kv[u][e] = 0.f; vv[u][e] = 0.f; }
+                }
+            }
+            float sc[ST_U];
+            float mb = m;
+#pragma unroll
+            for (int u = 0; u < ST_U; ++u) {
+                float d = 0.f;
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) d = fmaf(q[e], kv[u][e], d);
+#pragma unroll
+                for (int o = 1; o < LPR; o <<= 1) d += __shfl_xor(d, o, 64);
+                sc[u] = (k0 + u * G + grp <= t) ? d * scale : -INFINITY;
+                mb = fmaxf(mb, sc[u]);
+            }
+            // (a group without a key so far keeps m = -inf, l = 0, acc = 0: both factors below are then 0)
+            const float alpha = (m == -INFINITY) ? 0.f : expf(m - mb);
+            l *= alpha;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) acc[e] *= alpha;
+#pragma unroll
+            for (int u = 0; u < ST_U; ++u) {
+                const float p = (sc[u] == -INFINITY) ? 0.f : expf(sc[u] - mb);
+                l += p;
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) acc[e] = fmaf(p, vv[u][e], acc[e]);
+            }
+            m = mb;
+        }
+        // merge the G groups' (m, l, acc): lanes with the same channel slice sit LPR apart
+#pragma unroll
+        for (int o = LPR; o < 64; o <<= 1) {
+            const float mo = __shfl_xor(m, o, 64), lo = __shfl_xor(l, o, 64);
+            const float mn = fmaxf(m, mo);
+            const float a = (m == -INFINITY) ? 0.f : expf(m - mn), bb = (mo == -INFINITY) ? 0.f : expf(mo - mn);
+            l = l * a + lo * bb;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) { const float ao = __shfl_xor(acc[e], o, 64); acc[e] = acc[e] * a + ao * bb; }
+            m = mn;
+        }
+        if (grp == 0) {
+            const float inv = 1.f / l;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) acc[e] *= inv;
+            StreamVec<T>::st(out + ((long)(b * c + j) * S + s) * D + col, acc);
+        }
+    }
+}
+
+// causal_attention == 1 across chunks.  t0 == 0: tcow_cls_merge mode 1 on the chunk (frame 0's slot-0 row to every frame), the row kept in
+// cls_cache[b]; t0 > 0: cls_cache[b] to slot 0 of every chunk frame.  One thread per (b, 4 channels).
+__global__ void cls_stream_kernel(int B, int c, int S, int D, float* __restrict__ x, float* __restrict__ cls_cache, const int* __restrict__ t0_dev) {
+    const int d4 = D / 4;
+    const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (i >= (long)B * d4) return;
+    const int b = (int)(i / d4), ch = (int)(i - (long)b * d4) * 4;
+    float* base = x + (size_t)b * c * S * D + ch;
+    const size_t fs = (size_t)S * D;
+    float4 a;
+    if (*t0_dev == 0) {
+        a = ld4(base);
+        st4(cls_cache + (size_t)b * D + ch, a);
+    } else {
+        a = ld4(cls_cache + (size_t)b * D + ch);
+    }
+    for (int t = 0; t < c; ++t) st4(base + t * fs, a);
+}
+
+}  // namespace
+
+extern "C" {
+
+int tcow_attn_temporal_cached_fwd(void* stream, const tcow_attn_shape* chunk, int T_total, const int* t0_dev, const void* qkv, void* k_cache, void* v_cache,
+                                  void* out) {
+    TCOW_CHECK_ARG(chunk != nullptr, "tcow_attn_temporal_cached_fwd: null shape");
+    const tcow_attn_shape& s = *chunk;
+    TCOW_CHECK_ARG(s.B > 0 && s.T > 0 && s.S > 1 && s.heads > 0, "tcow_attn_temporal_cached_fwd: bad chunk shape B=%d c=%d S=%d heads=%d", s.B, s.T, s.S, s.heads);
+    TCOW_CHECK_ARG(s.D == s.heads * ATT_HD, "tcow_attn_temporal_cached_fwd: head_dim must be 64 (D=%d heads=%d)", s.D, s.heads);
+    TCOW_CHECK_ARG(s.causal == 1 || s.causal == 2, "tcow_attn_temporal_cached_fwd: causal must be 1 or 2 (got %d): other masks let a frame see later frames",
+                   s.causal);
+    TCOW_CHECK_ARG(T_total >= s.T && T_total <= TCOW_STREAM_MAX_FRAMES, "tcow_attn_temporal_cached_fwd: T_total=%d must be in [c=%d, %d]", T_total, s.T,
+                   TCOW_STREAM_MAX_FRAMES);
+    TCOW_CHECK_ARG(s.dtype == TCOW_F32 || s.dtype == TCOW_BF16, "tcow_attn_temporal_cached_fwd: dtype must be TCOW_F32 or TCOW_BF16 (got %d)", s.dtype);
+    TCOW_CHECK_ARG(t0_dev && qkv && k_cache && v_cache && out, "tcow_attn_temporal_cached_fwd: null pointer");
+    const long items = (long)s.B * s.S * s.heads;
+    const dim3 grid((unsigned)cdiv(items, ST_WAVES)), block(64 * ST_WAVES);
+    if (s.dtype == TCOW_BF16)
+        hipLaunchKernelGGL(temporal_cached_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, s.B, s.T, s.S, s.D, s.heads, T_total, t0_dev,
+                           (const bf16_t*)qkv, (bf16_t*)k_cache, (bf16_t*)v_cache, (bf16_t*)out);
+    else
+        hipLaunchKernelGGL(temporal_cached_kernel<float>, grid, block, 0, (hipStream_t)stream, s.B, s.T, s.S, s.D, s.heads, T_total, t0_dev,
+                           (const float*)qkv, (float*)k_cache, (float*)v_cache, (float*)out);
+    TCOW_CHECK_LAUNCH();
+    return TCOW_OK;
+}
+
+int tcow_cls_stream(void* stream, int B, int c, int S, int D, float* x, float* cls_cache, const int* t0_dev) {
+    TCOW_CHECK_ARG(B > 0 && c > 0 && S > 1 && D > 0 && D % 4 == 0 && x && cls_cache && t0_dev, "tcow_cls_stream: bad arguments");
+    hipLaunchKernelGGL(cls_stream_kernel, dim3(cdiv((long)B * D / 4, 64)), dim3(64), 0, (hipStream_t)stream, B, c, S, D, x, cls_cache, t0_dev);
+    TCOW_CHECK_LAUNCH();
+    return TCOW_OK;
+}
+
+}  // extern "C"

@@ -202,7 +202,7 @@ def _row_vectors(module, g, train):
     """mask0 [M] (0 on slot 0) and the DropPath row scales of every block (None in eval)."""
     B, T, S, N = g['B'], g['T'], g['S'], g['N']
     dev = module.vit.pos_embed.device
-    key = ('mask0', B, str(dev))
+    key = ('mask0', B, T, str(dev))          # (T: a stream's chunk geometry has fewer frames than the clip)
     mask0 = module._wcache.get(key)
     if mask0 is None:
         mask0 = torch.ones(B, T, S, dtype=torch.float32, device=dev)
@@ -306,13 +306,16 @@ def _effective_embeddings(module, g):
     return pos.contiguous(), te.contiguous(), pos_idx, time_idx
 
 
-def run_forward(module, rgb, qm, params, save):
+def run_forward(module, rgb, qm, params, save, stream=None):
+    """stream (inference only, tcow_amd/stream.py): the state of a SeekerStream step -- rgb / qm then hold the chunk's c frames, and the schedule
+    differs in three places: the time rows (stream.time_rows = rows t0 .. t0+c-1 of the effective table), the temporal attention (against the
+    block's K / V cache, tcow_attn_temporal_cached_fwd) and, for causal_attention == 1, the cls row (tcow_cls_stream)."""
     mode = module.mode
     gmode = module.gemm_mode           # the GEMM entry points' arithmetic: `mode`, or TCOW_F32X3 (f32 tensors, bf16 x 3 split products) for precision='bf16x3'
     dt = ops.tdtype(mode)
     dev = rgb.device
     B = qm.shape[0]                          # query rows (== clips unless the rgb frames are shared between a clip's queries)
-    g = module.geometry(B)
+    g = module.geometry(B) if stream is None else module.geometry(B, T=rgb.shape[2])
     T, S, D, M, P, heads = g['T'], g['S'], g['D'], g['M'], g['P'], g['heads']
     ca = module.causal_attention
     use_cls = ca in (0, 1)
@@ -351,7 +354,10 @@ def run_forward(module, rgb, qm, params, save):
         A_pe = E(M, Kpe)
         ops.im2col(mode, rgb, qm, P, module.tracker_pretrained, A_pe)
         ops.gemm_nt(gmode, A_pe, W(params[3]), X, bias=params[4].detach())
-    pos, te, pos_idx, time_idx = _effective_embeddings(module, g)
+    if stream is None:
+        pos, te, pos_idx, time_idx = _effective_embeddings(module, g)
+    else:
+        pos, te, pos_idx, time_idx = stream.pos, stream.time_rows, None, None
     ops.embed_fwd(X, B, T, S, params[0].detach().reshape(-1), pos, te)
     if save:
         sv.update(A_pe=A_pe, pos_idx=pos_idx, time_idx=time_idx)
@@ -396,7 +402,10 @@ def run_forward(module, rgb, qm, params, save):
             QKV = E(M, 3 * D)
             ops.gemm_nt(gmode, U, W(q[ix['tqkv']]), QKV, bias=tqkv_b)
             O = E(M, D); lse_t = E(M, heads, dtype=f32) if save else None
-            ops.attn_fwd(shape_attn, False, QKV, O, lse_t)
+            if stream is None:
+                ops.attn_fwd(shape_attn, False, QKV, O, lse_t)
+            else:
+                ops.attn_temporal_cached(amode, B, T, S, D, heads, ca, stream.T_total, stream.t0_dev, QKV, stream.k_cache[i], stream.v_cache[i], O)
             R1 = E(M, D, dtype=f32) if save else R0
             if fold:
                 Wf, _, bprime = _folded_weight(module, i, q, ix, train)
@@ -420,7 +429,9 @@ def run_forward(module, rgb, qm, params, save):
                 rs_s = mask0 if rs_s is None else rs_s * mask0
             R2 = E(M, D, dtype=f32) if save else R1
             ops.gemm_nt(gmode, O2, W(q[ix['proj']]), R2, bias=proj_b, row_scale=rs_s, resid=R1)
-            if use_cls:
+            if use_cls and stream is not None:
+                ops.cls_stream(R2, B, T, S, stream.cls_cache[i], stream.t0_dev)      # (a stream has causal_attention 1 or 2)
+            elif use_cls:
                 ops.cls_merge(R2, B, T, S, 1 if ca == 1 else 0)
             if save:
                 st.update(R1=R1, mu1=mu1, rs1=rs1, V=V, QKV_s=QKV2, O_s=O2, lse_s=lse_s, rs_s=rs_s)

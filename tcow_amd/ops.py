@@ -200,6 +200,24 @@ def attn_bwd(shape, spatial, qkv, out, dout, lse, dqkv):
     return dqkv
 
 
+def attn_temporal_cached(mode, B, c, S, D, heads, causal, T_total, t0_dev, qkv, k_cache, v_cache, out):
+    """Temporal attention of a c-frame chunk (qkv [B*c*S, 3D] -> out [B*c*S, D]) against the K / V cache [B, S-1, heads, T_total, 64] of the
+    frames before t0 = t0_dev[0] (int32 device scalar); appends the chunk's K / V at t0 (see tcow_attn_temporal_cached_fwd).  `mode` is the
+    attention mode: F32X3 (precision='bf16x3') stores f32 and runs as F32."""
+    _need_cuda(qkv, k_cache, v_cache, out, t0_dev)
+    lib, dm = _sel(mode)
+    sh = L.AttnShape(B, c, S, D, heads, int(causal), F32 if dm == F32X3 else dm)
+    L.check(lib.tcow_attn_temporal_cached_fwd(_stream(), ctypes.byref(sh), int(T_total), t0_dev.data_ptr(), qkv.data_ptr(), k_cache.data_ptr(),
+                                              v_cache.data_ptr(), out.data_ptr()), 'tcow_attn_temporal_cached_fwd', lib)
+    return out
+
+
+def cls_stream(x, B, c, S, cls_cache, t0_dev):
+    """causal_attention == 1 in a stream: t0 == 0 -> tcow_cls_merge mode 1 + keep the row in cls_cache [B, D]; t0 > 0 -> cls_cache to slot 0."""
+    L.check(L.lib().tcow_cls_stream(_stream(), B, c, S, x.shape[1], x.data_ptr(), cls_cache.data_ptr(), t0_dev.data_ptr()), 'tcow_cls_stream')
+    return x
+
+
 def im2col(mode, rgb, query, P, pretrained_norm, out):
     B, _, T, H, W = rgb.shape
     L.check(_sel(mode)[0].tcow_im2col(_stream(), _sel(mode)[1], B, T, H, W, P, rgb.data_ptr(), query.data_ptr(), int(pretrained_norm), out.data_ptr()), 'tcow_im2col', _sel(mode)[0])

@@ -238,12 +238,19 @@ class QueryMaskTracker(nn.Module):
     def vit(self):
         return self.tracker_backbone.timesformer.model
 
-    def geometry(self, B):
+    def geometry(self, B, T=None):
+        """T: frames per row block (default num_total_frames; a stream step passes its chunk length)."""
         P = self.patch_size
         Hp, Wp = self.frame_height // P, self.frame_width // P
         N = Hp * Wp
-        return dict(B=B, T=self.num_total_frames, Hp=Hp, Wp=Wp, N=N, S=N + 1, D=self.embed_dim, heads=self.num_heads,
-                    P=P, M=B * self.num_total_frames * (N + 1))
+        T = self.num_total_frames if T is None else T
+        return dict(B=B, T=T, Hp=Hp, Wp=Wp, N=N, S=N + 1, D=self.embed_dim, heads=self.num_heads, P=P, M=B * T * (N + 1))
+
+    def stream(self, batch_size=1, queries_per_clip=1, graph=False):
+        """Streaming inference (causal_attention 1 or 2, eval, CUDA): a SeekerStream of at most num_total_frames frames for `batch_size` clips with
+        `queries_per_clip` query masks each; stream.step(rgb, query_mask) takes the next frames and returns their outputs (tcow_amd/stream.py)."""
+        from .stream import SeekerStream
+        return SeekerStream(self, batch_size, queries_per_clip, graph)
 
     def param_list(self):
         """Fixed order of the parameters the autograd.Function sees.  Cached: walking ~250 module attributes costs 0.4 ms per call.  .to() /
@@ -318,3 +325,7 @@ class Seeker(nn.Module):
 
     def forward(self, *args):
         return self.seeker(*args)
+
+    def stream(self, batch_size=1, queries_per_clip=1, graph=False):
+        """See QueryMaskTracker.stream."""
+        return self.seeker.stream(batch_size, queries_per_clip, graph)

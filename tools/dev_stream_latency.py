@@ -1,0 +1,183 @@
+"""Dev: latency of streaming inference (Seeker.stream, tcow_amd/stream.py) against the clip forward, on the GPU.
+
+    python tools/dev_stream_latency.py --out profiles/stream_latency.json       # step latencies, whole-clip sums, clip forwards (one JSON file)
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o run -- python tools/dev_stream_latency.py --kprof
+                                        # one-frame bf16 steps at configs[3], t0 = 59: KPROF_WARMUP warm-up steps, then KPROF_STEPS profiled ones
+    python tools/dev_stream_latency.py --kstats DIR/run_kernel_trace.csv --out profiles/stream_step_kernel_stats.txt
+                                        # per-step kernel breakdown of the profiled steps only (the warm-up steps' dispatches are dropped)
+
+Times are device events around each call after warm-up, profiler off.  A step at a given t0 is timed by setting the stream's host frame counter
+(the kernels then read t0 from the device scalar the step writes): the work of a step depends on t0, not on what the cache holds.  Synthetic
+weights / clips (tcow_amd.synth); depth 12 ViT-B; one query per clip.
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tcow_amd import synth                      # noqa: E402
+from tcow_amd.seeker import Seeker              # noqa: E402
+
+CONFIGS = {'configs1': (30, 240, 320), 'configs3': (60, 480, 640)}
+
+
+def build(T, H, W, precision):
+    cfg = synth.seeker_config(num_total_frames=T, frame_height=H, frame_width=W, causal_attention=1)
+    net = Seeker(None, num_total_frames=T, frame_height=H, frame_width=W, causal_attention=1, drop_path_rate=0.0, precision=precision)
+    net.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_state_dict(cfg, 900).items()})
+    return net.cuda().eval()
+
+
+def inputs(B, T, H, W):
+    clip = synth.make_clip(1, T, H, W, seed=900)
+    rgb = torch.from_numpy(clip['rgb']).cuda().expand(B, -1, -1, -1, -1).contiguous()
+    qm = torch.from_numpy(synth.make_query_mask(clip, 0, 0)).cuda().expand(B, -1, -1, -1, -1).contiguous()
+    return rgb, qm
+
+
+def ev_time(fn, reps):
+    """Median device time (ms) of fn() over `reps` calls, each bracketed by events on the current stream."""
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(); fn(); b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b))
+    out.sort()
+    return out[len(out) // 2]
+
+
+def measure(name, B, precision, reps):
+    T, H, W = CONFIGS[name]
+    net = build(T, H, W, precision)
+    rgb, qm = inputs(B, T, H, W)
+    res = {'config': name, 'T': T, 'H': H, 'W': W, 'B': B, 'precision': precision}
+    with torch.no_grad():
+        for _ in range(3):
+            net(rgb, qm)
+        res['clip_forward_ms'] = ev_time(lambda: net(rgb, qm), reps)
+        for graph in (False, True):
+            st = net.stream(batch_size=B, graph=graph)
+            tag = 'graph' if graph else 'eager'
+            for t in range(T):                                    # warm-up: the whole clip once (captures the c = 1 graph)
+                st.step(rgb[:, :, t:t + 1], qm[:, :, t:t + 1])
+            lat = {}
+            for t0 in (0, T // 2, T - 1):
+                def one(t0=t0):
+                    st.frames_done = t0
+                    st.step(rgb[:, :, t0:t0 + 1], qm[:, :, t0:t0 + 1])
+                one()
+                lat[str(t0)] = ev_time(one, reps)
+            res[f'{tag}_step_ms'] = lat
+
+            def whole():
+                st.reset()
+                for t in range(T):
+                    st.step(rgb[:, :, t:t + 1], qm[:, :, t:t + 1])
+            res[f'{tag}_clip_sum_ms'] = ev_time(whole, max(3, reps // 5))
+        res['cache_bytes'] = st.cache_bytes
+        del st
+    del net
+    torch.cuda.empty_cache()
+    return res
+
+
+KPROF_WARMUP, KPROF_STEPS = 3, 20
+STEP_LAST_KERNEL = 'flags_fwd_kernel'      # the last launch of every step (the flags head, engine.run_forward)
+
+
+def cached_kernel_bytes(T, H, W, e=2, heads=12, D=768):
+    """Algorithmic bytes of one tcow_attn_temporal_cached_fwd launch of a one-frame step at t0 = T - 1 (B = 1, element size e)."""
+    S, t0 = (H // 16) * (W // 16) + 1, T - 1
+    alg = {'cache_read': (S - 1) * heads * t0 * 64 * 2 * e, 'chunk_qkv_read': S * 3 * D * e, 'out_write': S * D * e,
+           'cache_append': (S - 1) * heads * 64 * 2 * e}
+    alg['total'] = sum(alg.values())
+    return alg
+
+
+def kprof():
+    """One-frame bf16 steps at configs[3], t0 = 59, for a rocprofv3 kernel trace: KPROF_WARMUP steps that build the operand copies, then
+    KPROF_STEPS steady ones (--kstats keeps only those)."""
+    T, H, W = CONFIGS['configs3']
+    net = build(T, H, W, 'bf16')
+    rgb, qm = inputs(1, T, H, W)
+    with torch.no_grad():
+        st = net.stream(batch_size=1, graph=False)
+        for _ in range(KPROF_WARMUP + KPROF_STEPS):
+            st.frames_done = T - 1
+            st.step(rgb[:, :, T - 1:T], qm[:, :, T - 1:T])
+        torch.cuda.synchronize()
+
+
+def kstats(trace_csv, out):
+    """Per-step kernel breakdown of the KPROF_STEPS profiled steps from rocprofv3's kernel-trace CSV: dispatches in start order, everything up to
+    and including the KPROF_WARMUP-th STEP_LAST_KERNEL dropped, per-kernel totals divided by KPROF_STEPS."""
+    import csv
+    rows = list(csv.DictReader(open(trace_csv)))
+    rows.sort(key=lambda r: int(r['Start_Timestamp']))
+    ends = [i for i, r in enumerate(rows) if STEP_LAST_KERNEL in r['Kernel_Name']]
+    assert len(ends) == KPROF_WARMUP + KPROF_STEPS, f'{len(ends)} steps in the trace, expected {KPROF_WARMUP + KPROF_STEPS}'
+    rows = rows[ends[KPROF_WARMUP - 1] + 1:]
+    per = {}
+    for r in rows:
+        d = int(r['End_Timestamp']) - int(r['Start_Timestamp'])
+        n, tot, mn = per.get(r['Kernel_Name'], (0, 0, None))
+        per[r['Kernel_Name']] = (n + 1, tot + d, d if mn is None else min(mn, d))
+    T, H, W = CONFIGS['configs3']
+    alg = cached_kernel_bytes(T, H, W)
+    lines = [f'# {KPROF_STEPS} one-frame bf16 stream steps at BASELINE configs[3] (T=60, 480x640, B=1), t0 = 59, after {KPROF_WARMUP} warm-up steps',
+             '# (rocprofv3 --kernel-trace; tools/dev_stream_latency.py --kprof, then --kstats on the kernel-trace CSV: the warm-up dispatches are dropped)',
+             '#   us/step  launches/step   avg us   min us  kernel']
+    total = 0
+    for name, (n, tot, mn) in sorted(per.items(), key=lambda kv: -kv[1][1]):
+        total += tot
+        lines.append(f'{tot / KPROF_STEPS / 1e3:10.1f}  {n / KPROF_STEPS:13.1f} {tot / n / 1e3:8.1f} {mn / 1e3:8.1f}  {name[:110]}')
+    lines.append(f'total kernel time per step: {total / KPROF_STEPS / 1e3:.1f} us')
+    ck = [(n, tot) for name, (n, tot, _) in per.items() if 'temporal_cached_kernel' in name]
+    if ck:
+        avg = ck[0][1] / ck[0][0] / 1e9
+        lines.append('temporal_cached_kernel algorithmic bytes per launch: ' + ', '.join(f'{k} {v}' for k, v in alg.items()))
+        lines.append(f'-> {alg["total"] / avg / 1e12:.2f} TB/s at the {avg * 1e6:.1f} us average = {alg["total"] / avg / 8e12:.2f} of the 8 TB/s HBM peak')
+    txt = '\n'.join(lines) + '\n'
+    print(txt)
+    if out:
+        with open(out, 'w') as f:
+            f.write(txt)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--reps', type=int, default=20)
+    ap.add_argument('--kprof', action='store_true')
+    ap.add_argument('--kstats', default=None, metavar='KERNEL_TRACE_CSV')
+    ap.add_argument('--only', default=None, help='comma list of configs1_b1, configs1_b8, configs3_b1')
+    a = ap.parse_args()
+    if a.kstats:
+        kstats(a.kstats, a.out)
+        return
+    if not torch.cuda.is_available():
+        raise SystemExit('dev_stream_latency.py needs a GPU')
+    if a.kprof:
+        kprof()
+        return
+    runs = [('configs1', 1), ('configs1', 8), ('configs3', 1)]
+    if a.only:
+        keep = set(a.only.split(','))
+        runs = [r for r in runs if f'{r[0]}_b{r[1]}' in keep]
+    out = {'device': torch.cuda.get_device_name(0), 'runs': []}
+    for name, B in runs:
+        r = measure(name, B, 'bf16', a.reps)
+        print(json.dumps(r), flush=True)
+        out['runs'].append(r)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            json.dump(out, f, indent=1)
+
+
+if __name__ == '__main__':
+    main()

@@ -30,6 +30,8 @@ import torch
 
 from . import ops
 from .ops import ACT_GELU, ACT_GELU_DSAVE, ACT_MUL_AUX
+from .operands import fold_on
+
 
 def _layout(module):
     """(parameters per block, offset of each sub-module's weight inside a block's slice of QueryMaskTracker.param_list(); bias = +1)."""
@@ -42,50 +44,13 @@ def _joint_rows(module, g, dev):
     """Row indices [B * (1 + T*N)] of the joint-attention sequences inside the [B*T*S] token matrix: per clip its cls row (frame 0's
     slot 0) followed by every patch row.  The reference's sequence is (cls, patches in n-major order) (vision_tf.py:137); attention
     without a mask is invariant to the order of its keys / queries, so the frame-major order of our layout is used as is."""
-    key = ('jrows', g['B'], str(dev))
-    idx = module._wcache.get(key)
-    if idx is None:
+    def build():
         B, T, S = g['B'], g['T'], g['S']
         r = torch.arange(B * T * S, device=dev).reshape(B, T * S)
         keep = torch.ones(T * S, dtype=torch.bool, device=dev)
         keep[torch.arange(1, T, device=dev) * S] = False                      # cls replicas of frames 1..T-1 take no part
-        idx = r[:, keep].reshape(-1).contiguous()
-        module._wcache[key] = idx
-    return idx
-
-
-def _w2d(p):
-    return p.reshape(p.shape[0], -1)
-
-
-def _get_weight(module, p, train):
-    """Operand copies of a weight: (Wc [N,K] in the mode's dtype, Wt [K,N] or None), cached per parameter version."""
-    mode = module.mode
-    key = id(p)
-    ent = module._wcache.get(key)
-    ver = (p._version, getattr(module, '_wepoch', 0))
-    if ent is not None and ent[0] == ver and ent[1] == mode and (ent[3] is not None or not train):
-        return ent[2], ent[3]
-    w = _w2d(p.detach())
-    N, K = w.shape
-    dt = ops.tdtype(mode)
-    if ops.is16(mode):
-        Wc = torch.empty(N, K, dtype=dt, device=w.device)
-        Wt = torch.empty(K, N, dtype=dt, device=w.device) if train else None
-        ops.cast_transpose(mode, w.contiguous(), Wc, Wt)
-    else:
-        Wc = w.contiguous()
-        Wt = None
-        if train:
-            Wt = torch.empty(K, N, dtype=dt, device=w.device)
-            ops.cast_transpose(mode, Wc, None, Wt)
-    module._wcache[key] = (ver, mode, Wc, Wt)
-    if train:
-        # remember the buffers: after an optimizer step refresh_weights() re-casts ALL registered weights in one launch
-        reg = module.__dict__.setdefault('_wreg', {})
-        reg[key] = (p, Wc if ops.is16(mode) else None, Wt, N, K)
-        module.__dict__['_wreg_gen'] = module.__dict__.get('_wreg_gen', 0) + 1      # (FusedAdamWClip's tile table points into these buffers: it rebuilds when this moves)
-    return Wc, Wt
+        return r[:, keep].reshape(-1).contiguous()
+    return module._operands.constant(('jrows', g['B'], str(dev)), build)
 
 
 def group_sizes(depth, spec=None):
@@ -105,110 +70,15 @@ def group_sizes(depth, spec=None):
     return sizes
 
 
-def _fold_on(module):
-    return ops.is16(module.mode) and module.attention_type == 'divided_space_time'
-
-
-def _fold_products(ents):
-    """W' = Wfc Wproj and b' = Wfc b_proj for a list of fold entries: two batched launches (per 24 entries)."""
-    for c0 in range(0, len(ents), 24):
-        ops.sgemm_batched([(e['fc'].detach(), e['proj'].detach(), e['W32']) for e in ents[c0:c0 + 24]])
-        ops.sgemm_batched([(e['fc'].detach(), e['bproj'].detach().view(1, -1).t(), e['b32'].view(-1, 1)) for e in ents[c0:c0 + 24]])
-
-
-def _folded_weight(module, i, q, ix, train):
-    """Operands of block i's folded temporal projection: (Wc' [D,D], Wt' [D,D] or None, b' [D] f32), cached per parameter version."""
-    pfc, pproj, bproj = q[ix['tfc']], q[ix['tproj']], q[ix['tproj'] + 1]
-    key = ('fold', i)
-    ver = (pfc._version, pproj._version, bproj._version, getattr(module, '_wepoch', 0))
-    ent = module._wcache.get(key)
-    if ent is not None and ent['ver'] == ver and ent['mode'] == module.mode and (ent['Wt'] is not None or not train):
-        return ent['Wc'], ent['Wt'], ent['b32']
-    D = pfc.shape[0]
-    dev = pfc.device
-    dt = ops.tdtype(module.mode)
-    if ent is None or ent['mode'] != module.mode:
-        ent = dict(fc=pfc, proj=pproj, bproj=bproj, W32=torch.empty(D, D, dtype=torch.float32, device=dev), b32=torch.empty(D, dtype=torch.float32, device=dev),
-                   Wc=torch.empty(D, D, dtype=dt, device=dev), Wt=None, mode=module.mode)
-    if train and ent['Wt'] is None:
-        ent['Wt'] = torch.empty(D, D, dtype=dt, device=dev)
-    _fold_products([ent])
-    ops.cast_transpose(module.mode, ent['W32'], ent['Wc'], ent['Wt'])
-    ent['ver'] = ver
-    module._wcache[key] = ent
-    if train:
-        # registered like any GEMM weight: refresh_weights() recomputes W' (all blocks, one launch) and re-casts it with the others
-        module.__dict__.setdefault('_wreg', {})[key] = (ent['W32'], ent['Wc'], ent['Wt'], D, D)
-        module.__dict__.setdefault('_foldreg', {})[key] = ent
-    return ent['Wc'], ent['Wt'], ent['b32']
-
-
-def refresh_weights(module):
-    """Re-cast every registered GEMM weight (bf16 copy + transposed copy) with ONE kernel launch instead of one per weight;
-    called by QueryMaskTracker.invalidate_weight_cache() right after the optimizer has written the f32 master weights."""
-    import struct
-    reg = getattr(module, '_wreg', None)
-    if not reg:
-        return False
-    mode = module.mode
-    folds = module.__dict__.get('_foldreg')
-    if folds:
-        live = [ent for k, ent in folds.items() if k in reg]         # (a fold whose operand copies are no longer registered is stale: skip it)
-        if live:
-            _fold_products(live)
-    # weights whose copies the optimizer has just written itself (FusedAdamWClip's tile kernel, 16-bit modes): only their version stamps are refreshed below
-    done = module.__dict__.pop('_opt_cast_keys', None) or ()
-    all_ents = list(reg.items())
-    ents = [(k, v) for k, v in all_ents if k not in done]
-    if not ents:
-        _stamp_versions(module, all_ents, folds, mode)
-        return True
-    sig = tuple((k, p.data_ptr(), 0 if Wc is None else Wc.data_ptr(), 0 if Wt is None else Wt.data_ptr()) for k, (p, Wc, Wt, N, K) in ents) + (mode,)
-    tab = module.__dict__.get('_wtab')
-    if tab is None or tab[0] != sig:
-        rec, tiles = [], 0
-        edge = 64 if all(N % 64 == 0 and K % 64 == 0 for _, (_, _, _, N, K) in ents) else 32     # tile edge of tcow_cast_transpose_batched (all records alike)
-        for k, (p, Wc, Wt, N, K) in ents:
-            rec.append(struct.pack('<QQQiiii', p.data_ptr(), 0 if Wc is None else Wc.data_ptr(), 0 if Wt is None else Wt.data_ptr(), N, K, tiles, edge))
-            tiles += ((N + edge - 1) // edge) * ((K + edge - 1) // edge)
-        assert len(rec[0]) == L_cast_desc_bytes()
-        dev = ents[0][1][0].device
-        buf = torch.frombuffer(bytearray(b''.join(rec)), dtype=torch.uint8).to(dev)
-        tab = (sig, buf, len(rec), tiles)
-        module.__dict__['_wtab'] = tab
-    ops.cast_transpose_batched(mode, tab[1], tab[2], tab[3])
-    _stamp_versions(module, all_ents, folds, mode)
-    return True
-
-
-def _stamp_versions(module, ents, folds, mode):
-    """The operand copies of `ents` are current for the parameters' present versions (and this weight epoch)."""
-    epoch = getattr(module, '_wepoch', 0)
-    for k, (p, Wc, Wt, N, K) in ents:
-        if folds and k in folds:
-            e = folds[k]
-            e['ver'] = (e['fc']._version, e['proj']._version, e['bproj']._version, epoch)
-            continue
-        w = _w2d(p.detach())
-        module._wcache[k] = ((p._version, epoch), mode, Wc if Wc is not None else w.contiguous(), Wt)
-
-
-def L_cast_desc_bytes():
-    from . import _lib
-    return int(_lib.lib().tcow_cast_desc_bytes())
-
-
 def _row_vectors(module, g, train):
     """mask0 [M] (0 on slot 0) and the DropPath row scales of every block (None in eval)."""
     B, T, S, N = g['B'], g['T'], g['S'], g['N']
     dev = module.vit.pos_embed.device
-    key = ('mask0', B, T, str(dev))          # (T: a stream's chunk geometry has fewer frames than the clip)
-    mask0 = module._wcache.get(key)
-    if mask0 is None:
-        mask0 = torch.ones(B, T, S, dtype=torch.float32, device=dev)
-        mask0[:, :, 0] = 0
-        mask0 = mask0.reshape(-1).contiguous()
-        module._wcache[key] = mask0
+    def build_mask0():
+        m = torch.ones(B, T, S, dtype=torch.float32, device=dev)
+        m[:, :, 0] = 0
+        return m.reshape(-1).contiguous()
+    mask0 = module._operands.constant(('mask0', B, T, str(dev)), build_mask0)          # (T: a stream's chunk geometry has fewer frames than the clip)
     depth = module.network_depth
     rates = torch.linspace(0, module.drop_path_rate, depth).tolist() if depth > 1 else [0.0]   # vit.py:272
     scales = []
@@ -231,11 +101,7 @@ def _row_vectors(module, g, train):
     if forced is None and train and max(rates) > 0.:
         # all DropPath draws of the step in one batch (vit_utils.py:150-152 per call: keep = floor(rand + 1 - r), x / (1 - r) * keep):
         # one rand and three broadcasts instead of ~15 tiny launches per block
-        kkey = ('keep_p', tuple(rates), str(dev))
-        keep_p = module._wcache.get(kkey)
-        if keep_p is None:
-            keep_p = (1.0 - torch.tensor(rates, dtype=torch.float32)).to(dev)
-            module._wcache[kkey] = keep_p
+        keep_p = module._operands.constant(('keep_p', tuple(rates), str(dev)), lambda: (1.0 - torch.tensor(rates, dtype=torch.float32)).to(dev))
         u = torch.rand(depth, B * N + B * T + B, device=dev)
         if u.is_cuda and N == S - 1:
             from . import ops
@@ -325,7 +191,8 @@ def run_forward(module, rgb, qm, params, save, stream=None):
     def E(*shape, dtype=dt):
         return torch.empty(*shape, dtype=dtype, device=dev)
 
-    W = lambda p: _get_weight(module, p, train)[0]
+    opnd = module._operands
+    W = lambda p: opnd.weight(mode, p, train)[0]
     mask0, dps = _row_vectors(module, g, module.training)
     sv = {'g': g, 'blocks': [], 'mask0': mask0, 'dps': dps} if save else None
 
@@ -364,7 +231,7 @@ def run_forward(module, rgb, qm, params, save, stream=None):
 
     BP, ix = _layout(module)
     joint = module.attention_type != 'divided_space_time'
-    fold = _fold_on(module)
+    fold = fold_on(module)
     amode = gmode if gmode == ops.F32X3 else mode      # precision='bf16x3': the attention products on split-bf16 MFMAs too (csrc/attention_x3.hip)
     shape_attn = ops.attn_shape(amode, B, T, S, D, heads, ca)
     if joint:
@@ -408,7 +275,7 @@ def run_forward(module, rgb, qm, params, save, stream=None):
                 ops.attn_temporal_cached(amode, B, T, S, D, heads, ca, stream.T_total, stream.t0_dev, QKV, stream.k_cache[i], stream.v_cache[i], O)
             R1 = E(M, D, dtype=f32) if save else R0
             if fold:
-                Wf, _, bprime = _folded_weight(module, i, q, ix, train)
+                Wf, _, bprime = opnd.folded(mode, i, q, ix, train)
                 ops.gemm_nt(gmode, O, Wf, R1, bias=bprime, row_scale=dp['t0'], resid=R0, bias2=tfc_b, row_scale2=mask0)
                 Pj = None
             else:
@@ -514,9 +381,9 @@ def run_backward(module, sv, params, d_mask, d_flags):
     # out of the adjoint's own pass over d_mask (tcow_upsample_bwd_amax) instead of an abs + amax pair of passes.
     gscale = inv_gscale = None
     ls_mode = getattr(module, 'loss_scale', 'dynamic') if mode == ops.FP16 else None
-    if ls_mode == 'dynamic' and _live_optim(module) is None and not module.__dict__.get('_warned_ls'):
+    if ls_mode == 'dynamic' and module._live_optim() is None and not module._warned_ls:
         import warnings
-        module.__dict__['_warned_ls'] = True
+        module._warned_ls = True
         warnings.warn("precision='fp16' with the dynamic loss scale but no FusedAdamWClip(..., module=net) attached: nothing lowers the scale "
                       "after an overflow or skips the poisoned step -- pass module= to the optimizer or set net.seeker.loss_scale to a number")
 
@@ -538,7 +405,8 @@ def run_backward(module, sv, params, d_mask, d_flags):
     def E(*shape, dtype=dt):
         return torch.empty(*shape, dtype=dtype, device=dev)
 
-    Wt = lambda p: _get_weight(module, p, True)[1]
+    opnd = module._operands
+    Wt = lambda p: opnd.weight(mode, p, True)[1]
     grads = [None] * len(params)
 
     # Who undoes the loss scale.  With a data-parallel hook every finished bucket is multiplied back before the hook sees it (ranks choose their own
@@ -550,9 +418,9 @@ def run_backward(module, sv, params, d_mask, d_flags):
     # accumulation, DataParallel replicas) would make autograd add buckets that carry different scales -- so it is tied to `persistent_grads` (whose
     # contract is exactly that: each backward OVERWRITES the gradients), never taken by a DataParallel replica, and only while the attached optimizer is
     # still alive (a weak reference: a discarded or replaced FusedAdamWClip must not leave param.grad scaled for torch.optim.AdamW or clip_grad_norm_).
-    defer_unscale = ((module.grad_hook is None or getattr(module.grad_hook, 'active', True) is False) and _live_optim(module) is not None
+    defer_unscale = ((module.grad_hook is None or getattr(module.grad_hook, 'active', True) is False) and module._live_optim() is not None
                      and bool(getattr(module, 'persistent_grads', False)) and not getattr(module, '_is_replica', False)
-                     and module.__dict__.get('_defer_unscale', True))                 # (tests switch the deferral off to compare the two paths)
+                     and module._defer_unscale)                 # (tests switch the deferral off to compare the two paths)
 
     def publish(tag, flat):
         """A finished gradient bucket: undo the loss scale (unless the optimizer will), then hand it to the data-parallel hook."""
@@ -568,10 +436,7 @@ def run_backward(module, sv, params, d_mask, d_flags):
         total = sum(params[j].numel() for j in indices)
         flat = None
         if getattr(module, 'persistent_grads', False):      # stable gradient storage across steps (see QueryMaskTracker.persistent_grads)
-            key = ('gbuf', indices[0], total, str(dev))
-            flat = module._gbufs.get(key)
-            if flat is None:
-                flat = module._gbufs[key] = torch.empty(total, dtype=f32, device=dev)
+            flat = opnd.buffer(('gbuf', indices[0], total, str(dev)), lambda: torch.empty(total, dtype=f32, device=dev))
         if flat is None:
             flat = torch.empty(total, dtype=f32, device=dev)
         off = 0
@@ -607,7 +472,7 @@ def run_backward(module, sv, params, d_mask, d_flags):
 
     BP, ix = _layout(module)
     joint = module.attention_type != 'divided_space_time'
-    fold = _fold_on(module)
+    fold = fold_on(module)
     depth = module.network_depth
     nb = 5 + depth * BP
     Co = module.output_channels
@@ -640,10 +505,7 @@ def run_backward(module, sv, params, d_mask, d_flags):
     fold_jobs = []          # (block, dW' [D,D], db' [D])
 
     def fold_tmp(i):
-        t = module._gbufs.get(('foldtmp', i, str(dev)))
-        if t is None:
-            t = module._gbufs[('foldtmp', i, str(dev))] = (torch.empty(D, D, dtype=f32, device=dev), torch.empty(D, dtype=f32, device=dev))
-        return t
+        return opnd.buffer(('foldtmp', i, str(dev)), lambda: (torch.empty(D, D, dtype=f32, device=dev), torch.empty(D, dtype=f32, device=dev)))
 
     def finish_fold_group():
         """Z = P Wfc^T + b_fc with P = dp_t (O Wproj^T + b_proj) and dY' = dp_t dZ:  dWfc = dZ^T P = dW' Wproj^T + db' b_proj^T,
@@ -769,7 +631,7 @@ def run_backward(module, sv, params, d_mask, d_flags):
             # ---- temporal
             dO = E(M, D)
             if fold:
-                ops.gemm_nt(gmode, G1, _folded_weight(module, i, q, ix, True)[1], dO)
+                ops.gemm_nt(gmode, G1, opnd.folded(mode, i, q, ix, True)[1], dO)
                 tW, tb = fold_tmp(i)
                 pending.append((G1, st['O_t'], tW, tb))
                 fold_jobs.append((i, tW, tb))
@@ -829,19 +691,13 @@ def run_backward(module, sv, params, d_mask, d_flags):
         ops.gemm_tn(gmode, Gpe, sv['A_pe'], dWpe)
     grads[4].copy_(dtime_eff.sum(0))       # bias gradient = sum over all patch rows
     publish('g0', flat_cur)
-    module.__dict__['pending_inv_scale'] = inv_gscale if defer_unscale else None
+    module.pending_inv_scale = inv_gscale if defer_unscale else None
     if module.grad_hook is not None:
         # The collectives launched above were overlapped with the remaining backward compute; they must be complete (in
         # stream order) before autograd copies the bucket views into param.grad, so the hook is drained here.
         if hasattr(module.grad_hook, 'finish'):
             module.grad_hook.finish()
     return grads
-
-
-def _live_optim(module):
-    """The FusedAdamWClip attached to this module (FusedAdamWClip(..., module=net)), or None when there is none or it has been garbage-collected."""
-    ref = module.__dict__.get('_optim_ref')
-    return ref() if ref is not None else None
 
 
 class SeekerFunction(torch.autograd.Function):

@@ -52,16 +52,16 @@ class FusedAdamWClip(torch.optim.Optimizer):
         # fuse_cast (16-bit modes, module= given): GEMM weights are updated tile by tile and the update writes their 16-bit W / W^T operand copies itself
         # (tcow_adamw_clip_step_cast) -- the module's batched re-cast then only covers what is left (the folded products)
         self.fuse_cast = bool(fuse_cast)
-        self._tiles = None; self._flat_table = None; self._cast_keys = frozenset(); self._wreg_gen = None
+        self._tiles = None; self._flat_table = None; self._cast_keys = frozenset(); self._operand_gen = None
         if module is not None:     # a Seeker / QueryMaskTracker: batch re-cast of its GEMM operand copies right after the update
             tracker = getattr(module, 'seeker', module)
             self._tracker = tracker
             if hasattr(tracker, 'invalidate_weight_cache'):
                 self.on_step.append(tracker.invalidate_weight_cache)
-            # A WEAK reference to the attached optimizer (engine._live_optim).  While it is alive, precision='fp16' has somebody who lowers the loss scale
+            # A WEAK reference to the attached optimizer (QueryMaskTracker._live_optim).  While it is alive, precision='fp16' has somebody who lowers the loss scale
             # after an overflow (run_backward warns otherwise), and -- with persistent_grads, one backward per step -- gradient buckets may stay loss-scaled:
             # step() folds the inverse scale into the clip coefficient.  Once this optimizer is discarded the module unscales in the backward again.
-            tracker.__dict__['_optim_ref'] = weakref.ref(self)
+            tracker._optim_ref = weakref.ref(self)
         assert L.lib().tcow_adamw_chunk_bytes() == 40
 
     @property
@@ -89,25 +89,16 @@ class FusedAdamWClip(torch.optim.Optimizer):
             self._step_base += self._steps_pending
         self._steps_pending = 0
 
-    def _cast_registry(self):
-        """{id(parameter): (Wc, Wt, N, K)} of the GEMM weights whose 16-bit operand copies this optimizer may write (the module's registry of the current
-        training forward: engine._get_weight), or {}."""
-        trk = self._tracker
-        if not self.fuse_cast or trk is None or getattr(trk, 'precision', None) not in ('bf16', 'fp16') or getattr(trk, '_is_replica', False):
-            return {}
-        out = {}
-        for k, (p, Wc, Wt, N, K) in (trk.__dict__.get('_wreg') or {}).items():
-            if isinstance(k, int) and isinstance(p, torch.nn.Parameter) and Wc is not None and Wt is not None and N % 64 == 0 and K % 64 == 0 and p.numel() == N * K:
-                out[id(p)] = (Wc, Wt, N, K)
-        return out
-
     def _lib(self):
         """The build of the library whose 16-bit format the module's operand copies have."""
         trk = self._tracker
         return L.lib('fp16') if (trk is not None and getattr(trk, 'precision', None) == 'fp16' and self._tiles is not None) else L.lib()
 
     def _build(self, live):
-        reg = self._cast_registry()
+        # {id(parameter): (Wc, Wt, N, K)} of the GEMM weights whose 16-bit operand copies this optimizer may write (the module's registry of the current training forward), or {}
+        trk = self._tracker
+        own = self.fuse_cast and trk is not None and getattr(trk, 'precision', None) in ('bf16', 'fp16') and not getattr(trk, '_is_replica', False)
+        reg = trk._operands.castable() if own else {}
         fused = [p for p in live if id(p) in reg]
         rows, flat_rows = [], []        # every parameter (gradient norm, in the order of `live`: the partial sums are folded in that order) / the flat-updated ones
         for p in live:
@@ -132,8 +123,7 @@ class FusedAdamWClip(torch.optim.Optimizer):
         self.scratch = torch.zeros(len(rows) + 3, dtype=torch.float32, device=live[0].device)      # [chunk partials | coef, norm, skipped]
         self.scratch[-1] = self._skip_carry
         self._tiles = None; self._flat_table = None; self._cast_keys = frozenset()
-        trk = self._tracker
-        self._wreg_gen = trk.__dict__.get('_wreg_gen') if trk is not None else None
+        self._operand_gen = trk._operands.generation if trk is not None else None
         if fused:
             assert L.lib().tcow_adamw_tile_bytes() == 56
             recs = []
@@ -170,7 +160,7 @@ class FusedAdamWClip(torch.optim.Optimizer):
         if fast and self._live:
             fast = self._live[0].grad.data_ptr() == self._key[0][1] and self._live[-1].grad.data_ptr() == self._key[-1][1]
         if fast and self._tracker is not None and self.fuse_cast:
-            fast = self._tracker.__dict__.get('_wreg_gen') == self._wreg_gen       # the module's operand copies were re-allocated (or appeared): the tile table is stale
+            fast = self._tracker._operands.generation == self._operand_gen       # the module's operand copies were re-allocated (or appeared): the tile table is stale
         if fast:
             live = self._live
         else:
@@ -179,8 +169,8 @@ class FusedAdamWClip(torch.optim.Optimizer):
                 return loss
             self._flush_steps()
             key = tuple((id(p), p.grad.data_ptr(), self.state[p]['exp_avg'].data_ptr() if 'exp_avg' in self.state[p] else 0) for p in live)
-            gen = self._tracker.__dict__.get('_wreg_gen') if self._tracker is not None else None
-            if key != self._key or (self.fuse_cast and gen != self._wreg_gen):       # gradient / moment buffers moved (first step, re-allocated grads, load_state_dict) or the module's operand copies did: rebuild the pointer tables
+            gen = self._tracker._operands.generation if self._tracker is not None else None
+            if key != self._key or (self.fuse_cast and gen != self._operand_gen):       # gradient / moment buffers moved (first step, re-allocated grads, load_state_dict) or the module's operand copies did: rebuild the pointer tables
                 self._build(live)
                 self._key = tuple((id(p), p.grad.data_ptr(), self.state[p]['exp_avg'].data_ptr()) for p in live)
             self._live = live
@@ -191,7 +181,7 @@ class FusedAdamWClip(torch.optim.Optimizer):
             return loss
         step = self._step_base + self._steps_pending + 1
         trk = self._tracker
-        inv_scale = trk.__dict__.get('pending_inv_scale') if trk is not None else None      # binary16: the last backward left its gradients loss-scaled (it stays valid until the next backward rewrites them)
+        inv_scale = trk.pending_inv_scale if trk is not None else None      # binary16: the last backward left its gradients loss-scaled (it stays valid until the next backward rewrites them)
         if self._tiles is not None:
             lib = self._lib()
             L.check(lib.tcow_adamw_clip_step_cast(_ops_stream(), self._table.data_ptr(), self._table.shape[0], self._flat_table.data_ptr() if self._flat_table.shape[0] else None,
@@ -199,7 +189,7 @@ class FusedAdamWClip(torch.optim.Optimizer):
                                                   float(grp['lr']), float(grp['betas'][0]), float(grp['betas'][1]), float(grp['eps']), float(grp['weight_decay']), step,
                                                   float(self.max_norm or 0.0), self.scratch.data_ptr(), inv_scale.data_ptr() if inv_scale is not None else None),
                     'tcow_adamw_clip_step_cast', lib)
-            trk.__dict__['_opt_cast_keys'] = self._cast_keys          # (consumed by the module's refresh_weights in the on_step callback below)
+            trk._operands.optimizer_wrote(self._cast_keys)          # (consumed by the module's OperandCache.refresh in the on_step callback below)
         else:
             L.check(L.lib().tcow_adamw_clip_step_scaled(_ops_stream(), self._table.data_ptr(), self._table.shape[0], float(grp['lr']),
                                                         float(grp['betas'][0]), float(grp['betas'][1]), float(grp['eps']), float(grp['weight_decay']), step,
@@ -223,7 +213,7 @@ class FusedAdamWClip(torch.optim.Optimizer):
         gradient logging, another optimizer: multiplies every live gradient by the pending inverse scale (one pass over the gradients) and clears it.
         A no-op in every other mode."""
         trk = self._tracker
-        inv = trk.__dict__.get('pending_inv_scale') if trk is not None else None
+        inv = trk.pending_inv_scale if trk is not None else None
         if inv is None:
             return
         seen = set()
@@ -231,16 +221,15 @@ class FusedAdamWClip(torch.optim.Optimizer):
             if p.grad is not None and p.grad.data_ptr() not in seen:
                 seen.add(p.grad.data_ptr())
                 p.grad.mul_(inv)
-        trk.__dict__['pending_inv_scale'] = None
+        trk.pending_inv_scale = None
 
     def detach(self):
         """Detach from the module given as module= (its fp16 backwards unscale their gradients themselves again)."""
         trk = self._tracker
         if trk is not None:
             self.unscale_()
-            ref = trk.__dict__.get('_optim_ref')
-            if ref is not None and ref() is self:
-                trk.__dict__.pop('_optim_ref', None)
+            if trk._live_optim() is self:
+                trk._optim_ref = None
 
     def grad_norm(self):
         """Total gradient norm of the last step (device tensor, no sync)."""

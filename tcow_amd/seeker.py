@@ -27,6 +27,7 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import TcowError
+from .operands import OperandCache
 
 TIMESFORMER_MEAN = 0.45
 TIMESFORMER_STD = 0.225
@@ -143,6 +144,7 @@ class QueryMaskTracker(nn.Module):
         self.output_channels = output_channels
         self.flag_channels = flag_channels
         self.input_channels = 3 + query_channels
+        self._operands = OperandCache()   # every derived copy of the parameters and the persistent gradient buckets (tcow_amd/operands.py)
         self.set_precision(precision)
 
         from .checkpoint import parse_tracker_pretrained
@@ -182,8 +184,6 @@ class QueryMaskTracker(nn.Module):
         if self.tracker_pretrained:
             from .checkpoint import load_pretrained_vit
             load_pretrained_vit(self, self.pretrained_path, logger)
-        self._wcache = {}
-        self._gbufs = {}
         # dynamic loss scale of precision='fp16' (engine.run_backward): log2 of the target magnitude of the largest gradient seed element.  A
         # NON-persistent buffer: it follows .to() / DataParallel replication like any buffer, stays out of the 251-key state dict, and
         # save_tcow_checkpoint / resume_tcow_checkpoint carry it beside the optimizer state.
@@ -194,6 +194,11 @@ class QueryMaskTracker(nn.Module):
         self.persistent_grads = False
         self.forced_drop_masks = None     # tests can inject explicit DropPath keep masks
         self.grad_hook = None             # optional callable(bucket_name, tensors) fired during backward (DDP)
+        # ---- loss-scale / optimizer hand-off (engine.run_backward <-> optim.FusedAdamWClip)
+        self._optim_ref = None            # weakref to the attached FusedAdamWClip(module=net): set by its constructor, cleared by its detach(); dead once it is collected
+        self.pending_inv_scale = None     # device scalar 1 / loss scale while param.grad is loss-scaled: written by every backward, cleared by unscale_(); valid until the next backward
+        self._defer_unscale = True        # tests switch the deferral off to compare the two paths; never written by the product
+        self._warned_ls = False           # run_backward has warned once that nothing lowers the dynamic fp16 loss scale
 
     # ---- configuration helpers
     def set_precision(self, precision):
@@ -206,31 +211,22 @@ class QueryMaskTracker(nn.Module):
                 self.ls_log2.fill_(-2.0)
         self.loss_scale = 'dynamic'                                             # fp16 only: power-of-two factor on the backward's gradients (engine.run_backward); a number = static
         self.gemm_mode = ops.F32X3 if precision == 'bf16x3' else self.mode     # GEMM arithmetic; storage / every other kernel follow `mode`
-        self._wcache = {}
-        self.__dict__.pop('_wreg', None); self.__dict__.pop('_wtab', None); self.__dict__.pop('_foldreg', None)
-        self.__dict__['_wreg_gen'] = self.__dict__.get('_wreg_gen', 0) + 1
+        self._operands.drop(buckets=False)
         return self
 
     def invalidate_weight_cache(self):
         """Call after updating parameters through raw pointers (tcow_amd.optim.FusedAdamWClip does): in-place torch ops bump the
         parameters' autograd version counters, which the operand cache checks on its own."""
-        self._wepoch = getattr(self, '_wepoch', 0) + 1
-        if self.__dict__.get('_wreg'):
-            from . import engine
-            engine.refresh_weights(self)       # all operand copies of the next step in one launch
+        self._operands.invalidate(self.mode)
 
-    def _drop_operand_caches(self):
-        """Everything derived from the parameters' storage: 16-bit W / W^T copies, their registries and pointer tables, the folded
-        products and the persistent gradient buffers.  They are keyed by id(parameter), which survives a `.data` swap."""
-        self._wcache = {}
-        self.__dict__.pop('_wreg', None); self.__dict__.pop('_wtab', None); self.__dict__.pop('_foldreg', None)
-        self.__dict__['_wreg_gen'] = self.__dict__.get('_wreg_gen', 0) + 1
-        self._gbufs = {}
+    def _live_optim(self):
+        """The FusedAdamWClip attached to this module (FusedAdamWClip(..., module=net)), or None when there is none or it has been garbage-collected."""
+        return self._optim_ref() if self._optim_ref is not None else None
 
     def _apply(self, fn, *a, **kw):
         # .to() / .cuda() / .half() swap the parameters' .data (neither id() nor ._version changes): every cache that holds device
         # pointers or copies of the old storage must go, and so must the cached parameter list
-        self._drop_operand_caches()
+        self._operands.drop()
         self.invalidate_param_cache()
         return super()._apply(fn, *a, **kw)
 
@@ -299,9 +295,7 @@ class QueryMaskTracker(nn.Module):
         if getattr(self, '_is_replica', False):
             # torch.nn.DataParallel (train.py:222-223) re-creates shallow replicas every forward: their dicts alias the original's, so give
             # each replica private operand / gradient caches for this call instead of growing the shared ones with dead entries
-            self._wcache, self._gbufs = {}, {}
-            self.__dict__.pop('_wreg', None); self.__dict__.pop('_wtab', None); self.__dict__.pop('_foldreg', None)
-            self.__dict__['_wreg_gen'] = self.__dict__.get('_wreg_gen', 0) + 1
+            self._operands = self._operands.fresh()
         rgb = input_frames.to(torch.float32).contiguous()                 # mask_tracker.py:103-104 (inputs not mutated)
         qm = query_mask.to(torch.float32).contiguous()
         from .engine import SeekerFunction

@@ -44,8 +44,8 @@ def check_streamable(module):
 
 
 def _signature(module):
-    """Changes whenever a parameter (or the precision) changes: load_state_dict / optimizer steps bump _version, FusedAdamWClip bumps _wepoch."""
-    return (module.mode, module.gemm_mode, getattr(module, '_wepoch', 0)) + tuple((id(p), p._version, p.data_ptr()) for p in module.param_list())
+    """Changes whenever a parameter (or the precision) changes: load_state_dict / optimizer steps bump _version, FusedAdamWClip bumps the operand epoch."""
+    return (module.mode, module.gemm_mode, module._operands.epoch) + tuple((id(p), p._version, p.data_ptr()) for p in module.param_list())
 
 
 class SeekerStream:
@@ -136,10 +136,10 @@ class SeekerStream:
         return out_mask, (flags if m.flag_channels > 0 else None)
 
     def _operand_generation(self):
-        """Identifies the module's operand caches (16-bit weight copies, folded projection, row vectors in module._wcache).  .cuda() / .to()
+        """Identifies the module's operand caches (16-bit weight copies, folded projection, row vectors in module._operands).  .cuda() / .to()
         on the same device, set_precision() with the same precision and train-mode forwards replace them without changing a parameter."""
         m = self.module
-        return (id(m._wcache), m.__dict__.get('_wreg_gen', 0), m.mode)
+        return (m._operands.generation, m.mode)
 
     def _graph_step(self, c, rgb, qm):
         gen = self._operand_generation()
@@ -153,9 +153,9 @@ class SeekerStream:
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
                 g_mask, g_flags = self._run(s_rgb, s_qm)
-            # The graph holds raw pointers into tensors that only module._wcache owns (operand copies, folded W' / b', mask0): a shallow copy
+            # The graph holds raw pointers into tensors that only module._operands owns (operand copies, folded W' / b', mask0): a shallow copy
             # of the dictionary keeps them alive as long as the graph, whatever later replaces the dictionary or its entries.
-            keep = dict(self.module._wcache)
+            keep = self.module._operands.keep_alive()
             self._graphs[c] = dict(graph=graph, rgb=s_rgb, qm=s_qm, mask=g_mask, flags=g_flags, gen=self._operand_generation(), keep=keep)
             return out
         graph, s_rgb, s_qm, g_mask, g_flags = ent['graph'], ent['rgb'], ent['qm'], ent['mask'], ent['flags']

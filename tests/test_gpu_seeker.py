@@ -601,7 +601,7 @@ def test_optimizer_writes_the_operand_copies_itself(cuda, precision):
         if fuse:
             n_tiles = sum((p.shape[0] // 64) * (p.reshape(p.shape[0], -1).shape[1] // 64) for p in net.parameters() if id(p) in opt._cast_keys)
             assert opt._tiles.shape[0] == n_tiles and n_tiles > 0
-            reg = net.seeker.__dict__['_wreg']
+            reg = net.seeker._operands.registry
             for k, (p, Wc, Wt, N, K) in reg.items():
                 if isinstance(k, int):                                           # plain GEMM weights (fold entries: W' = Wfc Wproj, cast by the module)
                     w = p.detach().reshape(N, K).to(dt)
@@ -876,10 +876,11 @@ def test_moving_the_module_drops_every_operand_cache(cuda):
     net, opt = trainer(sd)
     step(net, opt); step(net, opt)
     sk = net.seeker
-    assert sk._wcache and sk.__dict__.get('_wreg') and sk._gbufs                 # the caches the move must drop exist
+    od = sk._operands
+    assert od.copies and od.registry and od.buckets                 # the caches the move must drop exist
     state = {k: v.detach().cpu().numpy().copy() for k, v in net.state_dict().items()}
     net.cpu()
-    assert not sk._wcache and not sk._gbufs and '_wreg' not in sk.__dict__ and '_wtab' not in sk.__dict__ and '_foldreg' not in sk.__dict__
+    assert sk._operands is od and not od.copies and not od.buckets and not od.registry and od.table is None and not od.folds
     assert sk.__dict__.get('_param_list_cache') is None
     net.cuda()
     fresh, fopt = trainer(state)

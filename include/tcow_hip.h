@@ -118,7 +118,7 @@ int tcow_gemm_tn(void* stream, int dtype, int M, int N, int K, const void* dY, l
 
 /* The same for several Linear layers at once (the weight gradients of one transformer block, train.py:98's backward through
  * vit.py:50-61,74-76,146): in bf16 mode, problems that share M run as ONE grid with a common, much smaller number of token slices
- * (see gemm_bf16.hip: gemm_tn_bf16_256_group_kernel; the more tiles a group has, the fewer slices fill the chip: five for one ViT-B block,
+ * (see gemm_tn_bf16.hip: gemm_tn_bf16_256_group_kernel; the more tiles a group has, the fewer slices fill the chip: five for one ViT-B block,
  * two for four blocks -- tcow_tn_group_slices); otherwise the call is a loop over tcow_gemm_tn.  Results are identical in
  * meaning to n calls of tcow_gemm_tn (f32 summation order over the token slices differs). */
 typedef struct {

@@ -29,10 +29,7 @@ constexpr int D_W = 32 * 1024;                      // W: 256 rows x 128 B (k = 
 constexpr int D_A = 20 * 1024;                      // A: 160 rows x 128 B, TWO buffers
 constexpr int D_LDS = D_W + 2 * D_A;                // 73 728 B; the epilogue needs 4 x 17 408 = 69 632 B of it
 
-// AB: ablation switches of tools/ubench_c2.hip (0 in the library): 1 = every workgroup loads tile (0, 0), 2 = no loads after the prologue,
-// 4 = no workgroup barriers in the loop, 8 = no epilogue (accumulators kept alive), 16 = no fragment reads in the loop, 32 = no MFMAs,
-// 64 = no W loads, 128 = no A loads.
-template <typename E, int AB = 0>
+template <typename E>
 __global__ __launch_bounds__(256, 2) void gemm_nt_bf16_c2_kernel(NtParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -43,7 +40,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_bf16_c2_kernel(NtParams p) {
     int pm, pn;
     nt_tile_of(pid, p.tiles_m, p.tiles_n, p.band, pm, pn);
     const int m0 = pm * D_BM, n0 = pn * D_BN;
-    f32x16 acc[5][2];                                 // (unused: the epilogue's 32x32x16 form)
     f32x4 acc16[10][4];
 #pragma unroll
     for (int i = 0; i < 10; ++i)
@@ -61,28 +57,19 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_bf16_c2_kernel(NtParams p) {
     // 16-lane service group.
     // W subtiles 8 w .. 8 w + 7 (= the 64 W rows of wave w's own columns) are loaded AND read by wave w only: W needs no workgroup barrier
     // and -- its fragments live in registers for a whole K tile -- only ONE buffer.  A subtile s is loaded by wave s & 3 and read by all.
-    typedef int i32x4_ __attribute__((ext_vector_type(4)));
-    auto make_srd = [](const void* base, long bytes) {
-        const uint64_t b = (uint64_t)(uintptr_t)base;
-        i32x4_ r; r[0] = (int)(uint32_t)b; r[1] = (int)(uint32_t)((b >> 32) & 0xffffu); r[2] = (int)(uint32_t)bytes; r[3] = 0x00020000;
-        return r;
-    };
     const i32x4_ srd_a = make_srd(p.A, ((long)(p.M - 1) * p.lda + p.K) * 2);
     const i32x4_ srd_w = make_srd(p.W, ((long)(p.N - 1) * p.ldw + p.K) * 2);
     const int lr = lane >> 3, lc = ((lane & 7) ^ (lr & 6)) * 8;
     const uint32_t a_vo = (uint32_t)(lr * p.lda + lc) * 2u;               // per-lane byte offsets inside a subtile
     const uint32_t w_vo = (uint32_t)(lr * p.ldw + lc) * 2u;
-    const uint32_t a_t0 = (AB & 1) ? 0u : (uint32_t)((long)m0 * p.lda * 2), w_t0 = (AB & 1) ? 0u : (uint32_t)((long)n0 * p.ldw * 2);
+    const uint32_t a_t0 = (uint32_t)((long)m0 * p.lda * 2), w_t0 = (uint32_t)((long)n0 * p.ldw * 2);
     const uint32_t sA0 = a_t0 + (uint32_t)(wave * 8 * p.lda * 2), sAs = (uint32_t)(32 * p.lda * 2);          // A subtiles wave + 4 q: 32 rows apart
     const uint32_t sW0 = w_t0 + (uint32_t)(wave * 64 * p.ldw * 2), sWs = (uint32_t)(8 * p.ldw * 2);          // W subtiles 8 wave + q: 8 rows apart
     const uint32_t lds0 = (uint32_t)(uintptr_t)(LDS_PTR(char))smem;
     const uint32_t dW0 = lds0 + wave * 8192, dA0 = lds0 + D_W + wave * 1024;
-    // One load = one statement: M0 (LDS destination, wave-uniform) is written in the statement that reads it.  hipcc does not count these loads
-    // (inline asm): every wait for them below is an explicit vmcnt.
-#define C2_GLDS(voff, srd, soff, ldsdst) \
-    asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" :: "v"(voff), "s"(srd), "s"(soff), "s"(ldsdst) : "memory")
-#define C2_LDWV(q, kb, vo) do { if (!(AB & 64)) C2_GLDS(vo, srd_w, sW0 + (q) * sWs + (kb), dW0 + (q) * 1024); } while (0)
-#define C2_LDAV(q, kb, bo, vo) do { if (!(AB & 128)) C2_GLDS(vo, srd_a, sA0 + (q) * sAs + (kb), dA0 + (bo) + (q) * 4096); } while (0)
+    // (TCOW_BUFFER_GLDS16, gemm_glds.h: hipcc does not count these loads -- every wait for them below is an explicit vmcnt)
+#define C2_LDWV(q, kb, vo) TCOW_BUFFER_GLDS16(vo, srd_w, sW0 + (q) * sWs + (kb), dW0 + (q) * 1024)
+#define C2_LDAV(q, kb, bo, vo) TCOW_BUFFER_GLDS16(vo, srd_a, sA0 + (q) * sAs + (kb), dA0 + (bo) + (q) * 4096)
 #define C2_LDW(q, kb) C2_LDWV(q, kb, w_vo)
 #define C2_LDA(q, kb, bo) C2_LDAV(q, kb, bo, a_vo)
 
@@ -94,10 +81,9 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_bf16_c2_kernel(NtParams p) {
     const uint32_t w_ad0 = lds0 + wave * 8192 + fo0, w_ad1 = lds0 + wave * 8192 + fo1;                       // W block jj of this wave: + jj * 2048
     const uint32_t a_adb0 = lds0 + D_W + fo0, a_adb1 = lds0 + D_W + fo1;                                     // A block i: + buffer + i * 2048
     u32x4_ fa[2][5], fw[2][4];
-#define C2_DSR0(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(off))
-#define C2_DSR(dst, addr, off) do { if (!(AB & 16)) C2_DSR0(dst, addr, off); } while (0)
+#define C2_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(off))
 #define C2_PIN __builtin_amdgcn_sched_barrier(0)
-#define C2_MF(RI, i, jj, FA, FW) if (!(AB & 32)) acc16[(RI) * 5 + (i)][jj] = TCOW_MFMA_16x16x32_H16(__builtin_bit_cast(bf16x8, FW[jj]), __builtin_bit_cast(bf16x8, FA[i]), acc16[(RI) * 5 + (i)][jj], 0, 0, 0)
+#define C2_MF(RI, i, jj, FA, FW) acc16[(RI) * 5 + (i)][jj] = TCOW_MFMA_16x16x32_H16(__builtin_bit_cast(bf16x8, FW[jj]), __builtin_bit_cast(bf16x8, FA[i]), acc16[(RI) * 5 + (i)][jj], 0, 0, 0)
     // 20 MFMAs of one (row half RI, k half) block; F0 .. F12 are placed one per gap after the first thirteen MFMAs (empty arguments allowed)
 #define C2_BLOCK(RI, FA, FW, F0, F1, F2, F3, F4, F5, F6, F7, F8, F9, F10, F11, F12)                                                       \
     do {                                                                                                                                  \
@@ -120,12 +106,8 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_bf16_c2_kernel(NtParams p) {
     for (int q = 0; q < 5; ++q) C2_LDA(q, 128u, (uint32_t)D_A);      // A of tile 1 (nk >= 2): stays in flight
     asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    C2_DSR0(fw[0][0], w_ad0, 0); C2_DSR0(fw[0][1], w_ad0, 2048); C2_DSR0(fw[0][2], w_ad0, 4096); C2_DSR0(fw[0][3], w_ad0, 6144);
-    C2_DSR0(fa[0][0], a_adb0, 0); C2_DSR0(fa[0][1], a_adb0, 2048); C2_DSR0(fa[0][2], a_adb0, 4096); C2_DSR0(fa[0][3], a_adb0, 6144); C2_DSR0(fa[0][4], a_adb0, 8192);
-    if (AB & 16) {
-        C2_DSR0(fw[1][0], w_ad1, 0); C2_DSR0(fw[1][1], w_ad1, 2048); C2_DSR0(fw[1][2], w_ad1, 4096); C2_DSR0(fw[1][3], w_ad1, 6144);
-        C2_DSR0(fa[1][0], a_adb0, 10240); C2_DSR0(fa[1][1], a_adb0, 12288); C2_DSR0(fa[1][2], a_adb0, 14336); C2_DSR0(fa[1][3], a_adb0, 16384); C2_DSR0(fa[1][4], a_adb0, 18432);
-    }
+    C2_DSR(fw[0][0], w_ad0, 0); C2_DSR(fw[0][1], w_ad0, 2048); C2_DSR(fw[0][2], w_ad0, 4096); C2_DSR(fw[0][3], w_ad0, 6144);
+    C2_DSR(fa[0][0], a_adb0, 0); C2_DSR(fa[0][1], a_adb0, 2048); C2_DSR(fa[0][2], a_adb0, 4096); C2_DSR(fa[0][3], a_adb0, 6144); C2_DSR(fa[0][4], a_adb0, 8192);
 
     // One K tile kt (A in buffer kt & 1 at byte offset bo_; on entry fw[0] = W k-half 0, fa[0] = A rows 0-79 k-half 0, both requested during the
     // previous tile's last block).  Four blocks of 20 MFMAs -- (rows 0-79, k0), (rows 80-159, k0), (rows 0-79, k1), (rows 80-159, k1) -- each with
@@ -139,41 +121,40 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_bf16_c2_kernel(NtParams p) {
     //   block 3: tile kt+1's W k-half-0 fragments -> fw[0] and A rows 0-79 k0 -> fa[0]; the wave's five A loads of tile kt+2 into the A buffer
     //            this tile has just left.
     // LOAD / LOAD2: tile kt+1 / kt+2 exists; PAR = kt & 1 (a literal constant at each expansion).
-#define C2_TILE(kt, LOAD, LOAD2, PAR)                                                                                                           \
+#define C2_TILE(kt, LOAD, LOAD2, PAR)                                                                                                     \
     do {                                                                                                                                  \
         const uint32_t bo_ = (PAR) * D_A;                                                                                                 \
         const uint32_t kb_ = (uint32_t)((kt) + 1) * 128u, kb2_ = (uint32_t)((kt) + 2) * 128u;                                             \
         /* no next tile: the per-lane offset is sent past the descriptor = zeros, no traffic */                                           \
         const uint32_t wv_ = (LOAD) ? w_vo : 0x80000000u, av_ = (LOAD2) ? a_vo : 0x80000000u;                                             \
-        const bool ld_ = !(AB & 2);                                                                                                       \
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); C2_PIN;                                                                        \
         C2_BLOCK(0, fa[0], fw[0],                                                                                                         \
-                 C2_DSR(fw[1][0], w_ad1, 0), C2_DSR(fw[1][1], w_ad1, 2048), C2_DSR(fw[1][2], w_ad1, 4096), C2_DSR(fw[1][3], w_ad1, 6144),   \
-                 C2_DSR(fa[1][0], a_adb0, (PAR) * D_A + 10240), C2_DSR(fa[1][1], a_adb0, (PAR) * D_A + 12288),                              \
-                 C2_DSR(fa[1][2], a_adb0, (PAR) * D_A + 14336), C2_DSR(fa[1][3], a_adb0, (PAR) * D_A + 16384),                              \
-                 C2_DSR(fa[1][4], a_adb0, (PAR) * D_A + 18432); asm volatile("s_waitcnt lgkmcnt(5)" ::: "memory"),                         \
-                 if (ld_) { C2_LDWV(0, kb_, wv_); C2_LDWV(1, kb_, wv_); }, if (ld_) { C2_LDWV(2, kb_, wv_); C2_LDWV(3, kb_, wv_); },                                \
-                 if (ld_) { C2_LDWV(4, kb_, wv_); C2_LDWV(5, kb_, wv_); }, if (ld_) { C2_LDWV(6, kb_, wv_); C2_LDWV(7, kb_, wv_); });                               \
+                 C2_DSR(fw[1][0], w_ad1, 0), C2_DSR(fw[1][1], w_ad1, 2048), C2_DSR(fw[1][2], w_ad1, 4096), C2_DSR(fw[1][3], w_ad1, 6144), \
+                 C2_DSR(fa[1][0], a_adb0, (PAR) * D_A + 10240), C2_DSR(fa[1][1], a_adb0, (PAR) * D_A + 12288),                            \
+                 C2_DSR(fa[1][2], a_adb0, (PAR) * D_A + 14336), C2_DSR(fa[1][3], a_adb0, (PAR) * D_A + 16384),                            \
+                 C2_DSR(fa[1][4], a_adb0, (PAR) * D_A + 18432); asm volatile("s_waitcnt lgkmcnt(5)" ::: "memory"),                        \
+                 C2_LDWV(0, kb_, wv_); C2_LDWV(1, kb_, wv_), C2_LDWV(2, kb_, wv_); C2_LDWV(3, kb_, wv_),                                  \
+                 C2_LDWV(4, kb_, wv_); C2_LDWV(5, kb_, wv_), C2_LDWV(6, kb_, wv_); C2_LDWV(7, kb_, wv_));                                 \
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); C2_PIN;                                                                        \
         C2_BLOCK(1, fa[1], fw[0],                                                                                                         \
                  C2_DSR(fa[0][0], a_adb1, (PAR) * D_A), C2_DSR(fa[0][1], a_adb1, (PAR) * D_A + 2048), C2_DSR(fa[0][2], a_adb1, (PAR) * D_A + 4096), \
-                 C2_DSR(fa[0][3], a_adb1, (PAR) * D_A + 6144), C2_DSR(fa[0][4], a_adb1, (PAR) * D_A + 8192),                                \
-                 C2_NONE, C2_NONE, C2_NONE, C2_NONE, C2_NONE, C2_NONE, C2_NONE, C2_NONE);                                                  \
+                 C2_DSR(fa[0][3], a_adb1, (PAR) * D_A + 6144), C2_DSR(fa[0][4], a_adb1, (PAR) * D_A + 8192),                              \
+                 C2_NONE, C2_NONE, C2_NONE, C2_NONE, C2_NONE, C2_NONE, C2_NONE, C2_NONE);                                                 \
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); C2_PIN;                                                                        \
         C2_BLOCK(0, fa[0], fw[1],                                                                                                         \
-                 C2_DSR(fa[1][0], a_adb1, (PAR) * D_A + 10240), C2_DSR(fa[1][1], a_adb1, (PAR) * D_A + 12288),                              \
-                 C2_DSR(fa[1][2], a_adb1, (PAR) * D_A + 14336), C2_DSR(fa[1][3], a_adb1, (PAR) * D_A + 16384),                              \
-                 C2_DSR(fa[1][4], a_adb1, (PAR) * D_A + 18432), C2_NONE, C2_NONE, C2_NONE, C2_NONE, C2_NONE, C2_NONE, C2_NONE, C2_NONE);    \
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                                                      \
-        if (!(AB & 4)) __builtin_amdgcn_s_barrier();                                                                                      \
+                 C2_DSR(fa[1][0], a_adb1, (PAR) * D_A + 10240), C2_DSR(fa[1][1], a_adb1, (PAR) * D_A + 12288),                            \
+                 C2_DSR(fa[1][2], a_adb1, (PAR) * D_A + 14336), C2_DSR(fa[1][3], a_adb1, (PAR) * D_A + 16384),                            \
+                 C2_DSR(fa[1][4], a_adb1, (PAR) * D_A + 18432), C2_NONE, C2_NONE, C2_NONE, C2_NONE, C2_NONE, C2_NONE, C2_NONE, C2_NONE);  \
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                                                       \
+        __builtin_amdgcn_s_barrier();                                                                                                     \
         C2_PIN;                                                                                                                           \
         C2_BLOCK(1, fa[1], fw[1],                                                                                                         \
-                 C2_DSR(fw[0][0], w_ad0, 0), C2_DSR(fw[0][1], w_ad0, 2048), C2_DSR(fw[0][2], w_ad0, 4096),   \
-                 C2_DSR(fw[0][3], w_ad0, 6144), C2_DSR(fa[0][0], a_adb0, (1 - (PAR)) * D_A),                           \
-                 C2_DSR(fa[0][1], a_adb0, (1 - (PAR)) * D_A + 2048), C2_DSR(fa[0][2], a_adb0, (1 - (PAR)) * D_A + 4096), \
-                 C2_DSR(fa[0][3], a_adb0, (1 - (PAR)) * D_A + 6144), C2_DSR(fa[0][4], a_adb0, (1 - (PAR)) * D_A + 8192), \
-                 if (ld_) { C2_LDAV(0, kb2_, bo_, av_); C2_LDAV(1, kb2_, bo_, av_); }, if (ld_) { C2_LDAV(2, kb2_, bo_, av_); C2_LDAV(3, kb2_, bo_, av_); },        \
-                 if (ld_) C2_LDAV(4, kb2_, bo_, av_), C2_NONE);                                                                                 \
+                 C2_DSR(fw[0][0], w_ad0, 0), C2_DSR(fw[0][1], w_ad0, 2048), C2_DSR(fw[0][2], w_ad0, 4096),                                \
+                 C2_DSR(fw[0][3], w_ad0, 6144), C2_DSR(fa[0][0], a_adb0, (1 - (PAR)) * D_A),                                              \
+                 C2_DSR(fa[0][1], a_adb0, (1 - (PAR)) * D_A + 2048), C2_DSR(fa[0][2], a_adb0, (1 - (PAR)) * D_A + 4096),                  \
+                 C2_DSR(fa[0][3], a_adb0, (1 - (PAR)) * D_A + 6144), C2_DSR(fa[0][4], a_adb0, (1 - (PAR)) * D_A + 8192),                  \
+                 C2_LDAV(0, kb2_, bo_, av_); C2_LDAV(1, kb2_, bo_, av_), C2_LDAV(2, kb2_, bo_, av_); C2_LDAV(3, kb2_, bo_, av_),          \
+                 C2_LDAV(4, kb2_, bo_, av_), C2_NONE);                                                                                    \
     } while (0)
 
     // (two tiles per iteration: the A buffer of a tile is a literal, so every fragment address is ONE per-lane register + an immediate)
@@ -190,12 +171,10 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_bf16_c2_kernel(NtParams p) {
 #undef C2_MF
 #undef C2_PIN
 #undef C2_DSR
-#undef C2_DSR0
 #undef C2_LDA
 #undef C2_LDAV
 #undef C2_LDWV
 #undef C2_LDW
-#undef C2_GLDS
     // The last tile's block 3 has requested the fragments of a tile that does not exist (stale bytes nobody uses) into fa[0] / fw[0].  hipcc knows
     // nothing of reads issued by asm statements: to it those registers are dead behind the loop, free for the epilogue's values -- and register-only
     // instructions may be scheduled ABOVE a wait that clobbers nothing but memory, where the late data then lands on top of them (round 5: whole wave
@@ -207,14 +186,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_bf16_c2_kernel(NtParams p) {
     __builtin_amdgcn_sched_barrier(0);
     // every wave has finished its fragment reads before any wave's staging writes land in the buffers
     __builtin_amdgcn_s_barrier();
-    if (AB & 8) {
-#pragma unroll
-        for (int i = 0; i < 10; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) asm volatile("" :: "v"(acc16[i][j]));
-        return;
-    }
-    wave_tile_epilogue_160x64<E, 1>(p, smem + wave * (64 * 68 * 4), acc, acc16, lane, m0, n0 + wave * 64);
+    wave_tile_epilogue_160x64<E>(p, smem + wave * (64 * 68 * 4), acc16, lane, m0, n0 + wave * 64);
 }
 
 }  // namespace
@@ -228,18 +200,8 @@ int tcow_gemm_nt_bf16_c2(hipStream_t stream, const tcow_gemm_args* a) {
     p.tiles_m = cdiv(a->M, D_BM); p.tiles_n = cdiv(a->N, D_BN);
     p.band = nt_band_for(a, p.tiles_n, 160);
     typedef void (*Kern)(NtParams);
-    const int rows = (a->row_scale ? 1 : 0) | (a->resid ? 2 : 0) | (a->bias2 ? 4 : 0);
-    const bool vec8 = a->N % 8 == 0 && a->ldc % 8 == 0 && a->ldr % 8 == 0 && a->ldaux % 8 == 0;   // the row-operand epilogues move 8 columns per lane
-    Kern k = gemm_nt_bf16_c2_kernel<EpiAny>;
-    if (!vec8) { /* run-time configured epilogue */ }
-    else if (a->act == TCOW_ACT_NONE && rows == 0) k = gemm_nt_bf16_c2_kernel<EpiCfg<TCOW_ACT_NONE, 0>>;
-    else if (a->act == TCOW_ACT_NONE && rows == 1) k = gemm_nt_bf16_c2_kernel<EpiCfg<TCOW_ACT_NONE, 1>>;
-    else if (a->act == TCOW_ACT_NONE && rows == 2) k = gemm_nt_bf16_c2_kernel<EpiCfg<TCOW_ACT_NONE, 2>>;
-    else if (a->act == TCOW_ACT_NONE && rows == 3) k = gemm_nt_bf16_c2_kernel<EpiCfg<TCOW_ACT_NONE, 3>>;
-    else if (a->act == TCOW_ACT_NONE && rows == 7) k = gemm_nt_bf16_c2_kernel<EpiCfg<TCOW_ACT_NONE, 7>>;
-    else if (a->act == TCOW_ACT_GELU_DSAVE && rows == 0) k = gemm_nt_bf16_c2_kernel<EpiCfg<TCOW_ACT_GELU_DSAVE, 0>>;
-    else if (a->act == TCOW_ACT_MUL_AUX && rows == 0) k = gemm_nt_bf16_c2_kernel<EpiCfg<TCOW_ACT_MUL_AUX, 0>>;
-    else if (a->act == TCOW_ACT_GELU && rows == 0) k = gemm_nt_bf16_c2_kernel<EpiCfg<TCOW_ACT_GELU, 0>>;
+    Kern k = nullptr;
+    nt_pick_epilogue(a, [&](auto e) { k = gemm_nt_bf16_c2_kernel<decltype(e)>; });
     tcow_ensure_lds(reinterpret_cast<const void*>(k), D_LDS);
     hipLaunchKernelGGL(k, dim3(p.tiles_m * p.tiles_n), dim3(256), D_LDS, stream, p);
     TCOW_CHECK_LAUNCH();

@@ -1,9 +1,10 @@
 // Shared pieces of the bf16 NT GEMM kernels (gemm_bf16.hip: 128 / 256 / 320-row tiles, one workgroup per CU for the big ones; gemm_nt_c2.hip: the
-// 160 x 256 tile that runs two workgroups per CU): launch parameters, the XCD-aware tile order, the direct-to-LDS load, the fused epilogue
-// arithmetic (bias / DropPath row scale / GELU / GELU' / residual / second masked bias; vit.py:50-61,74-76,111,146) and the epilogue of one
-// wave's 160 x 64 accumulator tile.
+// 160 x 256 tile that runs two workgroups per CU): launch parameters, the tile order, the fused epilogue arithmetic (bias / DropPath row scale /
+// GELU / GELU' / residual / second masked bias; vit.py:50-61,74-76,111,146), the table of compile-time epilogues and the epilogue of one wave's
+// 160 x 64 accumulator tile.  (The weight-gradient TN kernels are in gemm_tn_bf16.hip; gemm_glds.h holds the loads both families use.)
 #pragma once
 #include "common.h"
+#include "gemm_glds.h"
 
 #ifdef TCOW_FP16
 #define TCOW_MFMA_16x16x32_H16 __builtin_amdgcn_mfma_f32_16x16x32_f16
@@ -40,13 +41,6 @@ static inline NtParams nt_params_from_args(const tcow_gemm_args* a) {
     return p;
 }
 
-__device__ __forceinline__ int xcd_remap(int bid, int nblk) {
-    // Blocks are dispatched round-robin over the 8 XCDs; give each XCD a contiguous chunk of tile ids.
-    const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, k = bid >> 3;
-    const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + k;
-}
-
 // Tile of a (remapped) workgroup id.  band = 0: row-major -- an XCD's contiguous range of ids is a band of row tiles with ALL column tiles: its A rows
 // are fetched once, all of W passes through its L2 for every few row tiles (fine while W fits beside the A stream: N <= 2304 at K = 768).  band = b > 0:
 // the column tiles are walked in bands of b (tiles_n % b == 0): ids run over (band, row tile, column inside the band), so an XCD's range is a row
@@ -55,10 +49,6 @@ __device__ __forceinline__ void nt_tile_of(int pid, int tiles_m, int tiles_n, in
     if (band <= 0) { pm = pid / tiles_n; pn = pid - pm * tiles_n; return; }
     const int per = tiles_m * band, j = pid / per, rem = pid - j * per;
     pm = rem / band; pn = j * band + (rem - pm * band);
-}
-
-__device__ __forceinline__ void glds16(const void* gsrc, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((GLB_PTR(const uint32_t))gsrc, (LDS_PTR(uint32_t))lds_wave_base, 16, 0, 0);
 }
 
 // Epilogue: accumulators -> LDS (f32) -> coalesced row-wise stores.  The row loop is deliberately NOT unrolled and the erf-based
@@ -130,6 +120,24 @@ template <int ACT, int ROWS> struct EpiCfg {
 };
 typedef EpiCfg<-1, -1> EpiAny;
 
+// THE table of epilogue specialisations, for every kernel family with the 160 x 64 wave tile: calls f(E{}) with the EpiCfg of the combinations the
+// path uses and with EpiAny (the run-time-configured kernel) for anything else -- k = nullptr; nt_pick_epilogue(a, [&](auto e) { k = kernel<decltype(e)>; });
+template <typename F>
+static inline void nt_pick_epilogue(const tcow_gemm_args* a, F&& f) {
+    const int rows = (a->row_scale ? 1 : 0) | (a->resid ? 2 : 0) | (a->bias2 ? 4 : 0);
+    const bool vec8 = a->N % 8 == 0 && a->ldc % 8 == 0 && a->ldr % 8 == 0 && a->ldaux % 8 == 0;   // the specialised epilogues move 8 columns per lane
+    if (!vec8) f(EpiAny{});
+    else if (a->act == TCOW_ACT_NONE && rows == 0) f(EpiCfg<TCOW_ACT_NONE, 0>{});
+    else if (a->act == TCOW_ACT_NONE && rows == 1) f(EpiCfg<TCOW_ACT_NONE, 1>{});
+    else if (a->act == TCOW_ACT_NONE && rows == 2) f(EpiCfg<TCOW_ACT_NONE, 2>{});
+    else if (a->act == TCOW_ACT_NONE && rows == 3) f(EpiCfg<TCOW_ACT_NONE, 3>{});
+    else if (a->act == TCOW_ACT_NONE && rows == 7) f(EpiCfg<TCOW_ACT_NONE, 7>{});
+    else if (a->act == TCOW_ACT_GELU_DSAVE && rows == 0) f(EpiCfg<TCOW_ACT_GELU_DSAVE, 0>{});
+    else if (a->act == TCOW_ACT_MUL_AUX && rows == 0) f(EpiCfg<TCOW_ACT_MUL_AUX, 0>{});
+    else if (a->act == TCOW_ACT_GELU && rows == 0) f(EpiCfg<TCOW_ACT_GELU, 0>{});
+    else f(EpiAny{});
+}
+
 template <typename E = EpiAny>
 __device__ __forceinline__ EpiRow epi_row_fetch(const NtParams& p, int gm, int gn, bool ok) {
     EpiRow o; o.ext = make_float4(0.f, 0.f, 0.f, 0.f); o.rs = 1.0f; o.rs2 = 1.0f;
@@ -192,28 +200,42 @@ __device__ __forceinline__ void epi_rows(const NtParams& p, const float* ct, int
     }
 }
 
+// The store tail of the 8-columns-per-lane epilogues.  pack8: eight f32 -> eight 16-bit elements, stored with st16c<NT> (NT = non-temporal: the
+// GELU' aux tile, see the cache policy note).  Callers pack FIRST and form the address in the store statement: with the address computed in
+// front of the conversions hipcc hoists it out of the f32 / 16-bit branch and schedules the row loops differently.
+__device__ __forceinline__ uint4 pack8(float4 v0, float4 v1) {
+    uint4 w; w.x = pack_bf2(v0.x, v0.y); w.y = pack_bf2(v0.z, v0.w); w.z = pack_bf2(v1.x, v1.y); w.w = pack_bf2(v1.z, v1.w);
+    return w;
+}
+// 8 consecutive columns (gm, gn8 ..) of the output C: one 16-byte store of 16-bit elements or two of f32
+__device__ __forceinline__ void store8(const NtParams& p, int gm, int gn8, float4 v0, float4 v1) {
+    if (p.out_f32) {
+        float* d = reinterpret_cast<float*>(p.C) + (size_t)gm * p.ldc + gn8;
+        st4(d, v0); st4(d + 4, v1);
+    } else {
+        const uint4 w = pack8(v0, v1);
+        st16c<false>(reinterpret_cast<bf16_t*>(p.C) + (size_t)gm * p.ldc + gn8, w);
+    }
+}
+
 // Epilogue of one wave's 160 x 64 accumulator tile (rows row0 .. row0+159, columns col0 .. col0+63 of C), staged through the wave's private
-// 17 KiB LDS region `wave_lds` (64 rows x 68 floats).  ML = 1: accumulators in acc16 (16x16x32 MFMAs, [10 row blocks][4 column blocks]); ML = 0:
-// in acc (32x32x16, [5 row bands][2 column blocks]).  No workgroup barrier inside: a wave's LDS operations execute in order.
-template <typename E, int ML>
-__device__ __forceinline__ void wave_tile_epilogue_160x64(const NtParams& p, char* wave_lds, f32x16 (&acc)[5][2], f32x4 (&acc16)[10][4], int lane, int row0, int col0) {
-    const int l31 = lane & 31, hi = lane >> 5;
-    // ---- epilogue: every wave stages its 160 x 64 tile through a private 16 KiB LDS region, 64 rows at a time (the last pass 32),
-    // and writes full 64-column row segments.  No workgroup barrier: a wave's LDS operations execute in order.
-    // (explicit passes: a loop over the pass index that the optimizer declines to unroll would index acc[] dynamically -> scratch)
-    // The MFMAs were issued as (W fragment, A fragment), i.e. the accumulators hold C^T: lane (l31, hi) owns output ROW l31 of
-    // each 32-row band and, per register quad, four consecutive COLUMNS 8g + 4hi .. +3 -- a 16-byte LDS store per quad (40 per
-    // lane and tile instead of 160 four-byte ones).  LDS rows are padded to 68 floats: conflict-free for these writes and for
-    // the 8-columns-per-lane row reads below.
+// 17 KiB LDS region `wave_lds` (64 rows x 68 floats).  The accumulators are those of 16x16x32 MFMAs, [10 row blocks][4 column blocks].
+// No workgroup barrier inside: a wave's LDS operations execute in order.
+template <typename E>
+__device__ __forceinline__ void wave_tile_epilogue_160x64(const NtParams& p, char* wave_lds, f32x4 (&acc16)[10][4], int lane, int row0, int col0) {
+    // The tile goes through the region 64 rows at a time (the last pass 32) and leaves as full 64-column row segments.
+    // (explicit passes: a loop over the pass index that the optimizer declines to unroll would index acc16[] dynamically -> scratch)
+    // The MFMAs were issued as (W fragment, A fragment), i.e. the accumulators hold C^T: a lane owns one output ROW of a row block
+    // and, per accumulator, four consecutive COLUMNS -- a 16-byte LDS store each (40 per lane and tile instead of 160 four-byte
+    // ones).  LDS rows are padded to 68 floats: conflict-free for these writes and for the 8-columns-per-lane row reads below.
     constexpr int CT_LD = 68;
     float* ct = reinterpret_cast<float*>(wave_lds);
     const int c4 = (lane & 15) * 4;
     const int gn = col0 + c4;
     const bool col_ok = gn < p.N;
     const float4 b4 = (p.bias && col_ok) ? ld4(p.bias + gn) : make_float4(0.f, 0.f, 0.f, 0.f);
-    // ML = 1: band b = row blocks 2b, 2b+1; lane (l & 15, l >> 4) owns row l & 15 of a block and columns 16 cb + 4 (l >> 4) .. + 3
-#define TCOW_STAGE(b, ii) do { if constexpr (ML == 1) stage_band16(b, ii); else stage_band(acc[b], ii); } while (0)
-    auto stage_band16 = [&](int b, int ii) {
+    // band b = row blocks 2b, 2b+1 -> half ii of the region; lane (l & 15, l >> 4) owns row l & 15 of a block and columns 16 cb + 4 (l >> 4) .. + 3
+    auto stage = [&](int b, int ii) {
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
@@ -221,13 +243,6 @@ __device__ __forceinline__ void wave_tile_epilogue_160x64(const NtParams& p, cha
                 const f32x4 v = acc16[2 * b + rb][cb];
                 *reinterpret_cast<float4*>(ct + (ii * 32 + rb * 16 + (lane & 15)) * CT_LD + cb * 16 + 4 * (lane >> 4)) = make_float4(v[0], v[1], v[2], v[3]);
             }
-    };
-    auto stage_band = [&](const f32x16 (&a)[2], int ii) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-                *reinterpret_cast<float4*>(ct + (ii * 32 + l31) * CT_LD + j * 32 + 8 * g + 4 * hi) = make_float4(a[j][4 * g], a[j][4 * g + 1], a[j][4 * g + 2], a[j][4 * g + 3]);
     };
     const int mrow = row0 + (lane >> 4);
     const int mrow8 = row0 + (lane >> 3);
@@ -282,13 +297,7 @@ __device__ __forceinline__ void wave_tile_epilogue_160x64(const NtParams& p, cha
                 const float* cr = ct + (half * 32 + r8 + it * 8) * CT_LD + c8;
                 const float4 v0 = fin(*reinterpret_cast<const float4*>(cr), b40, c40, o[it].e0, o[it].rs, o[it].rs2);
                 const float4 v1 = fin(*reinterpret_cast<const float4*>(cr + 4), b41, c41, o[it].e1, o[it].rs, o[it].rs2);
-                if (p.out_f32) {
-                    float* d = reinterpret_cast<float*>(p.C) + (size_t)gm * p.ldc + gn8;
-                    st4(d, v0); st4(d + 4, v1);
-                } else {
-                    uint4 w; w.x = pack_bf2(v0.x, v0.y); w.y = pack_bf2(v0.z, v0.w); w.z = pack_bf2(v1.x, v1.y); w.w = pack_bf2(v1.z, v1.w);
-                    *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p.C) + (size_t)gm * p.ldc + gn8) = w;
-                }
+                store8(p, gm, gn8, v0, v1);
             }
         };
         if constexpr (E::kAuxOnly) {
@@ -314,45 +323,39 @@ __device__ __forceinline__ void wave_tile_epilogue_160x64(const NtParams& p, cha
                     const uint4 e = a[it];
                     v0.x = (v0.x + b40.x) * bflo(e.x); v0.y = (v0.y + b40.y) * bfhi(e.x); v0.z = (v0.z + b40.z) * bflo(e.y); v0.w = (v0.w + b40.w) * bfhi(e.y);
                     v1.x = (v1.x + b41.x) * bflo(e.z); v1.y = (v1.y + b41.y) * bfhi(e.z); v1.z = (v1.z + b41.z) * bflo(e.w); v1.w = (v1.w + b41.w) * bfhi(e.w);
-                    if (p.out_f32) {
-                        float* d = reinterpret_cast<float*>(p.C) + (size_t)gm * p.ldc + gn8;
-                        st4(d, v0); st4(d + 4, v1);
-                    } else {
-                        uint4 w; w.x = pack_bf2(v0.x, v0.y); w.y = pack_bf2(v0.z, v0.w); w.z = pack_bf2(v1.x, v1.y); w.w = pack_bf2(v1.z, v1.w);
-                        *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p.C) + (size_t)gm * p.ldc + gn8) = w;
-                    }
+                    store8(p, gm, gn8, v0, v1);
                 }
             };
-            TCOW_STAGE(0, 0); TCOW_STAGE(1, 1);
+            stage(0, 0); stage(1, 1);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             apply_ax(ax[0], 0, 0);
             fetch_ax(ax[0], 3);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            TCOW_STAGE(2, 0);
+            stage(2, 0);
             apply_ax(ax[1], 1, 1);
             fetch_ax(ax[1], 4);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            TCOW_STAGE(3, 1);
+            stage(3, 1);
             apply_ax(ax[2], 2, 0);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            TCOW_STAGE(4, 0);
+            stage(4, 0);
             apply_ax(ax[0], 3, 1);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             apply_ax(ax[1], 4, 0);
             return;
         }
-        fetch(oa, 0); TCOW_STAGE(0, 0);
-        fetch(ob, 1); TCOW_STAGE(1, 1);
+        fetch(oa, 0); stage(0, 0);
+        fetch(ob, 1); stage(1, 1);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         apply(oa, 0, 0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        fetch(oa, 2); TCOW_STAGE(2, 0);
+        fetch(oa, 2); stage(2, 0);
         apply(ob, 1, 1);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        fetch(ob, 3); TCOW_STAGE(3, 1);
+        fetch(ob, 3); stage(3, 1);
         apply(oa, 2, 0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        fetch(oa, 4); TCOW_STAGE(4, 0);
+        fetch(oa, 4); stage(4, 0);
         apply(ob, 3, 1);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         apply(oa, 4, 0);
@@ -374,50 +377,40 @@ __device__ __forceinline__ void wave_tile_epilogue_160x64(const NtParams& p, cha
                 v0.x += b40.x; v0.y += b40.y; v0.z += b40.z; v0.w += b40.w; v1.x += b41.x; v1.y += b41.y; v1.z += b41.z; v1.w += b41.w;
                 if (E::act(p) == TCOW_ACT_GELU_DSAVE) {
                     float4 g0, d0, g1, d1; gelu_both4(v0, g0, d0); gelu_both4(v1, g1, d1);
-                    uint4 w; w.x = pack_bf2(d0.x, d0.y); w.y = pack_bf2(d0.z, d0.w); w.z = pack_bf2(d1.x, d1.y); w.w = pack_bf2(d1.z, d1.w);
+                    const uint4 w = pack8(d0, d1);
                     st16c<true>(p.aux + (size_t)gm * p.ldaux + gn8, w);
                     v0 = g0; v1 = g1;
                 } else if (E::act(p) == TCOW_ACT_GELU) {
-                    if (p.aux) {
-                        uint4 w; w.x = pack_bf2(v0.x, v0.y); w.y = pack_bf2(v0.z, v0.w); w.z = pack_bf2(v1.x, v1.y); w.w = pack_bf2(v1.z, v1.w);
-                        *reinterpret_cast<uint4*>(p.aux + (size_t)gm * p.ldaux + gn8) = w;
-                    }
+                    if (p.aux) { const uint4 w = pack8(v0, v1); st16c<false>(p.aux + (size_t)gm * p.ldaux + gn8, w); }
                     v0 = gelu4(v0); v1 = gelu4(v1);
                 }
-                if (p.out_f32) {
-                    float* d = reinterpret_cast<float*>(p.C) + (size_t)gm * p.ldc + gn8;
-                    st4(d, v0); st4(d + 4, v1);
-                } else {
-                    uint4 w; w.x = pack_bf2(v0.x, v0.y); w.y = pack_bf2(v0.z, v0.w); w.z = pack_bf2(v1.x, v1.y); w.w = pack_bf2(v1.z, v1.w);
-                    *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p.C) + (size_t)gm * p.ldc + gn8) = w;
-                }
+                store8(p, gm, gn8, v0, v1);
             }
         };
-        TCOW_STAGE(0, 0); TCOW_STAGE(1, 1);
+        stage(0, 0); stage(1, 1);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         rows8(0, 8);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        TCOW_STAGE(2, 0); TCOW_STAGE(3, 1);
+        stage(2, 0); stage(3, 1);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         rows8(64, 8);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        TCOW_STAGE(4, 0);
+        stage(4, 0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         rows8(128, 4);
     } else {
-        TCOW_STAGE(0, 0); TCOW_STAGE(1, 1);
+        stage(0, 0); stage(1, 1);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if (col_ok) epi_rows<16, E>(p, ct, CT_LD, b4, mrow, lane >> 4, 4, c4, gn);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        TCOW_STAGE(2, 0); TCOW_STAGE(3, 1);
+        stage(2, 0); stage(3, 1);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if (col_ok) epi_rows<16, E>(p, ct, CT_LD, b4, mrow + 64, lane >> 4, 4, c4, gn);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        TCOW_STAGE(4, 0);
+        stage(4, 0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if (col_ok) epi_rows<8, E>(p, ct, CT_LD, b4, mrow + 128, lane >> 4, 4, c4, gn);
     }
-#undef TCOW_STAGE
 }
 
 }  // namespace

@@ -132,6 +132,63 @@ def test_gemm_nt_every_tile_kernel_at_bench_size(ops, cuda, N, K, fmt):
         assert rel(ops.gemm_nt(H16, A, W, bf(), act=ops.ACT_MUL_AUX, aux=pre, **t), ref0 * pre.double()) < BF           # <MUL_AUX, 0>: fc2 input gradient x GELU'
 
 
+@pytest.mark.parametrize('fmt', ['bf16', 'fp16'])
+def test_gemm_nt_specialised_epilogue_guards(ops, cuda, fmt):
+    """Every compile-time epilogue of the 320 x 256 and 160 x 256 tiles (the table nt_pick_epilogue of gemm_nt_common.h) on the smallest shape
+    that reaches all their guards: M = 330 = one full 320-row tile + 10 rows (four of the last tile's five 32-row bands are empty and the aux
+    prefetch three bands ahead runs out of range) = two full 160-row tiles + 10 rows; N = 264 = one full column tile + 8 columns, N % 8 == 0 so
+    that the specialisations are taken; K = 128, the least the 160 tile accepts.  Output and aux are column slices of [M + 1, N + 8] buffers
+    filled with a sentinel: the guard row and the guard columns must keep it.  References and bounds as in
+    test_gemm_nt_every_tile_kernel_at_bench_size (16-bit operands are exact, the error is f32 accumulation order + the output rounding, at most
+    2^-9 of the maximum for bf16); the two tiles accumulate K in the same order, so their results are bit-identical."""
+    M, K, N = 330, 128, 264
+    H16, h16 = _mode(ops, fmt)
+    g = torch.Generator(device='cuda').manual_seed(M + K + N)
+    A = torch.randn(M, K, device=cuda, generator=g).to(h16); W = (torch.randn(N, K, device=cuda, generator=g) * 0.05).to(h16)
+    bias = torch.randn(N, device=cuda, generator=g); rs = torch.rand(M, device=cuda, generator=g) + 0.5; rs[::7] = 0.0
+    resid = torch.randn(M, N, device=cuda, generator=g)
+    b2 = torch.randn(N, device=cuda, generator=g); rs2 = (torch.rand(M, device=cuda, generator=g) > 0.3).float()
+    SENT = 7.0
+    guarded = lambda dt: torch.full((M + 1, N + 8), SENT, device=cuda, dtype=dt)
+    pre_buf = guarded(h16); pre = pre_buf[:M, :N]; pre.copy_(torch.randn(M, N, device=cuda, generator=g))
+    ref0 = A.double() @ W.double().t()
+    refb = ref0 + bias.double()
+    xv = refb.clone().requires_grad_(True)
+    gel = F.gelu(xv); dgel = torch.autograd.grad(gel.sum(), xv)[0]; gel = gel.detach()
+    rsd, rs2d = rs.double()[:, None], rs2.double()[:, None]
+    BF, F32 = (4e-3 if fmt == 'bf16' else 5e-4), 2e-5
+    # (name, output dtype, arguments, reference of the output, reference of the aux tile the kernel writes or None)
+    cases = [
+        ('NONE,0 16-bit', h16, dict(bias=bias), refb, None),
+        ('NONE,0 f32', torch.float32, dict(), ref0, None),
+        ('NONE,1', h16, dict(bias=bias, row_scale=rs), refb * rsd, None),
+        ('NONE,2', torch.float32, dict(bias=bias, resid=resid), refb + resid.double(), None),
+        ('NONE,3', torch.float32, dict(bias=bias, row_scale=rs, resid=resid), refb * rsd + resid.double(), None),
+        ('NONE,7', torch.float32, dict(bias=bias, row_scale=rs, resid=resid, bias2=b2, row_scale2=rs2), refb * rsd + rs2d * b2.double() + resid.double(), None),
+        ('GELU_DSAVE,0', h16, dict(bias=bias, act=ops.ACT_GELU_DSAVE), gel, dgel),
+        ('GELU,0', h16, dict(bias=bias, act=ops.ACT_GELU), gel, refb),
+        ('MUL_AUX,0', h16, dict(act=ops.ACT_MUL_AUX, aux=pre), ref0 * pre.double(), None),
+    ]
+    for name, odt, kw, want, want_aux in cases:
+        got = {}
+        for tile in (320, 160):
+            out_buf = guarded(odt); aux_buf = guarded(h16)
+            if want_aux is not None:
+                kw = dict(kw, aux=aux_buf[:M, :N])
+            ops.gemm_nt(H16, A, W, out_buf[:M, :N], tile=tile, **kw)
+            tol = F32 if odt == torch.float32 else BF
+            e = rel(out_buf[:M, :N], want)
+            assert e < tol, f'{name} tile {tile}: {e:.3e}'
+            assert bool((out_buf[M] == SENT).all()) and bool((out_buf[:, N:] == SENT).all()), f'{name} tile {tile}: wrote past the output'
+            if want_aux is not None:
+                e = rel(aux_buf[:M, :N], want_aux)
+                assert e < BF, f'{name} tile {tile} aux: {e:.3e}'
+                assert bool((aux_buf[M] == SENT).all()) and bool((aux_buf[:, N:] == SENT).all()), f'{name} tile {tile}: wrote past the aux tile'
+            got[tile] = (out_buf, aux_buf)
+        assert torch.equal(got[320][0], got[160][0]) and torch.equal(got[320][1], got[160][1]), f'{name}: tiles 320 and 160 differ'
+    assert bool((pre_buf[M] == SENT).all()) and bool((pre_buf[:, N:] == SENT).all())
+
+
 @pytest.mark.parametrize('mname,tol', GEMM_MODES)
 @pytest.mark.parametrize('M,N,K', [(5, 64, 64), (300, 192, 256), (2057, 48, 1024), (9030, 768, 768),
                                    (9030, 2304, 768), (4200, 1032, 1288), (4099, 3072, 768)])     # the last three take the 256-tile kernel (incl. ragged tiles / last slice)

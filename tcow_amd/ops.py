@@ -110,13 +110,15 @@ def tn_group_max():
 
 
 def gemm_tn_grouped(mode, problems):
-    """Weight / bias gradients of several Linear layers in one call: problems = [(dY [M,N], X [M,K], dW [N,K] f32, bias_grad [N] or None), ...].
+    """Weight / bias gradients of several Linear layers in one call: problems = [(dY [M,N], X [M,K], dW [N,K] f32, bias_grad [N] or None), ...];
+    an optional fifth element `accumulate` (default 0) adds the problem's result to dW / bias_grad instead of overwriting them.
     In bf16 mode problems that share M run as one grid (tcow_gemm_tn_grouped); the other modes loop inside the library."""
     n = len(problems)
     arr = (L.TnProblem * n)()
-    for i, (dY, X, dW, db) in enumerate(problems):
+    for i, (dY, X, dW, db, *acc) in enumerate(problems):
         _need_cuda(dY, X, dW)
-        arr[i] = L.TnProblem(dY.shape[0], dY.shape[1], X.shape[1], dY.data_ptr(), dY.stride(0), X.data_ptr(), X.stride(0), dW.data_ptr(), dW.stride(0), _p(db), 0)
+        arr[i] = L.TnProblem(dY.shape[0], dY.shape[1], X.shape[1], dY.data_ptr(), dY.stride(0), X.data_ptr(), X.stride(0), dW.data_ptr(), dW.stride(0), _p(db),
+                             int(acc[0]) if acc else 0)
     lib, dm = _sel(mode)
     ws = workspace(lib.tcow_gemm_tn_grouped_workspace_bytes(dm, n, arr), problems[0][0].device, 'tn')
     L.check(lib.tcow_gemm_tn_grouped(_stream(), dm, n, arr, ws.data_ptr(), ws.numel()), 'tcow_gemm_tn_grouped', lib)

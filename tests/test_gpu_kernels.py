@@ -199,9 +199,9 @@ def test_gemm_tn_weight_and_bias_grad(ops, cuda, mname, tol, M, N, K):
     dW = torch.empty(N, K, device=cuda); db = torch.empty(N, device=cuda)
     ops.gemm_tn(mode, dY, X, dW, bias_grad=db)
     ref = dY.double().t() @ X.double()
-    assert rel(dW, ref) < max(tol / 4, 1e-5) and rel(db, dY.double().sum(0)) < 1e-4
+    assert rel(dW, ref) < 1e-5 and rel(db, dY.double().sum(0)) < 1e-4         # (operands exact in every mode: only the f32 summation order differs)
     ops.gemm_tn(mode, dY, X, dW, bias_grad=db, accumulate=True)
-    assert rel(dW, 2 * ref) < max(tol / 4, 1e-5) and rel(db, 2 * dY.double().sum(0)) < 1e-4
+    assert rel(dW, 2 * ref) < 1e-5 and rel(db, 2 * dY.double().sum(0)) < 1e-4
 
 
 @pytest.mark.parametrize('M,K,N', [(27090, 768, 768), (27090, 3072, 768), (333, 100, 70), (257, 50, 129), (5, 8, 3), (1, 4, 1)])

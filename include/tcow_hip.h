@@ -57,7 +57,7 @@ extern "C" {
 
 /* ABI version (bumped on any signature change) and last error text of the calling thread.  A host compares tcow_version() with the TCOW_ABI_VERSION it
  * was built against before the first call (tcow_amd/_lib.py does, for both builds of the library). */
-#define TCOW_ABI_VERSION 11
+#define TCOW_ABI_VERSION 12
 int tcow_version(void);
 const char* tcow_last_error(void);
 
@@ -213,11 +213,28 @@ int tcow_attn_spatial_bwd(void* stream, const tcow_attn_shape* shape, const void
  *   the cache's rows t0 .. t0+c-1.  Slot-0 rows of out are zero.  t0 is read from device memory (*t0_dev), so one captured graph serves every
  *   step; a t0 with t0 + c > T_total writes NaN to out and leaves the cache alone.  causal must be 1 or 2, T_total <= TCOW_STREAM_MAX_FRAMES.
  * tcow_cls_stream: x [B*c*S, D] f32 after the spatial projection (causal_attention == 1; replaces tcow_cls_merge mode 1, vit.py:189-198,215):
- *   t0 == 0: every frame's slot 0 <- frame 0's slot 0, and that row -> cls_cache [B, D]; t0 > 0: every frame's slot 0 <- cls_cache. */
+ *   t0 == 0: every frame's slot 0 <- frame 0's slot 0, and that row -> cls_cache [B, D]; t0 > 0: every frame's slot 0 <- cls_cache.
+ *
+ * A pool of live sessions (SeekerStreamPool) steps rows that stand at different frames in one launch: every row r of the step has its own
+ * t0 = t0_rows[r] and its own cache block slot_rows[r] of n_slots (both device int32 [n]).  The two pool entry points run the kernels of the two
+ * above (which are the case "one t0 for all rows, slot = row") and replace the same reference lines per row: vit.py:88-109 with the tril() of
+ * vit.py:93-99, and the frame-0 cls of vit.py:189-198,215.
+ * tcow_attn_temporal_pool_fwd: `chunk` = {B = n rows, T = c, S, D, heads, causal, dtype}; qkv / out in the row order (r*c + j)*S + s;
+ *   k_cache / v_cache [n_slots, S-1, heads, T_total, 64].  Row r is tcow_attn_temporal_cached_fwd of one clip at t0_rows[r] on block slot_rows[r]:
+ *   keys / values < t0 from the slot, >= t0 from the chunk, the chunk's K / V then rows t0 .. t0+c-1 of the slot, slot-0 rows of out zero.  A row
+ *   with t0 < 0, t0 + c > T_total or a slot outside [0, n_slots) writes NaN to its own rows of out and touches no cache row; the other rows are
+ *   unaffected.  Two rows of one launch that name the same slot are UNDEFINED (both append to it while the other reads): the caller must pass
+ *   distinct slots (SeekerStreamPool.step refuses a duplicate session).  causal 1 or 2, T_total <= TCOW_STREAM_MAX_FRAMES, n_slots >= 1.
+ * tcow_cls_pool: x [n*c*S, D] f32, cls_cache [n_slots, D]; per row r: t0_rows[r] == 0: every chunk frame's slot 0 <- chunk frame 0's slot 0,
+ *   and that row -> cls_cache[slot_rows[r]]; t0_rows[r] > 0: every chunk frame's slot 0 <- cls_cache[slot_rows[r]].  Rows of both kinds mix in
+ *   one launch; distinct slots as above. */
 #define TCOW_STREAM_MAX_FRAMES 1024
 int tcow_attn_temporal_cached_fwd(void* stream, const tcow_attn_shape* chunk, int T_total, const int* t0_dev, const void* qkv, void* k_cache,
                                   void* v_cache, void* out);
 int tcow_cls_stream(void* stream, int B, int c, int S, int D, float* x, float* cls_cache, const int* t0_dev);
+int tcow_attn_temporal_pool_fwd(void* stream, const tcow_attn_shape* chunk, int T_total, int n_slots, const int* t0_rows, const int* slot_rows,
+                                const void* qkv, void* k_cache, void* v_cache, void* out);
+int tcow_cls_pool(void* stream, int n, int c, int S, int D, float* x, float* cls_cache, int n_slots, const int* t0_rows, const int* slot_rows);
 
 /* ------------------------------------------------------------------------------------------- token glue
  * tcow_im2col: cat([rgb (B,3,T,H,W), query (B,1,T,H,W)]) (mask_tracker.py:107-108), optional (rgb-0.45)/0.225

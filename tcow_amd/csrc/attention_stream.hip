@@ -9,6 +9,10 @@
 // by xor shuffles at the end.  No LDS.  The cache of (b, s, h) is one contiguous [T_total, 64] block ([B, S-1, heads, T_total, 64]), so a
 // pass over it is a run of whole lines.  Keys of frames < t0 come from the cache, keys of the chunk's own frames from the chunk's qkv
 // rows; the same wave copies the chunk's K / V rows into cache positions t0 .. t0+c-1 (nothing reads them in this launch).
+//
+// tcow_attn_temporal_pool_fwd / tcow_cls_pool (a pool of live sessions, SeekerStreamPool): the same two kernels with a t0 and a cache slot per
+// row.  Row r reads t0_rows[r * t0_stride] and works on cache block slot_rows[r]; a stream is the case "t0 broadcast (stride 0), slot = b
+// (no table)".  Rows of different t0 run key loops of different length; nothing else differs.
 #include <math.h>
 
 #include "attention_common.h"
@@ -44,7 +48,8 @@ template <> struct StreamVec<float> {
 __device__ __forceinline__ void copy16(void* dst, const void* src) { *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src); }
 
 template <typename T>
-__global__ __launch_bounds__(64 * ST_WAVES) void temporal_cached_kernel(int B, int c, int S, int D, int heads, int T_total, const int* __restrict__ t0_dev,
+__global__ __launch_bounds__(64 * ST_WAVES) void temporal_cached_kernel(int B, int c, int S, int D, int heads, int T_total, int n_slots,
+                                                                       const int* __restrict__ t0_rows, int t0_stride, const int* __restrict__ slot_rows,
                                                                        const T* __restrict__ qkv, T* __restrict__ kc, T* __restrict__ vc, T* __restrict__ out) {
     constexpr int VEC = StreamVec<T>::VEC, LPR = ATT_HD / VEC, G = 64 / LPR;
     const int lane = threadIdx.x & 63, grp = lane / LPR, sub = lane - grp * LPR;
@@ -53,20 +58,22 @@ __global__ __launch_bounds__(64 * ST_WAVES) void temporal_cached_kernel(int B, i
     const int h = (int)(item % heads);
     const long bs = item / heads;
     const int s = (int)(bs % S), b = (int)(bs / S);
-    const int t0 = *t0_dev;
+    // (b is the same in every lane of the wave: t0 and the cache slot stay scalars, as the broadcast t0 of a stream was)
+    const int t0 = __builtin_amdgcn_readfirstlane(t0_rows[(long)b * t0_stride]);
+    const int slot = __builtin_amdgcn_readfirstlane(slot_rows ? slot_rows[b] : b);
     const long ld3 = 3L * D;
     const int col = h * ATT_HD + sub * VEC;
-    const bool bad_t0 = t0 < 0 || t0 + c > T_total;
+    const bool bad_t0 = t0 < 0 || t0 + c > T_total || slot < 0 || slot >= n_slots;
     if (s == 0 || bad_t0) {
-        // slot 0 takes no part in temporal attention: its rows are defined as zero (as in the clip path).  A t0 outside the stream (the host
-        // checks it before it writes t0) touches no cache row and writes NaN.
+        // slot 0 takes no part in temporal attention: its rows are defined as zero (as in the clip path).  A t0 outside the stream or a cache
+        // slot outside the pool (the host checks both before it writes them) touches no cache row and writes NaN to the row's own output.
         float z[VEC];
 #pragma unroll
         for (int e = 0; e < VEC; ++e) z[e] = bad_t0 ? __builtin_nanf("") : 0.f;
         for (int j = grp; j < c; j += G) StreamVec<T>::st(out + ((long)(b * c + j) * S + s) * D + col, z);
         return;
     }
-    const size_t cbase = ((((size_t)b * (S - 1) + (s - 1)) * heads + h) * T_total) * ATT_HD + sub * VEC;
+    const size_t cbase = ((((size_t)slot * (S - 1) + (s - 1)) * heads + h) * T_total) * ATT_HD + sub * VEC;
     // append the chunk's keys / values: cache[t0 + j] = chunk row j (bit copies)
     for (int j = grp; j < c; j += G) {
         const T* src = qkv + ((long)(b * c + j) * S + s) * ld3 + col;
@@ -142,23 +149,61 @@ __global__ __launch_bounds__(64 * ST_WAVES) void temporal_cached_kernel(int B, i
     }
 }
 
-// causal_attention == 1 across chunks.  t0 == 0: tcow_cls_merge mode 1 on the chunk (frame 0's slot-0 row to every frame), the row kept in
-// cls_cache[b]; t0 > 0: cls_cache[b] to slot 0 of every chunk frame.  One thread per (b, 4 channels).
-__global__ void cls_stream_kernel(int B, int c, int S, int D, float* __restrict__ x, float* __restrict__ cls_cache, const int* __restrict__ t0_dev) {
+// causal_attention == 1 across chunks, per row b with t0 = t0_rows[b * t0_stride] and cache row slot = slot_rows ? slot_rows[b] : b.
+// t0 == 0: tcow_cls_merge mode 1 on the chunk (frame 0's slot-0 row to every frame), the row kept in cls_cache[slot]; t0 > 0: cls_cache[slot]
+// to slot 0 of every chunk frame.  A slot outside [0, n_slots) writes NaN and touches no cache row.  One thread per (b, 4 channels).
+__global__ void cls_stream_kernel(int B, int c, int S, int D, float* __restrict__ x, float* __restrict__ cls_cache, int n_slots,
+                                  const int* __restrict__ t0_rows, int t0_stride, const int* __restrict__ slot_rows) {
     const int d4 = D / 4;
     const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
     if (i >= (long)B * d4) return;
     const int b = (int)(i / d4), ch = (int)(i - (long)b * d4) * 4;
+    const int slot = slot_rows ? slot_rows[b] : b;
     float* base = x + (size_t)b * c * S * D + ch;
     const size_t fs = (size_t)S * D;
     float4 a;
-    if (*t0_dev == 0) {
+    if (slot < 0 || slot >= n_slots) {
+        a.x = a.y = a.z = a.w = __builtin_nanf("");
+    } else if (t0_rows[(long)b * t0_stride] == 0) {
         a = ld4(base);
-        st4(cls_cache + (size_t)b * D + ch, a);
+        st4(cls_cache + (size_t)slot * D + ch, a);
     } else {
-        a = ld4(cls_cache + (size_t)b * D + ch);
+        a = ld4(cls_cache + (size_t)slot * D + ch);
     }
     for (int t = 0; t < c; ++t) st4(base + t * fs, a);
+}
+
+// Argument checks and launch of temporal_cached_kernel, shared by the stream (t0 broadcast, slot = b) and the pool entry point.
+int launch_temporal_cached(const char* who, void* stream, const tcow_attn_shape* chunk, int T_total, int n_slots, const int* t0_rows, int t0_stride,
+                           const int* slot_rows, const void* qkv, void* k_cache, void* v_cache, void* out) {
+    TCOW_CHECK_ARG(chunk != nullptr, "%s: null shape", who);
+    const tcow_attn_shape& s = *chunk;
+    TCOW_CHECK_ARG(s.B > 0 && s.T > 0 && s.S > 1 && s.heads > 0, "%s: bad chunk shape B=%d c=%d S=%d heads=%d", who, s.B, s.T, s.S, s.heads);
+    TCOW_CHECK_ARG(s.D == s.heads * ATT_HD, "%s: head_dim must be 64 (D=%d heads=%d)", who, s.D, s.heads);
+    TCOW_CHECK_ARG(s.causal == 1 || s.causal == 2, "%s: causal must be 1 or 2 (got %d): other masks let a frame see later frames", who, s.causal);
+    TCOW_CHECK_ARG(T_total >= s.T && T_total <= TCOW_STREAM_MAX_FRAMES, "%s: T_total=%d must be in [c=%d, %d]", who, T_total, s.T, TCOW_STREAM_MAX_FRAMES);
+    TCOW_CHECK_ARG(s.dtype == TCOW_F32 || s.dtype == TCOW_BF16, "%s: dtype must be TCOW_F32 or TCOW_BF16 (got %d)", who, s.dtype);
+    TCOW_CHECK_ARG(n_slots >= 1, "%s: n_slots=%d must be >= 1", who, n_slots);
+    TCOW_CHECK_ARG(t0_rows && qkv && k_cache && v_cache && out, "%s: null pointer", who);
+    const long items = (long)s.B * s.S * s.heads;
+    const dim3 grid((unsigned)cdiv(items, ST_WAVES)), block(64 * ST_WAVES);
+    if (s.dtype == TCOW_BF16)
+        hipLaunchKernelGGL(temporal_cached_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, s.B, s.T, s.S, s.D, s.heads, T_total, n_slots, t0_rows,
+                           t0_stride, slot_rows, (const bf16_t*)qkv, (bf16_t*)k_cache, (bf16_t*)v_cache, (bf16_t*)out);
+    else
+        hipLaunchKernelGGL(temporal_cached_kernel<float>, grid, block, 0, (hipStream_t)stream, s.B, s.T, s.S, s.D, s.heads, T_total, n_slots, t0_rows,
+                           t0_stride, slot_rows, (const float*)qkv, (float*)k_cache, (float*)v_cache, (float*)out);
+    TCOW_CHECK_LAUNCH();
+    return TCOW_OK;
+}
+
+int launch_cls(const char* who, void* stream, int B, int c, int S, int D, float* x, float* cls_cache, int n_slots, const int* t0_rows, int t0_stride,
+               const int* slot_rows) {
+    TCOW_CHECK_ARG(B > 0 && c > 0 && S > 1 && D > 0 && D % 4 == 0 && n_slots >= 1 && x && cls_cache && t0_rows, "%s: bad arguments", who);
+    hipLaunchKernelGGL(cls_stream_kernel, dim3(cdiv((long)B * D / 4, 64)), dim3(64), 0, (hipStream_t)stream, B, c, S, D, x, cls_cache, n_slots, t0_rows,
+                       t0_stride, slot_rows);
+    TCOW_CHECK_LAUNCH();
+    return TCOW_OK;
 }
 
 }  // namespace
@@ -167,33 +212,23 @@ extern "C" {
 
 int tcow_attn_temporal_cached_fwd(void* stream, const tcow_attn_shape* chunk, int T_total, const int* t0_dev, const void* qkv, void* k_cache, void* v_cache,
                                   void* out) {
-    TCOW_CHECK_ARG(chunk != nullptr, "tcow_attn_temporal_cached_fwd: null shape");
-    const tcow_attn_shape& s = *chunk;
-    TCOW_CHECK_ARG(s.B > 0 && s.T > 0 && s.S > 1 && s.heads > 0, "tcow_attn_temporal_cached_fwd: bad chunk shape B=%d c=%d S=%d heads=%d", s.B, s.T, s.S, s.heads);
-    TCOW_CHECK_ARG(s.D == s.heads * ATT_HD, "tcow_attn_temporal_cached_fwd: head_dim must be 64 (D=%d heads=%d)", s.D, s.heads);
-    TCOW_CHECK_ARG(s.causal == 1 || s.causal == 2, "tcow_attn_temporal_cached_fwd: causal must be 1 or 2 (got %d): other masks let a frame see later frames",
-                   s.causal);
-    TCOW_CHECK_ARG(T_total >= s.T && T_total <= TCOW_STREAM_MAX_FRAMES, "tcow_attn_temporal_cached_fwd: T_total=%d must be in [c=%d, %d]", T_total, s.T,
-                   TCOW_STREAM_MAX_FRAMES);
-    TCOW_CHECK_ARG(s.dtype == TCOW_F32 || s.dtype == TCOW_BF16, "tcow_attn_temporal_cached_fwd: dtype must be TCOW_F32 or TCOW_BF16 (got %d)", s.dtype);
-    TCOW_CHECK_ARG(t0_dev && qkv && k_cache && v_cache && out, "tcow_attn_temporal_cached_fwd: null pointer");
-    const long items = (long)s.B * s.S * s.heads;
-    const dim3 grid((unsigned)cdiv(items, ST_WAVES)), block(64 * ST_WAVES);
-    if (s.dtype == TCOW_BF16)
-        hipLaunchKernelGGL(temporal_cached_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, s.B, s.T, s.S, s.D, s.heads, T_total, t0_dev,
-                           (const bf16_t*)qkv, (bf16_t*)k_cache, (bf16_t*)v_cache, (bf16_t*)out);
-    else
-        hipLaunchKernelGGL(temporal_cached_kernel<float>, grid, block, 0, (hipStream_t)stream, s.B, s.T, s.S, s.D, s.heads, T_total, t0_dev,
-                           (const float*)qkv, (float*)k_cache, (float*)v_cache, (float*)out);
-    TCOW_CHECK_LAUNCH();
-    return TCOW_OK;
+    return launch_temporal_cached("tcow_attn_temporal_cached_fwd", stream, chunk, T_total, chunk ? chunk->B : 1, t0_dev, 0, nullptr, qkv, k_cache, v_cache,
+                                  out);
+}
+
+int tcow_attn_temporal_pool_fwd(void* stream, const tcow_attn_shape* chunk, int T_total, int n_slots, const int* t0_rows, const int* slot_rows,
+                                const void* qkv, void* k_cache, void* v_cache, void* out) {
+    TCOW_CHECK_ARG(slot_rows != nullptr, "tcow_attn_temporal_pool_fwd: null pointer");
+    return launch_temporal_cached("tcow_attn_temporal_pool_fwd", stream, chunk, T_total, n_slots, t0_rows, 1, slot_rows, qkv, k_cache, v_cache, out);
 }
 
 int tcow_cls_stream(void* stream, int B, int c, int S, int D, float* x, float* cls_cache, const int* t0_dev) {
-    TCOW_CHECK_ARG(B > 0 && c > 0 && S > 1 && D > 0 && D % 4 == 0 && x && cls_cache && t0_dev, "tcow_cls_stream: bad arguments");
-    hipLaunchKernelGGL(cls_stream_kernel, dim3(cdiv((long)B * D / 4, 64)), dim3(64), 0, (hipStream_t)stream, B, c, S, D, x, cls_cache, t0_dev);
-    TCOW_CHECK_LAUNCH();
-    return TCOW_OK;
+    return launch_cls("tcow_cls_stream", stream, B, c, S, D, x, cls_cache, B > 0 ? B : 1, t0_dev, 0, nullptr);
+}
+
+int tcow_cls_pool(void* stream, int n, int c, int S, int D, float* x, float* cls_cache, int n_slots, const int* t0_rows, const int* slot_rows) {
+    TCOW_CHECK_ARG(slot_rows != nullptr, "tcow_cls_pool: bad arguments");
+    return launch_cls("tcow_cls_pool", stream, n, c, S, D, x, cls_cache, n_slots, t0_rows, 1, slot_rows);
 }
 
 }  // extern "C"

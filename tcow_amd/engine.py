@@ -175,7 +175,9 @@ def _effective_embeddings(module, g):
 def run_forward(module, rgb, qm, params, save, stream=None):
     """stream (inference only, tcow_amd/stream.py): the state of a SeekerStream step -- rgb / qm then hold the chunk's c frames, and the schedule
     differs in three places: the time rows (stream.time_rows = rows t0 .. t0+c-1 of the effective table), the temporal attention (against the
-    block's K / V cache, tcow_attn_temporal_cached_fwd) and, for causal_attention == 1, the cls row (tcow_cls_stream)."""
+    block's K / V cache, tcow_attn_temporal_cached_fwd) and, for causal_attention == 1, the cls row (tcow_cls_stream).
+    A SeekerStreamPool step is the same with a frame index and a cache slot per row: the state then carries t0_rows / slot_rows (device int32 [B]),
+    its caches are [block][slot], stream.time_rows holds one row per (row, chunk frame) and the two substitutions are the pool entry points."""
     mode = module.mode
     gmode = module.gemm_mode           # the GEMM entry points' arithmetic: `mode`, or TCOW_F32X3 (f32 tensors, bf16 x 3 split products) for precision='bf16x3'
     dt = ops.tdtype(mode)
@@ -225,7 +227,12 @@ def run_forward(module, rgb, qm, params, save, stream=None):
         pos, te, pos_idx, time_idx = _effective_embeddings(module, g)
     else:
         pos, te, pos_idx, time_idx = stream.pos, stream.time_rows, None, None
-    ops.embed_fwd(X, B, T, S, params[0].detach().reshape(-1), pos, te)
+    pool = stream is not None and stream.t0_rows is not None
+    if pool:
+        # every row has its own frames: the time table [B*T, D] holds row t0_rows[b] + j at b*T + j, which tcow_embed_fwd indexes by (row / S) % (B*T)
+        ops.embed_fwd(X, 1, B * T, S, params[0].detach().reshape(-1), pos, te)
+    else:
+        ops.embed_fwd(X, B, T, S, params[0].detach().reshape(-1), pos, te)
     if save:
         sv.update(A_pe=A_pe, pos_idx=pos_idx, time_idx=time_idx)
 
@@ -271,6 +278,9 @@ def run_forward(module, rgb, qm, params, save, stream=None):
             O = E(M, D); lse_t = E(M, heads, dtype=f32) if save else None
             if stream is None:
                 ops.attn_fwd(shape_attn, False, QKV, O, lse_t)
+            elif pool:
+                ops.attn_temporal_pool(amode, B, T, S, D, heads, ca, stream.T_total, stream.n_slots, stream.t0_rows, stream.slot_rows, QKV,
+                                       stream.k_cache[i], stream.v_cache[i], O)
             else:
                 ops.attn_temporal_cached(amode, B, T, S, D, heads, ca, stream.T_total, stream.t0_dev, QKV, stream.k_cache[i], stream.v_cache[i], O)
             R1 = E(M, D, dtype=f32) if save else R0
@@ -296,7 +306,9 @@ def run_forward(module, rgb, qm, params, save, stream=None):
                 rs_s = mask0 if rs_s is None else rs_s * mask0
             R2 = E(M, D, dtype=f32) if save else R1
             ops.gemm_nt(gmode, O2, W(q[ix['proj']]), R2, bias=proj_b, row_scale=rs_s, resid=R1)
-            if use_cls and stream is not None:
+            if use_cls and pool:
+                ops.cls_pool(R2, B, T, S, stream.cls_cache[i], stream.n_slots, stream.t0_rows, stream.slot_rows)
+            elif use_cls and stream is not None:
                 ops.cls_stream(R2, B, T, S, stream.cls_cache[i], stream.t0_dev)      # (a stream has causal_attention 1 or 2)
             elif use_cls:
                 ops.cls_merge(R2, B, T, S, 1 if ca == 1 else 0)

@@ -220,6 +220,25 @@ def cls_stream(x, B, c, S, cls_cache, t0_dev):
     return x
 
 
+def attn_temporal_pool(mode, n, c, S, D, heads, causal, T_total, n_slots, t0_rows, slot_rows, qkv, k_cache, v_cache, out):
+    """attn_temporal_cached for n rows that stand at different frames: row r attends at t0_rows[r] against block slot_rows[r] of the caches
+    [n_slots, S-1, heads, T_total, 64] and appends there (int32 device tensors [n]; distinct slots -- see tcow_attn_temporal_pool_fwd)."""
+    _need_cuda(qkv, k_cache, v_cache, out, t0_rows, slot_rows)
+    lib, dm = _sel(mode)
+    sh = L.AttnShape(n, c, S, D, heads, int(causal), F32 if dm == F32X3 else dm)
+    L.check(lib.tcow_attn_temporal_pool_fwd(_stream(), ctypes.byref(sh), int(T_total), int(n_slots), t0_rows.data_ptr(), slot_rows.data_ptr(), qkv.data_ptr(),
+                                            k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr()), 'tcow_attn_temporal_pool_fwd', lib)
+    return out
+
+
+def cls_pool(x, n, c, S, cls_cache, n_slots, t0_rows, slot_rows):
+    """cls_stream per row: t0_rows[r] == 0 -> merge (mode 1) and keep the row in cls_cache[slot_rows[r]] ([n_slots, D]); > 0 -> that row to slot 0."""
+    _need_cuda(x, cls_cache, t0_rows, slot_rows)
+    L.check(L.lib().tcow_cls_pool(_stream(), n, c, S, x.shape[1], x.data_ptr(), cls_cache.data_ptr(), int(n_slots), t0_rows.data_ptr(), slot_rows.data_ptr()),
+            'tcow_cls_pool')
+    return x
+
+
 def im2col(mode, rgb, query, P, pretrained_norm, out):
     B, _, T, H, W = rgb.shape
     L.check(_sel(mode)[0].tcow_im2col(_stream(), _sel(mode)[1], B, T, H, W, P, rgb.data_ptr(), query.data_ptr(), int(pretrained_norm), out.data_ptr()), 'tcow_im2col', _sel(mode)[0])

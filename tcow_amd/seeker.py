@@ -248,6 +248,12 @@ class QueryMaskTracker(nn.Module):
         from .stream import SeekerStream
         return SeekerStream(self, batch_size, queries_per_clip, graph)
 
+    def stream_pool(self, capacity):
+        """Streaming inference for up to `capacity` live sessions that started at different moments: a SeekerStreamPool whose step(ids, rgb,
+        query_mask) advances any subset of the open sessions, each at its own frame, in one Seeker step (tcow_amd/stream.py)."""
+        from .stream import SeekerStreamPool
+        return SeekerStreamPool(self, capacity)
+
     def param_list(self):
         """Fixed order of the parameters the autograd.Function sees.  Cached: walking ~250 module attributes costs 0.4 ms per call.  .to() /
         load_state_dict keep the Parameter objects; code that ASSIGNS a new Parameter inside the module tree must call invalidate_param_cache()
@@ -323,3 +329,7 @@ class Seeker(nn.Module):
     def stream(self, batch_size=1, queries_per_clip=1, graph=False):
         """See QueryMaskTracker.stream."""
         return self.seeker.stream(batch_size, queries_per_clip, graph)
+
+    def stream_pool(self, capacity):
+        """See QueryMaskTracker.stream_pool."""
+        return self.seeker.stream_pool(capacity)

@@ -15,6 +15,11 @@ graph=True: the first step of each chunk length c runs eagerly and captures the 
 into the graph's static buffers, write t0 (a device scalar the kernels read) and replay.  No step synchronises the host except the one capture
 per chunk length.  A graph keeps the module's operand copies it was captured with alive; when the module replaces them (.cuda() / .to() on
 the same device, set_precision() with the same precision, a train-mode forward) the graphs are dropped and captured again.
+
+SeekerStreamPool (net.stream_pool(capacity)): live sessions that started at different moments, stepped together.  The three substitutions
+depend on a row's own frame index only, so a pool step is one Seeker step whose rows each carry their own t0 and their own cache slot
+(tcow_attn_temporal_pool_fwd, tcow_cls_pool; the time rows are gathered per row).  The pool holds the state of `capacity` one-row streams:
+per block K / V caches [capacity, S-1, heads, T, 64] and one cls row per slot.  Pool steps run eagerly.
 """
 import torch
 
@@ -24,7 +29,10 @@ from ._lib import TcowError
 
 class _StepState:
     """What engine.run_forward substitutes for a stream step."""
-    __slots__ = ('T_total', 't0_dev', 'pos', 'time_rows', 'k_cache', 'v_cache', 'cls_cache')
+    __slots__ = ('T_total', 't0_dev', 'pos', 'time_rows', 'k_cache', 'v_cache', 'cls_cache', 't0_rows', 'slot_rows', 'n_slots')
+
+    def __init__(self):
+        self.t0_rows = self.slot_rows = self.n_slots = None       # set by a pool step only: a frame index and a cache slot per row
 
 
 def check_streamable(module):
@@ -48,6 +56,49 @@ def _signature(module):
     return (module.mode, module.gemm_mode, module._operands.epoch) + tuple((id(p), p._version, p.data_ptr()) for p in module.param_list())
 
 
+def _new_state(module, rows):
+    """(state with the caches of `rows` rows allocated, effective time table [T, D], geometry) -- what a stream and a pool both start from."""
+    g = module.geometry(rows)
+    dev = module.vit.pos_embed.device
+    cdt = ops.tdtype(module.mode)                           # (bf16x3 stores f32, like fp32)
+    T = module.num_total_frames
+    shape = (module.network_depth, rows, g['S'] - 1, g['heads'], T, 64)
+    st = _StepState()
+    st.T_total = T
+    st.k_cache = torch.empty(shape, dtype=cdt, device=dev)
+    st.v_cache = torch.empty(shape, dtype=cdt, device=dev)
+    st.cls_cache = torch.empty(module.network_depth, rows, g['D'], dtype=torch.float32, device=dev)
+    with torch.no_grad():
+        st.pos, time, _, _ = engine._effective_embeddings(module, g)            # (nearest-resized when the stored tables differ)
+    st.time_rows = None
+    return st, time, g
+
+
+def _cache_bytes(st):
+    return sum(t.numel() * t.element_size() for t in (st.k_cache, st.v_cache, st.cls_cache))
+
+
+def _check_step(who, module, sig, device, clips, rows, rgb, query_mask):
+    """The checks of a step that do not depend on where its rows stand; returns the chunk length c."""
+    m = module
+    check_streamable(m)
+    if _signature(m) != sig:
+        raise TcowError('stream: a parameter (or the precision) changed since the stream was opened; the cached keys / values belong to the old '
+                        'weights -- open a new stream')
+    if not torch.is_tensor(rgb) or rgb.dim() != 5 or rgb.shape[0] != clips or rgb.shape[1] != 3 or rgb.shape[2] < 1 \
+            or rgb.shape[3] != m.frame_height or rgb.shape[4] != m.frame_width:
+        raise TcowError(f'{who}: rgb must be ({clips}, 3, c >= 1, {m.frame_height}, {m.frame_width}), got '
+                        f'{tuple(rgb.shape) if torch.is_tensor(rgb) else type(rgb).__name__}')
+    c = int(rgb.shape[2])
+    if query_mask is not None and (not torch.is_tensor(query_mask) or tuple(query_mask.shape) != (rows, 1, c, m.frame_height, m.frame_width)):
+        raise TcowError(f'{who}: query_mask must be ({rows}, 1, {c}, {m.frame_height}, {m.frame_width}) or None, got '
+                        f'{tuple(query_mask.shape) if torch.is_tensor(query_mask) else type(query_mask).__name__}')
+    for t in (rgb, query_mask):
+        if t is not None and (not t.is_cuda or t.device != device):
+            raise TcowError(f'{who}: inputs must be on the stream device {device}, got {t.device}')
+    return c
+
+
 class SeekerStream:
     """net.stream(batch_size, queries_per_clip, graph) of Seeker / QueryMaskTracker; see the module docstring."""
 
@@ -61,21 +112,10 @@ class SeekerStream:
         self.Bc, self.Qs, self.B = Bc, Qs, Bc * Qs
         self.T = module.num_total_frames
         self.graph = bool(graph)
-        g = module.geometry(self.B)
+        st, self._time, g = _new_state(module, self.B)
         self._S, self._D = g['S'], g['D']
-        dev = module.vit.pos_embed.device
-        self.device = dev
-        cdt = ops.tdtype(module.mode)                       # (bf16x3 stores f32, like fp32)
-        shape = (module.network_depth, self.B, g['S'] - 1, g['heads'], self.T, 64)
-        st = _StepState()
-        st.T_total = self.T
-        st.k_cache = torch.empty(shape, dtype=cdt, device=dev)
-        st.v_cache = torch.empty(shape, dtype=cdt, device=dev)
-        st.cls_cache = torch.empty(module.network_depth, self.B, g['D'], dtype=torch.float32, device=dev)
-        st.t0_dev = torch.zeros(1, dtype=torch.int32, device=dev)
-        with torch.no_grad():
-            st.pos, self._time, _, _ = engine._effective_embeddings(module, g)        # (nearest-resized when the stored tables differ)
-        st.time_rows = None
+        self.device = st.pos.device
+        st.t0_dev = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._st = st
         self._time_rows = {}            # c -> static [c, D] f32 time rows of the step
         self._graphs = {}               # c -> (graph, static rgb, static query mask, output mask, flags)
@@ -85,8 +125,7 @@ class SeekerStream:
     @property
     def cache_bytes(self):
         """Device bytes of the K / V caches and the cls rows."""
-        st = self._st
-        return sum(t.numel() * t.element_size() for t in (st.k_cache, st.v_cache, st.cls_cache))
+        return _cache_bytes(self._st)
 
     def reset(self):
         """Start again at frame 0 (the buffers, and any captured graphs, are kept)."""
@@ -95,22 +134,7 @@ class SeekerStream:
     def step(self, rgb, query_mask=None):
         """rgb (Bc, 3, c, H, W), query_mask (Bc*Qs, 1, c, H, W) or None (all zeros) for the next c >= 1 frames ->
         (mask logits (Bc*Qs, Co, c, H, W) f32, flags (Bc*Qs, c, F) or None) of exactly those frames, owned by the caller."""
-        m = self.module
-        check_streamable(m)
-        if _signature(m) != self._sig:
-            raise TcowError('stream: a parameter (or the precision) changed since the stream was opened; the cached keys / values belong to the old '
-                            'weights -- open a new stream')
-        if not torch.is_tensor(rgb) or rgb.dim() != 5 or rgb.shape[0] != self.Bc or rgb.shape[1] != 3 or rgb.shape[2] < 1 \
-                or rgb.shape[3] != m.frame_height or rgb.shape[4] != m.frame_width:
-            raise TcowError(f'stream.step: rgb must be ({self.Bc}, 3, c >= 1, {m.frame_height}, {m.frame_width}), got '
-                            f'{tuple(rgb.shape) if torch.is_tensor(rgb) else type(rgb).__name__}')
-        c = int(rgb.shape[2])
-        if query_mask is not None and (not torch.is_tensor(query_mask) or tuple(query_mask.shape) != (self.B, 1, c, m.frame_height, m.frame_width)):
-            raise TcowError(f'stream.step: query_mask must be ({self.B}, 1, {c}, {m.frame_height}, {m.frame_width}) or None, got '
-                            f'{tuple(query_mask.shape) if torch.is_tensor(query_mask) else type(query_mask).__name__}')
-        for t in (rgb, query_mask):
-            if t is not None and (not t.is_cuda or t.device != self.device):
-                raise TcowError(f'stream.step: inputs must be on the stream device {self.device}, got {t.device}')
+        c = _check_step('stream.step', self.module, self._sig, self.device, self.Bc, self.B, rgb, query_mask)
         t0 = self.frames_done
         if t0 + c > self.T:
             raise TcowError(f'stream.step: frames {t0}..{t0 + c - 1} run past the last frame {self.T - 1} of the stream (num_total_frames = {self.T}); '
@@ -166,3 +190,95 @@ class SeekerStream:
             s_qm.copy_(qm)
         graph.replay()
         return g_mask.clone(), (g_flags.clone() if g_flags is not None else None)
+
+
+class SeekerStreamPool:
+    """net.stream_pool(capacity) of Seeker / QueryMaskTracker: up to `capacity` live sessions (one clip and one query mask each) that stand at
+    different frames, stepped together; see the module docstring.  open() -> id, step(ids, rgb, query_mask), close(id)."""
+
+    def __init__(self, module, capacity):
+        module = getattr(module, 'seeker', module)
+        capacity = int(capacity)
+        if capacity < 1:
+            raise TcowError(f'stream_pool: capacity ({capacity}) must be >= 1')
+        check_streamable(module)
+        self.module = module
+        self.capacity = capacity
+        self.T = module.num_total_frames
+        st, self._time, g = _new_state(module, capacity)
+        st.n_slots = capacity
+        self._st = st
+        self.device = st.pos.device
+        self._sig = _signature(module)
+        self._slot = {}                 # open session id -> cache slot
+        self._done = {}                 # open session id -> frames consumed
+        self._next_id = 0
+
+    @property
+    def cache_bytes(self):
+        """Device bytes of the K / V caches and the cls rows of all `capacity` slots."""
+        return _cache_bytes(self._st)
+
+    def _known(self, sid):
+        if sid not in self._slot:
+            raise TcowError(f'stream_pool: session {sid!r} is not open (unknown or closed id)')
+        return sid
+
+    def open(self):
+        """A new session at frame 0 in the smallest free slot; returns its id (ids are never reused)."""
+        taken = set(self._slot.values())
+        free = [s for s in range(self.capacity) if s not in taken]
+        if not free:
+            raise TcowError(f'stream_pool.open: all {self.capacity} slots are taken; close() a session first')
+        sid = self._next_id
+        self._next_id += 1
+        self._slot[sid], self._done[sid] = free[0], 0
+        return sid
+
+    def close(self, sid):
+        """End the session; its slot is free for the next open()."""
+        self._known(sid)
+        del self._slot[sid], self._done[sid]
+
+    def frames_done(self, sid):
+        return self._done[self._known(sid)]
+
+    def reset(self, sid):
+        """Put the session back at frame 0 (it keeps its slot)."""
+        self._done[self._known(sid)] = 0
+
+    def step(self, ids, rgb, query_mask=None):
+        """ids: n distinct open sessions, at any phases; rgb (n, 3, c, H, W), query_mask (n, 1, c, H, W) or None (all zeros): the next c >= 1
+        frames of each -> (mask logits (n, Co, c, H, W) f32, flags (n, c, F) or None) in the order of `ids`, owned by the caller.  Every check
+        runs before anything is launched: a refused step leaves every session where it was."""
+        m = self.module
+        ids = list(ids)
+        n = len(ids)
+        if n < 1 or n > self.capacity:
+            raise TcowError(f'stream_pool.step: {n} sessions given; a step takes 1 .. capacity = {self.capacity}')
+        seen = set()
+        for sid in ids:
+            if sid in seen:
+                raise TcowError(f'stream_pool.step: duplicate session {sid!r}: a session is one row of a step')
+            seen.add(self._known(sid))
+        c = _check_step('stream_pool.step', m, self._sig, self.device, n, n, rgb, query_mask)
+        t0s = [self._done[sid] for sid in ids]
+        for sid, t0 in zip(ids, t0s):
+            if t0 + c > self.T:
+                raise TcowError(f'stream_pool.step: session {sid}: frames {t0}..{t0 + c - 1} run past the last frame {self.T - 1} of the stream '
+                                f'(num_total_frames = {self.T}); reset() or close() it')
+        st = self._st
+        with torch.no_grad(), torch.cuda.device(self.device):
+            st.t0_rows = torch.tensor(t0s, dtype=torch.int32, device=self.device)
+            st.slot_rows = torch.tensor([self._slot[sid] for sid in ids], dtype=torch.int32, device=self.device)
+            frames = (st.t0_rows[:, None] + torch.arange(c, dtype=torch.int32, device=self.device)[None, :]).reshape(-1)
+            st.time_rows = self._time.index_select(0, frames)                   # [n*c, D]: row r*c + j = time row t0_rows[r] + j
+            rgb32 = rgb.to(torch.float32).contiguous()
+            if query_mask is None:
+                qm32 = torch.zeros(n, 1, c, rgb.shape[3], rgb.shape[4], dtype=torch.float32, device=self.device)
+            else:
+                qm32 = query_mask.to(torch.float32).contiguous()
+            out_mask, flags, _ = engine.run_forward(m, rgb32, qm32, m.param_list(), save=False, stream=st)
+        for sid in ids:
+            self._done[sid] += c
+        return out_mask, (flags if m.flag_channels > 0 else None)

@@ -5,6 +5,9 @@
                                         # one-frame bf16 steps at configs[3], t0 = 59: KPROF_WARMUP warm-up steps, then KPROF_STEPS profiled ones
     python tools/dev_stream_latency.py --kstats DIR/run_kernel_trace.csv --out profiles/stream_step_kernel_stats.txt
                                         # per-step kernel breakdown of the profiled steps only (the warm-up steps' dispatches are dropped)
+    python tools/dev_stream_latency.py --pool --out profiles/stream_pool_latency.json
+                                        # eight live sessions at configs[1]: one pool step at eight different t0 against the in-phase B = 8 stream
+                                        # step and against eight one-session steps, the three legs alternating in one run
 
 Times are device events around each call after warm-up, profiler off.  A step at a given t0 is timed by setting the stream's host frame counter
 (the kernels then read t0 from the device scalar the step writes): the work of a step depends on t0, not on what the cache holds.  Synthetic
@@ -85,6 +88,64 @@ def measure(name, B, precision, reps):
     return res
 
 
+POOL_SESSIONS = 8
+
+
+def pool_leg(reps):
+    """Eight sessions at configs[1], bf16, one-frame steps, the three legs taken in turn `reps` times (so drift of the machine hits all alike):
+    (a) one SeekerStreamPool step with t0 spread evenly over 0 .. T-1, (b) the in-phase batch_size = 8 SeekerStream step at t0 = T-1 (it reads
+    at least as much cache as (a)), (c) eight one-session SeekerStream steps at the eight t0 of (a), one after the other.  The spread (b) is
+    judged against is max - min of (b)'s own samples in this run."""
+    name, n = 'configs1', POOL_SESSIONS
+    T, H, W = CONFIGS[name]
+    net = build(T, H, W, 'bf16')
+    rgb, qm = inputs(n, T, H, W)
+    t0s = [round(k * (T - 1) / (n - 1)) for k in range(n)]
+    f = lambda x, t0: x[:, :, t0:t0 + 1]
+    with torch.no_grad():
+        pool = net.stream_pool(n)
+        ids = [pool.open() for _ in range(n)]
+        inphase = net.stream(batch_size=n)
+        single = net.stream(batch_size=1)
+        for t in range(T):                                    # warm-up: the whole clip once through each (fills every cache row)
+            pool.step(ids, f(rgb, t), f(qm, t))
+            inphase.step(f(rgb, t), f(qm, t))
+            single.step(f(rgb[0:1], t), f(qm[0:1], t))
+        rgb_a = torch.cat([f(rgb[k:k + 1], t0) for k, t0 in enumerate(t0s)], 0)
+        qm_a = torch.cat([f(qm[k:k + 1], t0) for k, t0 in enumerate(t0s)], 0)
+
+        def leg_a():
+            for sid, t0 in zip(ids, t0s):
+                pool._done[sid] = t0                         # (the step's work depends on t0, not on what the cache holds)
+            pool.step(ids, rgb_a, qm_a)
+
+        def leg_b():
+            inphase.frames_done = T - 1
+            inphase.step(f(rgb, T - 1), f(qm, T - 1))
+
+        def leg_c():
+            for t0 in t0s:
+                single.frames_done = t0
+                single.step(f(rgb[0:1], t0), f(qm[0:1], t0))
+
+        legs = {'a_pool_step_ms': leg_a, 'b_inphase_b8_step_ms': leg_b, 'c_eight_single_steps_ms': leg_c}
+        samples = {k: [] for k in legs}
+        for fn in legs.values():
+            for _ in range(3):
+                fn()
+        for _ in range(reps):
+            for k, fn in legs.items():
+                samples[k].append(ev_time(fn, 1))
+    res = {'config': name, 'T': T, 'H': H, 'W': W, 'sessions': n, 'precision': 'bf16', 'reps': reps, 't0_rows': t0s, 'pool_cache_bytes': pool.cache_bytes}
+    for k, v in samples.items():
+        v = sorted(v)
+        res[k] = {'median': v[len(v) // 2], 'min': v[0], 'max': v[-1]}
+    a, b, c = (res[k]['median'] for k in legs)
+    spread = res['b_inphase_b8_step_ms']['max'] - res['b_inphase_b8_step_ms']['min']
+    res.update(b_spread_ms=spread, a_minus_b_ms=a - b, a_within_b_plus_spread=bool(a <= b + spread), a_over_c=a / c)
+    return res
+
+
 KPROF_WARMUP, KPROF_STEPS = 3, 20
 STEP_LAST_KERNEL = 'flags_fwd_kernel'      # the last launch of every step (the flags head, engine.run_forward)
 
@@ -153,6 +214,7 @@ def main():
     ap.add_argument('--out', default=None)
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--kprof', action='store_true')
+    ap.add_argument('--pool', action='store_true', help='the stream-pool leg (eight sessions at configs1)')
     ap.add_argument('--kstats', default=None, metavar='KERNEL_TRACE_CSV')
     ap.add_argument('--only', default=None, help='comma list of configs1_b1, configs1_b8, configs3_b1')
     a = ap.parse_args()
@@ -163,6 +225,14 @@ def main():
         raise SystemExit('dev_stream_latency.py needs a GPU')
     if a.kprof:
         kprof()
+        return
+    if a.pool:
+        out = {'device': torch.cuda.get_device_name(0), 'pool': pool_leg(a.reps)}
+        print(json.dumps(out['pool']), flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, 'w') as f:
+                json.dump(out, f, indent=1)
         return
     runs = [('configs1', 1), ('configs1', 8), ('configs3', 1)]
     if a.only:

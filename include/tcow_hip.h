@@ -57,7 +57,7 @@ extern "C" {
 
 /* ABI version (bumped on any signature change) and last error text of the calling thread.  A host compares tcow_version() with the TCOW_ABI_VERSION it
  * was built against before the first call (tcow_amd/_lib.py does, for both builds of the library). */
-#define TCOW_ABI_VERSION 12
+#define TCOW_ABI_VERSION 13
 int tcow_version(void);
 const char* tcow_last_error(void);
 
@@ -227,7 +227,21 @@ int tcow_attn_spatial_bwd(void* stream, const tcow_attn_shape* shape, const void
  *   distinct slots (SeekerStreamPool.step refuses a duplicate session).  causal 1 or 2, T_total <= TCOW_STREAM_MAX_FRAMES, n_slots >= 1.
  * tcow_cls_pool: x [n*c*S, D] f32, cls_cache [n_slots, D]; per row r: t0_rows[r] == 0: every chunk frame's slot 0 <- chunk frame 0's slot 0,
  *   and that row -> cls_cache[slot_rows[r]]; t0_rows[r] > 0: every chunk frame's slot 0 <- cls_cache[slot_rows[r]].  Rows of both kinds mix in
- *   one launch; distinct slots as above. */
+ *   one launch; distinct slots as above.
+ *
+ * A ragged step (SeekerStreamPool.step_ragged): n sessions, session r with c_rows[r] >= 1 frames, F = sum of c_rows frames flat in session
+ * order: session r owns the flat frames first_rows[r] .. first_rows[r] + c_rows[r] - 1 (first_rows = exclusive prefix sum of c_rows), rows of
+ * qkv / out / x are f*S + s.  Per session device int32 [n]: t0_rows, slot_rows, first_rows, c_rows; per frame device int32 [F]: row_of_frame.
+ * tcow_attn_temporal_ragged_fwd: `step` = {B = 1, T = F, S, D, heads, causal, dtype}; k_cache / v_cache [n_slots, S-1, heads, T_total, 64].
+ *   One wave per (flat frame f, slot s, head h): r = row_of_frame[f], j = f - first_rows[r], t = t0_rows[r] + j; frame f's K / V line becomes
+ *   position t of block slot_rows[r]; its query attends to keys 0 .. t, keys < t0 from the cache, keys t0 .. t from the step's rows at flat
+ *   frame first + (t' - t0).  No wave reads a cache position that the launch writes.  Per session the results (out and caches) are bit-identical
+ *   to tcow_attn_temporal_pool_fwd of that session alone.  Slot-0 rows of out are zero.  A frame whose session has t0 < 0, t0 + c > T_total, a
+ *   slot outside [0, n_slots) or j outside [0, c) writes NaN to its own rows of out and touches no cache row.  Distinct slots as above.
+ *   causal 1 or 2, T_total <= TCOW_STREAM_MAX_FRAMES, n_slots >= 1, 1 <= n <= F.
+ * tcow_cls_ragged: x [F*S, D] f32, cls_cache [n_slots, D]; per session r: t0_rows[r] == 0: slot 0 of every frame of the session <- slot 0 of
+ *   its frame first_rows[r], and that row -> cls_cache[slot_rows[r]]; t0_rows[r] > 0: slot 0 of every frame of the session <- cls_cache[slot].
+ *   A slot outside [0, n_slots) writes NaN and touches no cache row. */
 #define TCOW_STREAM_MAX_FRAMES 1024
 int tcow_attn_temporal_cached_fwd(void* stream, const tcow_attn_shape* chunk, int T_total, const int* t0_dev, const void* qkv, void* k_cache,
                                   void* v_cache, void* out);
@@ -235,6 +249,11 @@ int tcow_cls_stream(void* stream, int B, int c, int S, int D, float* x, float* c
 int tcow_attn_temporal_pool_fwd(void* stream, const tcow_attn_shape* chunk, int T_total, int n_slots, const int* t0_rows, const int* slot_rows,
                                 const void* qkv, void* k_cache, void* v_cache, void* out);
 int tcow_cls_pool(void* stream, int n, int c, int S, int D, float* x, float* cls_cache, int n_slots, const int* t0_rows, const int* slot_rows);
+int tcow_attn_temporal_ragged_fwd(void* stream, const tcow_attn_shape* step, int n, int T_total, int n_slots, const int* t0_rows, const int* slot_rows,
+                                  const int* first_rows, const int* c_rows, const int* row_of_frame, const void* qkv, void* k_cache, void* v_cache,
+                                  void* out);
+int tcow_cls_ragged(void* stream, int n, int F, int S, int D, float* x, float* cls_cache, int n_slots, const int* t0_rows, const int* slot_rows,
+                    const int* first_rows, const int* c_rows);
 
 /* ------------------------------------------------------------------------------------------- token glue
  * tcow_im2col: cat([rgb (B,3,T,H,W), query (B,1,T,H,W)]) (mask_tracker.py:107-108), optional (rgb-0.45)/0.225

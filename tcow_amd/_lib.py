@@ -95,6 +95,8 @@ SIGNATURES = {
     'tcow_cls_stream': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'tcow_attn_temporal_pool_fwd': (_i, [_vp, _ash, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'tcow_cls_pool': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    'tcow_attn_temporal_ragged_fwd': (_i, [_vp, _ash, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'tcow_cls_ragged': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     'tcow_im2col': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     'tcow_gather_frames': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'tcow_resize_aa': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp]),
@@ -136,7 +138,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 12       # TCOW_ABI_VERSION of include/tcow_hip.h
+ABI_VERSION = 13       # TCOW_ABI_VERSION of include/tcow_hip.h
 
 
 def _declare(L, tolerant=False):

@@ -13,6 +13,10 @@
 // tcow_attn_temporal_pool_fwd / tcow_cls_pool (a pool of live sessions, SeekerStreamPool): the same two kernels with a t0 and a cache slot per
 // row.  Row r reads t0_rows[r * t0_stride] and works on cache block slot_rows[r]; a stream is the case "t0 broadcast (stride 0), slot = b
 // (no table)".  Rows of different t0 run key loops of different length; nothing else differs.
+//
+// tcow_attn_temporal_ragged_fwd / tcow_cls_ragged (SeekerStreamPool.step_ragged): sessions that bring different numbers of frames to one step.
+// The frames lie flat in session order; the attention kernel runs one wave per (flat frame, slot, head) on the per-frame body it shares with
+// temporal_cached_kernel (temporal_query_frame), so a long chunk spreads over as many waves as it has frames.
 #include <math.h>
 
 #include "attention_common.h"
@@ -47,6 +51,81 @@ template <> struct StreamVec<float> {
 
 __device__ __forceinline__ void copy16(void* dst, const void* src) { *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src); }
 
+// One query frame of a temporal stream step, shared by every kernel of this file so that they agree bit for bit: chunk frame j (flat frame
+// fb + j of the step's rows, fb = the chunk's first flat frame) stands at t = t0 + j and attends to keys 0 .. t, keys < t0 from the cache line
+// run at cbase, keys t0 .. t from the step's qkv rows at flat frame fb + (kt - t0).  Every lane of the wave calls it; lane group 0 stores.
+template <typename T>
+__device__ __forceinline__ void temporal_query_frame(const T* qkv, const T* kc, const T* vc, T* out, size_t cbase, int fb, int j, int t0, int S, int s, int D,
+                                                     int col, int grp) {
+    constexpr int VEC = StreamVec<T>::VEC, LPR = ATT_HD / VEC, G = 64 / LPR;
+    const long ld3 = 3L * D;
+    const float scale = 0.125f;      // head_dim ** -0.5 (vit.py:74)
+    const int t = t0 + j;            // query frame; keys 0 .. t (tril() of causal 1 and 2)
+    float q[VEC];
+    StreamVec<T>::ld(qkv + ((long)(fb + j) * S + s) * ld3 + col, q);
+    float m = -INFINITY, l = 0.f, acc[VEC];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) acc[e] = 0.f;
+    for (int k0 = 0; k0 <= t; k0 += G * ST_U) {
+        float kv[ST_U][VEC], vv[ST_U][VEC];
+#pragma unroll
+        for (int u = 0; u < ST_U; ++u) {
+            const int kt = k0 + u * G + grp;
+            if (kt <= t) {
+                const T* kp = kt < t0 ? kc + cbase + (size_t)kt * ATT_HD : qkv + ((long)(fb + kt - t0) * S + s) * ld3 + D + col;
+                const T* vp = kt < t0 ? vc + cbase + (size_t)kt * ATT_HD : qkv + ((long)(fb + kt - t0) * S + s) * ld3 + 2 * D + col;
+                StreamVec<T>::ld(kp, kv[u]);
+                StreamVec<T>::ld(vp, vv[u]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) { kv[u][e] = 0.f; vv[u][e] = 0.f; }
+            }
+        }
+        float sc[ST_U];
+        float mb = m;
+#pragma unroll
+        for (int u = 0; u < ST_U; ++u) {
+            float d = 0.f;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) d = fmaf(q[e], kv[u][e], d);
+#pragma unroll
+            for (int o = 1; o < LPR; o <<= 1) d += __shfl_xor(d, o, 64);
+            sc[u] = (k0 + u * G + grp <= t) ? d * scale : -INFINITY;
+            mb = fmaxf(mb, sc[u]);
+        }
+        // (a group without a key so far keeps m = -inf, l = 0, acc = 0: both factors below are then 0)
+        const float alpha = (m == -INFINITY) ? 0.f : expf(m - mb);
+        l *= alpha;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc[e] *= alpha;
+#pragma unroll
+        for (int u = 0; u < ST_U; ++u) {
+            const float p = (sc[u] == -INFINITY) ? 0.f : expf(sc[u] - mb);
+            l += p;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) acc[e] = fmaf(p, vv[u][e], acc[e]);
+        }
+        m = mb;
+    }
+    // merge the G groups' (m, l, acc): lanes with the same channel slice sit LPR apart
+#pragma unroll
+    for (int o = LPR; o < 64; o <<= 1) {
+        const float mo = __shfl_xor(m, o, 64), lo = __shfl_xor(l, o, 64);
+        const float mn = fmaxf(m, mo);
+        const float a = (m == -INFINITY) ? 0.f : expf(m - mn), bb = (mo == -INFINITY) ? 0.f : expf(mo - mn);
+        l = l * a + lo * bb;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) { const float ao = __shfl_xor(acc[e], o, 64); acc[e] = acc[e] * a + ao * bb; }
+        m = mn;
+    }
+    if (grp == 0) {
+        const float inv = 1.f / l;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc[e] *= inv;
+        StreamVec<T>::st(out + ((long)(fb + j) * S + s) * D + col, acc);
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(64 * ST_WAVES) void temporal_cached_kernel(int B, int c, int S, int D, int heads, int T_total, int n_slots,
                                                                        const int* __restrict__ t0_rows, int t0_stride, const int* __restrict__ slot_rows,
@@ -80,73 +159,59 @@ __global__ __launch_bounds__(64 * ST_WAVES) void temporal_cached_kernel(int B, i
         copy16(kc + cbase + (size_t)(t0 + j) * ATT_HD, src + D);
         copy16(vc + cbase + (size_t)(t0 + j) * ATT_HD, src + 2 * D);
     }
-    const float scale = 0.125f;      // head_dim ** -0.5 (vit.py:74)
-    for (int j = 0; j < c; ++j) {
-        const int t = t0 + j;            // query frame; keys 0 .. t (tril() of causal 1 and 2)
-        float q[VEC];
-        StreamVec<T>::ld(qkv + ((long)(b * c + j) * S + s) * ld3 + col, q);
-        float m = -INFINITY, l = 0.f, acc[VEC];
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) acc[e] = 0.f;
-        for (int k0 = 0; k0 <= t; k0 += G * ST_U) {
-            float kv[ST_U][VEC], vv[ST_U][VEC];
-#pragma unroll
-            for (int u = 0; u < ST_U; ++u) {
-                const int kt = k0 + u * G + grp;
-                if (kt <= t) {
-                    const T* kp = kt < t0 ? kc + cbase + (size_t)kt * ATT_HD : qkv + ((long)(b * c + kt - t0) * S + s) * ld3 + D + col;
-                    const T* vp = kt < t0 ? vc + cbase + (size_t)kt * ATT_HD : qkv + ((long)(b * c + kt - t0) * S + s) * ld3 + 2 * D + col;
-                    StreamVec<T>::ld(kp, kv[u]);
-                    StreamVec<T>::ld(vp, vv[u]);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < VEC; ++e) { kv[u][e] = 0.f; vv[u][e] = 0.f; }
-                }
-            }
-            float sc[ST_U];
-            float mb = m;
-#pragma unroll
-            for (int u = 0; u < ST_U; ++u) {
-                float d = 0.f;
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) d = fmaf(q[e], kv[u][e], d);
-#pragma unroll
-                for (int o = 1; o < LPR; o <<= 1) d += __shfl_xor(d, o, 64);
-                sc[u] = (k0 + u * G + grp <= t) ? d * scale : -INFINITY;
-                mb = fmaxf(mb, sc[u]);
-            }
-            // (a group without a key so far keeps m = -inf, l = 0, acc = 0: both factors below are then 0)
-            const float alpha = (m == -INFINITY) ? 0.f : expf(m - mb);
-            l *= alpha;
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) acc[e] *= alpha;
-#pragma unroll
-            for (int u = 0; u < ST_U; ++u) {
-                const float p = (sc[u] == -INFINITY) ? 0.f : expf(sc[u] - mb);
-                l += p;
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) acc[e] = fmaf(p, vv[u][e], acc[e]);
-            }
-            m = mb;
-        }
-        // merge the G groups' (m, l, acc): lanes with the same channel slice sit LPR apart
-#pragma unroll
-        for (int o = LPR; o < 64; o <<= 1) {
-            const float mo = __shfl_xor(m, o, 64), lo = __shfl_xor(l, o, 64);
-            const float mn = fmaxf(m, mo);
-            const float a = (m == -INFINITY) ? 0.f : expf(m - mn), bb = (mo == -INFINITY) ? 0.f : expf(mo - mn);
-            l = l * a + lo * bb;
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) { const float ao = __shfl_xor(acc[e], o, 64); acc[e] = acc[e] * a + ao * bb; }
-            m = mn;
-        }
+    for (int j = 0; j < c; ++j) temporal_query_frame<T>(qkv, kc, vc, out, cbase, b * c, j, t0, S, s, D, col, grp);
+}
+
+// One wave per (flat frame f, token slot s, head h) of a ragged step: n sessions, session r with c_rows[r] frames at flat frames
+// first_rows[r] .. first_rows[r] + c_rows[r] - 1 (row_of_frame[f] = r), standing at t0_rows[r] on cache block slot_rows[r].  The wave copies
+// frame f's own K / V line to cache position t = t0 + (f - first) and attends frame f's query to keys 0 .. t with temporal_query_frame, the
+// pool kernel's per-frame body.
+// INVARIANT: no wave reads a cache position that this launch writes.  The launch writes positions t0 .. t0+c-1 of a session's block; a wave
+// reads cache positions < t0 only and takes keys t0 .. t from the step's qkv rows (flat frame first + (kt - t0)).  That is what makes the
+// per-frame split race-free: the waves of one session share no cache position between a writer and a reader, and sessions have distinct slots.
+template <typename T>
+__global__ __launch_bounds__(64 * ST_WAVES) void temporal_ragged_kernel(int n, int F, int S, int D, int heads, int T_total, int n_slots,
+                                                                       const int* __restrict__ t0_rows, const int* __restrict__ slot_rows,
+                                                                       const int* __restrict__ first_rows, const int* __restrict__ c_rows,
+                                                                       const int* __restrict__ row_of_frame, const T* __restrict__ qkv, T* __restrict__ kc,
+                                                                       T* __restrict__ vc, T* __restrict__ out) {
+    constexpr int VEC = StreamVec<T>::VEC, LPR = ATT_HD / VEC;
+    const int lane = threadIdx.x & 63, grp = lane / LPR, sub = lane - grp * LPR;
+    const long item = (long)blockIdx.x * ST_WAVES + (threadIdx.x >> 6);
+    if (item >= (long)F * S * heads) return;
+    const int h = (int)(item % heads);
+    const long fs = item / heads;
+    const int s = (int)(fs % S), f = (int)(fs / S);
+    // (f is the same in every lane of the wave: the session's entries stay scalars)
+    const int r = __builtin_amdgcn_readfirstlane(row_of_frame[f]);
+    const bool bad_r = r < 0 || r >= n;             // (a table entry outside the step names no session: nothing of a session is read)
+    const int rr = bad_r ? 0 : r;
+    const int t0 = __builtin_amdgcn_readfirstlane(t0_rows[rr]);
+    const int slot = __builtin_amdgcn_readfirstlane(slot_rows[rr]);
+    const int first = __builtin_amdgcn_readfirstlane(first_rows[rr]);
+    const int c = __builtin_amdgcn_readfirstlane(c_rows[rr]);
+    const int j = f - first;
+    const int col = h * ATT_HD + sub * VEC;
+    // (first + c <= F: the keys t0 .. t of the chunk are read at flat frames first .. f, all inside the step when j is inside [0, c))
+    const bool bad = bad_r || t0 < 0 || c < 1 || t0 > T_total - c || slot < 0 || slot >= n_slots || j < 0 || j >= c || first < 0 || first > F - c;
+    if (s == 0 || bad) {
+        // slot 0: zero, as in the pool kernel.  A bad row writes NaN to this frame's own output row and touches no cache row.
         if (grp == 0) {
-            const float inv = 1.f / l;
+            float z[VEC];
 #pragma unroll
-            for (int e = 0; e < VEC; ++e) acc[e] *= inv;
-            StreamVec<T>::st(out + ((long)(b * c + j) * S + s) * D + col, acc);
+            for (int e = 0; e < VEC; ++e) z[e] = bad ? __builtin_nanf("") : 0.f;
+            StreamVec<T>::st(out + ((long)f * S + s) * D + col, z);
         }
+        return;
     }
+    const size_t cbase = ((((size_t)slot * (S - 1) + (s - 1)) * heads + h) * T_total) * ATT_HD + sub * VEC;
+    if (grp == 0) {
+        // append this frame's key / value: cache[t0 + j] = the frame's own row (bit copies)
+        const T* src = qkv + ((long)f * S + s) * (3L * D) + col;
+        copy16(kc + cbase + (size_t)(t0 + j) * ATT_HD, src + D);
+        copy16(vc + cbase + (size_t)(t0 + j) * ATT_HD, src + 2 * D);
+    }
+    temporal_query_frame<T>(qkv, kc, vc, out, cbase, first, j, t0, S, s, D, col, grp);
 }
 
 // causal_attention == 1 across chunks, per row b with t0 = t0_rows[b * t0_stride] and cache row slot = slot_rows ? slot_rows[b] : b.
@@ -165,6 +230,33 @@ __global__ void cls_stream_kernel(int B, int c, int S, int D, float* __restrict_
     if (slot < 0 || slot >= n_slots) {
         a.x = a.y = a.z = a.w = __builtin_nanf("");
     } else if (t0_rows[(long)b * t0_stride] == 0) {
+        a = ld4(base);
+        st4(cls_cache + (size_t)slot * D + ch, a);
+    } else {
+        a = ld4(cls_cache + (size_t)slot * D + ch);
+    }
+    for (int t = 0; t < c; ++t) st4(base + t * fs, a);
+}
+
+// cls_stream_kernel for a ragged step: session r owns the flat frames first_rows[r] .. first_rows[r] + c_rows[r] - 1.  One thread per
+// (session, 4 channels), looping over the session's frames: a thread per frame would read frame `first` while another wrote it.
+// t0 == 0: frame `first`'s slot-0 row to every frame of the session and to cls_cache[slot]; t0 > 0: cls_cache[slot] to slot 0 of every frame
+// of the session.  A slot outside [0, n_slots) writes NaN and touches no cache row; frames outside the step are not written.
+__global__ void cls_ragged_kernel(int n, int F, int S, int D, float* __restrict__ x, float* __restrict__ cls_cache, int n_slots,
+                                  const int* __restrict__ t0_rows, const int* __restrict__ slot_rows, const int* __restrict__ first_rows,
+                                  const int* __restrict__ c_rows) {
+    const int d4 = D / 4;
+    const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (i >= (long)n * d4) return;
+    const int r = (int)(i / d4), ch = (int)(i - (long)r * d4) * 4;
+    const int slot = slot_rows[r], first = first_rows[r], c = c_rows[r];
+    if (first < 0 || c < 1 || first > F - c) return;          // (the host builds the tables; a session outside the step owns no row of x)
+    float* base = x + (size_t)first * S * D + ch;
+    const size_t fs = (size_t)S * D;
+    float4 a;
+    if (slot < 0 || slot >= n_slots) {
+        a.x = a.y = a.z = a.w = __builtin_nanf("");
+    } else if (t0_rows[r] == 0) {
         a = ld4(base);
         st4(cls_cache + (size_t)slot * D + ch, a);
     } else {
@@ -193,6 +285,32 @@ int launch_temporal_cached(const char* who, void* stream, const tcow_attn_shape*
     else
         hipLaunchKernelGGL(temporal_cached_kernel<float>, grid, block, 0, (hipStream_t)stream, s.B, s.T, s.S, s.D, s.heads, T_total, n_slots, t0_rows,
                            t0_stride, slot_rows, (const float*)qkv, (float*)k_cache, (float*)v_cache, (float*)out);
+    TCOW_CHECK_LAUNCH();
+    return TCOW_OK;
+}
+
+// Argument checks (those of launch_temporal_cached, with F frames in place of B * c) and launch of temporal_ragged_kernel.
+int launch_temporal_ragged(const char* who, void* stream, const tcow_attn_shape* step, int n, int T_total, int n_slots, const int* t0_rows,
+                           const int* slot_rows, const int* first_rows, const int* c_rows, const int* row_of_frame, const void* qkv, void* k_cache,
+                           void* v_cache, void* out) {
+    TCOW_CHECK_ARG(step != nullptr, "%s: null shape", who);
+    const tcow_attn_shape& s = *step;
+    TCOW_CHECK_ARG(s.B == 1 && s.T > 0 && s.S > 1 && s.heads > 0 && n > 0 && n <= s.T, "%s: bad step shape B=%d F=%d S=%d heads=%d n=%d (B must be 1, 1 <= n <= F)",
+                   who, s.B, s.T, s.S, s.heads, n);
+    TCOW_CHECK_ARG(s.D == s.heads * ATT_HD, "%s: head_dim must be 64 (D=%d heads=%d)", who, s.D, s.heads);
+    TCOW_CHECK_ARG(s.causal == 1 || s.causal == 2, "%s: causal must be 1 or 2 (got %d): other masks let a frame see later frames", who, s.causal);
+    TCOW_CHECK_ARG(T_total >= 1 && T_total <= TCOW_STREAM_MAX_FRAMES, "%s: T_total=%d must be in [1, %d]", who, T_total, TCOW_STREAM_MAX_FRAMES);
+    TCOW_CHECK_ARG(s.dtype == TCOW_F32 || s.dtype == TCOW_BF16, "%s: dtype must be TCOW_F32 or TCOW_BF16 (got %d)", who, s.dtype);
+    TCOW_CHECK_ARG(n_slots >= 1, "%s: n_slots=%d must be >= 1", who, n_slots);
+    TCOW_CHECK_ARG(t0_rows && slot_rows && first_rows && c_rows && row_of_frame && qkv && k_cache && v_cache && out, "%s: null pointer", who);
+    const long items = (long)s.T * s.S * s.heads;
+    const dim3 grid((unsigned)cdiv(items, ST_WAVES)), block(64 * ST_WAVES);
+    if (s.dtype == TCOW_BF16)
+        hipLaunchKernelGGL(temporal_ragged_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, n, s.T, s.S, s.D, s.heads, T_total, n_slots, t0_rows, slot_rows,
+                           first_rows, c_rows, row_of_frame, (const bf16_t*)qkv, (bf16_t*)k_cache, (bf16_t*)v_cache, (bf16_t*)out);
+    else
+        hipLaunchKernelGGL(temporal_ragged_kernel<float>, grid, block, 0, (hipStream_t)stream, n, s.T, s.S, s.D, s.heads, T_total, n_slots, t0_rows, slot_rows,
+                           first_rows, c_rows, row_of_frame, (const float*)qkv, (float*)k_cache, (float*)v_cache, (float*)out);
     TCOW_CHECK_LAUNCH();
     return TCOW_OK;
 }
@@ -229,6 +347,23 @@ int tcow_cls_stream(void* stream, int B, int c, int S, int D, float* x, float* c
 int tcow_cls_pool(void* stream, int n, int c, int S, int D, float* x, float* cls_cache, int n_slots, const int* t0_rows, const int* slot_rows) {
     TCOW_CHECK_ARG(slot_rows != nullptr, "tcow_cls_pool: bad arguments");
     return launch_cls("tcow_cls_pool", stream, n, c, S, D, x, cls_cache, n_slots, t0_rows, 1, slot_rows);
+}
+
+int tcow_attn_temporal_ragged_fwd(void* stream, const tcow_attn_shape* step, int n, int T_total, int n_slots, const int* t0_rows, const int* slot_rows,
+                                  const int* first_rows, const int* c_rows, const int* row_of_frame, const void* qkv, void* k_cache, void* v_cache,
+                                  void* out) {
+    return launch_temporal_ragged("tcow_attn_temporal_ragged_fwd", stream, step, n, T_total, n_slots, t0_rows, slot_rows, first_rows, c_rows, row_of_frame,
+                                  qkv, k_cache, v_cache, out);
+}
+
+int tcow_cls_ragged(void* stream, int n, int F, int S, int D, float* x, float* cls_cache, int n_slots, const int* t0_rows, const int* slot_rows,
+                    const int* first_rows, const int* c_rows) {
+    TCOW_CHECK_ARG(n > 0 && F >= n && S > 1 && D > 0 && D % 4 == 0 && n_slots >= 1 && x && cls_cache && t0_rows && slot_rows && first_rows && c_rows,
+                   "tcow_cls_ragged: bad arguments");
+    hipLaunchKernelGGL(cls_ragged_kernel, dim3(cdiv((long)n * D / 4, 64)), dim3(64), 0, (hipStream_t)stream, n, F, S, D, x, cls_cache, n_slots, t0_rows,
+                       slot_rows, first_rows, c_rows);
+    TCOW_CHECK_LAUNCH();
+    return TCOW_OK;
 }
 
 }  // extern "C"

@@ -61,6 +61,14 @@ class OperandCache:
             self.copies[key] = build()
         return self.copies[key]
 
+    def longest(self, key, n, build):
+        """A constant whose shorter forms are prefixes of its longer ones (mask0 of one row of frames): ONE entry per key, rebuilt only when a longer
+        one is asked for; returns the first n elements."""
+        t = self.copies.get(key)
+        if t is None or t.numel() < n:
+            t = self.copies[key] = build(n)
+        return t[:n]
+
     def buffer(self, key, alloc):
         """Persistent gradient storage: allocated once per key, the same pointers every step."""
         if key not in self.buckets:

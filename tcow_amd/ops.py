@@ -239,6 +239,46 @@ def cls_pool(x, n, c, S, cls_cache, n_slots, t0_rows, slot_rows):
     return x
 
 
+def _ragged_tables(who, n, F, t0_rows, slot_rows, first_rows, c_rows, row_of_frame=None):
+    """What a host can check of a ragged step's tables: on the device, int32, one entry per session (per frame: row_of_frame)."""
+    for name, t, want in (('t0_rows', t0_rows, n), ('slot_rows', slot_rows, n), ('first_rows', first_rows, n), ('c_rows', c_rows, n),
+                          ('row_of_frame', row_of_frame, F)):
+        if t is None and name == 'row_of_frame':
+            continue
+        _need_cuda(t)
+        if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != want or not t.is_contiguous():
+            raise L.TcowError(f'{who}: {name} must be a contiguous int32 tensor of {want} entries (n = {n} sessions, F = {F} frames), got '
+                              f'{t.dtype} {tuple(t.shape)}')
+
+
+def attn_temporal_ragged(mode, n, F, S, D, heads, causal, T_total, n_slots, t0_rows, slot_rows, first_rows, c_rows, row_of_frame, qkv, k_cache, v_cache,
+                         out):
+    """attn_temporal_pool for n sessions that bring different numbers of frames: session r owns the flat frames first_rows[r] .. + c_rows[r] - 1 of
+    the step's F frames (qkv [F*S, 3D] -> out [F*S, D]), row_of_frame[f] names the session of frame f (int32 device tensors [n] / [F]); one wave per
+    frame, bit-identical per session to attn_temporal_pool (see tcow_attn_temporal_ragged_fwd)."""
+    _need_cuda(qkv, k_cache, v_cache, out)
+    _ragged_tables('attn_temporal_ragged', n, F, t0_rows, slot_rows, first_rows, c_rows, row_of_frame)
+    if qkv.shape[0] != F * S or out.shape[0] != F * S:
+        raise L.TcowError(f'attn_temporal_ragged: qkv / out must have F * S = {F * S} rows, got {qkv.shape[0]} / {out.shape[0]}')
+    lib, dm = _sel(mode)
+    sh = L.AttnShape(1, F, S, D, heads, int(causal), F32 if dm == F32X3 else dm)
+    L.check(lib.tcow_attn_temporal_ragged_fwd(_stream(), ctypes.byref(sh), int(n), int(T_total), int(n_slots), t0_rows.data_ptr(), slot_rows.data_ptr(),
+                                              first_rows.data_ptr(), c_rows.data_ptr(), row_of_frame.data_ptr(), qkv.data_ptr(), k_cache.data_ptr(),
+                                              v_cache.data_ptr(), out.data_ptr()), 'tcow_attn_temporal_ragged_fwd', lib)
+    return out
+
+
+def cls_ragged(x, n, F, S, cls_cache, n_slots, t0_rows, slot_rows, first_rows, c_rows):
+    """cls_pool for sessions of different chunk lengths: x [F*S, D]; session r's frames are first_rows[r] .. + c_rows[r] - 1 (see tcow_cls_ragged)."""
+    _need_cuda(x, cls_cache)
+    _ragged_tables('cls_ragged', n, F, t0_rows, slot_rows, first_rows, c_rows)
+    if x.shape[0] != F * S:
+        raise L.TcowError(f'cls_ragged: x must have F * S = {F * S} rows, got {x.shape[0]}')
+    L.check(L.lib().tcow_cls_ragged(_stream(), int(n), int(F), S, x.shape[1], x.data_ptr(), cls_cache.data_ptr(), int(n_slots), t0_rows.data_ptr(),
+                                    slot_rows.data_ptr(), first_rows.data_ptr(), c_rows.data_ptr()), 'tcow_cls_ragged')
+    return x
+
+
 def im2col(mode, rgb, query, P, pretrained_norm, out):
     B, _, T, H, W = rgb.shape
     L.check(_sel(mode)[0].tcow_im2col(_stream(), _sel(mode)[1], B, T, H, W, P, rgb.data_ptr(), query.data_ptr(), int(pretrained_norm), out.data_ptr()), 'tcow_im2col', _sel(mode)[0])

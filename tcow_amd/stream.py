@@ -20,6 +20,11 @@ SeekerStreamPool (net.stream_pool(capacity)): live sessions that started at diff
 depend on a row's own frame index only, so a pool step is one Seeker step whose rows each carry their own t0 and their own cache slot
 (tcow_attn_temporal_pool_fwd, tcow_cls_pool; the time rows are gathered per row).  The pool holds the state of `capacity` one-row streams:
 per block K / V caches [capacity, S-1, heads, T, 64] and one cls row per slot.  Pool steps run eagerly.
+
+pool.step_ragged(ids, rgbs, query_masks): the sessions of one step bring different numbers of frames (cameras at different rates, a decoder's
+GOP, a session that catches up or prefills its history while its neighbours advance by one).  The step's F = sum of the c_i frames lie flat
+in session order and run as ONE row of F frames; ragged_tables() gives every session its t0, slot, first flat frame and chunk length and every
+frame its session, and the two substitutions are tcow_attn_temporal_ragged_fwd (one wave per frame, not per session) and tcow_cls_ragged.
 """
 import torch
 
@@ -29,10 +34,12 @@ from ._lib import TcowError
 
 class _StepState:
     """What engine.run_forward substitutes for a stream step."""
-    __slots__ = ('T_total', 't0_dev', 'pos', 'time_rows', 'k_cache', 'v_cache', 'cls_cache', 't0_rows', 'slot_rows', 'n_slots')
+    __slots__ = ('T_total', 't0_dev', 'pos', 'time_rows', 'k_cache', 'v_cache', 'cls_cache', 't0_rows', 'slot_rows', 'n_slots', 'first_rows', 'c_rows',
+                 'row_of_frame')
 
     def __init__(self):
         self.t0_rows = self.slot_rows = self.n_slots = None       # set by a pool step only: a frame index and a cache slot per row
+        self.first_rows = self.c_rows = self.row_of_frame = None  # set by a ragged pool step only: a first flat frame and a chunk length per session, a session per frame
 
 
 def check_streamable(module):
@@ -78,13 +85,22 @@ def _cache_bytes(st):
     return sum(t.numel() * t.element_size() for t in (st.k_cache, st.v_cache, st.cls_cache))
 
 
-def _check_step(who, module, sig, device, clips, rows, rgb, query_mask):
-    """The checks of a step that do not depend on where its rows stand; returns the chunk length c."""
-    m = module
-    check_streamable(m)
-    if _signature(m) != sig:
+def _check_module(module, sig):
+    """The module can still be streamed and is the one the caches were filled by."""
+    check_streamable(module)
+    if _signature(module) != sig:
         raise TcowError('stream: a parameter (or the precision) changed since the stream was opened; the cached keys / values belong to the old '
                         'weights -- open a new stream')
+
+
+def _check_step(who, module, sig, device, clips, rows, rgb, query_mask):
+    """The checks of a step that do not depend on where its rows stand; returns the chunk length c."""
+    _check_module(module, sig)
+    return _check_inputs(who, module, device, clips, rows, rgb, query_mask)
+
+
+def _check_inputs(who, m, device, clips, rows, rgb, query_mask):
+    """Shapes and devices of a step's frames (rgb of `clips` clips, query masks of `rows` query rows); returns the chunk length c."""
     if not torch.is_tensor(rgb) or rgb.dim() != 5 or rgb.shape[0] != clips or rgb.shape[1] != 3 or rgb.shape[2] < 1 \
             or rgb.shape[3] != m.frame_height or rgb.shape[4] != m.frame_width:
         raise TcowError(f'{who}: rgb must be ({clips}, 3, c >= 1, {m.frame_height}, {m.frame_width}), got '
@@ -97,6 +113,53 @@ def _check_step(who, module, sig, device, clips, rows, rgb, query_mask):
         if t is not None and (not t.is_cuda or t.device != device):
             raise TcowError(f'{who}: inputs must be on the stream device {device}, got {t.device}')
     return c
+
+
+def ragged_tables(t0s, slots, cs):
+    """The tables of a ragged step, as lists of ints: n sessions, session r at frame t0s[r] on cache slot slots[r] with cs[r] >= 1 new frames.
+    The F = sum(cs) frames lie flat in session order.  Returns a dictionary with, per session, 't0', 'slot', 'first' (its first flat frame: the
+    exclusive prefix sum of cs) and 'c', and per flat frame 'row_of_frame' (its session) and 'frames' (its index in the stream, t0 + j: the row
+    of the time table it takes)."""
+    t0s, slots, cs = [int(v) for v in t0s], [int(v) for v in slots], [int(v) for v in cs]
+    if not (len(t0s) == len(slots) == len(cs)) or not cs:
+        raise TcowError(f'ragged_tables: {len(t0s)} t0 / {len(slots)} slots / {len(cs)} chunk lengths: one of each per session, at least one session')
+    if min(cs) < 1:
+        raise TcowError(f'ragged_tables: chunk lengths must be >= 1, got {cs}')
+    first, row_of_frame, frames, f = [], [], [], 0
+    for r, (t0, c) in enumerate(zip(t0s, cs)):
+        first.append(f)
+        row_of_frame += [r] * c
+        frames += range(t0, t0 + c)
+        f += c
+    return {'t0': t0s, 'slot': slots, 'first': first, 'c': cs, 'row_of_frame': row_of_frame, 'frames': frames}
+
+
+def check_ragged_sessions(ids, n_rgbs, n_masks, capacity, open_ids):
+    """The checks of step_ragged that look at the lists alone: 1 .. capacity sessions, one rgb entry (and one query-mask entry, unless the list
+    is None: n_masks None) per session, every id open, none twice.  Returns the ids as a list."""
+    ids = list(ids)
+    n = len(ids)
+    if n < 1 or n > capacity:
+        raise TcowError(f'stream_pool.step_ragged: {n} sessions given; a step takes 1 .. capacity = {capacity}')
+    if n_rgbs != n or (n_masks is not None and n_masks != n):
+        raise TcowError(f'stream_pool.step_ragged: {n} ids, {n_rgbs} rgb entries' + ('' if n_masks is None else f', {n_masks} query_masks entries')
+                        + ': the lengths must agree (one entry per session)')
+    seen = set()
+    for sid in ids:
+        if sid not in open_ids:
+            raise TcowError(f'stream_pool: session {sid!r} is not open (unknown or closed id)')
+        if sid in seen:
+            raise TcowError(f'stream_pool.step_ragged: duplicate session {sid!r}: a session is one run of frames of a step')
+        seen.add(sid)
+    return ids
+
+
+def check_ragged_range(ids, t0s, cs, T):
+    """No session runs past the last frame: frames_done + c_i <= T for every session, the offender named."""
+    for sid, t0, c in zip(ids, t0s, cs):
+        if t0 + c > T:
+            raise TcowError(f'stream_pool.step_ragged: session {sid}: frames {t0}..{t0 + c - 1} run past the last frame {T - 1} of the stream '
+                            f'(num_total_frames = {T}); reset() or close() it')
 
 
 class SeekerStream:
@@ -194,7 +257,8 @@ class SeekerStream:
 
 class SeekerStreamPool:
     """net.stream_pool(capacity) of Seeker / QueryMaskTracker: up to `capacity` live sessions (one clip and one query mask each) that stand at
-    different frames, stepped together; see the module docstring.  open() -> id, step(ids, rgb, query_mask), close(id)."""
+    different frames, stepped together; see the module docstring.  open() -> id, step(ids, rgb, query_mask) (one chunk length for all) or
+    step_ragged(ids, rgbs, query_masks) (a chunk length per session), close(id)."""
 
     def __init__(self, module, capacity):
         module = getattr(module, 'seeker', module)
@@ -208,6 +272,8 @@ class SeekerStreamPool:
         st, self._time, g = _new_state(module, capacity)
         st.n_slots = capacity
         self._st = st
+        rg = self._st_ragged = _StepState()        # the state of a ragged step: the same caches, its own tables (step() never sees them)
+        rg.T_total, rg.n_slots, rg.pos, rg.k_cache, rg.v_cache, rg.cls_cache = st.T_total, st.n_slots, st.pos, st.k_cache, st.v_cache, st.cls_cache
         self.device = st.pos.device
         self._sig = _signature(module)
         self._slot = {}                 # open session id -> cache slot
@@ -282,3 +348,43 @@ class SeekerStreamPool:
         for sid in ids:
             self._done[sid] += c
         return out_mask, (flags if m.flag_channels > 0 else None)
+
+    def step_ragged(self, ids, rgbs, query_masks=None):
+        """ids: n distinct open sessions, at any phases; rgbs: n tensors (1, 3, c_i, H, W), the next c_i >= 1 frames of each session (the c_i need
+        not be equal); query_masks: None, or n entries, each None (all zeros) or (1, 1, c_i, H, W) -> (a list of n mask-logit tensors
+        (1, Co, c_i, H, W) f32, a list of n flag tensors (1, c_i, F) or None), in the order of `ids`.  The outputs are slices of buffers allocated
+        for this step and owned by the caller.  The whole step is ONE Seeker step over the sum of the c_i frames.  Every check runs before anything
+        is launched: a refused step leaves every session where it was."""
+        m = self.module
+        rgbs = list(rgbs)
+        qms = None if query_masks is None else list(query_masks)
+        ids = check_ragged_sessions(ids, len(rgbs), None if qms is None else len(qms), self.capacity, self._slot)
+        n = len(ids)
+        _check_module(m, self._sig)
+        cs = [_check_inputs(f'stream_pool.step_ragged: session {sid}', m, self.device, 1, 1, rgbs[k], None if qms is None else qms[k])
+              for k, sid in enumerate(ids)]
+        t0s = [self._done[sid] for sid in ids]
+        check_ragged_range(ids, t0s, cs, self.T)
+        tab = ragged_tables(t0s, [self._slot[sid] for sid in ids], cs)
+        F = len(tab['frames'])
+        st = self._st_ragged
+        with torch.no_grad(), torch.cuda.device(self.device):
+            # all six tables in one host-to-device copy: [t0 | slot | first | c] per session, [row_of_frame | frames] per flat frame
+            dev = torch.tensor(tab['t0'] + tab['slot'] + tab['first'] + tab['c'] + tab['row_of_frame'] + tab['frames'], dtype=torch.int32).to(self.device)
+            st.t0_rows, st.slot_rows, st.first_rows, st.c_rows = dev[0:n], dev[n:2 * n], dev[2 * n:3 * n], dev[3 * n:4 * n]
+            st.row_of_frame = dev[4 * n:4 * n + F]
+            st.time_rows = self._time.index_select(0, dev[4 * n + F:])             # [F, D]: flat frame f = time row t0 + j of its session
+            H, W = m.frame_height, m.frame_width
+            rgb32 = rgbs[0].to(torch.float32).contiguous() if n == 1 else torch.cat([r.to(torch.float32) for r in rgbs], 2)
+            if qms is not None and all(q is not None for q in qms):
+                qm32 = qms[0].to(torch.float32).contiguous() if n == 1 else torch.cat([q.to(torch.float32) for q in qms], 2)
+            else:
+                qm32 = torch.zeros(1, 1, F, H, W, dtype=torch.float32, device=self.device)
+                for q, f0, c in zip(qms or (), tab['first'], cs):
+                    if q is not None:
+                        qm32[:, :, f0:f0 + c] = q
+            out_mask, flags, _ = engine.run_forward(m, rgb32, qm32, m.param_list(), save=False, stream=st)
+        for sid, c in zip(ids, cs):
+            self._done[sid] += c
+        masks = [out_mask[:, :, f0:f0 + c] for f0, c in zip(tab['first'], cs)]
+        return masks, ([flags[:, f0:f0 + c] for f0, c in zip(tab['first'], cs)] if m.flag_channels > 0 else None)

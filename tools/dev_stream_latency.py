@@ -8,6 +8,9 @@
     python tools/dev_stream_latency.py --pool --out profiles/stream_pool_latency.json
                                         # eight live sessions at configs[1]: one pool step at eight different t0 against the in-phase B = 8 stream
                                         # step and against eight one-session steps, the three legs alternating in one run
+    python tools/dev_stream_latency.py --ragged --out profiles/stream_ragged_latency.json
+                                        # the same eight sessions with chunk lengths 1, 1, 1, 1, 2, 2, 4, 8 in one tick: one step_ragged against one
+                                        # pool.step per distinct length, and step_ragged with every length 1 against pool.step
 
 Times are device events around each call after warm-up, profiler off.  A step at a given t0 is timed by setting the stream's host frame counter
 (the kernels then read t0 from the device scalar the step writes): the work of a step depends on t0, not on what the cache holds.  Synthetic
@@ -146,6 +149,78 @@ def pool_leg(reps):
     return res
 
 
+RAGGED_CHUNKS = [1, 1, 1, 1, 2, 2, 4, 8]
+
+
+def ragged_leg(reps):
+    """Eight sessions at configs[1], bf16, at the spread t0 of pool_leg, the four legs taken in turn `reps` times: (a) one step_ragged with chunk
+    lengths RAGGED_CHUNKS (a t0 is moved back where t0 + c would pass the last frame), (b) the same tick as one pool.step per distinct chunk
+    length (four calls), (c) one step_ragged with every chunk length 1, (d) pool.step on the same eight sessions.  Spreads are max - min of a
+    leg's own samples in this run."""
+    name, n = 'configs1', POOL_SESSIONS
+    T, H, W = CONFIGS[name]
+    net = build(T, H, W, 'bf16')
+    rgb, qm = inputs(n, T, H, W)
+    t0s = [round(k * (T - 1) / (n - 1)) for k in range(n)]
+    cs = RAGGED_CHUNKS
+    t0s_a = [min(t0, T - c) for t0, c in zip(t0s, cs)]
+    f = lambda x, t0, c=1: x[:, :, t0:t0 + c]
+    with torch.no_grad():
+        pool = net.stream_pool(n)
+        ids = [pool.open() for _ in range(n)]
+        for t in range(T):                                    # warm-up: the whole clip once (fills every cache row)
+            pool.step(ids, f(rgb, t), f(qm, t))
+        rgbs_a = [f(rgb[k:k + 1], t0, c).contiguous() for k, (t0, c) in enumerate(zip(t0s_a, cs))]
+        qms_a = [f(qm[k:k + 1], t0, c).contiguous() for k, (t0, c) in enumerate(zip(t0s_a, cs))]
+        groups = [(c, [k for k in range(n) if cs[k] == c]) for c in sorted(set(cs))]
+        rgb_b = [torch.cat([rgbs_a[k] for k in ks], 0) for _, ks in groups]
+        qm_b = [torch.cat([qms_a[k] for k in ks], 0) for _, ks in groups]
+        rgbs_c = [f(rgb[k:k + 1], t0).contiguous() for k, t0 in enumerate(t0s)]
+        qms_c = [f(qm[k:k + 1], t0).contiguous() for k, t0 in enumerate(t0s)]
+        rgb_d, qm_d = torch.cat(rgbs_c, 0), torch.cat(qms_c, 0)
+
+        def at(t0_list):
+            for sid, t0 in zip(ids, t0_list):
+                pool._done[sid] = t0                         # (the step's work depends on t0, not on what the cache holds)
+
+        def leg_a():
+            at(t0s_a)
+            pool.step_ragged(ids, rgbs_a, qms_a)
+
+        def leg_b():
+            at(t0s_a)
+            for (c, ks), r, q in zip(groups, rgb_b, qm_b):
+                pool.step([ids[k] for k in ks], r, q)
+
+        def leg_c():
+            at(t0s)
+            pool.step_ragged(ids, rgbs_c, qms_c)
+
+        def leg_d():
+            at(t0s)
+            pool.step(ids, rgb_d, qm_d)
+
+        legs = {'a_ragged_step_ms': leg_a, 'b_pool_step_per_length_ms': leg_b, 'c_ragged_step_all_one_ms': leg_c, 'd_pool_step_ms': leg_d}
+        samples = {k: [] for k in legs}
+        for fn in legs.values():
+            for _ in range(3):
+                fn()
+        for _ in range(reps):
+            for k, fn in legs.items():
+                samples[k].append(ev_time(fn, 1))
+    res = {'config': name, 'T': T, 'H': H, 'W': W, 'sessions': n, 'precision': 'bf16', 'reps': reps, 'chunk_lengths': cs, 't0_rows_a_b': t0s_a,
+           't0_rows_c_d': t0s, 'pool_steps_in_b': len(groups)}
+    for k, v in samples.items():
+        v = sorted(v)
+        res[k] = {'median': v[len(v) // 2], 'min': v[0], 'max': v[-1]}
+    a, b, c, d = (res[k]['median'] for k in legs)
+    b_spread = res['b_pool_step_per_length_ms']['max'] - res['b_pool_step_per_length_ms']['min']
+    d_spread = res['d_pool_step_ms']['max'] - res['d_pool_step_ms']['min']
+    res.update(b_spread_ms=b_spread, b_minus_a_ms=b - a, a_below_b_by_more_than_b_spread=bool(b - a > b_spread), a_over_b=a / b,
+               d_spread_ms=d_spread, c_minus_d_ms=c - d, c_not_above_d_by_more_than_d_spread=bool(c - d <= d_spread))
+    return res
+
+
 KPROF_WARMUP, KPROF_STEPS = 3, 20
 STEP_LAST_KERNEL = 'flags_fwd_kernel'      # the last launch of every step (the flags head, engine.run_forward)
 
@@ -215,6 +290,7 @@ def main():
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--kprof', action='store_true')
     ap.add_argument('--pool', action='store_true', help='the stream-pool leg (eight sessions at configs1)')
+    ap.add_argument('--ragged', action='store_true', help='the ragged-step leg (eight sessions at configs1, chunk lengths 1, 1, 1, 1, 2, 2, 4, 8)')
     ap.add_argument('--kstats', default=None, metavar='KERNEL_TRACE_CSV')
     ap.add_argument('--only', default=None, help='comma list of configs1_b1, configs1_b8, configs3_b1')
     a = ap.parse_args()
@@ -229,6 +305,14 @@ def main():
     if a.pool:
         out = {'device': torch.cuda.get_device_name(0), 'pool': pool_leg(a.reps)}
         print(json.dumps(out['pool']), flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, 'w') as f:
+                json.dump(out, f, indent=1)
+        return
+    if a.ragged:
+        out = {'device': torch.cuda.get_device_name(0), 'ragged': ragged_leg(a.reps)}
+        print(json.dumps(out['ragged']), flush=True)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, 'w') as f:

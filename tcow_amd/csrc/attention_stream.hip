@@ -214,9 +214,24 @@ __global__ __launch_bounds__(64 * ST_WAVES) void temporal_ragged_kernel(int n, i
     temporal_query_frame<T>(qkv, kc, vc, out, cbase, first, j, t0, S, s, D, col, grp);
 }
 
-// causal_attention == 1 across chunks, per row b with t0 = t0_rows[b * t0_stride] and cache row slot = slot_rows ? slot_rows[b] : b.
-// t0 == 0: tcow_cls_merge mode 1 on the chunk (frame 0's slot-0 row to every frame), the row kept in cls_cache[slot]; t0 > 0: cls_cache[slot]
-// to slot 0 of every chunk frame.  A slot outside [0, n_slots) writes NaN and touches no cache row.  One thread per (b, 4 channels).
+// causal_attention == 1 across chunks, for one session and 4 channels: `base` is slot 0 of the session's first frame of this step (these 4
+// channels), its c frames lie fs floats apart, cls_cache + at is the session's cache row (these 4 channels).  t0 == 0: tcow_cls_merge mode 1 on the chunk
+// (frame 0's slot-0 row to every frame), the row kept in the cache; t0 > 0: the cache row to slot 0 of every chunk frame.  A slot outside
+// [0, n_slots) writes NaN and touches no cache row.
+__device__ __forceinline__ void cls_session(int slot, int n_slots, int t0, float* base, int c, size_t fs, float* cls_cache, size_t at) {
+    float4 a;
+    if (slot < 0 || slot >= n_slots) {
+        a.x = a.y = a.z = a.w = __builtin_nanf("");
+    } else if (t0 == 0) {
+        a = ld4(base);
+        st4(cls_cache + at, a);
+    } else {
+        a = ld4(cls_cache + at);
+    }
+    for (int t = 0; t < c; ++t) st4(base + t * fs, a);
+}
+
+// Row b is a session of c frames with t0 = t0_rows[b * t0_stride] and cache row slot = slot_rows ? slot_rows[b] : b.  One thread per (b, 4 channels).
 __global__ void cls_stream_kernel(int B, int c, int S, int D, float* __restrict__ x, float* __restrict__ cls_cache, int n_slots,
                                   const int* __restrict__ t0_rows, int t0_stride, const int* __restrict__ slot_rows) {
     const int d4 = D / 4;
@@ -224,24 +239,11 @@ __global__ void cls_stream_kernel(int B, int c, int S, int D, float* __restrict_
     if (i >= (long)B * d4) return;
     const int b = (int)(i / d4), ch = (int)(i - (long)b * d4) * 4;
     const int slot = slot_rows ? slot_rows[b] : b;
-    float* base = x + (size_t)b * c * S * D + ch;
-    const size_t fs = (size_t)S * D;
-    float4 a;
-    if (slot < 0 || slot >= n_slots) {
-        a.x = a.y = a.z = a.w = __builtin_nanf("");
-    } else if (t0_rows[(long)b * t0_stride] == 0) {
-        a = ld4(base);
-        st4(cls_cache + (size_t)slot * D + ch, a);
-    } else {
-        a = ld4(cls_cache + (size_t)slot * D + ch);
-    }
-    for (int t = 0; t < c; ++t) st4(base + t * fs, a);
+    cls_session(slot, n_slots, t0_rows[(long)b * t0_stride], x + (size_t)b * c * S * D + ch, c, (size_t)S * D, cls_cache, (size_t)slot * D + ch);
 }
 
-// cls_stream_kernel for a ragged step: session r owns the flat frames first_rows[r] .. first_rows[r] + c_rows[r] - 1.  One thread per
-// (session, 4 channels), looping over the session's frames: a thread per frame would read frame `first` while another wrote it.
-// t0 == 0: frame `first`'s slot-0 row to every frame of the session and to cls_cache[slot]; t0 > 0: cls_cache[slot] to slot 0 of every frame
-// of the session.  A slot outside [0, n_slots) writes NaN and touches no cache row; frames outside the step are not written.
+// A ragged step: session r owns the flat frames first_rows[r] .. first_rows[r] + c_rows[r] - 1.  One thread per (session, 4 channels), looping
+// over the session's frames: a thread per frame would read frame `first` while another wrote it.  Frames outside the step are not written.
 __global__ void cls_ragged_kernel(int n, int F, int S, int D, float* __restrict__ x, float* __restrict__ cls_cache, int n_slots,
                                   const int* __restrict__ t0_rows, const int* __restrict__ slot_rows, const int* __restrict__ first_rows,
                                   const int* __restrict__ c_rows) {
@@ -251,18 +253,19 @@ __global__ void cls_ragged_kernel(int n, int F, int S, int D, float* __restrict_
     const int r = (int)(i / d4), ch = (int)(i - (long)r * d4) * 4;
     const int slot = slot_rows[r], first = first_rows[r], c = c_rows[r];
     if (first < 0 || c < 1 || first > F - c) return;          // (the host builds the tables; a session outside the step owns no row of x)
-    float* base = x + (size_t)first * S * D + ch;
-    const size_t fs = (size_t)S * D;
-    float4 a;
-    if (slot < 0 || slot >= n_slots) {
-        a.x = a.y = a.z = a.w = __builtin_nanf("");
-    } else if (t0_rows[r] == 0) {
-        a = ld4(base);
-        st4(cls_cache + (size_t)slot * D + ch, a);
-    } else {
-        a = ld4(cls_cache + (size_t)slot * D + ch);
-    }
-    for (int t = 0; t < c; ++t) st4(base + t * fs, a);
+    cls_session(slot, n_slots, t0_rows[r], x + (size_t)first * S * D + ch, c, (size_t)S * D, cls_cache, (size_t)slot * D + ch);
+}
+
+// What both temporal launchers ask of their arguments: a step of s.T >= 1 frames per row, head_dim 64, a causal mask, a stream of
+// T_min .. TCOW_STREAM_MAX_FRAMES frames, a storage type of this file and at least one cache slot.
+int check_temporal_args(const char* who, const tcow_attn_shape& s, int T_min, int T_total, int n_slots) {
+    TCOW_CHECK_ARG(s.B > 0 && s.T > 0 && s.S > 1 && s.heads > 0, "%s: bad step shape B=%d T=%d S=%d heads=%d", who, s.B, s.T, s.S, s.heads);
+    TCOW_CHECK_ARG(s.D == s.heads * ATT_HD, "%s: head_dim must be 64 (D=%d heads=%d)", who, s.D, s.heads);
+    TCOW_CHECK_ARG(s.causal == 1 || s.causal == 2, "%s: causal must be 1 or 2 (got %d): other masks let a frame see later frames", who, s.causal);
+    TCOW_CHECK_ARG(T_total >= T_min && T_total <= TCOW_STREAM_MAX_FRAMES, "%s: T_total=%d must be in [%d, %d]", who, T_total, T_min, TCOW_STREAM_MAX_FRAMES);
+    TCOW_CHECK_ARG(s.dtype == TCOW_F32 || s.dtype == TCOW_BF16, "%s: dtype must be TCOW_F32 or TCOW_BF16 (got %d)", who, s.dtype);
+    TCOW_CHECK_ARG(n_slots >= 1, "%s: n_slots=%d must be >= 1", who, n_slots);
+    return TCOW_OK;
 }
 
 // Argument checks and launch of temporal_cached_kernel, shared by the stream (t0 broadcast, slot = b) and the pool entry point.
@@ -270,12 +273,7 @@ int launch_temporal_cached(const char* who, void* stream, const tcow_attn_shape*
                            const int* slot_rows, const void* qkv, void* k_cache, void* v_cache, void* out) {
     TCOW_CHECK_ARG(chunk != nullptr, "%s: null shape", who);
     const tcow_attn_shape& s = *chunk;
-    TCOW_CHECK_ARG(s.B > 0 && s.T > 0 && s.S > 1 && s.heads > 0, "%s: bad chunk shape B=%d c=%d S=%d heads=%d", who, s.B, s.T, s.S, s.heads);
-    TCOW_CHECK_ARG(s.D == s.heads * ATT_HD, "%s: head_dim must be 64 (D=%d heads=%d)", who, s.D, s.heads);
-    TCOW_CHECK_ARG(s.causal == 1 || s.causal == 2, "%s: causal must be 1 or 2 (got %d): other masks let a frame see later frames", who, s.causal);
-    TCOW_CHECK_ARG(T_total >= s.T && T_total <= TCOW_STREAM_MAX_FRAMES, "%s: T_total=%d must be in [c=%d, %d]", who, T_total, s.T, TCOW_STREAM_MAX_FRAMES);
-    TCOW_CHECK_ARG(s.dtype == TCOW_F32 || s.dtype == TCOW_BF16, "%s: dtype must be TCOW_F32 or TCOW_BF16 (got %d)", who, s.dtype);
-    TCOW_CHECK_ARG(n_slots >= 1, "%s: n_slots=%d must be >= 1", who, n_slots);
+    if (const int err = check_temporal_args(who, s, s.T, T_total, n_slots)) return err;        // (the cache holds the chunk: T_total >= c)
     TCOW_CHECK_ARG(t0_rows && qkv && k_cache && v_cache && out, "%s: null pointer", who);
     const long items = (long)s.B * s.S * s.heads;
     const dim3 grid((unsigned)cdiv(items, ST_WAVES)), block(64 * ST_WAVES);
@@ -285,32 +283,6 @@ int launch_temporal_cached(const char* who, void* stream, const tcow_attn_shape*
     else
         hipLaunchKernelGGL(temporal_cached_kernel<float>, grid, block, 0, (hipStream_t)stream, s.B, s.T, s.S, s.D, s.heads, T_total, n_slots, t0_rows,
                            t0_stride, slot_rows, (const float*)qkv, (float*)k_cache, (float*)v_cache, (float*)out);
-    TCOW_CHECK_LAUNCH();
-    return TCOW_OK;
-}
-
-// Argument checks (those of launch_temporal_cached, with F frames in place of B * c) and launch of temporal_ragged_kernel.
-int launch_temporal_ragged(const char* who, void* stream, const tcow_attn_shape* step, int n, int T_total, int n_slots, const int* t0_rows,
-                           const int* slot_rows, const int* first_rows, const int* c_rows, const int* row_of_frame, const void* qkv, void* k_cache,
-                           void* v_cache, void* out) {
-    TCOW_CHECK_ARG(step != nullptr, "%s: null shape", who);
-    const tcow_attn_shape& s = *step;
-    TCOW_CHECK_ARG(s.B == 1 && s.T > 0 && s.S > 1 && s.heads > 0 && n > 0 && n <= s.T, "%s: bad step shape B=%d F=%d S=%d heads=%d n=%d (B must be 1, 1 <= n <= F)",
-                   who, s.B, s.T, s.S, s.heads, n);
-    TCOW_CHECK_ARG(s.D == s.heads * ATT_HD, "%s: head_dim must be 64 (D=%d heads=%d)", who, s.D, s.heads);
-    TCOW_CHECK_ARG(s.causal == 1 || s.causal == 2, "%s: causal must be 1 or 2 (got %d): other masks let a frame see later frames", who, s.causal);
-    TCOW_CHECK_ARG(T_total >= 1 && T_total <= TCOW_STREAM_MAX_FRAMES, "%s: T_total=%d must be in [1, %d]", who, T_total, TCOW_STREAM_MAX_FRAMES);
-    TCOW_CHECK_ARG(s.dtype == TCOW_F32 || s.dtype == TCOW_BF16, "%s: dtype must be TCOW_F32 or TCOW_BF16 (got %d)", who, s.dtype);
-    TCOW_CHECK_ARG(n_slots >= 1, "%s: n_slots=%d must be >= 1", who, n_slots);
-    TCOW_CHECK_ARG(t0_rows && slot_rows && first_rows && c_rows && row_of_frame && qkv && k_cache && v_cache && out, "%s: null pointer", who);
-    const long items = (long)s.T * s.S * s.heads;
-    const dim3 grid((unsigned)cdiv(items, ST_WAVES)), block(64 * ST_WAVES);
-    if (s.dtype == TCOW_BF16)
-        hipLaunchKernelGGL(temporal_ragged_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, n, s.T, s.S, s.D, s.heads, T_total, n_slots, t0_rows, slot_rows,
-                           first_rows, c_rows, row_of_frame, (const bf16_t*)qkv, (bf16_t*)k_cache, (bf16_t*)v_cache, (bf16_t*)out);
-    else
-        hipLaunchKernelGGL(temporal_ragged_kernel<float>, grid, block, 0, (hipStream_t)stream, n, s.T, s.S, s.D, s.heads, T_total, n_slots, t0_rows, slot_rows,
-                           first_rows, c_rows, row_of_frame, (const float*)qkv, (float*)k_cache, (float*)v_cache, (float*)out);
     TCOW_CHECK_LAUNCH();
     return TCOW_OK;
 }
@@ -352,8 +324,22 @@ int tcow_cls_pool(void* stream, int n, int c, int S, int D, float* x, float* cls
 int tcow_attn_temporal_ragged_fwd(void* stream, const tcow_attn_shape* step, int n, int T_total, int n_slots, const int* t0_rows, const int* slot_rows,
                                   const int* first_rows, const int* c_rows, const int* row_of_frame, const void* qkv, void* k_cache, void* v_cache,
                                   void* out) {
-    return launch_temporal_ragged("tcow_attn_temporal_ragged_fwd", stream, step, n, T_total, n_slots, t0_rows, slot_rows, first_rows, c_rows, row_of_frame,
-                                  qkv, k_cache, v_cache, out);
+    const char* who = "tcow_attn_temporal_ragged_fwd";
+    TCOW_CHECK_ARG(step != nullptr, "%s: null shape", who);
+    const tcow_attn_shape& s = *step;
+    if (const int err = check_temporal_args(who, s, 1, T_total, n_slots)) return err;          // (F counts the frames of all sessions: it may exceed T_total)
+    TCOW_CHECK_ARG(s.B == 1 && n > 0 && n <= s.T, "%s: a ragged step is one row of F frames of 1 <= n <= F sessions (B=%d F=%d n=%d)", who, s.B, s.T, n);
+    TCOW_CHECK_ARG(t0_rows && slot_rows && first_rows && c_rows && row_of_frame && qkv && k_cache && v_cache && out, "%s: null pointer", who);
+    const long items = (long)s.T * s.S * s.heads;
+    const dim3 grid((unsigned)cdiv(items, ST_WAVES)), block(64 * ST_WAVES);
+    if (s.dtype == TCOW_BF16)
+        hipLaunchKernelGGL(temporal_ragged_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, n, s.T, s.S, s.D, s.heads, T_total, n_slots, t0_rows, slot_rows,
+                           first_rows, c_rows, row_of_frame, (const bf16_t*)qkv, (bf16_t*)k_cache, (bf16_t*)v_cache, (bf16_t*)out);
+    else
+        hipLaunchKernelGGL(temporal_ragged_kernel<float>, grid, block, 0, (hipStream_t)stream, n, s.T, s.S, s.D, s.heads, T_total, n_slots, t0_rows, slot_rows,
+                           first_rows, c_rows, row_of_frame, (const float*)qkv, (float*)k_cache, (float*)v_cache, (float*)out);
+    TCOW_CHECK_LAUNCH();
+    return TCOW_OK;
 }
 
 int tcow_cls_ragged(void* stream, int n, int F, int S, int D, float* x, float* cls_cache, int n_slots, const int* t0_rows, const int* slot_rows,

@@ -70,25 +70,25 @@ def group_sizes(depth, spec=None):
     return sizes
 
 
-def _row_vectors(module, g, train, frames_only=False):
+def _row_vectors(module, g, train, stream_step=False):
     """mask0 [M] (0 on slot 0) and the DropPath row scales of every block (None in eval).
-    frames_only (a ragged stream step, B = 1): T takes many values over a session's life, and mask0 of F frames is a prefix of mask0 of more
-    frames, so one vector -- the longest asked for so far -- serves them all instead of one cache entry per distinct F."""
+    stream_step: B * T takes many values from one stream step to the next, and mask0 of fewer frames is a prefix of mask0 of more frames (the
+    same S entries per frame, whatever B and T), so one vector -- the longest asked for so far -- serves them all instead of one cache entry
+    per distinct (B, T)."""
     B, T, S, N = g['B'], g['T'], g['S'], g['N']
     dev = module.vit.pos_embed.device
     def build_mask0():
         m = torch.ones(B, T, S, dtype=torch.float32, device=dev)
         m[:, :, 0] = 0
         return m.reshape(-1).contiguous()
-    if frames_only:
-        assert B == 1 and not train
+    if stream_step:
         def build_frames(n):
             m = torch.ones(-(-n // S), S, dtype=torch.float32, device=dev)
             m[:, 0] = 0
             return m.reshape(-1).contiguous()
-        mask0 = module._operands.longest(('mask0_frames', S, str(dev)), T * S, build_frames)
+        mask0 = module._operands.longest(('mask0_frames', S, str(dev)), B * T * S, build_frames)
     else:
-        mask0 = module._operands.constant(('mask0', B, T, str(dev)), build_mask0)          # (T: a stream's chunk geometry has fewer frames than the clip)
+        mask0 = module._operands.constant(('mask0', B, T, str(dev)), build_mask0)
     depth = module.network_depth
     rates = torch.linspace(0, module.drop_path_rate, depth).tolist() if depth > 1 else [0.0]   # vit.py:272
     scales = []
@@ -183,14 +183,10 @@ def _effective_embeddings(module, g):
 
 
 def run_forward(module, rgb, qm, params, save, stream=None):
-    """stream (inference only, tcow_amd/stream.py): the state of a SeekerStream step -- rgb / qm then hold the chunk's c frames, and the schedule
-    differs in three places: the time rows (stream.time_rows = rows t0 .. t0+c-1 of the effective table), the temporal attention (against the
-    block's K / V cache, tcow_attn_temporal_cached_fwd) and, for causal_attention == 1, the cls row (tcow_cls_stream).
-    A SeekerStreamPool step is the same with a frame index and a cache slot per row: the state then carries t0_rows / slot_rows (device int32 [B]),
-    its caches are [block][slot], stream.time_rows holds one row per (row, chunk frame) and the two substitutions are the pool entry points.
-    A ragged pool step (sessions of different chunk lengths) also carries first_rows / c_rows [n] and row_of_frame [F]: rgb / qm are then ONE row of
-    F = sum of the chunk lengths frames (B = 1, T = F), stream.time_rows [F, D] is gathered per frame and the two substitutions are
-    tcow_attn_temporal_ragged_fwd and tcow_cls_ragged; everything else is the pool path."""
+    """stream (inference only): one stream step, built by tcow_amd/stream.py -- rgb / qm then hold the step's T = rgb.shape[2] frames
+    per row, and the schedule differs in three places: the embeddings (stream.pos, and stream.time_rows [B*T, D], one row of the time table per
+    (row, frame)), the temporal attention (stream.attn_temporal: against the block's K / V cache, which it extends) and, for
+    causal_attention == 1, the cls row (stream.cls_row: frame 0's, kept per block)."""
     mode = module.mode
     gmode = module.gemm_mode           # the GEMM entry points' arithmetic: `mode`, or TCOW_F32X3 (f32 tensors, bf16 x 3 split products) for precision='bf16x3'
     dt = ops.tdtype(mode)
@@ -208,8 +204,7 @@ def run_forward(module, rgb, qm, params, save, stream=None):
 
     opnd = module._operands
     W = lambda p: opnd.weight(mode, p, train)[0]
-    ragged = stream is not None and stream.row_of_frame is not None
-    mask0, dps = _row_vectors(module, g, module.training, frames_only=ragged)
+    mask0, dps = _row_vectors(module, g, module.training, stream_step=stream is not None)
     sv = {'g': g, 'blocks': [], 'mask0': mask0, 'dps': dps} if save else None
 
     # ---- patch embed (vit.py:233-241) + embeddings (vision_tf.py:99-138)
@@ -239,16 +234,12 @@ def run_forward(module, rgb, qm, params, save, stream=None):
         ops.gemm_nt(gmode, A_pe, W(params[3]), X, bias=params[4].detach())
     if stream is None:
         pos, te, pos_idx, time_idx = _effective_embeddings(module, g)
-    else:
-        pos, te, pos_idx, time_idx = stream.pos, stream.time_rows, None, None
-    pool = stream is not None and stream.t0_rows is not None
-    if pool:
-        # every row has its own frames: the time table [B*T, D] holds row t0_rows[b] + j at b*T + j, which tcow_embed_fwd indexes by (row / S) % (B*T)
-        ops.embed_fwd(X, 1, B * T, S, params[0].detach().reshape(-1), pos, te)
-    else:
         ops.embed_fwd(X, B, T, S, params[0].detach().reshape(-1), pos, te)
-    if save:
-        sv.update(A_pe=A_pe, pos_idx=pos_idx, time_idx=time_idx)
+        if save:
+            sv.update(A_pe=A_pe, pos_idx=pos_idx, time_idx=time_idx)
+    else:
+        # every row has its own frames: the table [B*T, D] holds the time row of (b, j) at b*T + j, which tcow_embed_fwd indexes by (row / S) % (B*T)
+        ops.embed_fwd(X, 1, B * T, S, params[0].detach().reshape(-1), stream.pos, stream.time_rows)
 
     BP, ix = _layout(module)
     joint = module.attention_type != 'divided_space_time'
@@ -292,14 +283,8 @@ def run_forward(module, rgb, qm, params, save, stream=None):
             O = E(M, D); lse_t = E(M, heads, dtype=f32) if save else None
             if stream is None:
                 ops.attn_fwd(shape_attn, False, QKV, O, lse_t)
-            elif ragged:
-                ops.attn_temporal_ragged(amode, stream.t0_rows.numel(), T, S, D, heads, ca, stream.T_total, stream.n_slots, stream.t0_rows, stream.slot_rows,
-                                         stream.first_rows, stream.c_rows, stream.row_of_frame, QKV, stream.k_cache[i], stream.v_cache[i], O)
-            elif pool:
-                ops.attn_temporal_pool(amode, B, T, S, D, heads, ca, stream.T_total, stream.n_slots, stream.t0_rows, stream.slot_rows, QKV,
-                                       stream.k_cache[i], stream.v_cache[i], O)
             else:
-                ops.attn_temporal_cached(amode, B, T, S, D, heads, ca, stream.T_total, stream.t0_dev, QKV, stream.k_cache[i], stream.v_cache[i], O)
+                stream.attn_temporal(i, amode, B, T, S, D, heads, ca, QKV, O)
             R1 = E(M, D, dtype=f32) if save else R0
             if fold:
                 Wf, _, bprime = opnd.folded(mode, i, q, ix, train)
@@ -323,13 +308,8 @@ def run_forward(module, rgb, qm, params, save, stream=None):
                 rs_s = mask0 if rs_s is None else rs_s * mask0
             R2 = E(M, D, dtype=f32) if save else R1
             ops.gemm_nt(gmode, O2, W(q[ix['proj']]), R2, bias=proj_b, row_scale=rs_s, resid=R1)
-            if use_cls and ragged:
-                ops.cls_ragged(R2, stream.t0_rows.numel(), T, S, stream.cls_cache[i], stream.n_slots, stream.t0_rows, stream.slot_rows, stream.first_rows,
-                               stream.c_rows)
-            elif use_cls and pool:
-                ops.cls_pool(R2, B, T, S, stream.cls_cache[i], stream.n_slots, stream.t0_rows, stream.slot_rows)
-            elif use_cls and stream is not None:
-                ops.cls_stream(R2, B, T, S, stream.cls_cache[i], stream.t0_dev)      # (a stream has causal_attention 1 or 2)
+            if use_cls and stream is not None:
+                stream.cls_row(i, R2, B, T, S)                                       # (a stream has causal_attention 1 or 2)
             elif use_cls:
                 ops.cls_merge(R2, B, T, S, 1 if ca == 1 else 0)
             if save:

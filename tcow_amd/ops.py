@@ -202,14 +202,19 @@ def attn_bwd(shape, spatial, qkv, out, dout, lse, dqkv):
     return dqkv
 
 
+def _stream_attn(mode, B, c, S, D, heads, causal, *tensors):
+    """What the stream attention wrappers start with: (library, reference to the step's shape).  `mode` is the attention mode: F32X3
+    (precision='bf16x3') stores f32 and runs as F32."""
+    _need_cuda(*tensors)
+    lib, dm = _sel(mode)
+    return lib, ctypes.byref(L.AttnShape(B, c, S, D, heads, int(causal), F32 if dm == F32X3 else dm))
+
+
 def attn_temporal_cached(mode, B, c, S, D, heads, causal, T_total, t0_dev, qkv, k_cache, v_cache, out):
     """Temporal attention of a c-frame chunk (qkv [B*c*S, 3D] -> out [B*c*S, D]) against the K / V cache [B, S-1, heads, T_total, 64] of the
-    frames before t0 = t0_dev[0] (int32 device scalar); appends the chunk's K / V at t0 (see tcow_attn_temporal_cached_fwd).  `mode` is the
-    attention mode: F32X3 (precision='bf16x3') stores f32 and runs as F32."""
-    _need_cuda(qkv, k_cache, v_cache, out, t0_dev)
-    lib, dm = _sel(mode)
-    sh = L.AttnShape(B, c, S, D, heads, int(causal), F32 if dm == F32X3 else dm)
-    L.check(lib.tcow_attn_temporal_cached_fwd(_stream(), ctypes.byref(sh), int(T_total), t0_dev.data_ptr(), qkv.data_ptr(), k_cache.data_ptr(),
+    frames before t0 = t0_dev[0] (int32 device scalar); appends the chunk's K / V at t0 (see tcow_attn_temporal_cached_fwd)."""
+    lib, sh = _stream_attn(mode, B, c, S, D, heads, causal, qkv, k_cache, v_cache, out, t0_dev)
+    L.check(lib.tcow_attn_temporal_cached_fwd(_stream(), sh, int(T_total), t0_dev.data_ptr(), qkv.data_ptr(), k_cache.data_ptr(),
                                               v_cache.data_ptr(), out.data_ptr()), 'tcow_attn_temporal_cached_fwd', lib)
     return out
 
@@ -223,10 +228,8 @@ def cls_stream(x, B, c, S, cls_cache, t0_dev):
 def attn_temporal_pool(mode, n, c, S, D, heads, causal, T_total, n_slots, t0_rows, slot_rows, qkv, k_cache, v_cache, out):
     """attn_temporal_cached for n rows that stand at different frames: row r attends at t0_rows[r] against block slot_rows[r] of the caches
     [n_slots, S-1, heads, T_total, 64] and appends there (int32 device tensors [n]; distinct slots -- see tcow_attn_temporal_pool_fwd)."""
-    _need_cuda(qkv, k_cache, v_cache, out, t0_rows, slot_rows)
-    lib, dm = _sel(mode)
-    sh = L.AttnShape(n, c, S, D, heads, int(causal), F32 if dm == F32X3 else dm)
-    L.check(lib.tcow_attn_temporal_pool_fwd(_stream(), ctypes.byref(sh), int(T_total), int(n_slots), t0_rows.data_ptr(), slot_rows.data_ptr(), qkv.data_ptr(),
+    lib, sh = _stream_attn(mode, n, c, S, D, heads, causal, qkv, k_cache, v_cache, out, t0_rows, slot_rows)
+    L.check(lib.tcow_attn_temporal_pool_fwd(_stream(), sh, int(T_total), int(n_slots), t0_rows.data_ptr(), slot_rows.data_ptr(), qkv.data_ptr(),
                                             k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr()), 'tcow_attn_temporal_pool_fwd', lib)
     return out
 
@@ -256,13 +259,11 @@ def attn_temporal_ragged(mode, n, F, S, D, heads, causal, T_total, n_slots, t0_r
     """attn_temporal_pool for n sessions that bring different numbers of frames: session r owns the flat frames first_rows[r] .. + c_rows[r] - 1 of
     the step's F frames (qkv [F*S, 3D] -> out [F*S, D]), row_of_frame[f] names the session of frame f (int32 device tensors [n] / [F]); one wave per
     frame, bit-identical per session to attn_temporal_pool (see tcow_attn_temporal_ragged_fwd)."""
-    _need_cuda(qkv, k_cache, v_cache, out)
+    lib, sh = _stream_attn(mode, 1, F, S, D, heads, causal, qkv, k_cache, v_cache, out)
     _ragged_tables('attn_temporal_ragged', n, F, t0_rows, slot_rows, first_rows, c_rows, row_of_frame)
     if qkv.shape[0] != F * S or out.shape[0] != F * S:
         raise L.TcowError(f'attn_temporal_ragged: qkv / out must have F * S = {F * S} rows, got {qkv.shape[0]} / {out.shape[0]}')
-    lib, dm = _sel(mode)
-    sh = L.AttnShape(1, F, S, D, heads, int(causal), F32 if dm == F32X3 else dm)
-    L.check(lib.tcow_attn_temporal_ragged_fwd(_stream(), ctypes.byref(sh), int(n), int(T_total), int(n_slots), t0_rows.data_ptr(), slot_rows.data_ptr(),
+    L.check(lib.tcow_attn_temporal_ragged_fwd(_stream(), sh, int(n), int(T_total), int(n_slots), t0_rows.data_ptr(), slot_rows.data_ptr(),
                                               first_rows.data_ptr(), c_rows.data_ptr(), row_of_frame.data_ptr(), qkv.data_ptr(), k_cache.data_ptr(),
                                               v_cache.data_ptr(), out.data_ptr()), 'tcow_attn_temporal_ragged_fwd', lib)
     return out

@@ -1,30 +1,37 @@
 """Streaming inference: the Seeker one chunk of frames at a time, for callers that receive frames live (a camera, a decoder).
 
 With causal_attention 1 or 2 the model is causal along time: frame t's mask logits and flags depend on frames 0..t only (the tril() mask of
-vit.py:93-99, the cls row taken from frame 0, vit.py:192-198; everything else works per token or per frame).  A SeekerStream therefore runs
-the eval schedule of engine.run_forward on the c new frames of a step alone, with three substitutions (see run_forward's `stream`): the
-chunk's rows of the time table, temporal attention against a per-block K / V cache of the earlier frames (tcow_attn_temporal_cached_fwd, which
-also appends the chunk's K / V), and for causal_attention == 1 the cls row of frame 0 kept per block (tcow_cls_stream).  For any split of
-0..T-1 into chunks the concatenated outputs equal forward() of the whole clip, to the precision mode's rounding.
+vit.py:93-99, the cls row taken from frame 0, vit.py:192-198; everything else works per token or per frame).  A stream step therefore runs
+the eval schedule of engine.run_forward on its new frames alone, with three substitutions: the frames' rows of the time table, temporal
+attention against a per-block K / V cache of the earlier frames (which the same launch extends by the new frames' K / V), and for
+causal_attention == 1 the cls row of frame 0 kept per block.  For any split of 0..T-1 into chunks the concatenated outputs equal forward() of
+the whole clip, to the precision mode's rounding.
 
-State, allocated once by stream(): per block a K and a V cache [B, S-1, heads, T, 64] in the mode's storage type (16-bit modes: bf16 / binary16;
-fp32 and bf16x3: f32) with B = clips x queries (the query mask changes every token's K / V), and one f32 cls row per query row.  At BASELINE
-configs[1] (T = 30, 240x320, depth 12) that is 332 MB per query row in the 16-bit modes; at configs[3] (T = 60, 480x640) 2.65 GB; f32 twice that.
+What lives as long as a stream or a pool is a _State: per block a K and a V cache [rows, S-1, heads, T, 64] in the mode's storage type (16-bit
+modes: bf16 / binary16; fp32 and bf16x3: f32), one f32 cls row per row and block, and the effective pos / time tables.  A stream has rows =
+clips x queries (the query mask changes every token's K / V), a pool rows = capacity.  At BASELINE configs[1] (T = 30, 240x320, depth 12)
+that is 332 MB per row in the 16-bit modes; at configs[3] (T = 60, 480x640) 2.65 GB; f32 twice that.
 
-graph=True: the first step of each chunk length c runs eagerly and captures the step as a torch.cuda.CUDAGraph; later steps copy their inputs
-into the graph's static buffers, write t0 (a device scalar the kernels read) and replay.  No step synchronises the host except the one capture
-per chunk length.  A graph keeps the module's operand copies it was captured with alive; when the module replaces them (.cuda() / .to() on
-the same device, set_precision() with the same precision, a train-mode forward) the graphs are dropped and captured again.
+What belongs to one step is a _Step, and it is all run_forward sees (its `stream` argument): pos, time_rows [B*T, D] (one row of the time table
+per (row, frame) of the step), attn_temporal(i, ...) and cls_row(i, ...) for block i.  There are three forms, each a _Step subclass that holds
+its device tables and calls its own pair of ops entry points; step(), pool.step() and pool.step_ragged() each build the tables and construct
+their form, and nothing else asks which form a step has:
 
-SeekerStreamPool (net.stream_pool(capacity)): live sessions that started at different moments, stepped together.  The three substitutions
-depend on a row's own frame index only, so a pool step is one Seeker step whose rows each carry their own t0 and their own cache slot
-(tcow_attn_temporal_pool_fwd, tcow_cls_pool; the time rows are gathered per row).  The pool holds the state of `capacity` one-row streams:
-per block K / V caches [capacity, S-1, heads, T, 64] and one cls row per slot.  Pool steps run eagerly.
+  _StreamStep (SeekerStream.step): every row stands at the same frame t0, a device scalar, and row b uses cache slot b
+  (tcow_attn_temporal_cached_fwd, tcow_cls_stream).
+  _PoolStep (SeekerStreamPool.step): live sessions that started at different moments, stepped together with one chunk length: a t0 and a
+  cache slot per row (tcow_attn_temporal_pool_fwd, tcow_cls_pool -- the stream's kernels, of which the stream is the case "one t0, slot = row").
+  _RaggedStep (SeekerStreamPool.step_ragged): the sessions bring different numbers of frames (cameras at different rates, a decoder's GOP, a
+  session that catches up while its neighbours advance by one).  The F = sum of the c_i frames lie flat in session order and run as ONE row
+  of F frames; ragged_tables() gives every session its t0, slot, first flat frame and chunk length and every frame its session
+  (tcow_attn_temporal_ragged_fwd, one wave per frame, not per session, and tcow_cls_ragged).
 
-pool.step_ragged(ids, rgbs, query_masks): the sessions of one step bring different numbers of frames (cameras at different rates, a decoder's
-GOP, a session that catches up or prefills its history while its neighbours advance by one).  The step's F = sum of the c_i frames lie flat
-in session order and run as ONE row of F frames; ragged_tables() gives every session its t0, slot, first flat frame and chunk length and every
-frame its session, and the two substitutions are tcow_attn_temporal_ragged_fwd (one wave per frame, not per session) and tcow_cls_ragged.
+graph=True (SeekerStream): the first step of each chunk length c runs eagerly and captures the step as a torch.cuda.CUDAGraph; later steps copy
+their inputs into the graph's static buffers, write t0 and the time rows (the stream keeps one _StreamStep with static time rows per chunk
+length, and one t0 scalar: the graph points into both) and replay.  No step synchronises the host except the one capture per chunk length.  A
+graph keeps the module's operand copies it was captured with alive; when the module replaces them (.cuda() / .to() on the same device,
+set_precision() with the same precision, a train-mode forward) the graphs are dropped and captured again.  Pool steps run eagerly and build a
+fresh step object per call.
 """
 import torch
 
@@ -32,14 +39,69 @@ from . import engine, ops
 from ._lib import TcowError
 
 
-class _StepState:
-    """What engine.run_forward substitutes for a stream step."""
-    __slots__ = ('T_total', 't0_dev', 'pos', 'time_rows', 'k_cache', 'v_cache', 'cls_cache', 't0_rows', 'slot_rows', 'n_slots', 'first_rows', 'c_rows',
-                 'row_of_frame')
+class _State:
+    """What lives as long as a stream or a pool of `rows` query rows: per block the K / V caches [rows, S-1, heads, T, 64] in the mode's storage
+    type and one f32 cls row per query row, and the effective pos table and time table [T, D]."""
 
-    def __init__(self):
-        self.t0_rows = self.slot_rows = self.n_slots = None       # set by a pool step only: a frame index and a cache slot per row
-        self.first_rows = self.c_rows = self.row_of_frame = None  # set by a ragged pool step only: a first flat frame and a chunk length per session, a session per frame
+    def __init__(self, module, rows):
+        g = module.geometry(rows)
+        dev = module.vit.pos_embed.device
+        cdt = ops.tdtype(module.mode)                           # (bf16x3 stores f32, like fp32)
+        self.T_total, self.n_slots, self.D = module.num_total_frames, rows, g['D']
+        shape = (module.network_depth, rows, g['S'] - 1, g['heads'], self.T_total, 64)
+        self.k_cache = torch.empty(shape, dtype=cdt, device=dev)
+        self.v_cache = torch.empty(shape, dtype=cdt, device=dev)
+        self.cls_cache = torch.empty(module.network_depth, rows, g['D'], dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            self.pos, self.time, _, _ = engine._effective_embeddings(module, g)     # (nearest-resized when the stored tables differ)
+
+    @property
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in (self.k_cache, self.v_cache, self.cls_cache))
+
+
+class _Step:
+    """What engine.run_forward asks of one stream step: pos, time_rows [B*T, D] (one row of the time table per (row, chunk frame)) and the two
+    substitutions of block i, attn_temporal and cls_row.  A form is its tables and its two ops entry points; it is chosen by constructing one of
+    the three classes below, where the tables are built, and nowhere else."""
+
+    def __init__(self, state, time_rows, *tables):
+        self.state, self.pos, self.time_rows, self.tables = state, state.pos, time_rows, tables
+
+
+class _StreamStep(_Step):
+    """tables: t0_dev, the one frame index of all rows (a device scalar: a captured graph reads it); row b works on cache slot b."""
+
+    def attn_temporal(self, i, amode, B, T, S, D, heads, ca, QKV, O):
+        st = self.state
+        ops.attn_temporal_cached(amode, B, T, S, D, heads, ca, st.T_total, *self.tables, QKV, st.k_cache[i], st.v_cache[i], O)
+
+    def cls_row(self, i, R2, B, T, S):
+        ops.cls_stream(R2, B, T, S, self.state.cls_cache[i], *self.tables)
+
+
+class _PoolStep(_Step):
+    """tables: t0_rows, slot_rows (device int32 [B]): a frame index and a cache slot per row."""
+
+    def attn_temporal(self, i, amode, B, T, S, D, heads, ca, QKV, O):
+        st = self.state
+        ops.attn_temporal_pool(amode, B, T, S, D, heads, ca, st.T_total, st.n_slots, *self.tables, QKV, st.k_cache[i], st.v_cache[i], O)
+
+    def cls_row(self, i, R2, B, T, S):
+        ops.cls_pool(R2, B, T, S, self.state.cls_cache[i], self.state.n_slots, *self.tables)
+
+
+class _RaggedStep(_Step):
+    """tables: t0_rows, slot_rows, first_rows, c_rows (device int32 [n], per session) and row_of_frame ([F], per flat frame); the step is ONE row
+    of F = T frames."""
+
+    def attn_temporal(self, i, amode, B, T, S, D, heads, ca, QKV, O):
+        st = self.state
+        ops.attn_temporal_ragged(amode, self.tables[0].numel(), T, S, D, heads, ca, st.T_total, st.n_slots, *self.tables, QKV, st.k_cache[i],
+                                 st.v_cache[i], O)
+
+    def cls_row(self, i, R2, B, T, S):
+        ops.cls_ragged(R2, self.tables[0].numel(), T, S, self.state.cls_cache[i], self.state.n_slots, *self.tables[:4])
 
 
 def check_streamable(module):
@@ -63,40 +125,12 @@ def _signature(module):
     return (module.mode, module.gemm_mode, module._operands.epoch) + tuple((id(p), p._version, p.data_ptr()) for p in module.param_list())
 
 
-def _new_state(module, rows):
-    """(state with the caches of `rows` rows allocated, effective time table [T, D], geometry) -- what a stream and a pool both start from."""
-    g = module.geometry(rows)
-    dev = module.vit.pos_embed.device
-    cdt = ops.tdtype(module.mode)                           # (bf16x3 stores f32, like fp32)
-    T = module.num_total_frames
-    shape = (module.network_depth, rows, g['S'] - 1, g['heads'], T, 64)
-    st = _StepState()
-    st.T_total = T
-    st.k_cache = torch.empty(shape, dtype=cdt, device=dev)
-    st.v_cache = torch.empty(shape, dtype=cdt, device=dev)
-    st.cls_cache = torch.empty(module.network_depth, rows, g['D'], dtype=torch.float32, device=dev)
-    with torch.no_grad():
-        st.pos, time, _, _ = engine._effective_embeddings(module, g)            # (nearest-resized when the stored tables differ)
-    st.time_rows = None
-    return st, time, g
-
-
-def _cache_bytes(st):
-    return sum(t.numel() * t.element_size() for t in (st.k_cache, st.v_cache, st.cls_cache))
-
-
 def _check_module(module, sig):
     """The module can still be streamed and is the one the caches were filled by."""
     check_streamable(module)
     if _signature(module) != sig:
         raise TcowError('stream: a parameter (or the precision) changed since the stream was opened; the cached keys / values belong to the old '
                         'weights -- open a new stream')
-
-
-def _check_step(who, module, sig, device, clips, rows, rgb, query_mask):
-    """The checks of a step that do not depend on where its rows stand; returns the chunk length c."""
-    _check_module(module, sig)
-    return _check_inputs(who, module, device, clips, rows, rgb, query_mask)
 
 
 def _check_inputs(who, m, device, clips, rows, rgb, query_mask):
@@ -134,32 +168,37 @@ def ragged_tables(t0s, slots, cs):
     return {'t0': t0s, 'slot': slots, 'first': first, 'c': cs, 'row_of_frame': row_of_frame, 'frames': frames}
 
 
-def check_ragged_sessions(ids, n_rgbs, n_masks, capacity, open_ids):
-    """The checks of step_ragged that look at the lists alone: 1 .. capacity sessions, one rgb entry (and one query-mask entry, unless the list
-    is None: n_masks None) per session, every id open, none twice.  Returns the ids as a list."""
+def check_sessions(who, ids, n_rgbs, n_masks, capacity, open_ids):
+    """The checks of a pool step (`who`) that look at the lists alone: 1 .. capacity sessions, every id open, none twice, and for a list of rgb
+    entries (n_rgbs not None) one entry per session, the same for a list of query masks (n_masks not None).  Returns the ids as a list."""
     ids = list(ids)
     n = len(ids)
     if n < 1 or n > capacity:
-        raise TcowError(f'stream_pool.step_ragged: {n} sessions given; a step takes 1 .. capacity = {capacity}')
-    if n_rgbs != n or (n_masks is not None and n_masks != n):
-        raise TcowError(f'stream_pool.step_ragged: {n} ids, {n_rgbs} rgb entries' + ('' if n_masks is None else f', {n_masks} query_masks entries')
+        raise TcowError(f'{who}: {n} sessions given; a step takes 1 .. capacity = {capacity}')
+    if n_rgbs is not None and (n_rgbs != n or (n_masks is not None and n_masks != n)):
+        raise TcowError(f'{who}: {n} ids, {n_rgbs} rgb entries' + ('' if n_masks is None else f', {n_masks} query_masks entries')
                         + ': the lengths must agree (one entry per session)')
     seen = set()
     for sid in ids:
         if sid not in open_ids:
             raise TcowError(f'stream_pool: session {sid!r} is not open (unknown or closed id)')
         if sid in seen:
-            raise TcowError(f'stream_pool.step_ragged: duplicate session {sid!r}: a session is one run of frames of a step')
+            raise TcowError(f'{who}: duplicate session {sid!r}: a session is one run of frames of a step')
         seen.add(sid)
     return ids
 
 
-def check_ragged_range(ids, t0s, cs, T):
+def check_range(who, ids, t0s, cs, T):
     """No session runs past the last frame: frames_done + c_i <= T for every session, the offender named."""
     for sid, t0, c in zip(ids, t0s, cs):
         if t0 + c > T:
-            raise TcowError(f'stream_pool.step_ragged: session {sid}: frames {t0}..{t0 + c - 1} run past the last frame {T - 1} of the stream '
+            raise TcowError(f'{who}: session {sid}: frames {t0}..{t0 + c - 1} run past the last frame {T - 1} of the stream '
                             f'(num_total_frames = {T}); reset() or close() it')
+
+
+def _zero_mask(rows, rgb):
+    """The query mask of a step that was given none: all zeros, (rows, 1, c, H, W) for rgb (clips, 3, c, H, W)."""
+    return torch.zeros(rows, 1, *rgb.shape[2:], dtype=torch.float32, device=rgb.device)
 
 
 class SeekerStream:
@@ -175,12 +214,10 @@ class SeekerStream:
         self.Bc, self.Qs, self.B = Bc, Qs, Bc * Qs
         self.T = module.num_total_frames
         self.graph = bool(graph)
-        st, self._time, g = _new_state(module, self.B)
-        self._S, self._D = g['S'], g['D']
-        self.device = st.pos.device
-        st.t0_dev = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self._st = st
-        self._time_rows = {}            # c -> static [c, D] f32 time rows of the step
+        self._st = _State(module, self.B)
+        self.device = self._st.pos.device
+        self._t0_dev = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._steps = {}                # c -> the step of chunk length c; its time_rows [B*c, D] f32 are static: a captured graph points into both
         self._graphs = {}               # c -> (graph, static rgb, static query mask, output mask, flags)
         self._sig = _signature(module)
         self.frames_done = 0
@@ -188,7 +225,7 @@ class SeekerStream:
     @property
     def cache_bytes(self):
         """Device bytes of the K / V caches and the cls rows."""
-        return _cache_bytes(self._st)
+        return self._st.nbytes
 
     def reset(self):
         """Start again at frame 0 (the buffers, and any captured graphs, are kept)."""
@@ -197,29 +234,27 @@ class SeekerStream:
     def step(self, rgb, query_mask=None):
         """rgb (Bc, 3, c, H, W), query_mask (Bc*Qs, 1, c, H, W) or None (all zeros) for the next c >= 1 frames ->
         (mask logits (Bc*Qs, Co, c, H, W) f32, flags (Bc*Qs, c, F) or None) of exactly those frames, owned by the caller."""
-        c = _check_step('stream.step', self.module, self._sig, self.device, self.Bc, self.B, rgb, query_mask)
+        _check_module(self.module, self._sig)
+        c = _check_inputs('stream.step', self.module, self.device, self.Bc, self.B, rgb, query_mask)
         t0 = self.frames_done
         if t0 + c > self.T:
             raise TcowError(f'stream.step: frames {t0}..{t0 + c - 1} run past the last frame {self.T - 1} of the stream (num_total_frames = {self.T}); '
                             'reset() to start again')
         with torch.no_grad(), torch.cuda.device(self.device):
-            tr = self._time_rows.get(c)
-            if tr is None:
-                tr = self._time_rows[c] = torch.empty(c, self._D, dtype=torch.float32, device=self.device)
-            tr.copy_(self._time[t0:t0 + c])
-            self._st.t0_dev.fill_(t0)
-            self._st.time_rows = tr
+            step = self._steps.get(c)
+            if step is None:
+                step = self._steps[c] = _StreamStep(self._st, torch.empty(self.B * c, self._st.D, dtype=torch.float32, device=self.device), self._t0_dev)
+            step.time_rows.view(self.B, c, -1).copy_(self._st.time[t0:t0 + c])      # row b*c + j = time row t0 + j, for every b
+            self._t0_dev.fill_(t0)
             rgb32 = rgb.to(torch.float32).contiguous()
             qm32 = None if query_mask is None else query_mask.to(torch.float32).contiguous()
-            out = self._graph_step(c, rgb32, qm32) if self.graph else self._run(rgb32, qm32)
+            out = self._graph_step(step, rgb32, qm32) if self.graph else self._run(step, rgb32, qm32)
         self.frames_done = t0 + c
         return out
 
-    def _run(self, rgb, qm):
+    def _run(self, step, rgb, qm):
         m = self.module
-        if qm is None:
-            qm = torch.zeros(self.B, 1, rgb.shape[2], rgb.shape[3], rgb.shape[4], dtype=torch.float32, device=rgb.device)
-        out_mask, flags, _ = engine.run_forward(m, rgb, qm, m.param_list(), save=False, stream=self._st)
+        out_mask, flags, _ = engine.run_forward(m, rgb, _zero_mask(self.B, rgb) if qm is None else qm, m.param_list(), save=False, stream=step)
         return out_mask, (flags if m.flag_channels > 0 else None)
 
     def _operand_generation(self):
@@ -228,18 +263,19 @@ class SeekerStream:
         m = self.module
         return (m._operands.generation, m.mode)
 
-    def _graph_step(self, c, rgb, qm):
+    def _graph_step(self, step, rgb, qm):
+        c = rgb.shape[2]
         gen = self._operand_generation()
         if any(e['gen'] != gen for e in self._graphs.values()):
             self._graphs.clear()                # captured against replaced operand copies: capture again (the pool of a dropped graph is stream-ordered)
         ent = self._graphs.get(c)
         if ent is None:
-            out = self._run(rgb, qm)            # this step's result; it also creates every lazily built operand the capture needs
+            out = self._run(step, rgb, qm)      # this step's result; it also creates every lazily built operand the capture needs
             s_rgb = rgb.clone()
-            s_qm = qm.clone() if qm is not None else torch.zeros(self.B, 1, *rgb.shape[2:], dtype=torch.float32, device=rgb.device)
+            s_qm = qm.clone() if qm is not None else _zero_mask(self.B, rgb)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                g_mask, g_flags = self._run(s_rgb, s_qm)
+                g_mask, g_flags = self._run(step, s_rgb, s_qm)
             # The graph holds raw pointers into tensors that only module._operands owns (operand copies, folded W' / b', mask0): a shallow copy
             # of the dictionary keeps them alive as long as the graph, whatever later replaces the dictionary or its entries.
             keep = self.module._operands.keep_alive()
@@ -269,12 +305,8 @@ class SeekerStreamPool:
         self.module = module
         self.capacity = capacity
         self.T = module.num_total_frames
-        st, self._time, g = _new_state(module, capacity)
-        st.n_slots = capacity
-        self._st = st
-        rg = self._st_ragged = _StepState()        # the state of a ragged step: the same caches, its own tables (step() never sees them)
-        rg.T_total, rg.n_slots, rg.pos, rg.k_cache, rg.v_cache, rg.cls_cache = st.T_total, st.n_slots, st.pos, st.k_cache, st.v_cache, st.cls_cache
-        self.device = st.pos.device
+        self._st = _State(module, capacity)
+        self.device = self._st.pos.device
         self._sig = _signature(module)
         self._slot = {}                 # open session id -> cache slot
         self._done = {}                 # open session id -> frames consumed
@@ -283,7 +315,7 @@ class SeekerStreamPool:
     @property
     def cache_bytes(self):
         """Device bytes of the K / V caches and the cls rows of all `capacity` slots."""
-        return _cache_bytes(self._st)
+        return self._st.nbytes
 
     def _known(self, sid):
         if sid not in self._slot:
@@ -313,41 +345,40 @@ class SeekerStreamPool:
         """Put the session back at frame 0 (it keeps its slot)."""
         self._done[self._known(sid)] = 0
 
+    def _checked(self, who, ids, rgbs, qms, per):
+        """Every check of a step (`who`), before anything is launched or any counter moves.  rgbs / qms: one tensor of all sessions, or (per) a list
+        with an entry per session.  Returns (ids, the frame every session stands at, the chunk length of every session)."""
+        m = self.module
+        ids = check_sessions(who, ids, len(rgbs) if per else None, len(qms) if per and qms is not None else None, self.capacity, self._slot)
+        _check_module(m, self._sig)
+        if per:
+            cs = [_check_inputs(f'{who}: session {sid}', m, self.device, 1, 1, rgbs[k], None if qms is None else qms[k]) for k, sid in enumerate(ids)]
+        else:
+            cs = [_check_inputs(who, m, self.device, len(ids), len(ids), rgbs, qms)] * len(ids)
+        t0s = [self._done[sid] for sid in ids]
+        check_range(who, ids, t0s, cs, self.T)
+        return ids, t0s, cs
+
+    def _run(self, step, ids, cs, rgb, qm):
+        """One Seeker step (qm None: all zeros), after which every session has moved on by its chunk length."""
+        m = self.module
+        out_mask, flags, _ = engine.run_forward(m, rgb, _zero_mask(rgb.shape[0], rgb) if qm is None else qm, m.param_list(), save=False, stream=step)
+        for sid, c in zip(ids, cs):
+            self._done[sid] += c
+        return out_mask, (flags if m.flag_channels > 0 else None)
+
     def step(self, ids, rgb, query_mask=None):
         """ids: n distinct open sessions, at any phases; rgb (n, 3, c, H, W), query_mask (n, 1, c, H, W) or None (all zeros): the next c >= 1
         frames of each -> (mask logits (n, Co, c, H, W) f32, flags (n, c, F) or None) in the order of `ids`, owned by the caller.  Every check
         runs before anything is launched: a refused step leaves every session where it was."""
-        m = self.module
-        ids = list(ids)
-        n = len(ids)
-        if n < 1 or n > self.capacity:
-            raise TcowError(f'stream_pool.step: {n} sessions given; a step takes 1 .. capacity = {self.capacity}')
-        seen = set()
-        for sid in ids:
-            if sid in seen:
-                raise TcowError(f'stream_pool.step: duplicate session {sid!r}: a session is one row of a step')
-            seen.add(self._known(sid))
-        c = _check_step('stream_pool.step', m, self._sig, self.device, n, n, rgb, query_mask)
-        t0s = [self._done[sid] for sid in ids]
-        for sid, t0 in zip(ids, t0s):
-            if t0 + c > self.T:
-                raise TcowError(f'stream_pool.step: session {sid}: frames {t0}..{t0 + c - 1} run past the last frame {self.T - 1} of the stream '
-                                f'(num_total_frames = {self.T}); reset() or close() it')
-        st = self._st
+        ids, t0s, cs = self._checked('stream_pool.step', ids, rgb, query_mask, False)
+        st, c = self._st, cs[0]
         with torch.no_grad(), torch.cuda.device(self.device):
-            st.t0_rows = torch.tensor(t0s, dtype=torch.int32, device=self.device)
-            st.slot_rows = torch.tensor([self._slot[sid] for sid in ids], dtype=torch.int32, device=self.device)
-            frames = (st.t0_rows[:, None] + torch.arange(c, dtype=torch.int32, device=self.device)[None, :]).reshape(-1)
-            st.time_rows = self._time.index_select(0, frames)                   # [n*c, D]: row r*c + j = time row t0_rows[r] + j
-            rgb32 = rgb.to(torch.float32).contiguous()
-            if query_mask is None:
-                qm32 = torch.zeros(n, 1, c, rgb.shape[3], rgb.shape[4], dtype=torch.float32, device=self.device)
-            else:
-                qm32 = query_mask.to(torch.float32).contiguous()
-            out_mask, flags, _ = engine.run_forward(m, rgb32, qm32, m.param_list(), save=False, stream=st)
-        for sid in ids:
-            self._done[sid] += c
-        return out_mask, (flags if m.flag_channels > 0 else None)
+            t0_rows = torch.tensor(t0s, dtype=torch.int32, device=self.device)
+            slot_rows = torch.tensor([self._slot[sid] for sid in ids], dtype=torch.int32, device=self.device)
+            frames = (t0_rows[:, None] + torch.arange(c, dtype=torch.int32, device=self.device)[None, :]).reshape(-1)
+            step = _PoolStep(st, st.time.index_select(0, frames), t0_rows, slot_rows)         # [n*c, D]: row r*c + j = time row t0_rows[r] + j
+            return self._run(step, ids, cs, rgb.to(torch.float32).contiguous(), None if query_mask is None else query_mask.to(torch.float32).contiguous())
 
     def step_ragged(self, ids, rgbs, query_masks=None):
         """ids: n distinct open sessions, at any phases; rgbs: n tensors (1, 3, c_i, H, W), the next c_i >= 1 frames of each session (the c_i need
@@ -355,36 +386,25 @@ class SeekerStreamPool:
         (1, Co, c_i, H, W) f32, a list of n flag tensors (1, c_i, F) or None), in the order of `ids`.  The outputs are slices of buffers allocated
         for this step and owned by the caller.  The whole step is ONE Seeker step over the sum of the c_i frames.  Every check runs before anything
         is launched: a refused step leaves every session where it was."""
-        m = self.module
         rgbs = list(rgbs)
         qms = None if query_masks is None else list(query_masks)
-        ids = check_ragged_sessions(ids, len(rgbs), None if qms is None else len(qms), self.capacity, self._slot)
-        n = len(ids)
-        _check_module(m, self._sig)
-        cs = [_check_inputs(f'stream_pool.step_ragged: session {sid}', m, self.device, 1, 1, rgbs[k], None if qms is None else qms[k])
-              for k, sid in enumerate(ids)]
-        t0s = [self._done[sid] for sid in ids]
-        check_ragged_range(ids, t0s, cs, self.T)
+        ids, t0s, cs = self._checked('stream_pool.step_ragged', ids, rgbs, qms, True)
+        n, st = len(ids), self._st
         tab = ragged_tables(t0s, [self._slot[sid] for sid in ids], cs)
         F = len(tab['frames'])
-        st = self._st_ragged
         with torch.no_grad(), torch.cuda.device(self.device):
             # all six tables in one host-to-device copy: [t0 | slot | first | c] per session, [row_of_frame | frames] per flat frame
             dev = torch.tensor(tab['t0'] + tab['slot'] + tab['first'] + tab['c'] + tab['row_of_frame'] + tab['frames'], dtype=torch.int32).to(self.device)
-            st.t0_rows, st.slot_rows, st.first_rows, st.c_rows = dev[0:n], dev[n:2 * n], dev[2 * n:3 * n], dev[3 * n:4 * n]
-            st.row_of_frame = dev[4 * n:4 * n + F]
-            st.time_rows = self._time.index_select(0, dev[4 * n + F:])             # [F, D]: flat frame f = time row t0 + j of its session
-            H, W = m.frame_height, m.frame_width
+            step = _RaggedStep(st, st.time.index_select(0, dev[4 * n + F:]),              # [F, D]: flat frame f = time row t0 + j of its session
+                               dev[0:n], dev[n:2 * n], dev[2 * n:3 * n], dev[3 * n:4 * n], dev[4 * n:4 * n + F])
             rgb32 = rgbs[0].to(torch.float32).contiguous() if n == 1 else torch.cat([r.to(torch.float32) for r in rgbs], 2)
             if qms is not None and all(q is not None for q in qms):
                 qm32 = qms[0].to(torch.float32).contiguous() if n == 1 else torch.cat([q.to(torch.float32) for q in qms], 2)
             else:
-                qm32 = torch.zeros(1, 1, F, H, W, dtype=torch.float32, device=self.device)
+                qm32 = _zero_mask(1, rgb32)
                 for q, f0, c in zip(qms or (), tab['first'], cs):
                     if q is not None:
                         qm32[:, :, f0:f0 + c] = q
-            out_mask, flags, _ = engine.run_forward(m, rgb32, qm32, m.param_list(), save=False, stream=st)
-        for sid, c in zip(ids, cs):
-            self._done[sid] += c
+            out_mask, flags = self._run(step, ids, cs, rgb32, qm32)
         masks = [out_mask[:, :, f0:f0 + c] for f0, c in zip(tab['first'], cs)]
-        return masks, ([flags[:, f0:f0 + c] for f0, c in zip(tab['first'], cs)] if m.flag_channels > 0 else None)
+        return masks, (None if flags is None else [flags[:, f0:f0 + c] for f0, c in zip(tab['first'], cs)])

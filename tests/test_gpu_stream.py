@@ -267,24 +267,26 @@ def test_stream_shared_rgb_and_batched_clips(cuda, precision, tol):
 
 @pytest.mark.parametrize('precision', ['bf16', 'fp16', 'fp32'])
 def test_stream_graph_mode_is_bit_identical_to_eager(cuda, precision):
+    """(the split [1, 2, 1, 2] asks for the longer mask0 while the graph of c = 1 is live; two clips: time rows of B * c rows under capture)"""
     cfg = synth.seeker_config(num_total_frames=6, frame_height=32, frame_width=48, embed_dim=128, depth=2, num_heads=2, causal_attention=1)
     net = build_hip_seeker(cfg, synth.make_state_dict(cfg, 5), precision).cuda().eval()
-    clip = synth.make_clip(1, 6, 32, 48, seed=2)
-    rgb = torch.from_numpy(clip['rgb']).cuda(); qm = torch.from_numpy(synth.make_query_mask(clip, 0, 0)).cuda()
-    for split in ([1] * 6, [2, 1, 2, 1]):
-        eager = net.stream(graph=False); graph = net.stream(graph=True)
-        for rep in range(2):                                    # the second pass replays every captured chunk length
-            eager.reset(); graph.reset()
-            t = 0
-            for c in split:
-                a = eager.step(rgb[:, :, t:t + c], qm[:, :, t:t + c])
-                b = graph.step(rgb[:, :, t:t + c], qm[:, :, t:t + c])
-                assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), (split, rep, t)
-                t += c
-        held = b[0].clone()
-        c = split[-1]
-        graph.reset(); graph.step(rgb[:, :, 0:c] * 0.5, qm[:, :, 0:c])
-        assert torch.equal(b[0], held)                          # returned tensors are the caller's: the next replay does not overwrite them
+    for clips, splits in ((1, ([1] * 6, [2, 1, 2, 1], [1, 2, 1, 2])), (2, ([2, 1, 2, 1],))):
+        clip = synth.make_clip(clips, 6, 32, 48, seed=2)
+        rgb = torch.from_numpy(clip['rgb']).cuda(); qm = torch.from_numpy(synth.make_query_mask(clip, 0, 0)).cuda()
+        for split in splits:
+            eager = net.stream(batch_size=clips, graph=False); graph = net.stream(batch_size=clips, graph=True)
+            for rep in range(2):                                # the second pass replays every captured chunk length
+                eager.reset(); graph.reset()
+                t = 0
+                for c in split:
+                    a = eager.step(rgb[:, :, t:t + c], qm[:, :, t:t + c])
+                    b = graph.step(rgb[:, :, t:t + c], qm[:, :, t:t + c])
+                    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), (clips, split, rep, t)
+                    t += c
+            held = b[0].clone()
+            c = split[-1]
+            graph.reset(); graph.step(rgb[:, :, 0:c] * 0.5, qm[:, :, 0:c])
+            assert torch.equal(b[0], held)                      # returned tensors are the caller's: the next replay does not overwrite them
 
 
 def test_stream_lifecycle(cuda):
@@ -349,7 +351,8 @@ def _recycle_freed_blocks(net):
 @pytest.mark.parametrize('precision', ['bf16', 'fp32'])
 def test_stream_graph_mode_survives_replaced_operand_copies(cuda, precision):
     """An idempotent .cuda(), set_precision() with the same precision and a train-mode forward replace the module's operand copies without
-    changing a parameter: the stream stays valid, and graph steps after each of them still equal the eager stream."""
+    changing a parameter, and a longer pool step replaces the mask0 all stream steps share: the stream stays valid, and graph steps after
+    each of them still equal the eager stream."""
     cfg = synth.seeker_config(num_total_frames=6, frame_height=32, frame_width=48, embed_dim=128, depth=2, num_heads=2, causal_attention=1)
     net = build_hip_seeker(cfg, synth.make_state_dict(cfg, 8), precision).cuda().eval()
     clip = synth.make_clip(1, 6, 32, 48, seed=3)
@@ -367,7 +370,11 @@ def test_stream_graph_mode_survives_replaced_operand_copies(cuda, precision):
         net(rgb, qm)                                            # gradients enabled: the forward builds operand copies for a backward
         net.eval()
 
-    events = {2: cuda_again, 3: same_precision, 4: train_forward}
+    def longer_pool_step():
+        pool = net.stream_pool(1)                               # four frames in one ragged step: a longer shared mask0 replaces the captured one
+        pool.step_ragged([pool.open()], [rgb[:, :, 0:4]], [qm[:, :, 0:4]])
+
+    events = {2: cuda_again, 3: same_precision, 4: train_forward, 5: longer_pool_step}
     junk = []
     for t in range(6):
         if t in events:

@@ -1,10 +1,10 @@
 """CPU: the host side of SeekerStreamPool.step_ragged (tcow_amd/stream.py) -- the table builder against a brute-force restatement, the
-argument refusals that look at the lists alone, the row vector shared by ragged steps of every length, and the ABI entries."""
+argument refusals that look at the lists alone, and the ABI entries."""
 import pytest
 import torch
 
 from test_stream_host import _net
-from tcow_amd import _lib, engine, stream
+from tcow_amd import _lib, stream
 from tcow_amd._lib import TcowError
 
 
@@ -49,7 +49,7 @@ def test_ragged_tables_refuse_bad_lists():
 
 def test_step_ragged_list_refusals():
     open_ids = {3: 0, 5: 1, 6: 2}                               # session id -> slot, as the pool keeps it
-    chk = stream.check_ragged_sessions
+    chk = lambda *a: stream.check_sessions('stream_pool.step_ragged', *a)
     assert chk((5, 3), 2, None, 4, open_ids) == [5, 3] and chk([6], 1, 1, 4, open_ids) == [6]
     with pytest.raises(TcowError, match='1 .. capacity'):
         chk([], 0, None, 4, open_ids)
@@ -66,11 +66,11 @@ def test_step_ragged_list_refusals():
 
 
 def test_step_ragged_range_refusal_names_the_session():
-    stream.check_ragged_range([3, 5], [0, 26], [30, 4], 30)                     # both end exactly at the last frame
+    stream.check_range('stream_pool.step_ragged', [3, 5], [0, 26], [30, 4], 30)                     # both end exactly at the last frame
     with pytest.raises(TcowError, match='session 5: frames 27..30'):
-        stream.check_ragged_range([3, 5], [0, 27], [1, 4], 30)
+        stream.check_range('stream_pool.step_ragged', [3, 5], [0, 27], [1, 4], 30)
     with pytest.raises(TcowError, match='session 9'):                            # the offender is the last of the list
-        stream.check_ragged_range([3, 5, 9], [0, 1, 30], [1, 1, 1], 30)
+        stream.check_range('stream_pool.step_ragged', [3, 5, 9], [0, 1, 30], [1, 1, 1], 30)
 
 
 def test_step_ragged_input_refusals():
@@ -86,23 +86,6 @@ def test_step_ragged_input_refusals():
             stream._check_inputs(who, m, dev, 1, 1, ok, bad)
     with pytest.raises(TcowError, match='device'):                              # (a CPU tensor is on no stream device)
         stream._check_inputs(who, m, dev, 1, 1, ok, torch.zeros(1, 1, 2, 32, 48))
-
-
-def test_ragged_mask0_is_one_cache_entry_and_a_prefix():
-    """A ragged step's mask0 (B = 1, F frames) is cached once per module: the longest vector asked for so far, shorter ones its prefixes."""
-    m = _net(1).eval().seeker
-    before = len(m._operands.copies)
-    S = m.geometry(1)['S']
-    seen = {}
-    for F in (3, 1, 7, 2, 7, 12, 5):
-        mask0, _ = engine._row_vectors(m, m.geometry(1, T=F), False, frames_only=True)
-        want, _ = engine._row_vectors(m, m.geometry(1, T=F), False)
-        assert mask0.shape == (F * S,) and torch.equal(mask0, want) and mask0.is_contiguous()
-        seen[F] = mask0.data_ptr()
-    keys = [k for k in m._operands.copies if isinstance(k, tuple) and k[0] == 'mask0_frames']
-    assert len(keys) == 1 and m._operands.copies[keys[0]].numel() == 12 * S
-    assert len(m._operands.copies) == before + 1 + 6                              # (the six distinct F of the unshared form above, for comparison)
-    assert seen[5] == seen[12]                                                     # a shorter vector after the longest one is its prefix
 
 
 def test_ragged_abi_entries():

@@ -15,6 +15,9 @@ LIB16 := tcow_amd/libtcow_hip_fp16.so
 all: $(LIB) $(LIB16)
 
 # (attention: no NaN arithmetic on the path -- lets fmaxf chains become v_max3_f32 without canonicalising v_max instructions)
+# attention_bf16.hip includes its three kernel families (attention_bf16_*.inc): one translation unit
+ATTN_INC := $(wildcard $(CSRC)/attention_bf16_*.inc)
+$(OBJ)/attention_bf16.hip.o $(OBJ16)/attention_bf16.hip.o: $(ATTN_INC)
 $(OBJ)/attention_bf16.hip.o: EXTRA := -fno-honor-nans -fno-slp-vectorize
 $(OBJ)/%.hip.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/gemm_f32.h $(CSRC)/gemm_glds.h $(CSRC)/gemm_nt_common.h $(CSRC)/attention_tiles.h $(CSRC)/attention_common.h include/tcow_hip.h
 	@mkdir -p $(OBJ)
@@ -51,7 +54,7 @@ build/ubench_gemm: tools/ubench_gemm.hip tools/gemm_p8.hip $(CSRC)/common.h
 
 ubench_gemm: build/ubench_gemm
 
-build/ubench_valu: tools/ubench_valu.hip tools/attn_fwd_variants.inc $(CSRC)/attention_bf16.hip $(CSRC)/common.h
+build/ubench_valu: tools/ubench_valu.hip tools/attn_fwd_variants.inc $(CSRC)/attention_tiles.h $(CSRC)/attention_common.h $(CSRC)/common.h include/tcow_hip.h
 	@mkdir -p build
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -fno-honor-nans -fno-slp-vectorize -Wno-unused-result -x hip $< -o $@
 

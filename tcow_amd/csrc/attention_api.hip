@@ -42,7 +42,6 @@ static int check_shape(const tcow_attn_shape* s, const char* who) {
     return TCOW_OK;
 }
 
-bool tcow_attn_mfma_supported(const SeqDesc& d, bool shared);
 bool tcow_attn_mfma_zeroes_slot0(const SeqDesc& d, bool shared, bool backward);
 int tcow_attn_mfma_fwd(hipStream_t st, const SeqDesc& d, bool shared, const void* qkv, void* out, float* lse);
 long tcow_attn_mfma_bwd_workspace_bytes(const SeqDesc& d);
@@ -57,18 +56,14 @@ bool tcow_attn_x3_supported(const SeqDesc& d);
 int tcow_attn_x3_fwd(hipStream_t st, const SeqDesc& d, const void* qkv, void* out, float* lse);
 int tcow_attn_x3_bwd(hipStream_t st, const SeqDesc& d, const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv);
 
-static bool use_mfma(const tcow_attn_shape* s, const SeqDesc& d, int spatial) {
-    return s->dtype == TCOW_BF16 && tcow_attn_mfma_supported(d, spatial != 0);
-}
-
 int tcow_attn_fwd_dispatch(hipStream_t st, const tcow_attn_shape* s, int spatial, const void* qkv, void* out, float* lse) {
     const SeqDesc d = spatial ? spatial_desc(s) : temporal_desc(s);
     int rc;
-    if ((!spatial || d.offset == 1) && !(use_mfma(s, d, spatial) && tcow_attn_mfma_zeroes_slot0(d, spatial != 0, false))) {   // slot-0 rows are not produced by the kernels: define them as zero
+    if ((!spatial || d.offset == 1) && !(s->dtype == TCOW_BF16 && tcow_attn_mfma_zeroes_slot0(d, spatial != 0, false))) {   // slot-0 rows are not produced by the kernels: define them as zero
         rc = (s->dtype == TCOW_BF16) ? zero_slot0<bf16_t>(st, out, s->D, s, s->D) : zero_slot0<float>(st, out, s->D, s, s->D);
         if (rc) return rc;
     }
-    if (use_mfma(s, d, spatial)) return tcow_attn_mfma_fwd(st, d, spatial != 0, qkv, out, lse);      // 16-bit storage: attention_bf16.hip
+    if (s->dtype == TCOW_BF16) return tcow_attn_mfma_fwd(st, d, spatial != 0, qkv, out, lse);      // 16-bit storage: attention_bf16.hip
     if (s->dtype == TCOW_F32X3 && tcow_attn_x3_supported(d)) return tcow_attn_x3_fwd(st, d, qkv, out, lse);   // f32 storage, bf16 x 3 split products (attention_x3.hip)
     return tcow_attn_f32_fwd(st, d, qkv, out, lse);                                                   // f32 storage: exact-f32 MFMA kernels (attention_f32.hip)
 }
@@ -89,11 +84,11 @@ int tcow_attn_bwd_dispatch(hipStream_t st, const tcow_attn_shape* s, int spatial
                            void* ws, void* dqkv) {
     const SeqDesc d = spatial ? spatial_desc(s) : temporal_desc(s);
     int rc;
-    if ((!spatial || d.offset == 1) && !(use_mfma(s, d, spatial) && tcow_attn_mfma_zeroes_slot0(d, spatial != 0, true))) {
+    if ((!spatial || d.offset == 1) && !(s->dtype == TCOW_BF16 && tcow_attn_mfma_zeroes_slot0(d, spatial != 0, true))) {
         rc = (s->dtype == TCOW_BF16) ? zero_slot0<bf16_t>(st, dqkv, 3L * s->D, s, 3 * s->D) : zero_slot0<float>(st, dqkv, 3L * s->D, s, 3 * s->D);
         if (rc) return rc;
     }
-    if (use_mfma(s, d, spatial)) return tcow_attn_mfma_bwd(st, d, spatial != 0, qkv, out, dout, lse, ws, dqkv);
+    if (s->dtype == TCOW_BF16) return tcow_attn_mfma_bwd(st, d, spatial != 0, qkv, out, dout, lse, ws, dqkv);
     if (s->dtype == TCOW_F32X3 && tcow_attn_x3_supported(d)) return tcow_attn_x3_bwd(st, d, qkv, out, dout, lse, (float*)ws, dqkv);
     return tcow_attn_f32_bwd(st, d, qkv, out, dout, lse, (float*)ws, dqkv);
 }

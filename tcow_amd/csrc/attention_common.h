@@ -19,6 +19,32 @@ __device__ __forceinline__ long seq_base(const SeqDesc& s, int item) {
     return o * s.outer_stride + i * s.inner_stride + s.offset;
 }
 
+// Work placement of the kernels in which several workgroups share one (sequence, head) "pair": the workgroups that own different query (key)
+// chunks of the SAME pair stream the same K / V (Q / dO) tiles, so they should run at the same time on the same XCD (private L2): workgroups are
+// dispatched round-robin over the 8 XCDs, so XCD x takes pairs x, x+8, ... and walks the chunks of one pair back to back.  (With the chunk in
+// blockIdx.y the sharers ran a whole grid row apart and every chunk re-read its K / V from HBM: FETCH_SIZE 2.3x the algorithmic bytes.)
+struct StreamWork { int pair, chunk; bool valid; };
+__device__ __forceinline__ StreamWork stream_work(int pairs, int nchunk) {
+    const int b = blockIdx.x, x = b & 7, k = b >> 3;
+    const int i = k / nchunk;
+    StreamWork w; w.chunk = k - i * nchunk; w.pair = 8 * i + x; w.valid = w.pair < pairs;
+    return w;
+}
+static inline int stream_grid(int pairs, int nchunk) { return 8 * ((pairs + 7) / 8) * nchunk; }
+
+// Causal tile ranges over the nt 32-position tiles of a sequence (key allowed iff key_pos <= query_pos + diag).  A workgroup's range is the
+// same function of its last query tile / first key tile.
+// key tiles [0, end) that query tile qt sees: its last query, 32 qt + 31, sees keys up to 32 qt + 31 + diag
+__device__ __forceinline__ int causal_key_tiles(const SeqDesc& s, int nt, int qt) {
+    const long klim = (long)32 * qt + 31 + s.diag;
+    return klim >= (long)s.L - 1 ? nt : (int)(klim / 32) + 1;
+}
+// first query tile that sees any key of key tile j: q >= 32 j - diag
+__device__ __forceinline__ int causal_first_query_tile(const SeqDesc& s, int j) {
+    const long qlo = (long)32 * j - s.diag;
+    return qlo > 0 ? (int)(qlo / 32) : 0;
+}
+
 static inline int diag_from_causal(int ca) {
     // vit.py:93-99: ca in {1,2}: tril(); ca >= 3: tril(diagonal=ca-2); ca <= 0: no mask.
     if (ca <= 0) return 1 << 28;

@@ -66,23 +66,12 @@ __device__ __forceinline__ void load_frag(const float* __restrict__ row, int hi,
     for (int s = 0; s < 32; ++s) f[s] = row[2 * s + hi] * scale;
 }
 
-// Workgroups that own different 4-tile chunks of the SAME (sequence, head) stream the same tiles of the other side: run them back to back
-// on one XCD (blocks are dispatched round-robin over the 8 XCDs), so the re-reads hit that XCD's L2.
-struct Work { int pair, chunk; bool valid; };
-__device__ __forceinline__ Work work_of(int pairs, int nchunk) {
-    const int b = blockIdx.x, x = b & 7, k = b >> 3;
-    const int i = k / nchunk;
-    Work w; w.chunk = k - i * nchunk; w.pair = 8 * i + x; w.valid = w.pair < pairs;
-    return w;
-}
-inline int grid_of(int pairs, int nchunk) { return 8 * ((pairs + 7) / 8) * nchunk; }
-
 // ------------------------------------------------------------------------------------------------ forward
 __global__ __launch_bounds__(256, 2) void attn_f32_fwd(SeqDesc sd, int nt, const float* __restrict__ qkv, float* __restrict__ out, float* __restrict__ lse) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Ks = smem; float* Vs = smem + NC * TILE_F;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
-    const Work w = work_of(sd.n_outer * sd.n_inner * sd.heads, (nt + 3) / 4);
+    const StreamWork w = stream_work(sd.n_outer * sd.n_inner * sd.heads, (nt + 3) / 4);
     if (!w.valid) return;
     const int item = w.pair / sd.heads, head = w.pair - item * sd.heads;
     const long base = seq_base(sd, item);
@@ -95,13 +84,9 @@ __global__ __launch_bounds__(256, 2) void attn_f32_fwd(SeqDesc sd, int nt, const
     load_frag(qh + (size_t)qc * pse, hi, kScale, qf);
     f32x16 o0 = zero16(), o1 = zero16();
     float m = kNeg, l = 0.f;
-    auto tiles_seen = [&](int t) {                                       // key tiles a query tile can see (causal limit)
-        const long klim = (long)32 * t + 31 + sd.diag;
-        return klim >= (long)sd.L - 1 ? nt : (int)(klim / 32) + 1;
-    };
-    const int my_end = active ? tiles_seen(qt) : 0;
+    const int my_end = active ? causal_key_tiles(sd, nt, qt) : 0;
     const int last_qt = w.chunk * 4 + 3 < nt ? w.chunk * 4 + 3 : nt - 1;
-    const int wg_end = tiles_seen(last_qt);
+    const int wg_end = causal_key_tiles(sd, nt, last_qt);
     for (int c0 = 0; c0 < wg_end; c0 += NC) {
         __syncthreads();
 #pragma unroll
@@ -162,7 +147,7 @@ __global__ __launch_bounds__(256, 2) void attn_f32_bwd_dq(SeqDesc sd, int nt, co
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Ks = smem; float* Vs = smem + NC * TILE_F;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
-    const Work w = work_of(sd.n_outer * sd.n_inner * sd.heads, (nt + 3) / 4);
+    const StreamWork w = stream_work(sd.n_outer * sd.n_inner * sd.heads, (nt + 3) / 4);
     if (!w.valid) return;
     const int item = w.pair / sd.heads, head = w.pair - item * sd.heads;
     const long base = seq_base(sd, item);
@@ -186,13 +171,9 @@ __global__ __launch_bounds__(256, 2) void attn_f32_bwd_dq(SeqDesc sd, int nt, co
     }
     const float ls = lse[row * sd.heads + head];
     f32x16 dq0 = zero16(), dq1 = zero16();
-    auto tiles_seen = [&](int t) {
-        const long klim = (long)32 * t + 31 + sd.diag;
-        return klim >= (long)sd.L - 1 ? nt : (int)(klim / 32) + 1;
-    };
-    const int my_end = active ? tiles_seen(qt) : 0;
+    const int my_end = active ? causal_key_tiles(sd, nt, qt) : 0;
     const int last_qt = w.chunk * 4 + 3 < nt ? w.chunk * 4 + 3 : nt - 1;
-    const int wg_end = tiles_seen(last_qt);
+    const int wg_end = causal_key_tiles(sd, nt, last_qt);
     for (int c0 = 0; c0 < wg_end; c0 += NC) {
         __syncthreads();
 #pragma unroll
@@ -235,7 +216,7 @@ __global__ __launch_bounds__(256, 2) void attn_f32_bwd_dkv(SeqDesc sd, int nt, c
     float* Qs = smem; float* Os = smem + NC * TILE_F;
     float* Ls = smem + 2 * NC * TILE_F; float* Dl = Ls + NC * 32;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
-    const Work w = work_of(sd.n_outer * sd.n_inner * sd.heads, (nt + 3) / 4);
+    const StreamWork w = stream_work(sd.n_outer * sd.n_inner * sd.heads, (nt + 3) / 4);
     if (!w.valid) return;
     const int item = w.pair / sd.heads, head = w.pair - item * sd.heads;
     const long base = seq_base(sd, item);
@@ -250,9 +231,8 @@ __global__ __launch_bounds__(256, 2) void attn_f32_bwd_dkv(SeqDesc sd, int nt, c
     load_frag(qh + (size_t)kc * pse + 2 * sd.D, hi, 1.0f, vf);
     f32x16 dk0 = zero16(), dk1 = zero16(), dv0 = zero16(), dv1 = zero16();
     // first query tile that can see any key of this wave / of this workgroup
-    auto first_q = [&](int t) { const long qlo = (long)32 * t - sd.diag; return qlo > 0 ? (int)(qlo / 32) : 0; };
-    const int my_i0 = first_q(jt);
-    const int c_start = first_q(w.chunk * 4) & ~(NC - 1);
+    const int my_i0 = causal_first_query_tile(sd, jt);
+    const int c_start = causal_first_query_tile(sd, w.chunk * 4) & ~(NC - 1);
     for (int c0 = c_start; c0 < nt; c0 += NC) {
         __syncthreads();
 #pragma unroll
@@ -475,7 +455,7 @@ constexpr int kLdsDkv = (2 * NC * TILE_F + 2 * NC * 32) * 4;
 }  // namespace
 
 int tcow_attn_f32_fwd(hipStream_t st, const SeqDesc& d, const void* qkv, void* out, float* lse) {
-    const int nt = cdiv(d.L, 32), grid = grid_of(d.n_outer * d.n_inner * d.heads, cdiv(nt, 4));
+    const int nt = cdiv(d.L, 32), grid = stream_grid(d.n_outer * d.n_inner * d.heads, cdiv(nt, 4));
     if (nt == 1) {
         tcow_ensure_lds((const void*)attn_f32_fwd_solo, kLdsFwdSolo);
         hipLaunchKernelGGL(attn_f32_fwd_solo, dim3(cdiv(d.n_outer * d.n_inner * d.heads, 4)), dim3(256), kLdsFwdSolo, st, d, (const float*)qkv, (float*)out, lse);
@@ -490,7 +470,7 @@ int tcow_attn_f32_fwd(hipStream_t st, const SeqDesc& d, const void* qkv, void* o
 
 // `delta` = rows * heads floats of workspace (the layout of lse)
 int tcow_attn_f32_bwd(hipStream_t st, const SeqDesc& d, const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv) {
-    const int nt = cdiv(d.L, 32), grid = grid_of(d.n_outer * d.n_inner * d.heads, cdiv(nt, 4));
+    const int nt = cdiv(d.L, 32), grid = stream_grid(d.n_outer * d.n_inner * d.heads, cdiv(nt, 4));
     if (nt == 1) {
         tcow_ensure_lds((const void*)attn_f32_bwd_solo, kLdsBwdSolo);
         hipLaunchKernelGGL(attn_f32_bwd_solo, dim3(cdiv(d.n_outer * d.n_inner * d.heads, 4)), dim3(256), kLdsBwdSolo, st, d, (const float*)qkv, (const float*)out, (const float*)dout, lse,

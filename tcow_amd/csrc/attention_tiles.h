@@ -1,7 +1,8 @@
-// Tile helpers shared by the 16-bit MFMA attention kernels (attention_bf16.hip, attention_fwd_p4.hip): the [32 rows][64 x 16-bit] LDS tile with its
-// universal swizzle, direct-to-LDS tile loads, MFMA operand fragments (row fragments / transpose reads), the half-wave exchange, the forward
-// tile step of the streaming kernels and the whole-row store of a transposed accumulator pair.  Everything lives in an anonymous namespace:
-// each translation unit gets its own copy.
+// Tile helpers shared by the 16-bit MFMA attention kernels (attention_bf16.hip and its three family files) and
+// the micro-benchmark tools/ubench_valu.hip: the [32 rows][64 x 16-bit] LDS tile with its universal swizzle, direct-to-LDS tile loads, MFMA operand
+// fragments (row fragments / transpose reads), the half-wave exchange, the forward and backward tile steps that more than one kernel family uses,
+// and the stores of a transposed accumulator pair (a row per lane, or whole rows through LDS).  Everything lives in an anonymous namespace: each
+// translation unit gets its own copy.
 #pragma once
 #include "attention_common.h"
 
@@ -14,9 +15,6 @@
 namespace {
 
 constexpr int TILE_B = 4096;                 // 32 rows x 128 B
-#ifdef UBENCH_ATTN
-__device__ long long* g_attn_dbg;
-#endif
 constexpr float kScale = 0.125f;             // head_dim^-0.5 (vit.py:70)
 constexpr float kLog2e = 1.4426950408889634f;
 
@@ -109,11 +107,11 @@ __device__ __forceinline__ bf16x8 pack8(const float* v) {
     return __builtin_convertvector(t, bf16x8);
 }
 
+// wave-private kernels: four waves of a workgroup own four consecutive (sequence, head) pairs
 struct WorkId { int item, head; bool valid; };
-template <bool SHARED>
 __device__ __forceinline__ WorkId work_id(const SeqDesc& sd, int wave) {
     const int items = sd.n_outer * sd.n_inner;
-    const int idx = SHARED ? blockIdx.x : blockIdx.x * 4 + wave;
+    const int idx = blockIdx.x * 4 + wave;
     WorkId w; w.valid = idx < items * sd.heads; w.item = idx / sd.heads; w.head = idx - w.item * sd.heads;
     return w;
 }
@@ -171,6 +169,17 @@ __device__ __forceinline__ void fwd_tile(const SeqDesc& sd, const char* ktile, c
     o1 = TCOW_MFMA_32x32x16_H16(frag_tr(vtile, 1, 1, lane), pb1, o1, 0, 0, 0);
 }
 
+// The P V and gradient MFMAs are issued as (transposed-read fragment, P or dS), i.e. they accumulate O^T / dV^T / dK^T / dQ^T: lane (l31, hi)
+// owns ONE token row and per 32-wide d tile the channels d = 8*(r>>2) + 4*hi + (r&3) -- groups of 4 consecutive channels, each
+// an 8-byte store (instead of 64 two-byte stores per lane with the untransposed layout).
+__device__ __forceinline__ void store_rowT(bf16_t* drow, int hi, const f32x16& a0, const f32x16& a1) {
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {
+        st4(drow + 8 * gq + 4 * hi, make_float4(a0[4 * gq], a0[4 * gq + 1], a0[4 * gq + 2], a0[4 * gq + 3]));
+        st4(drow + 32 + 8 * gq + 4 * hi, make_float4(a1[4 * gq], a1[4 * gq + 1], a1[4 * gq + 2], a1[4 * gq + 3]));
+    }
+}
+
 // normalise and store one query tile's output (+ log-sum-exp)
 __device__ __forceinline__ void fwd_store(const SeqDesc& sd, long base, int head, int q, int hi, float m, float l, const f32x16& o0, const f32x16& o1,
                                           bf16_t* __restrict__ out, float* __restrict__ lse) {
@@ -179,12 +188,7 @@ __device__ __forceinline__ void fwd_store(const SeqDesc& sd, long base, int head
         const float inv = 1.0f / l;
         const long row = base + (long)q * sd.pos_stride;
         bf16_t* orow = out + row * sd.D + head * ATT_HD;
-        // O^T C layout: register r of lane (q, hi) holds d = 32*dt + 8*(r>>2) + 4*hi + (r&3): 4 consecutive d per group
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-            st4(orow + 8 * gq + 4 * hi, make_float4(o0[4 * gq] * inv, o0[4 * gq + 1] * inv, o0[4 * gq + 2] * inv, o0[4 * gq + 3] * inv));
-            st4(orow + 32 + 8 * gq + 4 * hi, make_float4(o1[4 * gq] * inv, o1[4 * gq + 1] * inv, o1[4 * gq + 2] * inv, o1[4 * gq + 3] * inv));
-        }
+        store_rowT(orow, hi, o0 * inv, o1 * inv);
         if (lse && hi == 0) lse[row * sd.heads + head] = (m + log2f(l)) * 0.6931471805599453f;   // natural-log LSE of the scaled scores
     }
 }
@@ -238,6 +242,115 @@ __device__ __forceinline__ void fwd_store_rows(const SeqDesc& sd, long base, int
     store_tile_staged(stage, lane, 1.0f / l, o0, o1, out + (base + (long)q0 * sd.pos_stride) * sd.D + head * ATT_HD, sd.pos_stride * (long)sd.D, sd.L - q0);
     const int q = q0 + l31;
     if (lse && hi == 0 && q < sd.L) lse[(base + (long)q * sd.pos_stride) * sd.heads + head] = (m + log2f(l)) * 0.6931471805599453f;
+}
+
+// ------------------------------------------------------------------------------------------------ backward tile steps
+// One 32-query tile against the wave's 32-key tile (backward, dK / dV side).
+__device__ __forceinline__ void dkv_tile(const SeqDesc& sd, const char* qtile, const char* dotile, const float2* __restrict__ ldh, int i, int key,
+                                         const bf16x8 (&kf)[4], const bf16x8 (&vf)[4], int l31, int hi, int lane, f32x16& dk0, f32x16& dk1, f32x16& dv0, f32x16& dv1,
+                                         bf16x8* ds_out = nullptr) {
+    f32x16 s, dp;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+        s = TCOW_MFMA_32x32x16_H16(frag_row(qtile, l31, ks, hi), kf[ks], s, 0, 0, 0);
+        dp = TCOW_MFMA_32x32x16_H16(frag_row(dotile, l31, ks, hi), vf[ks], dp, 0, 0, 0);
+    }
+    // rows of the accumulators are queries q = 32*i + 8*(r>>2) + 4*hi + (r&3); lse/delta for 4 consecutive q per group.
+    // (VALU diet: masks only on boundary tiles -- masked scores are pushed to -1e30 so that exp2 underflows to 0; the 1/sqrt(d)
+    // factor of dS is applied once to the finished dK / dQ tiles in dkv_store / dq_store instead of per element here.)
+    const bool need_mask = (32 * i + 31 >= sd.L) || (key - l31 + 31 >= sd.L) || ((long)(key - l31) + 31 > (long)32 * i + sd.diag);
+    if (need_mask) {
+        TCOW_NO_IFCVT();
+        if ((32 * i + 31 < sd.L) && ((long)(key - l31) + 31 <= (long)32 * i + sd.diag)) {
+            // only key padding (the last key tile of a sequence, every step of its wave): one lane-constant test instead of three per element
+            const bool kv = key < sd.L;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[r] = kv ? s[r] : -1e30f;
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int q = 32 * i + crow32(r, hi);
+                if (!(q < sd.L && key < sd.L && (long)key <= (long)q + sd.diag)) s[r] = -1e30f;
+            }
+        }
+    }
+    float pv[16], dsv[16];
+    const float4* tab = reinterpret_cast<const float4*>(ldh + 32 * i + 4 * hi);     // (lse2, delta) of queries 8 gq + 4 hi + e: two float4 per group
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {
+        const float4 a = tab[4 * gq], b = tab[4 * gq + 1];   // (lse0, d0, lse1, d1), (lse2, d2, lse3, d3)
+        const float ls[4] = {a.x, a.z, b.x, b.z}, dl[4] = {a.y, a.w, b.y, b.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int r = 4 * gq + e;
+            const float sv = s[r];
+            const float p = __builtin_amdgcn_exp2f(fmaf(sv, kScale * kLog2e, -ls[e]));
+            pv[r] = p;
+            dsv[r] = p * (dp[r] - dl[e]);
+        }
+    }
+    const bf16x8 pa0 = pack8(pv), pa1 = pack8(pv + 8), da0 = pack8(dsv), da1 = pack8(dsv + 8);
+    if (ds_out) { ds_out[0] = da0; ds_out[1] = da1; }        // (one-kernel backward: the dS block goes to the dQ strip)
+    dv0 = TCOW_MFMA_32x32x16_H16(frag_tr(dotile, 0, 0, lane), pa0, dv0, 0, 0, 0);
+    dv0 = TCOW_MFMA_32x32x16_H16(frag_tr(dotile, 1, 0, lane), pa1, dv0, 0, 0, 0);
+    dv1 = TCOW_MFMA_32x32x16_H16(frag_tr(dotile, 0, 1, lane), pa0, dv1, 0, 0, 0);
+    dv1 = TCOW_MFMA_32x32x16_H16(frag_tr(dotile, 1, 1, lane), pa1, dv1, 0, 0, 0);
+    dk0 = TCOW_MFMA_32x32x16_H16(frag_tr(qtile, 0, 0, lane), da0, dk0, 0, 0, 0);
+    dk0 = TCOW_MFMA_32x32x16_H16(frag_tr(qtile, 1, 0, lane), da1, dk0, 0, 0, 0);
+    dk1 = TCOW_MFMA_32x32x16_H16(frag_tr(qtile, 0, 1, lane), da0, dk1, 0, 0, 0);
+    dk1 = TCOW_MFMA_32x32x16_H16(frag_tr(qtile, 1, 1, lane), da1, dk1, 0, 0, 0);
+}
+
+__device__ __forceinline__ void dkv_store(const SeqDesc& sd, long base, long ld3, int head, int j, int l31, int hi, const f32x16& dk0, const f32x16& dk1,
+                                          const f32x16& dv0, const f32x16& dv1, bf16_t* __restrict__ dqkv) {
+    const int kr = 32 * j + l31;
+    if (kr < sd.L) {
+        bf16_t* drow = dqkv + (base + (long)kr * sd.pos_stride) * ld3 + head * ATT_HD;
+        store_rowT(drow + sd.D, hi, dk0 * kScale, dk1 * kScale);        // dS was accumulated without its 1/sqrt(d) factor
+        store_rowT(drow + 2 * sd.D, hi, dv0, dv1);
+    }
+}
+
+// One 32-key tile against the wave's 32-query tile (backward, dQ side).
+__device__ __forceinline__ void dq_tile(const SeqDesc& sd, const char* ktile, const char* vtile, int j, int q, const bf16x8 (&qf)[4], const bf16x8 (&dof)[4],
+                                        float ls, float dl, int l31, int hi, int lane, f32x16& dq0, f32x16& dq1) {
+    f32x16 s, dp;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+        s = TCOW_MFMA_32x32x16_H16(frag_row(ktile, l31, ks, hi), qf[ks], s, 0, 0, 0);
+        dp = TCOW_MFMA_32x32x16_H16(frag_row(vtile, l31, ks, hi), dof[ks], dp, 0, 0, 0);
+    }
+    const bool need_mask = (32 * j + 31 >= sd.L) || (q - l31 + 31 >= sd.L) || ((long)32 * j + 31 > (long)(q - l31) + sd.diag);
+    if (need_mask) {
+        TCOW_NO_IFCVT();
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int key = 32 * j + crow32(r, hi);
+            if (!(q < sd.L && key < sd.L && (long)key <= (long)q + sd.diag)) s[r] = -1e30f;
+        }
+    }
+    float dsv[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const float sv = s[r];
+        const float p = __builtin_amdgcn_exp2f(fmaf(sv, kScale * kLog2e, -ls));
+        dsv[r] = p * (dp[r] - dl);
+    }
+    const bf16x8 da0 = pack8(dsv), da1 = pack8(dsv + 8);
+    dq0 = TCOW_MFMA_32x32x16_H16(frag_tr(ktile, 0, 0, lane), da0, dq0, 0, 0, 0);
+    dq0 = TCOW_MFMA_32x32x16_H16(frag_tr(ktile, 1, 0, lane), da1, dq0, 0, 0, 0);
+    dq1 = TCOW_MFMA_32x32x16_H16(frag_tr(ktile, 0, 1, lane), da0, dq1, 0, 0, 0);
+    dq1 = TCOW_MFMA_32x32x16_H16(frag_tr(ktile, 1, 1, lane), da1, dq1, 0, 0, 0);
+}
+
+__device__ __forceinline__ void dq_store(const SeqDesc& sd, long base, long ld3, int head, int qt, int l31, int hi, const f32x16& dq0, const f32x16& dq1,
+                                         bf16_t* __restrict__ dqkv) {
+    const int qr = 32 * qt + l31;
+    if (qr < sd.L) store_rowT(dqkv + (base + (long)qr * sd.pos_stride) * ld3 + head * ATT_HD, hi, dq0 * kScale, dq1 * kScale);
 }
 
 }  // namespace

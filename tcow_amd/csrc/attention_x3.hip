@@ -4,12 +4,12 @@
 // Until round 6 the mode ran its attention on the exact-f32 MFMA (attention_f32.hip: 1/16 of the bf16 rate): 1 499 us per spatial forward at configs[1], a fifth
 // of that mode's step.  Same contract as attention_f32.hip (f32 qkv [rows, 3D] in, f32 out / dqkv, natural-log LSE, delta workspace in the lse layout).
 //
-// Structure = the streaming kernels of attention_bf16.hip: a 256-thread workgroup owns 4 query (forward, dQ) or 4 key (dK / dV) tiles of one (sequence, head),
+// Structure = the kernels of attention_bf16_chunked.inc: a 256-thread workgroup owns 4 query (forward, dQ) or 4 key (dK / dV) tiles of one (sequence, head),
 // one per wave, and walks the other side in chunks of CH tiles.  A chunk is read as f32 by all 256 threads (one 8-element piece of a row per thread and
 // tile: two 16-byte loads), split ONCE in registers and stored as two [32][64] bf16 LDS tiles (hi, lo) in the layout of attention_tiles.h (16-byte chunk c of row
 // r at c ^ g(r): conflict-free ds_read_b128 row fragments and ds_read_b64_tr_b16 transpose reads).  The wave's own rows (Q, dO or K, V) are split when
 // their fragments are loaded; probabilities / dS are split in registers before they become MFMA B operands.  Softmax statistics, masks, the lazy running
-// maximum and the accumulation order are those of attention_bf16.hip's fwd_tile / dq_tile / dkv_tile.
+// maximum and the accumulation order are those of attention_tiles.h's fwd_tile / dq_tile / dkv_tile.
 // MFMAs per (query tile, key tile) pair: forward 24, dQ 36, dK / dV 48 (bf16 mode: 8 / 12 / 16).
 #include <stdlib.h>
 
@@ -143,16 +143,6 @@ __device__ __forceinline__ void xfrag_global(const float* __restrict__ row, int 
     }
 }
 
-// same placement as the other streaming kernels: the workgroups of one (sequence, head) back to back on one XCD
-struct XWork { int pair, chunk; bool valid; };
-__device__ __forceinline__ XWork x_work(int pairs, int nchunk) {
-    const int b = blockIdx.x, x = b & 7, k = b >> 3;
-    const int i = k / nchunk;
-    XWork w; w.chunk = k - i * nchunk; w.pair = 8 * i + x; w.valid = w.pair < pairs;
-    return w;
-}
-inline int x_grid(int pairs, int nchunk) { return 8 * ((pairs + 7) / 8) * nchunk; }
-
 // f32 row store of a transposed accumulator pair: lane (row l31, hi) owns channels 32 dt + 8 g + 4 hi + 0..3 of register quad g
 __device__ __forceinline__ void x_store_row(float* __restrict__ drow, int hi, const f32x16& a0, const f32x16& a1, float mul) {
 #pragma unroll
@@ -169,7 +159,7 @@ __global__ __launch_bounds__(256, 2) void attn_x3_fwd(SeqDesc sd, int nt, const 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hi = lane >> 5;
-    XWork w = x_work(sd.n_outer * sd.n_inner * sd.heads, (nt + 3) / 4);
+    StreamWork w = stream_work(sd.n_outer * sd.n_inner * sd.heads, (nt + 3) / 4);
     if (SOLO) { w.pair = blockIdx.x * 4 + wave; w.chunk = 0; w.valid = w.pair < sd.n_outer * sd.n_inner * sd.heads; }
     if (!w.valid) return;
     char* smem = SOLO ? smem_ + wave * (4 * XTILE) : smem_;
@@ -188,10 +178,8 @@ __global__ __launch_bounds__(256, 2) void attn_x3_fwd(SeqDesc sd, int nt, const 
     for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
     float m = -1e30f, l = 0.f;
     const float sc = xScale * xLog2e;
-    const long klim = (long)32 * qt + 31 + sd.diag;
-    const int kt_end = (!active) ? 0 : (klim >= (long)sd.L - 1 ? nt : (int)(klim / 32) + 1);
-    const long klim_wg = (long)32 * (w.chunk * 4 + 3) + 31 + sd.diag;          // last key tile any wave of this workgroup needs
-    const int kt_end_wg = klim_wg >= (long)sd.L - 1 ? nt : (int)(klim_wg / 32) + 1;
+    const int kt_end = (!active) ? 0 : causal_key_tiles(sd, nt, qt);
+    const int kt_end_wg = causal_key_tiles(sd, nt, w.chunk * 4 + 3);          // key tiles any wave of this workgroup needs
     for (int c0 = 0; c0 < kt_end_wg; c0 += CH) {
         if (!SOLO) {
             __syncthreads();                                               // previous chunk fully consumed
@@ -264,7 +252,7 @@ __global__ __launch_bounds__(256, 2) void attn_x3_bwd_dq(SeqDesc sd, int nt, con
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hi = lane >> 5;
-    XWork w = x_work(sd.n_outer * sd.n_inner * sd.heads, (nt + 3) / 4);
+    StreamWork w = stream_work(sd.n_outer * sd.n_inner * sd.heads, (nt + 3) / 4);
     if (SOLO) { w.pair = blockIdx.x * 4 + wave; w.chunk = 0; w.valid = w.pair < sd.n_outer * sd.n_inner * sd.heads; }
     if (!w.valid) return;
     char* smem = SOLO ? smem_ + wave * (4 * XTILE) : smem_;
@@ -300,10 +288,8 @@ __global__ __launch_bounds__(256, 2) void attn_x3_bwd_dq(SeqDesc sd, int nt, con
     f32x16 dq0, dq1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { dq0[r] = 0.f; dq1[r] = 0.f; }
-    const long klim = (long)32 * qt + 31 + sd.diag;
-    const int kt_end = (!active) ? 0 : (klim >= (long)sd.L - 1 ? nt : (int)(klim / 32) + 1);
-    const long klim_wg = (long)32 * (w.chunk * 4 + 3) + 31 + sd.diag;
-    const int kt_end_wg = klim_wg >= (long)sd.L - 1 ? nt : (int)(klim_wg / 32) + 1;
+    const int kt_end = (!active) ? 0 : causal_key_tiles(sd, nt, qt);
+    const int kt_end_wg = causal_key_tiles(sd, nt, w.chunk * 4 + 3);
     for (int c0 = 0; c0 < kt_end_wg; c0 += CH) {
         if (!SOLO) {
             __syncthreads();
@@ -357,7 +343,7 @@ __global__ __launch_bounds__(256, 2) void attn_x3_bwd_dkv(SeqDesc sd, int nt, co
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hi = lane >> 5;
-    XWork w = x_work(sd.n_outer * sd.n_inner * sd.heads, (nt + 3) / 4);
+    StreamWork w = stream_work(sd.n_outer * sd.n_inner * sd.heads, (nt + 3) / 4);
     if (SOLO) { w.pair = blockIdx.x * 4 + wave; w.chunk = 0; w.valid = w.pair < sd.n_outer * sd.n_inner * sd.heads; }
     if (!w.valid) return;
     char* smem = SOLO ? smem_ + wave * (4 * XTILE + 256) : smem_;
@@ -385,10 +371,11 @@ __global__ __launch_bounds__(256, 2) void attn_x3_bwd_dkv(SeqDesc sd, int nt, co
     for (int r = 0; r < 16; ++r) { dk0[r] = 0.f; dk1[r] = 0.f; dv0[r] = 0.f; dv1[r] = 0.f; }
     const float sc = xScale * xLog2e;
     // first query tile that can see any key of this wave / of this workgroup
+    // (i0 = causal_first_query_tile(sd, jt), written out: with jt = 0 in the SOLO instantiation hipcc folds this form to a 32-bit value that it knows
+    // to be non-negative and drops the max(c0, i0) of the loop below; through the function that kernel needs 234 registers instead of 226)
     const long qlo = (long)32 * jt - sd.diag;
     const int i0 = qlo > 0 ? (int)(qlo / 32) : 0;
-    const long qlo_wg = (long)32 * (w.chunk * 4) - sd.diag;
-    const int c_start = qlo_wg > 0 ? ((int)(qlo_wg / 32) / CH) * CH : 0;
+    const int c_start = (causal_first_query_tile(sd, w.chunk * 4) / CH) * CH;
     for (int c0 = c_start; c0 < nt; c0 += CH) {
         if (!SOLO) {
             __syncthreads();
@@ -484,7 +471,7 @@ int x3_bwd_launch(hipStream_t st, const SeqDesc& d, int nt, int grid, const void
 bool tcow_attn_x3_supported(const SeqDesc& d) { (void)d; return true; }
 
 int tcow_attn_x3_fwd(hipStream_t st, const SeqDesc& d, const void* qkv, void* out, float* lse) {
-    const int nt = cdiv(d.L, 32), pairs = d.n_outer * d.n_inner * d.heads, grid = x_grid(pairs, cdiv(nt, 4));
+    const int nt = cdiv(d.L, 32), pairs = d.n_outer * d.n_inner * d.heads, grid = stream_grid(pairs, cdiv(nt, 4));
     if (nt == 1) {                       // one-tile sequences: a wave per (sequence, head), wave-private 16 KiB
         constexpr int lds = 4 * 4 * XTILE;
         tcow_ensure_lds((const void*)attn_x3_fwd<1, true>, lds);
@@ -497,7 +484,7 @@ int tcow_attn_x3_fwd(hipStream_t st, const SeqDesc& d, const void* qkv, void* ou
 
 // `delta` = rows * heads floats of workspace (the layout of lse)
 int tcow_attn_x3_bwd(hipStream_t st, const SeqDesc& d, const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv) {
-    const int nt = cdiv(d.L, 32), pairs = d.n_outer * d.n_inner * d.heads, grid = x_grid(pairs, cdiv(nt, 4));
+    const int nt = cdiv(d.L, 32), pairs = d.n_outer * d.n_inner * d.heads, grid = stream_grid(pairs, cdiv(nt, 4));
     if (nt == 1) {
         constexpr int lds = 4 * 4 * XTILE, lds_dkv = 4 * (4 * XTILE + 256);
         tcow_ensure_lds((const void*)attn_x3_bwd_dq<1, true>, lds);

@@ -195,9 +195,9 @@ def test_attn_ref64_against_autograd(spatial, B, T, S, heads, ca):
 # ---------------------------------------------------------------------------------------------------- shape matrix (GPU)
 # (id, spatial, B, T, S, heads, causal).  Kernels: 16-bit (bf16 / fp16 builds) forward / backward | f32x3 | f32.  nt = 32-position tiles.
 MATRIX = [
-    # temporal, nt = 1: attn_fwd_mfma<false> (zeroes slot 0 itself) / attn_bwd_one_tile | attn_x3_fwd<1,true> / attn_x3_bwd_dq,dkv<1,true> | attn_f32_fwd_solo / attn_f32_bwd_solo
+    # temporal, nt = 1: attn_fwd_mfma (zeroes slot 0 itself) / attn_bwd_one_tile | attn_x3_fwd<1,true> / attn_x3_bwd_dq,dkv<1,true> | attn_f32_fwd_solo / attn_f32_bwd_solo
     ('t30_bench', False, 3, 30, 301, 12, 1),
-    # temporal, nt = 2 (wave-private): attn_fwd_mfma<false> / attn_bwd_prep_kernel + attn_bwd_dkv_mfma<false> + attn_bwd_dq_mfma<false> + zero_rows_kernel
+    # temporal, nt = 2 (wave-private): attn_fwd_mfma / attn_bwd_prep_kernel + attn_bwd_dkv_mfma + attn_bwd_dq_mfma + zero_rows_kernel
     #   | attn_x3_fwd<2> / attn_x3_bwd_dq,dkv<4> | attn_f32_fwd / attn_f32_bwd_dq,dkv;  no mask (ca <= 0) included
     ('t60_c1', False, 1, 60, 5, 2, 1), ('t60_c0', False, 1, 60, 5, 2, 0), ('t60_cm1', False, 1, 60, 5, 2, -1),
     ('t33_c3', False, 1, 33, 4, 3, 3),                     # look-ahead 1: one valid key in tile 2

@@ -1,7 +1,7 @@
 // Forward-attention variants that were built, measured and NOT adopted (profiles/r03_attention.md section 4, profiles/HISTORY.md): the resident
 // kernel (whole K / V of a (frame, head) in 80 KiB of LDS, two query tiles per wave) and the persistent 10-wave kernel.  They lived in
 // libtcow_hip.so behind TCOW_ATTN_RES until round 4; now they are part of the micro-benchmark only (tools/ubench_valu.hip includes this file
-// right after csrc/attention_bf16.hip, whose helpers -- load_tile, frag_row, fwd_store, SeqDesc ... -- it uses).
+// right after csrc/attention_tiles.h, whose helpers -- load_tile, frag_row, fwd_store, SeqDesc ... -- it uses).
 namespace {
 
 // ------------------------------------------------------------------------------------------------ resident forward (spatial, S <= 320)

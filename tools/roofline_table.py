@@ -34,7 +34,7 @@ c, t = fam('gemm_tn_bf16'); c2, t2 = fam('slab_reduce4'); row('weight-gradient G
 c, t = fam('attn_fwd_stream'); row('spatial attention forward', c, t, sp_f, L * (qkv_b + o_b), 'VALU-issue / latency-bound at d = 64 (62 VALU + 16 v_exp_f32 per 8 MFMAs, 4 waves per SIMD; profiles/r05_attn_fwd_p4.txt, r06_attn_pack_half.txt), traffic at the algorithmic minimum')
 c, t = fam('attn_bwd_one_kernel', 'attn_bwd_dq_stream', 'attn_bwd_dkv_stream')
 row('spatial attention backward (one kernel: dK/dV tiles + dQ^T from the dS strip in LDS)', c, t, 2.5 * sp_f, L * (2 * qkv_b + 2 * o_b), 'VALU / LDS-traffic bound tile steps (10 tile waves + 2 dQ chain waves per CU); prologue at the one-CU miss rate')
-c, t = fam('attn_fwd_mfma<false>'); row('temporal attention forward', c, t, tp_f, L * (qkv_b + o_b), 'HBM-bound (81 % of a float4 copy)')
+c, t = fam('attn_fwd_mfma'); row('temporal attention forward', c, t, tp_f, L * (qkv_b + o_b), 'HBM-bound (81 % of a float4 copy)')
 c, t = fam('attn_bwd_one_tile'); row('temporal attention backward', c, t, 2.5 * tp_f, L * (2 * qkv_b + o_b), 'HBM-bound (84 % of a float4 copy)')
 c, t = fam('ln_fwd_kernel'); row('LayerNorm forward', c, t, None, c * M * D * 6.0, 'HBM-bound')
 c, t = fam('ln_bwd_kernel'); row('LayerNorm backward (+ residual add, + 16-bit copy of dx for the next GEMM)', c, t, None, c * M * D * (2 + 4 + 4 + 4 + 2.0), 'HBM-bound')

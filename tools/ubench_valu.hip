@@ -5,9 +5,11 @@
 //      v_permlane32_swap.
 //   B  the same instructions as FILLERS between v_mfma_f32_32x32x16_bf16 (4 independent accumulators, so the matrix pipe is the only
 //      limit at 0 fillers): cycles per MFMA for n = 0 .. 16 fillers per MFMA gap, 1 and 2 waves per SIMD.
-//   C  the shipped forward tile function (attention_bf16.hip::fwd_tile) on LDS-resident K / V tiles, no global traffic inside the
+//   C  the shipped forward tile function (attention_tiles.h::fwd_tile) on LDS-resident K / V tiles, no global traffic inside the
 //      timed loop: cycles per (32 query x 32 key) step and per SIMD with 1 .. 4 waves per SIMD -> what the step ARITHMETIC costs when
 //      nothing waits for memory, i.e. the MFMA utilisation ceiling of this formulation (8 MFMAs = 256 matrix-pipe cycles per step).
+//      C2 / C3: the same for the steps of the resident and the persistent forward variants (attn_fwd_variants.inc).
+//   D  phase timelines of those two variants at the benchmark shape.
 //
 // Cycles are s_memtime ticks (= shader cycles, MI355X_MICROARCH.md "Per-instruction cycle constants"), taken per wave around the
 // timed loop; one workgroup on one CU, so "per SIMD" = the longest wave of that SIMD.   build: make ubench   run: build/ubench_valu
@@ -19,13 +21,8 @@
 #include <algorithm>
 #include <string>
 
-#define UBENCH_ATTN 1
-#include "../tcow_amd/csrc/attention_bf16.hip"
+#include "../tcow_amd/csrc/attention_tiles.h"
 #include "attn_fwd_variants.inc"
-
-// the library's error plumbing, not linked here
-void tcow_set_error(const char*, ...) {}
-void tcow_ensure_lds(const void*, int) {}
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s:%d %s\n", __FILE__, __LINE__, hipGetErrorString(e_)); exit(1); } } while (0)
 
@@ -439,80 +436,6 @@ int main(int argc, char** argv) {
                 for (int w = 0; w < 10; ++w) { double sm = 0; for (int b = 0; b < 256; ++b) { const long long* t = &h2[(size_t)(b * 10 + w) * 8]; sm += (double)(t[i + 1] - t[i]); } fprintf(f, " %7.0f", sm / 256); }
                 fprintf(f, "\n");
             }
-        }
-        // E: phase timeline of the shipped streaming backward kernels (wave 0..3 of every workgroup that owns four live tiles)
-        {
-            bf16_t *dout, *dqkv; float2* ldt; long long* dbg3;
-            CK(hipMalloc(&dout, M * D * 2)); CK(hipMalloc(&dqkv, M * 3 * D * 2)); CK(hipMalloc(&ldt, (size_t)pairs * 320 * 8));
-            CK(hipMemcpy(dout, qkv, M * D * 2, hipMemcpyDeviceToDevice));
-            const int nchunk = 3, grid = stream_grid(pairs, nchunk);
-            CK(hipMalloc(&dbg3, (size_t)grid * 4 * 24 * 8));
-            hipLaunchKernelGGL(attn_fwd_stream<5>, dim3(grid), dim3(256), 0, 0, sd, 10, qkv, o, lse); CK(hipDeviceSynchronize());
-            for (int which = 0; which < 4; ++which) {
-                auto launch = [&](long long* d) {
-                    CK(hipMemcpyToSymbol(HIP_SYMBOL(g_attn_dbg), &d, sizeof(d)));
-                    if (which == 0) hipLaunchKernelGGL(attn_bwd_dq_stream<4>, dim3(grid), dim3(256), 0, 0, sd, 10, qkv, o, dout, lse, ldt, dqkv);
-                    else if (which == 1) hipLaunchKernelGGL(attn_bwd_dkv_stream<4>, dim3(grid), dim3(256), 0, 0, sd, 10, qkv, dout, ldt, dqkv);
-                    else if (which == 2) hipLaunchKernelGGL(attn_bwd_dq_stream<5>, dim3(grid), dim3(256), 0, 0, sd, 10, qkv, o, dout, lse, ldt, dqkv);
-                    else hipLaunchKernelGGL(attn_bwd_dkv_stream<5>, dim3(grid), dim3(256), 0, 0, sd, 10, qkv, dout, ldt, dqkv);
-                };
-                for (int rep = 0; rep < 3; ++rep) launch(nullptr);
-                CK(hipEventRecord(e0)); for (int rep = 0; rep < 20; ++rep) launch(nullptr);
-                CK(hipEventRecord(e1)); CK(hipDeviceSynchronize()); CK(hipEventElapsedTime(&ms, e0, e1));
-                fprintf(f, "E  %s at B*Qs=3 T=30 S=301 h=12: %.1f us per launch\n", (which & 1) ? (which > 1 ? "attn_bwd_dkv_stream<5>" : "attn_bwd_dkv_stream<4>") : (which > 1 ? "attn_bwd_dq_stream<5>" : "attn_bwd_dq_stream<4>"), ms * 1000 / 20);
-                CK(hipMemset(dbg3, 0, (size_t)grid * 4 * 24 * 8));
-                launch(dbg3); CK(hipDeviceSynchronize());
-                std::vector<long long> h3((size_t)grid * 4 * 24); CK(hipMemcpy(h3.data(), dbg3, h3.size() * 8, hipMemcpyDeviceToHost));
-                const char* ph[5] = {"barrier in", "issue loads", "loads land", "barrier", "tile steps"};
-                const int nch = which > 1 ? 2 : 3;
-                for (int w = 0; w < 4; w += 3) {
-                    double acc[3][5] = {{0}}; double store = 0, total = 0; int n = 0;
-                    for (int b = 0; b < grid; ++b) {
-                        const int k = b >> 3, ch = k % nchunk; if (ch == 2) continue;            // (the workgroup of tiles 8, 9 has two idle waves)
-                        const long long* t = &h3[(size_t)(b * 4 + w) * 24]; if (!t[21]) continue;
-                        ++n; store += (double)(t[21] - t[5 * nch]); total += (double)(t[21] - t[0]);
-                        for (int c = 0; c < nch; ++c) for (int i = 0; i < 5; ++i) { const int a = 1 + 5 * c + i; acc[c][i] += (double)(t[a] - t[a - 1]); }
-                    }
-                    fprintf(f, "E    wave %d (%d workgroups): total %.0f cycles; issue of the first chunk's loads %.0f, fragment loads (+ delta) %.0f; store %.0f\n", w, n, total / n, acc[0][0] / n, acc[0][1] / n, store / n);
-                    for (int c = 0; c < nch; ++c) {
-                        fprintf(f, "E      chunk %d:", c);
-                        for (int i = (c ? 0 : 2); i < 5; ++i) fprintf(f, "  %s %.0f", ph[i], acc[c][i] / n);
-                        fprintf(f, "\n");
-                    }
-                }
-            }
-        }
-        // F: phase timeline of the one-kernel spatial backward (round 4): per wave index, mean shader cycles
-        {
-            bf16_t *dout, *dqkv; long long* dbg4;
-            CK(hipMalloc(&dout, M * D * 2)); CK(hipMalloc(&dqkv, M * 3 * D * 2));
-            CK(hipMemcpy(dout, qkv, M * D * 2, hipMemcpyDeviceToDevice));
-            CK(hipMalloc(&dbg4, (size_t)pairs * 12 * 40 * 8));
-            CK(hipFuncSetAttribute((const void*)attn_bwd_one_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ONE_LDS));
-            auto launch = [&](long long* d) {
-                CK(hipMemcpyToSymbol(HIP_SYMBOL(g_attn_dbg), &d, sizeof(d)));
-                hipLaunchKernelGGL(attn_bwd_one_kernel, dim3(pairs), dim3(768), ONE_LDS, 0, sd, 10, qkv, o, dout, lse, dqkv);
-            };
-            for (int rep = 0; rep < 3; ++rep) launch(nullptr);
-            CK(hipEventRecord(e0)); for (int rep = 0; rep < 20; ++rep) launch(nullptr);
-            CK(hipEventRecord(e1)); CK(hipDeviceSynchronize()); CK(hipEventElapsedTime(&ms, e0, e1));
-            fprintf(f, "F  attn_bwd_one_kernel at B*Qs=3 T=30 S=301 h=12: %.1f us per launch\n", ms * 1000 / 20);
-            CK(hipMemset(dbg4, 0, (size_t)pairs * 12 * 40 * 8));
-            launch(dbg4); CK(hipDeviceSynchronize());
-            std::vector<long long> h4((size_t)pairs * 12 * 40); CK(hipMemcpy(h4.data(), dbg4, h4.size() * 8, hipMemcpyDeviceToHost));
-            fprintf(f, "F  mean shader cycles per phase over %d workgroups, per wave index 0..11 (10, 11 = the dQ chain waves):\n", pairs);
-            auto row = [&](const char* name, auto get) {
-                fprintf(f, "F    %-44s", name);
-                for (int w = 0; w < 12; ++w) { double sm = 0; for (int b = 0; b < pairs; ++b) sm += get(&h4[((size_t)b * 12 + w) * 40]); fprintf(f, " %7.0f", sm / pairs); }
-                fprintf(f, "\n");
-            };
-            row("prologue (loads, table, first barrier)", [](const long long* t) { return (double)(t[1] - t[0]); });
-            row("step: tile arithmetic + strip write (mean of 10)", [](const long long* t) { double s = 0; for (int i = 0; i < 10; ++i) s += (double)(t[2 + 3 * i] - (i ? t[4 + 3 * (i - 1)] : t[1])); return s / 10; });
-            row("step: wait for own loads + barrier (mean of 10)", [](const long long* t) { double s = 0; for (int i = 0; i < 10; ++i) s += (double)(t[3 + 3 * i] - t[2 + 3 * i]); return s / 10; });
-            row("step: requests + dQ chains / dQ stores (mean of 10)", [](const long long* t) { double s = 0; for (int i = 0; i < 10; ++i) s += (double)(t[4 + 3 * i] - t[3 + 3 * i]); return s / 10; });
-            row("final barrier", [](const long long* t) { return (double)(t[32] - t[31]); });
-            row("last dQ tile + dK / dV stores", [](const long long* t) { return (double)(t[33] - t[32]); });
-            row("workgroup lifetime", [](const long long* t) { return (double)(t[33] - t[0]); });
         }
         hipLaunchKernelGGL(attn_fwd_res, dim3(pairs), dim3(256), RES_LDS, 0, sd, 10, qkv, o, lse, dbg); CK(hipDeviceSynchronize());
         std::vector<long long> h((size_t)pairs * 16); CK(hipMemcpy(h.data(), dbg, h.size() * 8, hipMemcpyDeviceToHost));

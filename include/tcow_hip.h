@@ -57,7 +57,7 @@ extern "C" {
 
 /* ABI version (bumped on any signature change) and last error text of the calling thread.  A host compares tcow_version() with the TCOW_ABI_VERSION it
  * was built against before the first call (tcow_amd/_lib.py does, for both builds of the library). */
-#define TCOW_ABI_VERSION 13
+#define TCOW_ABI_VERSION 14
 int tcow_version(void);
 const char* tcow_last_error(void);
 
@@ -94,6 +94,16 @@ typedef struct {
     const float* row_scale2;   /* [M] or NULL */
 } tcow_gemm_args;
 int tcow_gemm_nt(void* stream, const tcow_gemm_args* args);
+
+/* The same product and epilogue for SMALL M (a streaming step's few hundred rows), 16-bit mode only: 64 x 64 tiles and a deterministic split
+ * over K into `split` (1 .. 16, <= K / 64) runs of 64-wide k-slices.  split == 1: one launch, the bits of the 128 x 128 tile of tcow_gemm_nt.
+ * split > 1: every (tile, slice) workgroup writes its f32 partial to slab s of `workspace` ([split, M, N] f32, 16-byte aligned, at least
+ * tcow_gemm_nt_skinny_workspace_bytes(M, N, split) bytes), a second launch on the same stream adds the slabs in slice order and runs the
+ * epilogue: the result is a fixed function of the inputs.  The workspace needs no initialisation and may be reused by the next call on
+ * the stream.  args->tile is ignored; any M is valid (which M is "small" is the caller's routing).  resid may alias an f32 C.  Every refusal
+ * happens before any launch. */
+long tcow_gemm_nt_skinny_workspace_bytes(int M, int N, int split);   /* 0 for split == 1 */
+int tcow_gemm_nt_skinny(void* stream, const tcow_gemm_args* args, int split, void* workspace, long workspace_bytes);
 
 /* Measurement aid for bench.py: between _begin and _end every tcow_gemm_nt launch is bracketed by HIP events recorded
  * on its own stream; _end synchronises on them and returns the summed event time (ms), the summed 2*M*N*K and the

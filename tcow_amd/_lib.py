@@ -71,6 +71,8 @@ SIGNATURES = {
     'tcow_version': (_i, []),
     'tcow_last_error': (ctypes.c_char_p, []),
     'tcow_gemm_nt': (_i, [_vp, ctypes.POINTER(GemmArgs)]),
+    'tcow_gemm_nt_skinny_workspace_bytes': (_l, [_i, _i, _i]),
+    'tcow_gemm_nt_skinny': (_i, [_vp, ctypes.POINTER(GemmArgs), _i, _vp, _l]),
     'tcow_prof_gemm_begin': (_i, [_i]),
     'tcow_prof_gemm_end': (_i, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]),
     'tcow_prof_attn_begin': (_i, [_i]),
@@ -138,7 +140,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 13       # TCOW_ABI_VERSION of include/tcow_hip.h
+ABI_VERSION = 14       # TCOW_ABI_VERSION of include/tcow_hip.h
 
 
 def _declare(L, tolerant=False):

@@ -32,6 +32,7 @@ void tcow_ensure_lds(const void* kernel, int bytes) {
 
 int tcow_gemm_nt_bf16(hipStream_t stream, const tcow_gemm_args* a);
 int tcow_gemm_nt_f32(hipStream_t stream, const tcow_gemm_args* a);
+int tcow_gemm_nt_skinny_bf16(hipStream_t stream, const tcow_gemm_args* a, int split, float* slab);
 int tcow_gemm_tn_bf16(hipStream_t stream, int M, int N, int K, const bf16_t* dY, long ldy, const bf16_t* X, long ldx, float* slab, int splits, int* nz_out,
                       float* bias_part, int* bias_parts_out);
 int tcow_gemm_tn_f32(hipStream_t stream, int M, int N, int K, const float* dY, long ldy, const float* X, long ldx, float* dW, long lddw, int accumulate,
@@ -127,6 +128,33 @@ static int gemm_nt_dispatch(void* stream, const tcow_gemm_args* a) {
     if (a->dtype == TCOW_F32X3) return tcow_gemm_nt_x3((hipStream_t)stream, a);
     tcow_set_error("tcow_gemm_nt: unknown dtype %d", a->dtype);
     return TCOW_ERR_INVALID_ARG;
+}
+
+// ---- skinny-M NT GEMM (gemm_nt_skinny.hip): 64 x 64 tiles with a deterministic split over K, for the streaming steps
+long tcow_gemm_nt_skinny_workspace_bytes(int M, int N, int split) {
+    if (M <= 0 || N <= 0 || split <= 1) return 0;
+    return (long)split * M * N * 4;
+}
+
+int tcow_gemm_nt_skinny(void* stream, const tcow_gemm_args* a, int split, void* workspace, long workspace_bytes) {
+    TCOW_CHECK_ARG(a != nullptr, "tcow_gemm_nt_skinny: null args");
+    TCOW_CHECK_ARG(a->dtype == TCOW_BF16, "tcow_gemm_nt_skinny: dtype %d is not served (the 16-bit mode only; TCOW_F32 and TCOW_F32X3 go to tcow_gemm_nt)", a->dtype);
+    TCOW_CHECK_ARG(a->M > 0 && a->N > 0 && a->K > 0, "tcow_gemm_nt_skinny: bad shape M=%d N=%d K=%d", a->M, a->N, a->K);
+    TCOW_CHECK_ARG(a->A && a->W && a->C, "tcow_gemm_nt_skinny: null operand");
+    TCOW_CHECK_ARG((a->act != TCOW_ACT_DGELU && a->act != TCOW_ACT_GELU_DSAVE && a->act != TCOW_ACT_MUL_AUX) || a->aux, "tcow_gemm_nt_skinny: this activation needs aux");
+    TCOW_CHECK_ARG(a->act >= TCOW_ACT_NONE && a->act <= TCOW_ACT_MUL_AUX, "tcow_gemm_nt_skinny: unknown activation %d", a->act);
+    TCOW_CHECK_ARG(a->bias2 || !a->row_scale2, "tcow_gemm_nt_skinny: row_scale2 without bias2");
+    TCOW_CHECK_ARG(a->K % 64 == 0, "tcow_gemm_nt_skinny: K=%d must be a multiple of 64", a->K);
+    TCOW_CHECK_ARG(a->lda % 8 == 0 && a->ldw % 8 == 0, "tcow_gemm_nt_skinny: lda/ldw must be multiples of 8 elements");
+    TCOW_CHECK_ARG(a->ldc % 4 == 0 && a->N % 4 == 0, "tcow_gemm_nt_skinny: N and ldc must be multiples of 4");
+    TCOW_CHECK_ARG((!a->resid || a->ldr % 4 == 0) && (!a->aux || a->ldaux % 4 == 0), "tcow_gemm_nt_skinny: ldr / ldaux must be multiples of 4");
+    TCOW_CHECK_ARG(split >= 1 && split <= 16, "tcow_gemm_nt_skinny: split=%d must be 1 .. 16", split);
+    TCOW_CHECK_ARG(split <= a->K / 64, "tcow_gemm_nt_skinny: split=%d exceeds the K/64 = %d k-slices of K=%d", split, a->K / 64, a->K);
+    const long need = tcow_gemm_nt_skinny_workspace_bytes(a->M, a->N, split);
+    TCOW_CHECK_ARG(need == 0 || workspace != nullptr, "tcow_gemm_nt_skinny: workspace is NULL (split=%d needs %ld bytes)", split, need);
+    TCOW_CHECK_ARG(workspace_bytes >= need, "tcow_gemm_nt_skinny: workspace too small (workspace_bytes %ld < %ld)", workspace_bytes, need);
+    TCOW_CHECK_ARG(need == 0 || ((uintptr_t)workspace & 15) == 0, "tcow_gemm_nt_skinny: workspace must be 16-byte aligned");
+    return tcow_gemm_nt_skinny_bf16((hipStream_t)stream, a, split, (float*)workspace);
 }
 
 static const int kColsumParts = 64 * 24 * 2;   // >= nz * tiles_k * 2 partial rows of the fused bias gradient (nz <= 64, K <= 3072)

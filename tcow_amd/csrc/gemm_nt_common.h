@@ -1,5 +1,5 @@
 // Shared pieces of the bf16 NT GEMM kernels (gemm_bf16.hip: 128 / 256 / 320-row tiles, one workgroup per CU for the big ones; gemm_nt_c2.hip: the
-// 160 x 256 tile that runs two workgroups per CU): launch parameters, the tile order, the fused epilogue arithmetic (bias / DropPath row scale /
+// 160 x 256 tile that runs two workgroups per CU; gemm_nt_skinny.hip: the 64 x 64 tile with a split over K of the streaming steps): launch parameters, the tile order, the fused epilogue arithmetic (bias / DropPath row scale /
 // GELU / GELU' / residual / second masked bias; vit.py:50-61,74-76,111,146), the table of compile-time epilogues and the epilogue of one wave's
 // 160 x 64 accumulator tile.  (The weight-gradient TN kernels are in gemm_tn_bf16.hip; gemm_glds.h holds the loads both families use.)
 #pragma once

@@ -186,7 +186,8 @@ def run_forward(module, rgb, qm, params, save, stream=None):
     """stream (inference only): one stream step, built by tcow_amd/stream.py -- rgb / qm then hold the step's T = rgb.shape[2] frames
     per row, and the schedule differs in three places: the embeddings (stream.pos, and stream.time_rows [B*T, D], one row of the time table per
     (row, frame)), the temporal attention (stream.attn_temporal: against the block's K / V cache, which it extends) and, for
-    causal_attention == 1, the cls row (stream.cls_row: frame 0's, kept per block)."""
+    causal_attention == 1, the cls row (stream.cls_row: frame 0's, kept per block).  A fifth thing is asked of the step: stream.skinny, whether its
+    GEMMs may take the skinny-M entry point (ops.gemm_nt(..., skinny=)); the clip path never passes the keyword."""
     mode = module.mode
     gmode = module.gemm_mode           # the GEMM entry points' arithmetic: `mode`, or TCOW_F32X3 (f32 tensors, bf16 x 3 split products) for precision='bf16x3'
     dt = ops.tdtype(mode)
@@ -202,6 +203,7 @@ def run_forward(module, rgb, qm, params, save, stream=None):
     def E(*shape, dtype=dt):
         return torch.empty(*shape, dtype=dtype, device=dev)
 
+    sk = {} if stream is None else {'skinny': stream.skinny}        # GEMM routing of a stream step (ops.gemm_nt)
     opnd = module._operands
     W = lambda p: opnd.weight(mode, p, train)[0]
     mask0, dps = _row_vectors(module, g, module.training, stream_step=stream is not None)
@@ -222,16 +224,16 @@ def run_forward(module, rgb, qm, params, save, stream=None):
         ops.im2col_channels(mode, rgb, P, module.tracker_pretrained, A_rgb)
         ops.im2col_channels(mode, qm, P, False, A_m)
         Xrgb = E(Bc * T * S, D, dtype=f32)
-        ops.gemm_nt(gmode, A_rgb, Wc[:, :Krgb], Xrgb, bias=params[4].detach())
+        ops.gemm_nt(gmode, A_rgb, Wc[:, :Krgb], Xrgb, bias=params[4].detach(), **sk)
         TS = T * S
         for bq in range(B):
             b = bq // Qs
-            ops.gemm_nt(gmode, A_m[bq * TS:(bq + 1) * TS], Wc[:, Krgb:], X[bq * TS:(bq + 1) * TS], resid=Xrgb[b * TS:(b + 1) * TS])
+            ops.gemm_nt(gmode, A_m[bq * TS:(bq + 1) * TS], Wc[:, Krgb:], X[bq * TS:(bq + 1) * TS], resid=Xrgb[b * TS:(b + 1) * TS], **sk)
         A_pe = (A_rgb, A_m)
     else:
         A_pe = E(M, Kpe)
         ops.im2col(mode, rgb, qm, P, module.tracker_pretrained, A_pe)
-        ops.gemm_nt(gmode, A_pe, W(params[3]), X, bias=params[4].detach())
+        ops.gemm_nt(gmode, A_pe, W(params[3]), X, bias=params[4].detach(), **sk)
     if stream is None:
         pos, te, pos_idx, time_idx = _effective_embeddings(module, g)
         ops.embed_fwd(X, B, T, S, params[0].detach().reshape(-1), pos, te)
@@ -262,7 +264,7 @@ def run_forward(module, rgb, qm, params, save, stream=None):
             V = E(M, D); mu1 = E(M, dtype=f32) if save else None; rs1 = E(M, dtype=f32) if save else None
             ops.layernorm_fwd(mode, R0, n1_w, n1_b, V, mu1, rs1)
             QKV2 = E(M, 3 * D)
-            ops.gemm_nt(gmode, V, W(q[ix['qkv']]), QKV2, bias=qkv_b)
+            ops.gemm_nt(gmode, V, W(q[ix['qkv']]), QKV2, bias=qkv_b, **sk)
             QJ = QKV2.index_select(0, jrows)                                # compact (cls, patches) sequences: the kernels take contiguous ones
             OJ = E(B * Lj, D); lse_s = E(B * Lj, heads, dtype=f32) if save else None
             ops.attn_fwd(shape_joint, True, QJ, OJ, lse_s)
@@ -270,7 +272,7 @@ def run_forward(module, rgb, qm, params, save, stream=None):
             O2.index_copy_(0, jrows, OJ)                                    # (the unused cls replicas of frames 1.. get a zero attention output)
             rs_s = dp['s']
             R2 = E(M, D, dtype=f32) if save else R0
-            ops.gemm_nt(gmode, O2, W(q[ix['proj']]), R2, bias=proj_b, row_scale=rs_s, resid=R0)
+            ops.gemm_nt(gmode, O2, W(q[ix['proj']]), R2, bias=proj_b, row_scale=rs_s, resid=R0, **sk)
             if save:
                 st.update(R1=R0, mu1=mu1, rs1=rs1, V=V, QKV_s=QJ, O_s=O2, OJ=OJ, lse_s=lse_s, rs_s=rs_s)
         else:
@@ -279,7 +281,7 @@ def run_forward(module, rgb, qm, params, save, stream=None):
             U = E(M, D); mu0 = E(M, dtype=f32) if save else None; rs0 = E(M, dtype=f32) if save else None
             ops.layernorm_fwd(mode, R0, tn_w, tn_b, U, mu0, rs0)
             QKV = E(M, 3 * D)
-            ops.gemm_nt(gmode, U, W(q[ix['tqkv']]), QKV, bias=tqkv_b)
+            ops.gemm_nt(gmode, U, W(q[ix['tqkv']]), QKV, bias=tqkv_b, **sk)
             O = E(M, D); lse_t = E(M, heads, dtype=f32) if save else None
             if stream is None:
                 ops.attn_fwd(shape_attn, False, QKV, O, lse_t)
@@ -288,26 +290,26 @@ def run_forward(module, rgb, qm, params, save, stream=None):
             R1 = E(M, D, dtype=f32) if save else R0
             if fold:
                 Wf, _, bprime = opnd.folded(mode, i, q, ix, train)
-                ops.gemm_nt(gmode, O, Wf, R1, bias=bprime, row_scale=dp['t0'], resid=R0, bias2=tfc_b, row_scale2=mask0)
+                ops.gemm_nt(gmode, O, Wf, R1, bias=bprime, row_scale=dp['t0'], resid=R0, bias2=tfc_b, row_scale2=mask0, **sk)
                 Pj = None
             else:
                 Pj = E(M, D)
-                ops.gemm_nt(gmode, O, W(q[ix['tproj']]), Pj, bias=tproj_b, row_scale=dp['t'])
-                ops.gemm_nt(gmode, Pj, W(q[ix['tfc']]), R1, bias=tfc_b, row_scale=mask0, resid=R0)
+                ops.gemm_nt(gmode, O, W(q[ix['tproj']]), Pj, bias=tproj_b, row_scale=dp['t'], **sk)
+                ops.gemm_nt(gmode, Pj, W(q[ix['tfc']]), R1, bias=tfc_b, row_scale=mask0, resid=R0, **sk)
             if save:
                 st.update(R0=R0, mu0=mu0, rs0=rs0, U=U, QKV_t=QKV, O_t=O, lse_t=lse_t, Pj=Pj)
             # spatial
             V = E(M, D); mu1 = E(M, dtype=f32) if save else None; rs1 = E(M, dtype=f32) if save else None
             ops.layernorm_fwd(mode, R1, n1_w, n1_b, V, mu1, rs1)
             QKV2 = E(M, 3 * D)
-            ops.gemm_nt(gmode, V, W(q[ix['qkv']]), QKV2, bias=qkv_b)
+            ops.gemm_nt(gmode, V, W(q[ix['qkv']]), QKV2, bias=qkv_b, **sk)
             O2 = E(M, D); lse_s = E(M, heads, dtype=f32) if save else None
             ops.attn_fwd(shape_attn, True, QKV2, O2, lse_s)
             rs_s = dp['s']
             if not use_cls:
                 rs_s = mask0 if rs_s is None else rs_s * mask0
             R2 = E(M, D, dtype=f32) if save else R1
-            ops.gemm_nt(gmode, O2, W(q[ix['proj']]), R2, bias=proj_b, row_scale=rs_s, resid=R1)
+            ops.gemm_nt(gmode, O2, W(q[ix['proj']]), R2, bias=proj_b, row_scale=rs_s, resid=R1, **sk)
             if use_cls and stream is not None:
                 stream.cls_row(i, R2, B, T, S)                                       # (a stream has causal_attention 1 or 2)
             elif use_cls:
@@ -321,9 +323,9 @@ def run_forward(module, rgb, qm, params, save, stream=None):
         pre = E(M, Hd) if save else None
         H = E(M, Hd)
         # training saves GELU'(pre-activation) instead of the pre-activation: the backward is then one multiply per element
-        ops.gemm_nt(gmode, Wn, W(q[ix['fc1']]), H, bias=fc1_b, act=ACT_GELU_DSAVE if save else ACT_GELU, aux=pre)
+        ops.gemm_nt(gmode, Wn, W(q[ix['fc1']]), H, bias=fc1_b, act=ACT_GELU_DSAVE if save else ACT_GELU, aux=pre, **sk)
         R3 = E(M, D, dtype=f32) if save else R2
-        ops.gemm_nt(gmode, H, W(q[ix['fc2']]), R3, bias=fc2_b, row_scale=dp['m'], resid=R2)
+        ops.gemm_nt(gmode, H, W(q[ix['fc2']]), R3, bias=fc2_b, row_scale=dp['m'], resid=R2, **sk)
         if save:
             st.update(R2=R2, mu2=mu2, rs2=rs2, Wn=Wn, pre=pre, H=H)
             sv['blocks'].append(st)
@@ -350,7 +352,7 @@ def run_forward(module, rgb, qm, params, save, stream=None):
         ops.scale_cast(mode, X, None, Fm)
     Co = module.output_channels
     Pm = E(M, Co * P * P)
-    ops.gemm_nt(gmode, Fm, W(head_w), Pm, bias=head_b.detach())           # mask_tracker.py:113
+    ops.gemm_nt(gmode, Fm, W(head_w), Pm, bias=head_b.detach(), **sk)           # mask_tracker.py:113
     stp = module.track_map_stride if module.track_map_stride > 1 else 1
     h, w = module.frame_height // stp, module.frame_width // stp
     pooled = E(B * T, Co, h, w, dtype=f32)

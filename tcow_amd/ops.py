@@ -55,20 +55,88 @@ def _need_cuda(*ts):
             raise L.TcowError('libtcow_hip kernels need CUDA/HIP tensors (no CPU fallback on this path)')
 
 
-def gemm_nt(mode, A, W, out, bias=None, row_scale=None, resid=None, act=ACT_NONE, aux=None, tile=0, bias2=None, row_scale2=None):
-    """out[M,N] = epilogue(A[M,K] @ W[N,K]^T); see tcow_gemm_nt. `out` dtype f32 or the mode's dtype."""
-    _need_cuda(A, W, out)
+def _gemm_args(dm, A, W, out, bias, row_scale, resid, act, aux, tile, bias2, row_scale2):
     M, K = A.shape
-    N = W.shape[0]
+    return L.GemmArgs(M, W.shape[0], K, dm, A.data_ptr(), A.stride(0), W.data_ptr(), W.stride(0), out.data_ptr(), out.stride(0),
+                      1 if out.dtype == torch.float32 else 0, _p(bias), _p(row_scale), _p(resid),
+                      resid.stride(0) if resid is not None else 0, act, _p(aux), aux.stride(0) if aux is not None else 0, int(tile), _p(bias2), _p(row_scale2))
+
+
+def gemm_nt(mode, A, W, out, bias=None, row_scale=None, resid=None, act=ACT_NONE, aux=None, tile=0, bias2=None, row_scale2=None, skinny=False):
+    """out[M,N] = epilogue(A[M,K] @ W[N,K]^T); see tcow_gemm_nt. `out` dtype f32 or the mode's dtype.
+    skinny=True (the streaming steps): a 16-bit product that skinny_plan routes goes to gemm_nt_skinny instead."""
+    if skinny and is16(mode) and not tile:
+        split = skinny_plan(A.shape[0], W.shape[0], A.shape[1])
+        if split > 0:
+            return gemm_nt_skinny(mode, A, W, out, bias=bias, row_scale=row_scale, resid=resid, act=act, aux=aux, bias2=bias2, row_scale2=row_scale2, split=split)
+    _need_cuda(A, W, out)
     lib, dm = _sel(mode)
-    a = L.GemmArgs(M, N, K, dm, A.data_ptr(), A.stride(0), W.data_ptr(), W.stride(0), out.data_ptr(), out.stride(0),
-                   1 if out.dtype == torch.float32 else 0, _p(bias), _p(row_scale), _p(resid),
-                   resid.stride(0) if resid is not None else 0, act, _p(aux), aux.stride(0) if aux is not None else 0, int(tile), _p(bias2), _p(row_scale2))
+    a = _gemm_args(dm, A, W, out, bias, row_scale, resid, act, aux, tile, bias2, row_scale2)
     L.check(lib.tcow_gemm_nt(_stream(), ctypes.byref(a)), 'tcow_gemm_nt', lib)
     return out
 
 
+SKINNY_SPLITS = (1, 2, 3, 4, 6, 8)
+
+
+def skinny_plan(M, N, K):
+    """THE routing rule of the skinny-M NT GEMM (host arithmetic only): 0 = use tcow_gemm_nt, else the split S >= 1 of tcow_gemm_nt_skinny.
+    Routed: K % 64 == 0 and fewer than 256 tiles of 128 x 128 -- where the 128 tile runs less than one round of the 256 CUs.  S is the smallest of
+    SKINNY_SPLITS that starts at least 192 workgroups of 64 x 64 (three quarters of the CUs) while every slice keeps at least twelve 64-wide
+    k-slices; if none does, the largest allowed.  Measured (profiles/gemm_skinny.json): the 64 tile itself is the gain; the
+    second launch of a split costs about 4 us, more than a chain of fewer than twelve k-slices takes, so K = 768 never splits and K = 3072 splits
+    only while its tiles leave most of the chip idle (M = 301: S = 4)."""
+    M, N, K = int(M), int(N), int(K)
+    if M < 1 or N < 1 or K < 64 or K % 64 or -(-M // 128) * -(-N // 128) >= 256:
+        return 0
+    tiles, nk = -(-M // 64) * -(-N // 64), K // 64
+    allowed = [s for s in SKINNY_SPLITS if s == 1 or s <= nk // 12]
+    for s in allowed:
+        if tiles * s >= 192:
+            return s
+    return allowed[-1]
+
+
+def gemm_nt_skinny(mode, A, W, out, bias=None, row_scale=None, resid=None, act=ACT_NONE, aux=None, bias2=None, row_scale2=None, split=1):
+    """gemm_nt on 64 x 64 tiles with a deterministic split over K (tcow_gemm_nt_skinny; the 16-bit modes only).  split > 1 takes its [split, M, N]
+    f32 slabs from workspace(tag='nt_skinny')."""
+    _need_cuda(A, W, out)
+    if not is16(mode):
+        raise L.TcowError('gemm_nt_skinny: the 16-bit modes only (fp32 and bf16x3 products go through gemm_nt)')
+    lib, dm = _sel(mode)
+    split = int(split)
+    a = _gemm_args(dm, A, W, out, bias, row_scale, resid, act, aux, 0, bias2, row_scale2)
+    nbytes = lib.tcow_gemm_nt_skinny_workspace_bytes(a.M, a.N, split)
+    ws = workspace(nbytes, A.device, 'nt_skinny') if nbytes > 0 else None
+    L.check(lib.tcow_gemm_nt_skinny(_stream(), ctypes.byref(a), split, _p(ws), ws.numel() if ws is not None else 0), 'tcow_gemm_nt_skinny', lib)
+    return out
+
+
 _ws_cache = {}
+_ws_pinned = threading.local()
+
+
+class pinned_workspace:
+    """with pinned_workspace(tag, buf): workspace(..., tag) of this thread returns `buf` whatever the current stream is (and raises if it is too
+    small).  A stream-graph capture runs on a side stream; pinning hands it the scratch that the eager step before it sized, so nothing is
+    allocated inside the capture and the graph's owner knows the tensor the graph points into."""
+
+    def __init__(self, tag, buf):
+        self.tag, self.buf = tag, buf
+
+    def __enter__(self):
+        d = _ws_pinned.__dict__.setdefault('tags', {})
+        self.prev = d.get(self.tag)
+        d[self.tag] = self.buf
+        return self.buf
+
+    def __exit__(self, *exc):
+        d = _ws_pinned.tags
+        if self.prev is None:
+            del d[self.tag]
+        else:
+            d[self.tag] = self.prev
+        return False
 
 
 def workspace(nbytes, device, tag='default'):
@@ -79,6 +147,11 @@ def workspace(nbytes, device, tag='default'):
     it for this stream until the work queued on it has drained."""
     # (_stream(): the current stream of the current device -- the same call the launch that follows makes; the thread id: two host threads that share
     # a stream -- torch.nn.DataParallel replicas placed on one device -- interleave their launches, and some scratch lives across two launches)
+    pinned = getattr(_ws_pinned, 'tags', None)
+    if pinned and tag in pinned:
+        if pinned[tag].numel() < nbytes:
+            raise L.TcowError(f'workspace({tag!r}): the pinned buffer holds {pinned[tag].numel()} bytes, {nbytes} are needed')
+        return pinned[tag]
     key = (str(device), _stream(), tag, threading.get_ident())
     buf = _ws_cache.get(key)
     if buf is None or buf.numel() < nbytes:

@@ -242,17 +242,19 @@ class QueryMaskTracker(nn.Module):
         T = self.num_total_frames if T is None else T
         return dict(B=B, T=T, Hp=Hp, Wp=Wp, N=N, S=N + 1, D=self.embed_dim, heads=self.num_heads, P=P, M=B * T * (N + 1))
 
-    def stream(self, batch_size=1, queries_per_clip=1, graph=False):
+    def stream(self, batch_size=1, queries_per_clip=1, graph=False, skinny_gemm=None):
         """Streaming inference (causal_attention 1 or 2, eval, CUDA): a SeekerStream of at most num_total_frames frames for `batch_size` clips with
-        `queries_per_clip` query masks each; stream.step(rgb, query_mask) takes the next frames and returns their outputs (tcow_amd/stream.py)."""
+        `queries_per_clip` query masks each; stream.step(rgb, query_mask) takes the next frames and returns their outputs (tcow_amd/stream.py).
+        skinny_gemm: the steps' 16-bit GEMMs of a few hundred rows run on 64 x 64 tiles with a split over K (ops.skinny_plan); None = the
+        measured default, stream.SKINNY_GEMM_DEFAULT."""
         from .stream import SeekerStream
-        return SeekerStream(self, batch_size, queries_per_clip, graph)
+        return SeekerStream(self, batch_size, queries_per_clip, graph, skinny_gemm)
 
-    def stream_pool(self, capacity):
+    def stream_pool(self, capacity, skinny_gemm=None):
         """Streaming inference for up to `capacity` live sessions that started at different moments: a SeekerStreamPool whose step(ids, rgb,
         query_mask) advances any subset of the open sessions, each at its own frame, in one Seeker step (tcow_amd/stream.py)."""
         from .stream import SeekerStreamPool
-        return SeekerStreamPool(self, capacity)
+        return SeekerStreamPool(self, capacity, skinny_gemm)
 
     def param_list(self):
         """Fixed order of the parameters the autograd.Function sees.  Cached: walking ~250 module attributes costs 0.4 ms per call.  .to() /
@@ -326,10 +328,10 @@ class Seeker(nn.Module):
     def forward(self, *args):
         return self.seeker(*args)
 
-    def stream(self, batch_size=1, queries_per_clip=1, graph=False):
+    def stream(self, batch_size=1, queries_per_clip=1, graph=False, skinny_gemm=None):
         """See QueryMaskTracker.stream."""
-        return self.seeker.stream(batch_size, queries_per_clip, graph)
+        return self.seeker.stream(batch_size, queries_per_clip, graph, skinny_gemm)
 
-    def stream_pool(self, capacity):
+    def stream_pool(self, capacity, skinny_gemm=None):
         """See QueryMaskTracker.stream_pool."""
-        return self.seeker.stream_pool(capacity)
+        return self.seeker.stream_pool(capacity, skinny_gemm)

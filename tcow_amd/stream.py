@@ -13,7 +13,8 @@ clips x queries (the query mask changes every token's K / V), a pool rows = capa
 that is 332 MB per row in the 16-bit modes; at configs[3] (T = 60, 480x640) 2.65 GB; f32 twice that.
 
 What belongs to one step is a _Step, and it is all run_forward sees (its `stream` argument): pos, time_rows [B*T, D] (one row of the time table
-per (row, frame) of the step), attn_temporal(i, ...) and cls_row(i, ...) for block i.  There are three forms, each a _Step subclass that holds
+per (row, frame) of the step), attn_temporal(i, ...) and cls_row(i, ...) for block i, and skinny: whether the step's 16-bit GEMMs take the
+skinny-M entry point where ops.skinny_plan routes them (the skinny_gemm keyword of net.stream / net.stream_pool).  There are three forms, each a _Step subclass that holds
 its device tables and calls its own pair of ops entry points; step(), pool.step() and pool.step_ragged() each build the tables and construct
 their form, and nothing else asks which form a step has:
 
@@ -31,19 +32,26 @@ their inputs into the graph's static buffers, write t0 and the time rows (the st
 length, and one t0 scalar: the graph points into both) and replay.  No step synchronises the host except the one capture per chunk length.  A
 graph keeps the module's operand copies it was captured with alive; when the module replaces them (.cuda() / .to() on the same device,
 set_precision() with the same precision, a train-mode forward) the graphs are dropped and captured again.  Pool steps run eagerly and build a
-fresh step object per call.
+fresh step object per call.  With skinny_gemm the captured launches also point into the split-K workspace of ops.gemm_nt_skinny: the capture
+runs on the workspace that the eager step before it sized, and the graph's entry keeps that tensor (ops.workspace replaces, never resizes).
 """
 import torch
 
 from . import engine, ops
 from ._lib import TcowError
 
+# Default of the skinny_gemm keyword.  True: measured (DESIGN.md section 9, profiles/stream_skinny_latency.json) -- a one-frame bf16 step takes
+# 1.42 ms instead of 2.41 at configs[1] B = 1, 2.41 instead of 3.35 at configs[3] B = 1 and 2.60 instead of 3.24 at configs[1] B = 8, on / off
+# alternating in one run, each difference several times the off leg's own max - min.  False runs the steps on tcow_gemm_nt alone.
+SKINNY_GEMM_DEFAULT = True
+
 
 class _State:
     """What lives as long as a stream or a pool of `rows` query rows: per block the K / V caches [rows, S-1, heads, T, 64] in the mode's storage
     type and one f32 cls row per query row, and the effective pos table and time table [T, D]."""
 
-    def __init__(self, module, rows):
+    def __init__(self, module, rows, skinny=False):
+        self.skinny = bool(skinny)                              # every step built on this state carries it (_Step.skinny)
         g = module.geometry(rows)
         dev = module.vit.pos_embed.device
         cdt = ops.tdtype(module.mode)                           # (bf16x3 stores f32, like fp32)
@@ -67,6 +75,7 @@ class _Step:
 
     def __init__(self, state, time_rows, *tables):
         self.state, self.pos, self.time_rows, self.tables = state, state.pos, time_rows, tables
+        self.skinny = state.skinny
 
 
 class _StreamStep(_Step):
@@ -202,9 +211,9 @@ def _zero_mask(rows, rgb):
 
 
 class SeekerStream:
-    """net.stream(batch_size, queries_per_clip, graph) of Seeker / QueryMaskTracker; see the module docstring."""
+    """net.stream(batch_size, queries_per_clip, graph, skinny_gemm) of Seeker / QueryMaskTracker; see the module docstring."""
 
-    def __init__(self, module, batch_size=1, queries_per_clip=1, graph=False):
+    def __init__(self, module, batch_size=1, queries_per_clip=1, graph=False, skinny_gemm=None):
         module = getattr(module, 'seeker', module)
         check_streamable(module)
         Bc, Qs = int(batch_size), int(queries_per_clip)
@@ -214,7 +223,8 @@ class SeekerStream:
         self.Bc, self.Qs, self.B = Bc, Qs, Bc * Qs
         self.T = module.num_total_frames
         self.graph = bool(graph)
-        self._st = _State(module, self.B)
+        self.skinny_gemm = SKINNY_GEMM_DEFAULT if skinny_gemm is None else bool(skinny_gemm)
+        self._st = _State(module, self.B, self.skinny_gemm)
         self.device = self._st.pos.device
         self._t0_dev = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._steps = {}                # c -> the step of chunk length c; its time_rows [B*c, D] f32 are static: a captured graph points into both
@@ -274,12 +284,19 @@ class SeekerStream:
             s_rgb = rgb.clone()
             s_qm = qm.clone() if qm is not None else _zero_mask(self.B, rgb)
             graph = torch.cuda.CUDAGraph()
+            # the split-K workspace as the eager step above left it (current stream; the capture runs on a side stream): large enough for this
+            # chunk length, so the capture allocates none, and this entry owns the tensor its launches point into
+            ws = ops.workspace(0, self.device, 'nt_skinny') if step.skinny else None
             with torch.cuda.graph(graph):
-                g_mask, g_flags = self._run(step, s_rgb, s_qm)
+                if ws is None:
+                    g_mask, g_flags = self._run(step, s_rgb, s_qm)
+                else:
+                    with ops.pinned_workspace('nt_skinny', ws):
+                        g_mask, g_flags = self._run(step, s_rgb, s_qm)
             # The graph holds raw pointers into tensors that only module._operands owns (operand copies, folded W' / b', mask0): a shallow copy
             # of the dictionary keeps them alive as long as the graph, whatever later replaces the dictionary or its entries.
             keep = self.module._operands.keep_alive()
-            self._graphs[c] = dict(graph=graph, rgb=s_rgb, qm=s_qm, mask=g_mask, flags=g_flags, gen=self._operand_generation(), keep=keep)
+            self._graphs[c] = dict(graph=graph, rgb=s_rgb, qm=s_qm, mask=g_mask, flags=g_flags, gen=self._operand_generation(), keep=keep, ws=ws)
             return out
         graph, s_rgb, s_qm, g_mask, g_flags = ent['graph'], ent['rgb'], ent['qm'], ent['mask'], ent['flags']
         s_rgb.copy_(rgb)
@@ -292,11 +309,11 @@ class SeekerStream:
 
 
 class SeekerStreamPool:
-    """net.stream_pool(capacity) of Seeker / QueryMaskTracker: up to `capacity` live sessions (one clip and one query mask each) that stand at
+    """net.stream_pool(capacity, skinny_gemm) of Seeker / QueryMaskTracker: up to `capacity` live sessions (one clip and one query mask each) that stand at
     different frames, stepped together; see the module docstring.  open() -> id, step(ids, rgb, query_mask) (one chunk length for all) or
     step_ragged(ids, rgbs, query_masks) (a chunk length per session), close(id)."""
 
-    def __init__(self, module, capacity):
+    def __init__(self, module, capacity, skinny_gemm=None):
         module = getattr(module, 'seeker', module)
         capacity = int(capacity)
         if capacity < 1:
@@ -305,7 +322,8 @@ class SeekerStreamPool:
         self.module = module
         self.capacity = capacity
         self.T = module.num_total_frames
-        self._st = _State(module, capacity)
+        self.skinny_gemm = SKINNY_GEMM_DEFAULT if skinny_gemm is None else bool(skinny_gemm)
+        self._st = _State(module, capacity, self.skinny_gemm)
         self.device = self._st.pos.device
         self._sig = _signature(module)
         self._slot = {}                 # open session id -> cache slot

@@ -1,0 +1,100 @@
+"""CPU: the routing rule of the skinny-M NT GEMM (ops.skinny_plan, host arithmetic only) and its two entry points in the C ABI."""
+import ctypes
+import json
+import os
+import re
+
+from conftest import ROOT
+
+WEIGHTS = [(768, 768), (2304, 768), (3072, 768), (768, 3072)]          # (N, K) of a ViT-B block: qkv, proj / temporal fc, fc1, fc2
+STREAM_M = [301, 1201, 2408]                                           # one-frame steps: configs[1] B = 1, configs[3] B = 1, configs[1] B = 8
+
+
+def _plan():
+    from tcow_amd import ops
+    return ops.skinny_plan
+
+
+def test_plan_leaves_the_clip_and_training_shapes_alone():
+    plan = _plan()
+    for N, K in WEIGHTS:
+        assert plan(27090, N, K) == 0
+    for K in (96, 100, 767, 32, 1):
+        assert plan(301, 768, K) == 0
+    for M, N in [(2048, 2048), (128 * 256, 128), (128, 128 * 256), (4000, 1024), (2408, 2304), (2408, 3072)]:
+        assert -(-M // 128) * -(-N // 128) >= 256 and plan(M, N, 768) == 0
+
+
+def test_plan_routes_the_stream_shapes_within_the_kernels_limits():
+    plan = _plan()
+    routed = 0
+    for M in STREAM_M:
+        for N, K in WEIGHTS:
+            S = plan(M, N, K)
+            if -(-M // 128) * -(-N // 128) >= 256:
+                assert S == 0
+                continue
+            if S:
+                routed += 1
+                assert 1 <= S <= min(K // 64, 16), (M, N, K, S)
+    assert routed >= 1
+    assert plan(1, 4, 64) in (0, 1)                                                       # one k-slice cannot be split
+
+
+def test_plan_is_monotone():
+    """More rows (more tiles) never raise the split; a longer K never lowers it."""
+    plan = _plan()
+    for N, K in WEIGHTS:
+        prev = None
+        for M in range(1, 4200, 37):
+            S = plan(M, N, K)
+            if S == 0:
+                continue
+            assert prev is None or S <= prev, (M, N, K, S, prev)
+            prev = S
+    for M in STREAM_M:
+        for N in (768, 2304, 3072):
+            seq = [plan(M, N, K) for K in range(64, 4097, 64)]
+            routed = [s for s in seq if s]
+            assert routed == sorted(routed), (M, N, seq)
+
+
+def test_plan_reproduces_the_measured_table():
+    """profiles/gemm_skinny.json (tools/dev_gemm_skinny.py) states per shape what the measurement asks of the rule: 'route' false = today's kernel
+    holds the shape; true = the skinny entry point with one of 'accept', the splits within the best one's spread."""
+    path = os.path.join(ROOT, 'profiles', 'gemm_skinny.json')
+    rows = json.load(open(path))['shapes']
+    assert len(rows) == 12
+    plan = _plan()
+    for r in rows:
+        S = plan(r['M'], r['N'], r['K'])
+        if r['route']:
+            assert S in r['accept'], (r['M'], r['N'], r['K'], S, r['accept'])
+        else:
+            assert S == 0, (r['M'], r['N'], r['K'], S)
+
+
+def test_abi_14_declares_the_two_entry_points():
+    from tcow_amd import _lib
+    hdr = open(os.path.join(ROOT, 'include', 'tcow_hip.h')).read()
+    assert int(re.search(r'#define\s+TCOW_ABI_VERSION\s+(\d+)', hdr).group(1)) == 14 and _lib.ABI_VERSION == 14
+    assert re.search(r'long\s+tcow_gemm_nt_skinny_workspace_bytes\(int M, int N, int split\);', hdr)
+    assert re.search(r'int\s+tcow_gemm_nt_skinny\(void\* stream, const tcow_gemm_args\* args, int split, void\* workspace, long workspace_bytes\);', hdr)
+    i, l, vp = ctypes.c_int, ctypes.c_long, ctypes.c_void_p
+    assert _lib.SIGNATURES['tcow_gemm_nt_skinny_workspace_bytes'] == (l, [i, i, i])
+    assert _lib.SIGNATURES['tcow_gemm_nt_skinny'] == (i, [vp, ctypes.POINTER(_lib.GemmArgs), i, vp, l])
+    for fmt in ('bf16', 'fp16'):
+        lib = _lib.lib(fmt)
+        assert lib.tcow_version() == 14
+        assert lib.tcow_gemm_nt_skinny_workspace_bytes(301, 768, 1) == 0 and lib.tcow_gemm_nt_skinny_workspace_bytes(301, 768, 4) == 4 * 301 * 768 * 4
+
+
+def test_public_keyword_and_default():
+    """net.stream / net.stream_pool take skinny_gemm; its default is the measured constant of tcow_amd/stream.py."""
+    import inspect
+    from tcow_amd import ops, seeker, stream
+    for cls in (seeker.QueryMaskTracker, seeker.Seeker):
+        for name in ('stream', 'stream_pool'):
+            assert inspect.signature(getattr(cls, name)).parameters['skinny_gemm'].default is None
+    assert isinstance(stream.SKINNY_GEMM_DEFAULT, bool)
+    assert inspect.signature(ops.gemm_nt).parameters['skinny'].default is False

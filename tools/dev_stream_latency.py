@@ -11,6 +11,9 @@
     python tools/dev_stream_latency.py --ragged --out profiles/stream_ragged_latency.json
                                         # the same eight sessions with chunk lengths 1, 1, 1, 1, 2, 2, 4, 8 in one tick: one step_ragged against one
                                         # pool.step per distinct length, and step_ragged with every length 1 against pool.step
+    python tools/dev_stream_latency.py --skinny --out profiles/stream_skinny_latency.json
+                                        # one-frame steps at t0 = T - 1 with skinny_gemm=True against skinny_gemm=False (the code as it was before the
+                                        # keyword existed), alternating in one run: configs[1] B = 1 and B = 8, configs[3] B = 1, eager and graph
 
 Times are device events around each call after warm-up, profiler off.  A step at a given t0 is timed by setting the stream's host frame counter
 (the kernels then read t0 from the device scalar the step writes): the work of a step depends on t0, not on what the cache holds.  Synthetic
@@ -221,6 +224,52 @@ def ragged_leg(reps):
     return res
 
 
+def skinny_leg(reps):
+    """One-frame bf16 steps at t0 = T - 1, skinny_gemm on / off, eager and graph: the four streams of a config are stepped in turn `reps` times, one
+    sample (one step between a pair of events) each per round.  The verdict of DESIGN.md section 9: the eager medians at configs[1] B = 1 and
+    configs[3] B = 1 are lower with the flag by more than the off-leg's own max - min, and the B = 8 leg is not slower by more than that spread."""
+    runs = []
+    for name, B in (('configs1', 1), ('configs1', 8), ('configs3', 1)):
+        T, H, W = CONFIGS[name]
+        net = build(T, H, W, 'bf16')
+        rgb, qm = inputs(B, T, H, W)
+        f = lambda x, t: x[:, :, t:t + 1]
+        with torch.no_grad():
+            legs = {}
+            for graph in (False, True):
+                for flag in (False, True):
+                    st = net.stream(batch_size=B, graph=graph, skinny_gemm=flag)
+                    for t in (0, T - 1, T - 1, T - 1):          # warm-up: operand copies, the c = 1 graph, the workspace
+                        st.frames_done = t
+                        st.step(f(rgb, t), f(qm, t))
+
+                    def one(st=st):
+                        st.frames_done = T - 1
+                        st.step(f(rgb, T - 1), f(qm, T - 1))
+                    legs[f"{'graph' if graph else 'eager'}_{'on' if flag else 'off'}"] = one
+            samples = {k: [] for k in legs}
+            for _ in range(reps):
+                for k, fn in legs.items():
+                    samples[k].append(ev_time(fn, 1))
+        r = {'config': name, 'T': T, 'H': H, 'W': W, 'B': B, 'precision': 'bf16', 't0': T - 1, 'reps': reps}
+        for k, v in samples.items():
+            v = sorted(v)
+            r[k + '_step_ms'] = {'median': v[len(v) // 2], 'min': v[0], 'max': v[-1]}
+        for mode in ('eager', 'graph'):
+            off, on = r[mode + '_off_step_ms'], r[mode + '_on_step_ms']
+            r[mode + '_off_spread_ms'] = off['max'] - off['min']
+            r[mode + '_off_minus_on_ms'] = off['median'] - on['median']
+            r[mode + '_on_lower_by_more_than_off_spread'] = bool(off['median'] - on['median'] > off['max'] - off['min'])
+            r[mode + '_on_not_slower_by_more_than_off_spread'] = bool(on['median'] - off['median'] <= off['max'] - off['min'])
+        runs.append(r)
+        del legs, net
+        torch.cuda.empty_cache()
+    by = {(r['config'], r['B']): r for r in runs}
+    verdict = bool(by[('configs1', 1)]['eager_on_lower_by_more_than_off_spread'] and by[('configs3', 1)]['eager_on_lower_by_more_than_off_spread']
+                   and by[('configs1', 8)]['eager_on_not_slower_by_more_than_off_spread'])
+    return {'runs': runs, 'verdict_default_true': verdict}
+
+
 KPROF_WARMUP, KPROF_STEPS = 3, 20
 STEP_LAST_KERNEL = 'flags_fwd_kernel'      # the last launch of every step (the flags head, engine.run_forward)
 
@@ -291,6 +340,7 @@ def main():
     ap.add_argument('--kprof', action='store_true')
     ap.add_argument('--pool', action='store_true', help='the stream-pool leg (eight sessions at configs1)')
     ap.add_argument('--ragged', action='store_true', help='the ragged-step leg (eight sessions at configs1, chunk lengths 1, 1, 1, 1, 2, 2, 4, 8)')
+    ap.add_argument('--skinny', action='store_true', help='skinny_gemm=True against False, one-frame steps at configs1 B = 1 / 8 and configs3 B = 1')
     ap.add_argument('--kstats', default=None, metavar='KERNEL_TRACE_CSV')
     ap.add_argument('--only', default=None, help='comma list of configs1_b1, configs1_b8, configs3_b1')
     a = ap.parse_args()
@@ -313,6 +363,14 @@ def main():
     if a.ragged:
         out = {'device': torch.cuda.get_device_name(0), 'ragged': ragged_leg(a.reps)}
         print(json.dumps(out['ragged']), flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, 'w') as f:
+                json.dump(out, f, indent=1)
+        return
+    if a.skinny:
+        out = {'device': torch.cuda.get_device_name(0), 'skinny': skinny_leg(a.reps)}
+        print(json.dumps(out['skinny']), flush=True)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, 'w') as f:

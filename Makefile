@@ -19,11 +19,11 @@ all: $(LIB) $(LIB16)
 ATTN_INC := $(wildcard $(CSRC)/attention_bf16_*.inc)
 $(OBJ)/attention_bf16.hip.o $(OBJ16)/attention_bf16.hip.o: $(ATTN_INC)
 $(OBJ)/attention_bf16.hip.o: EXTRA := -fno-honor-nans -fno-slp-vectorize
-$(OBJ)/%.hip.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/gemm_f32.h $(CSRC)/gemm_glds.h $(CSRC)/gemm_nt_common.h $(CSRC)/attention_tiles.h $(CSRC)/attention_common.h include/tcow_hip.h
+$(OBJ)/%.hip.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/tcow_hip.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA) -x hip -c $< -o $@
 
-$(OBJ)/%.cpp.o: $(CSRC)/%.cpp $(CSRC)/common.h include/tcow_hip.h
+$(OBJ)/%.cpp.o: $(CSRC)/%.cpp $(wildcard $(CSRC)/*.h) include/tcow_hip.h
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
@@ -31,11 +31,11 @@ $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS)
 
 $(OBJ16)/attention_bf16.hip.o: EXTRA := -fno-honor-nans -fno-slp-vectorize
-$(OBJ16)/%.hip.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/gemm_f32.h $(CSRC)/gemm_glds.h $(CSRC)/gemm_nt_common.h $(CSRC)/attention_tiles.h $(CSRC)/attention_common.h include/tcow_hip.h
+$(OBJ16)/%.hip.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/tcow_hip.h
 	@mkdir -p $(OBJ16)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA) -DTCOW_FP16 -x hip -c $< -o $@
 
-$(OBJ16)/%.cpp.o: $(CSRC)/%.cpp $(CSRC)/common.h include/tcow_hip.h
+$(OBJ16)/%.cpp.o: $(CSRC)/%.cpp $(wildcard $(CSRC)/*.h) include/tcow_hip.h
 	@mkdir -p $(OBJ16)
 	$(HIPCC) $(HIPFLAGS) -DTCOW_FP16 -x hip -c $< -o $@
 

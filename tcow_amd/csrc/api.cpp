@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "common.h"
+#include "internal.h"
 
 static thread_local char g_err[512] = "";
 
@@ -29,34 +30,6 @@ void tcow_ensure_lds(const void* kernel, int bytes) {
     if (done.insert(std::make_pair(dev, kernel)).second)
         (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
-
-int tcow_gemm_nt_bf16(hipStream_t stream, const tcow_gemm_args* a);
-int tcow_gemm_nt_f32(hipStream_t stream, const tcow_gemm_args* a);
-int tcow_gemm_nt_skinny_bf16(hipStream_t stream, const tcow_gemm_args* a, int split, float* slab);
-int tcow_gemm_tn_bf16(hipStream_t stream, int M, int N, int K, const bf16_t* dY, long ldy, const bf16_t* X, long ldx, float* slab, int splits, int* nz_out,
-                      float* bias_part, int* bias_parts_out);
-int tcow_gemm_tn_f32(hipStream_t stream, int M, int N, int K, const float* dY, long ldy, const float* X, long ldx, float* dW, long lddw, int accumulate,
-                     float* slab, int splits, const float* bias_part, int bias_nparts, float* bias_out);
-int tcow_gemm_nt_x3(hipStream_t stream, const tcow_gemm_args* a);
-int tcow_gemm_tn_x3(hipStream_t stream, int M, int N, int K, const float* dY, long ldy, const float* X, long ldx, float* dW, long lddw, int accumulate,
-                    float* slab, int splits, const float* bias_part, int bias_nparts, float* bias_out);
-int tcow_tn_group_max(void);
-bool tcow_tn_group_ok(int n, const tcow_tn_problem* pr);
-int tcow_tn_group_slices(int n, const tcow_tn_problem* pr);
-int tcow_gemm_tn_bf16_group(hipStream_t stream, int n, const tcow_tn_problem* pr, int nz_req, float* const* slabs, float* const* bias_parts, int* nz_out,
-                            int* bias_nparts);
-int tcow_tn_splits(int M, int N, int K, int tile_outputs);
-int tcow_tn_splits_x3(int M, int N, int K);
-int tcow_tn_splits_256(int M, int N, int K);
-bool tcow_tn_use_256(int M, int N, int K);
-int tcow_launch_slab_reduce(hipStream_t stream, const float* slab, int nz, long slab_stride, long rows, long cols, float* out, long ldo, int accumulate,
-                            const float* bias_part, int bias_nparts, int bias_n, float* bias_out);
-int tcow_launch_row_reduce(hipStream_t stream, const float* part, int nrows, long ld, int N, float* out, int accumulate);
-bool tcow_fold_vec_ok(const float* slab, long slab_stride, long cols, float* out, long ldo);
-int tcow_launch_slab_reduce_group(hipStream_t stream, int n, const float* const* slab, int nz, const long* rows, const long* cols, float* const* out, const long* ldo,
-                                  const int* accumulate, const float* const* bias_part, const int* bias_nparts, float* const* bias_out);
-int tcow_launch_colsum(hipStream_t stream, int dtype, const void* Y, long ldy, int M, int N, float* out, int accumulate, float* part, int max_parts);
-int tcow_launch_colsum_partials(hipStream_t stream, int dtype, const void* Y, long ldy, int M, int N, float* part, int max_parts, int* nparts);
 
 extern "C" {
 
@@ -159,6 +132,18 @@ int tcow_gemm_nt_skinny(void* stream, const tcow_gemm_args* a, int split, void* 
 
 static const int kColsumParts = 64 * 24 * 2;   // >= nz * tiles_k * 2 partial rows of the fused bias gradient (nz <= 64, K <= 3072)
 
+// number of token-dimension slices used by the weight-gradient GEMMs (both dtypes): ~2 workgroups per CU, a multiple of
+// 8 so that every XCD owns the same number of slices (gemm_tn_bf16_kernel pins slice z to XCD z % 8), >= 256 tokens each.
+static int tcow_tn_splits(int M, int N, int K, int tile_outputs) {
+    const int tiles = cdiv(N, tile_outputs) * cdiv(K, tile_outputs);
+    int s = ((cdiv(512, tiles) + 7) / 8) * 8;
+    const int max_s = M / 256;
+    if (s > max_s) s = max_s >= 8 ? (max_s / 8) * 8 : max_s;
+    if (s < 1) s = 1;
+    if (s > 64) s = 64;
+    return s;
+}
+
 long tcow_gemm_tn_workspace_bytes(int M, int N, int K) {
     const int s_bf = tcow_tn_splits(M, N, K, 128), s_f = tcow_tn_splits(M, N, K, 64), s_big = tcow_tn_splits_256(M, N, K);
     int s = s_bf > s_f ? s_bf : s_f;
@@ -214,7 +199,7 @@ static long tn_group_bytes(int n, const tcow_tn_problem* pr, int nz) {
     return b;
 }
 
-int tcow_gemm_tn_group_max(void) { return tcow_tn_group_max(); }
+int tcow_gemm_tn_group_max(void) { return TCOW_TN_GROUP_MAX; }
 
 long tcow_gemm_tn_grouped_workspace_bytes(int dtype, int n, const tcow_tn_problem* pr) {
     if (n <= 0 || pr == nullptr) return 0;
@@ -239,7 +224,7 @@ int tcow_gemm_tn_grouped(void* stream, int dtype, int n, const tcow_tn_problem* 
         return TCOW_OK;
     }
     const int nz_req = tcow_tn_group_slices(n, pr);
-    float* slabs[40]; float* parts[40]; int nparts[40];          // (tcow_tn_group_ok: n <= tcow_tn_group_max() = 40)
+    float* slabs[TCOW_TN_GROUP_MAX]; float* parts[TCOW_TN_GROUP_MAX]; int nparts[TCOW_TN_GROUP_MAX];          // (tcow_tn_group_ok: n <= TCOW_TN_GROUP_MAX)
     char* w = (char*)workspace;
     for (int i = 0; i < n; ++i) {
         slabs[i] = (float*)w; w += (long)(nz_req + 1) * pr[i].N * pr[i].K * 4;
@@ -256,7 +241,8 @@ int tcow_gemm_tn_grouped(void* stream, int dtype, int n, const tcow_tn_problem* 
     bool vec = true;
     for (int i = 0; i < n; ++i) vec = vec && tcow_fold_vec_ok(slabs[i], (long)pr[i].N * pr[i].K, pr[i].K, pr[i].dW, pr[i].lddw);
     if (vec) {       // one fold launch for the whole group
-        long rows[40], cols[40], ldo[40]; int acc[40]; float* outs[40]; float* bouts[40]; const float* cparts[40]; const float* cslabs[40];
+        constexpr int G = TCOW_TN_GROUP_MAX;
+        long rows[G], cols[G], ldo[G]; int acc[G]; float* outs[G]; float* bouts[G]; const float* cparts[G]; const float* cslabs[G];
         for (int i = 0; i < n; ++i) {
             rows[i] = pr[i].N; cols[i] = pr[i].K; ldo[i] = pr[i].lddw; acc[i] = pr[i].accumulate; outs[i] = pr[i].dW; bouts[i] = pr[i].bias_grad;
             cparts[i] = parts[i]; cslabs[i] = slabs[i]; if (!parts[i]) nparts[i] = 0;

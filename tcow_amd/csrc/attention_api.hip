@@ -42,20 +42,6 @@ static int check_shape(const tcow_attn_shape* s, const char* who) {
     return TCOW_OK;
 }
 
-bool tcow_attn_mfma_zeroes_slot0(const SeqDesc& d, bool shared, bool backward);
-int tcow_attn_mfma_fwd(hipStream_t st, const SeqDesc& d, bool shared, const void* qkv, void* out, float* lse);
-long tcow_attn_mfma_bwd_workspace_bytes(const SeqDesc& d);
-int tcow_attn_mfma_bwd(hipStream_t st, const SeqDesc& d, bool shared, const void* qkv, const void* out, const void* dout, const float* lse, void* ws,
-                       void* dqkv);
-
-int tcow_attn_f32_fwd(hipStream_t st, const SeqDesc& d, const void* qkv, void* out, float* lse);
-int tcow_attn_f32_bwd(hipStream_t st, const SeqDesc& d, const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv);
-
-// f32 storage, split-bf16 MFMA arithmetic (attention_x3.hip; dtype TCOW_F32X3): sequences of two or more tiles
-bool tcow_attn_x3_supported(const SeqDesc& d);
-int tcow_attn_x3_fwd(hipStream_t st, const SeqDesc& d, const void* qkv, void* out, float* lse);
-int tcow_attn_x3_bwd(hipStream_t st, const SeqDesc& d, const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv);
-
 int tcow_attn_fwd_dispatch(hipStream_t st, const tcow_attn_shape* s, int spatial, const void* qkv, void* out, float* lse) {
     const SeqDesc d = spatial ? spatial_desc(s) : temporal_desc(s);
     int rc;
@@ -64,7 +50,7 @@ int tcow_attn_fwd_dispatch(hipStream_t st, const tcow_attn_shape* s, int spatial
         if (rc) return rc;
     }
     if (s->dtype == TCOW_BF16) return tcow_attn_mfma_fwd(st, d, spatial != 0, qkv, out, lse);      // 16-bit storage: attention_bf16.hip
-    if (s->dtype == TCOW_F32X3 && tcow_attn_x3_supported(d)) return tcow_attn_x3_fwd(st, d, qkv, out, lse);   // f32 storage, bf16 x 3 split products (attention_x3.hip)
+    if (s->dtype == TCOW_F32X3) return tcow_attn_x3_fwd(st, d, qkv, out, lse);   // f32 storage, bf16 x 3 split products (attention_x3.hip)
     return tcow_attn_f32_fwd(st, d, qkv, out, lse);                                                   // f32 storage: exact-f32 MFMA kernels (attention_f32.hip)
 }
 
@@ -89,7 +75,7 @@ int tcow_attn_bwd_dispatch(hipStream_t st, const tcow_attn_shape* s, int spatial
         if (rc) return rc;
     }
     if (s->dtype == TCOW_BF16) return tcow_attn_mfma_bwd(st, d, spatial != 0, qkv, out, dout, lse, ws, dqkv);
-    if (s->dtype == TCOW_F32X3 && tcow_attn_x3_supported(d)) return tcow_attn_x3_bwd(st, d, qkv, out, dout, lse, (float*)ws, dqkv);
+    if (s->dtype == TCOW_F32X3) return tcow_attn_x3_bwd(st, d, qkv, out, dout, lse, (float*)ws, dqkv);
     return tcow_attn_f32_bwd(st, d, qkv, out, dout, lse, (float*)ws, dqkv);
 }
 

@@ -64,3 +64,17 @@ static inline SeqDesc spatial_desc(const tcow_attn_shape* s) {
     d.pos_stride = 1; d.L = s->S - s0; d.diag = 1 << 28; d.heads = s->heads; d.D = s->D;
     return d;
 }
+
+// ---- the attention back ends behind attention_api.hip's dispatch (host)
+// 16-bit storage: MFMA flash attention (attention_bf16.hip)
+bool tcow_attn_mfma_zeroes_slot0(const SeqDesc& d, bool shared, bool backward);
+int tcow_attn_mfma_fwd(hipStream_t st, const SeqDesc& d, bool shared, const void* qkv, void* out, float* lse);
+long tcow_attn_mfma_bwd_workspace_bytes(const SeqDesc& d);
+int tcow_attn_mfma_bwd(hipStream_t st, const SeqDesc& d, bool shared, const void* qkv, const void* out, const void* dout, const float* lse, void* ws,
+                       void* dqkv);
+// f32 storage: exact-f32 MFMA (attention_f32.hip; dtype TCOW_F32)
+int tcow_attn_f32_fwd(hipStream_t st, const SeqDesc& d, const void* qkv, void* out, float* lse);
+int tcow_attn_f32_bwd(hipStream_t st, const SeqDesc& d, const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv);
+// f32 storage, split-bf16 MFMA arithmetic (attention_x3.hip; dtype TCOW_F32X3)
+int tcow_attn_x3_fwd(hipStream_t st, const SeqDesc& d, const void* qkv, void* out, float* lse);
+int tcow_attn_x3_bwd(hipStream_t st, const SeqDesc& d, const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv);

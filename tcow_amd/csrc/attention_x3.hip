@@ -468,8 +468,6 @@ int x3_bwd_launch(hipStream_t st, const SeqDesc& d, int nt, int grid, const void
 // Every length.  One-tile sequences (temporal attention, T <= 32) run the SOLO instantiations: a wave per (sequence, head) with wave-private LDS tiles, no barriers
 // (the same kernels with one tile per chunk and one active wave per workgroup measured 84 / 302 us forward / backward at configs[1], attention_f32.hip's wave-private
 // exact-f32 kernels 127 / 407 us).
-bool tcow_attn_x3_supported(const SeqDesc& d) { (void)d; return true; }
-
 int tcow_attn_x3_fwd(hipStream_t st, const SeqDesc& d, const void* qkv, void* out, float* lse) {
     const int nt = cdiv(d.L, 32), pairs = d.n_outer * d.n_inner * d.heads, grid = stream_grid(pairs, cdiv(nt, 4));
     if (nt == 1) {                       // one-tile sequences: a wave per (sequence, head), wave-private 16 KiB

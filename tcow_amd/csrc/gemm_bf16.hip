@@ -15,6 +15,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "internal.h"
 #include "gemm_nt_common.h"
 
 namespace {
@@ -401,15 +402,13 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_bf16_kernel(NtParams p) {
 
 }  // namespace
 
-bool tcow_gemm_nt_c2_ok(const tcow_gemm_args* a);
-int tcow_gemm_nt_bf16_c2(hipStream_t stream, const tcow_gemm_args* a);
 
 // Tile order of the wide-output GEMMs (fc1, fc2's input gradient: N = 3072 at K = 768).  Row-major order gives an XCD a band of row tiles with all of W:
 // 4.7 MB of W do not stay in a 4 MB L2 beside the A stream, every round of workgroups re-fetches them (FETCH_SIZE 4.4x the algorithmic bytes on the 320
 // tile, 7.2x on the 160 tile).  Column bands (nt_tile_of) halve what an XCD keeps of W: measured per launch (profiles/r06_pmc_band.txt) 205 -> 172 MB with
 // bands of 6 tiles on the 320 tile, 341 -> 227 MB with bands of 4 on the 160 tile -- and the same time within +-1 % (the refills come from the Infinity
 // Cache and the kernel is not bound by them); narrower bands make more XCDs read the same A rows and fetch MORE (band 1: 516 MB).  Kept for the traffic.
-int nt_band_for(const tcow_gemm_args* a, int tiles_n, int tile) {
+int tcow_nt_band_for(const tcow_gemm_args* a, int tiles_n, int tile) {
     if (a->N < 3072) return 0;
     const int band = tile == 320 ? 6 : 4;
     return (tiles_n % band == 0 && tiles_n > band) ? band : 0;
@@ -442,7 +441,7 @@ int tcow_gemm_nt_bf16(hipStream_t stream, const tcow_gemm_args* a) {
         }
         if (a->tile == 320 || (a->tile == 0 && fills && t320 >= 200)) {
             p.tiles_m = cdiv(a->M, C_BM); p.tiles_n = cdiv(a->N, C_BN);
-            p.band = nt_band_for(a, p.tiles_n, 320);
+            p.band = tcow_nt_band_for(a, p.tiles_n, 320);
             typedef void (*Kern)(NtParams);
             Kern k = nullptr;                    // (K % 64 == 0: checked above)
             nt_pick_epilogue(a, [&](auto e) { k = gemm_nt_bf16_320_kernel<decltype(e)>; });

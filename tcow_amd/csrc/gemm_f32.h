@@ -1,6 +1,8 @@
-// Parameter block and element epilogue shared by the two f32-storage GEMM kernels (gemm_f32.hip: exact f32 MFMA, gemm_x3.hip: bf16 x 3).
+// Parameter block, its host-side builders and the element epilogue shared by the two f32-storage GEMM kernels (gemm_f32.hip: exact f32 MFMA,
+// gemm_x3.hip: bf16 x 3).  Their split-K slabs are folded by reduce.hip.
 #pragma once
 #include "common.h"
+#include "internal.h"
 
 //   C[i,j] = sum_k A(i,k) * B(j,k),  A(i,k) = A[i*sai + k*sak],  B(j,k) = B[j*sbj + k*sbk]   (NT: sak = sbk = 1, TN: sai = sbj = 1)
 struct F32Params {
@@ -14,6 +16,26 @@ struct F32Params {
     int kps;          // contraction elements per z-slice (multiple of the kernel's k-slice)
     float* slab;      // if non-NULL: raw partial sums to slab[z][M][N], no epilogue
 };
+
+// the NT form of tcow_gemm_args with all its epilogue; one z-slice of the whole K, rounded up to the kernel's k-slice
+static inline F32Params f32_params_nt(const tcow_gemm_args* a, int kslice) {
+    F32Params p;
+    p.M = a->M; p.N = a->N; p.K = a->K;
+    p.A = (const float*)a->A; p.sai = a->lda; p.sak = 1;
+    p.B = (const float*)a->W; p.sbj = a->ldw; p.sbk = 1;
+    p.C = a->C; p.ldc = a->ldc; p.bias = a->bias; p.row_scale = a->row_scale; p.resid = a->resid; p.ldr = a->ldr;
+    p.act = a->act; p.aux = (float*)a->aux; p.ldaux = a->ldaux; p.bias2 = a->bias2; p.row_scale2 = a->row_scale2; p.kps = ((a->K + kslice - 1) / kslice) * kslice; p.slab = nullptr;
+    return p;
+}
+// a product with no epilogue (C, ldc and every epilogue field null): the TN forms write slabs, tcow_sgemm_x3_batched sets C itself
+static inline F32Params f32_params_plain(int M, int N, int K, const float* A, long sai, long sak, const float* B, long sbj, long sbk, int kps, float* slab) {
+    F32Params p = {};
+    p.M = M; p.N = N; p.K = K;
+    p.A = A; p.sai = sai; p.sak = sak;
+    p.B = B; p.sbj = sbj; p.sbk = sbk;
+    p.kps = kps; p.slab = slab;
+    return p;
+}
 
 // bias, DropPath row scale, activation (with its side input / output), residual -- the semantics of tcow_gemm_args, one element
 __device__ __forceinline__ void f32_epilogue_store(const F32Params& p, int gm, int gn, float x, float bv) {

@@ -20,6 +20,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "internal.h"
 #include "gemm_nt_common.h"
 
 namespace {
@@ -191,14 +192,13 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_bf16_c2_kernel(NtParams p) {
 
 }  // namespace
 
-int nt_band_for(const tcow_gemm_args* a, int tiles_n, int tile);
 bool tcow_gemm_nt_c2_ok(const tcow_gemm_args* a) { return a->K % 128 == 0 && (long)a->M * a->lda < (1L << 30) && (long)a->N * a->ldw < (1L << 30); }   // (32-bit byte offsets below 2^31 + the out-of-range marker)
 
 // launch the 160 x 256 kernel (the caller -- tcow_gemm_nt_bf16 -- has validated the arguments)
 int tcow_gemm_nt_bf16_c2(hipStream_t stream, const tcow_gemm_args* a) {
     NtParams p = nt_params_from_args(a);
     p.tiles_m = cdiv(a->M, D_BM); p.tiles_n = cdiv(a->N, D_BN);
-    p.band = nt_band_for(a, p.tiles_n, 160);
+    p.band = tcow_nt_band_for(a, p.tiles_n, 160);
     typedef void (*Kern)(NtParams);
     Kern k = nullptr;
     nt_pick_epilogue(a, [&](auto e) { k = gemm_nt_bf16_c2_kernel<decltype(e)>; });

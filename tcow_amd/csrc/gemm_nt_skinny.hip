@@ -11,6 +11,7 @@
 // S == 1 therefore gives the 128 tile's bits; S > 1 is a fixed function of the inputs (no atomics, no arrival order).
 // The kernel boundary makes the slabs visible: workgroups do not communicate inside a launch.
 #include "common.h"
+#include "internal.h"
 #include "gemm_nt_common.h"
 
 namespace {

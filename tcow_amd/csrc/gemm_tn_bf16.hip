@@ -10,6 +10,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "internal.h"
 #include "gemm_glds.h"
 
 namespace {
@@ -458,8 +459,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_bf16_256_kernel(TnParams p) {
 // one by one, a 768 x 768 weight has 9 tiles and needs 28 token slices to fill the chip -- 66 MB of f32 partials written and read back per
 // GEMM (11.5 GB per training step), a fold launch each, and a ramp / tail per launch.  Together the tiles fill three rounds with FIVE slices:
 // every workgroup walks 5 418 token rows, the partials shrink 5x and one launch replaces seven.
-constexpr int TN_GROUP_MAX = 40;          // (five divided space-time blocks: 35-40 problems; TnGroup = 3.7 KiB, below the 4 KiB kernel-argument limit)
-struct TnGroup { int n; int first[TN_GROUP_MAX + 1]; TnParams p[TN_GROUP_MAX]; };
+struct TnGroup { int n; int first[TCOW_TN_GROUP_MAX + 1]; TnParams p[TCOW_TN_GROUP_MAX]; };
 template <int SCHED>
 __global__ __launch_bounds__(512, 2) void gemm_tn_bf16_256_group_kernel(TnGroup g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -528,9 +528,8 @@ int tcow_gemm_tn_bf16(hipStream_t stream, int M, int N, int K, const bf16_t* dY,
 }
 
 // ---- grouped weight-gradient launch (see gemm_tn_bf16_256_group_kernel).  All problems share M and the slice count nz.
-int tcow_tn_group_max(void) { return TN_GROUP_MAX; }
 bool tcow_tn_group_ok(int n, const tcow_tn_problem* pr) {
-    if (n < 2 || n > TN_GROUP_MAX) return false;
+    if (n < 2 || n > TCOW_TN_GROUP_MAX) return false;
     for (int i = 0; i < n; ++i) {
         if (pr[i].M != pr[0].M || !tcow_tn_use_256(pr[i].M, pr[i].N, pr[i].K)) return false;
         if (pr[i].N % 8 || pr[i].K % 8 || pr[i].ldy % 8 || pr[i].ldx % 8) return false;
@@ -567,7 +566,7 @@ int tcow_gemm_tn_bf16_group(hipStream_t stream, int n, const tcow_tn_problem* pr
         first += p.nz * p.tiles_n * p.tiles_k;
     }
     g.first[n] = first;
-    for (int i = n + 1; i <= TN_GROUP_MAX; ++i) g.first[i] = first;
+    for (int i = n + 1; i <= TCOW_TN_GROUP_MAX; ++i) g.first[i] = first;
     *nz_out = nz;
     bool whole = true;
     for (int i = 0; i < n; ++i) whole = whole && tn_whole(pr[i].M, pr[i].N, pr[i].K, pr[i].ldy, pr[i].ldx);

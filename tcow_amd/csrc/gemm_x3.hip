@@ -296,16 +296,8 @@ __global__ __launch_bounds__(256, (LDA == LD_ANY || LDB == LD_ANY) ? 2 : 3) void
 
 }  // namespace
 
-int tcow_launch_slab_reduce(hipStream_t stream, const float* slab, int nz, long slab_stride, long rows, long cols, float* out, long ldo, int accumulate,
-                            const float* bias_part, int bias_nparts, int bias_n, float* bias_out);
-
 int tcow_gemm_nt_x3(hipStream_t stream, const tcow_gemm_args* a) {
-    F32Params p;
-    p.M = a->M; p.N = a->N; p.K = a->K;
-    p.A = (const float*)a->A; p.sai = a->lda; p.sak = 1;
-    p.B = (const float*)a->W; p.sbj = a->ldw; p.sbk = 1;
-    p.C = a->C; p.ldc = a->ldc; p.bias = a->bias; p.row_scale = a->row_scale; p.resid = a->resid; p.ldr = a->ldr;
-    p.act = a->act; p.aux = (float*)a->aux; p.ldaux = a->ldaux; p.bias2 = a->bias2; p.row_scale2 = a->row_scale2; p.kps = ((a->K + XK - 1) / XK) * XK; p.slab = nullptr;
+    const F32Params p = f32_params_nt(a, XK);
     const bool vec = ((reinterpret_cast<uintptr_t>(p.A) | reinterpret_cast<uintptr_t>(p.B)) & 15) == 0 && ((p.sai | p.sbj | p.K) & 3) == 0;
     const dim3 grid(cdiv(a->N, XT) * cdiv(a->M, XT), 1);
     if (vec) hipLaunchKernelGGL(gemm_x3_kernel<LD_KVEC>, grid, dim3(256), 0, stream, p);
@@ -328,14 +320,9 @@ int tcow_tn_splits_x3(int M, int N, int K) {
 
 int tcow_gemm_tn_x3(hipStream_t stream, int M, int N, int K, const float* dY, long ldy, const float* X, long ldx, float* dW, long lddw,
                     int accumulate, float* slab, int splits, const float* bias_part, int bias_nparts, float* bias_out) {
-    F32Params p;
-    p.M = N; p.N = K; p.K = M;                       // output [N,K], contraction over tokens
-    p.A = dY; p.sai = 1; p.sak = ldy;
-    p.B = X; p.sbj = 1; p.sbk = ldx;
-    p.C = nullptr; p.ldc = 0; p.bias = nullptr; p.row_scale = nullptr; p.resid = nullptr; p.ldr = 0; p.act = 0; p.aux = nullptr; p.ldaux = 0; p.bias2 = nullptr; p.row_scale2 = nullptr;
     int kps = cdiv(M, splits); kps = ((kps + XK - 1) / XK) * XK;
     const int nz = cdiv(M, kps);
-    p.kps = kps; p.slab = slab;
+    const F32Params p = f32_params_plain(N, K, M, dY, 1, ldy, X, 1, ldx, kps, slab);      // output [N,K], contraction over tokens
     const bool vec = ((reinterpret_cast<uintptr_t>(dY) | reinterpret_cast<uintptr_t>(X)) & 15) == 0 && ((ldy | ldx | N | K) & 3) == 0;
     const dim3 grid(cdiv(K, XT) * cdiv(N, XT), nz);
     if (vec) hipLaunchKernelGGL(gemm_x3_kernel<LD_RVEC>, grid, dim3(256), 0, stream, p);
@@ -361,9 +348,8 @@ extern "C" int tcow_sgemm_x3_batched(void* stream, int n, const tcow_sgemm* prob
         const tcow_sgemm& s = probs[i];
         TCOW_CHECK_ARG(s.M > 0 && s.N > 0 && s.K > 0 && s.A && s.B && s.C && s.ldc >= s.N, "tcow_sgemm_x3_batched: bad problem %d", i);
         F32Params& p = b.p[i];
-        p.M = s.M; p.N = s.N; p.K = s.K; p.A = s.A; p.sai = s.sai; p.sak = s.sak; p.B = s.B; p.sbj = s.sbj; p.sbk = s.sbk;
-        p.C = s.C; p.ldc = s.ldc; p.bias = nullptr; p.row_scale = nullptr; p.resid = nullptr; p.ldr = 0; p.act = 0; p.aux = nullptr; p.ldaux = 0; p.bias2 = nullptr; p.row_scale2 = nullptr;
-        p.kps = ((s.K + XK - 1) / XK) * XK; p.slab = nullptr;
+        p = f32_params_plain(s.M, s.N, s.K, s.A, s.sai, s.sak, s.B, s.sbj, s.sbk, ((s.K + XK - 1) / XK) * XK, nullptr);
+        p.C = s.C; p.ldc = s.ldc;
         if (s.accumulate) { p.resid = s.C; p.ldr = s.ldc; }           // (the epilogue reads the residual element it then overwrites)
         const int la = x3_loader(s.A, s.sai, s.sak, s.M, s.K), lb = x3_loader(s.B, s.sbj, s.sbk, s.N, s.K);
         lda = (lda < 0 || lda == la) ? la : LD_ANY; ldb = (ldb < 0 || ldb == lb) ? lb : LD_ANY;

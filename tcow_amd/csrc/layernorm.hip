@@ -5,6 +5,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "internal.h"
 
 namespace {
 
@@ -193,11 +194,6 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(int rows, int D, const T* _
 
 }  // namespace
 
-int tcow_launch_row_reduce2(hipStream_t stream, const float* part, int nrows, long ld, int N1, float* out1, int N2, float* out2, int accumulate);
-int tcow_launch_row_reduce_group(hipStream_t stream, int n, const float* const* part, const int* nrows, const long* ld, const int* N1, float* const* out1, const int* N2,
-                                 float* const* out2, const int* N3, float* const* out3, const int* accumulate);
-int tcow_launch_row_reduce3(hipStream_t stream, const float* part, int nrows, long ld, int N1, float* out1, int N2, float* out2, int N3, float* out3, int accumulate);
-
 static const int kLnBwdBlocks = 768;
 // (grid-stride blocks of the backward: 768 = three 4-wave workgroups per CU in ONE round -- the kernel needs 154 VGPRs at D = 768, i.e. three
 // waves per SIMD; 512 -> 768: 78 -> 73.5 us, 1024 (1.33 rounds) 84 us.  The colsum variant needs 180 VGPRs = two waves per SIMD: 512 blocks.)
@@ -261,8 +257,8 @@ int tcow_layernorm_bwd(void* stream, int dtype, int rows, int D, const void* dy,
     TCOW_CHECK_LAUNCH();
     if (want_param_grads && !(accumulate & 2)) {
         // part is [blocks][2 or 3][D]: dgamma partials first, dbeta partials at +D, the fused bias gradient at +2D
-        if (csum) return tcow_launch_row_reduce3((hipStream_t)stream, part, blocks, 3L * D, D, dgamma, D, dbeta, D, colsum_out, accumulate & 1);
-        return tcow_launch_row_reduce2((hipStream_t)stream, part, blocks, 2L * D, D, dgamma, D, dbeta, accumulate & 1);
+        if (csum) return tcow_launch_row_reduce((hipStream_t)stream, part, blocks, 3L * D, D, dgamma, D, dbeta, D, colsum_out, accumulate & 1);
+        return tcow_launch_row_reduce((hipStream_t)stream, part, blocks, 2L * D, D, dgamma, D, dbeta, 0, nullptr, accumulate & 1);
     }
     return TCOW_OK;            // (accumulate & 2: the partial table stays in `workspace` for tcow_layernorm_fold)
 }
@@ -274,8 +270,9 @@ int tcow_layernorm_bwd_parts(int rows, int with_colsum) {
 }
 
 int tcow_layernorm_fold(void* stream, int n, const tcow_ln_fold_job* jobs) {
-    TCOW_CHECK_ARG(n > 0 && n <= 16 && jobs, "tcow_layernorm_fold: 1..16 jobs");
-    const float* part[16]; int nrows[16]; long ld[16]; int N1[16], N2[16], N3[16], acc[16]; float* o1[16]; float* o2[16]; float* o3[16];
+    TCOW_CHECK_ARG(n > 0 && n <= TCOW_LN_FOLD_MAX && jobs, "tcow_layernorm_fold: 1..%d jobs", TCOW_LN_FOLD_MAX);
+    constexpr int G = TCOW_LN_FOLD_MAX;
+    const float* part[G]; int nrows[G]; long ld[G]; int N1[G], N2[G], N3[G], acc[G]; float* o1[G]; float* o2[G]; float* o3[G];
     for (int i = 0; i < n; ++i) {
         const tcow_ln_fold_job& j = jobs[i];
         TCOW_CHECK_ARG(j.part && j.dgamma && j.dbeta && j.parts > 0 && j.D > 0, "tcow_layernorm_fold: bad job %d", i);

@@ -105,6 +105,12 @@ int tcow_gemm_nt(void* stream, const tcow_gemm_args* args);
 long tcow_gemm_nt_skinny_workspace_bytes(int M, int N, int split);   /* 0 for split == 1 */
 int tcow_gemm_nt_skinny(void* stream, const tcow_gemm_args* args, int split, void* workspace, long workspace_bytes);
 
+/* The skinny-M product for dtype TCOW_F32X3 (f32 operands and outputs, bf16 x 3 split products): the same tile, split, workspace
+ * (tcow_gemm_nt_skinny_workspace_bytes) and summation order.  split == 1 gives the bits of tcow_gemm_nt with TCOW_F32X3.  K % 64 == 0 and
+ * N % 4 == 0; A, W, C, bias, resid, aux and bias2 16-byte aligned, every leading dimension a multiple of 4 elements (the kernel has no scalar
+ * path).  TCOW_F32 is not served: the exact-f32 mode has no skinny kernel. */
+int tcow_gemm_nt_skinny_x3(void* stream, const tcow_gemm_args* args, int split, void* workspace, long workspace_bytes);
+
 /* Measurement aid for bench.py: between _begin and _end every tcow_gemm_nt launch is bracketed by HIP events recorded
  * on its own stream; _end synchronises on them and returns the summed event time (ms), the summed 2*M*N*K and the
  * number of launches (at most max_launches are recorded). */

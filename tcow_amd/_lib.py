@@ -73,6 +73,7 @@ SIGNATURES = {
     'tcow_gemm_nt': (_i, [_vp, ctypes.POINTER(GemmArgs)]),
     'tcow_gemm_nt_skinny_workspace_bytes': (_l, [_i, _i, _i]),
     'tcow_gemm_nt_skinny': (_i, [_vp, ctypes.POINTER(GemmArgs), _i, _vp, _l]),
+    'tcow_gemm_nt_skinny_x3': (_i, [_vp, ctypes.POINTER(GemmArgs), _i, _vp, _l]),
     'tcow_prof_gemm_begin': (_i, [_i]),
     'tcow_prof_gemm_end': (_i, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]),
     'tcow_prof_attn_begin': (_i, [_i]),

@@ -37,6 +37,20 @@ static inline F32Params f32_params_plain(int M, int N, int K, const float* A, lo
     return p;
 }
 
+// The operand split of the bf16 x 3 kernels (gemm_x3.hip, gemm_nt_skinny_x3.hip): hi = bf16(x) (round to nearest even), lo = bf16(x - hi), two
+// elements per call, packed.  (always bfloat16 splits, whatever 16-bit format the rest of the library is built for: bf16 keeps the f32 exponent
+// range, so lo never underflows)
+typedef __attribute__((ext_vector_type(8))) __bf16 x3_bf16x8;
+typedef __attribute__((ext_vector_type(2))) __bf16 x3_bf16x2;
+__device__ __forceinline__ uint32_t x3_pack(float a, float b) {
+    f32x2 v = {a, b};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, x3_bf16x2));
+}
+__device__ __forceinline__ void split2(float x0, float x1, uint32_t& h, uint32_t& l) {
+    h = x3_pack(x0, x1);
+    l = x3_pack(x0 - __builtin_bit_cast(float, h << 16), x1 - __builtin_bit_cast(float, h & 0xffff0000u));     // exact differences (hi shares the leading bits of x)
+}
+
 // bias, DropPath row scale, activation (with its side input / output), residual -- the semantics of tcow_gemm_args, one element
 __device__ __forceinline__ void f32_epilogue_store(const F32Params& p, int gm, int gn, float x, float bv) {
     x += bv;

@@ -22,18 +22,7 @@ constexpr int XK = 32;               // k-slice
 constexpr int XP = 80;               // LDS row pitch in bytes (32 bf16 + 16 B pad)
 constexpr int XPLANE = XT * XP;      // 10 KiB per plane
 
-// (always bfloat16 splits, whatever 16-bit format the rest of the library is built for: bf16 keeps the f32 exponent range, so lo never
-// underflows)
-typedef __attribute__((ext_vector_type(8))) __bf16 x3_bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 x3_bf16x2;
-__device__ __forceinline__ uint32_t x3_pack(float a, float b) {
-    f32x2 v = {a, b};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, x3_bf16x2));
-}
-__device__ __forceinline__ void split2(float x0, float x1, uint32_t& h, uint32_t& l) {
-    h = x3_pack(x0, x1);
-    l = x3_pack(x0 - __builtin_bit_cast(float, h << 16), x1 - __builtin_bit_cast(float, h & 0xffff0000u));     // exact differences (hi shares the leading bits of x)
-}
+// (x3_pack / split2, the operand split: gemm_f32.h)
 
 // Loaders of one 128-row x 32-k operand slice into 16 registers per thread: nothing but loads from clamped addresses -- a guarded load per
 // basic block, or a select on the loaded value, makes hipcc wait for the data right behind the load and the prefetch is gone.  Elements

@@ -64,11 +64,17 @@ def _gemm_args(dm, A, W, out, bias, row_scale, resid, act, aux, tile, bias2, row
 
 def gemm_nt(mode, A, W, out, bias=None, row_scale=None, resid=None, act=ACT_NONE, aux=None, tile=0, bias2=None, row_scale2=None, skinny=False):
     """out[M,N] = epilogue(A[M,K] @ W[N,K]^T); see tcow_gemm_nt. `out` dtype f32 or the mode's dtype.
-    skinny=True (the streaming steps): a 16-bit product that skinny_plan routes goes to gemm_nt_skinny instead."""
+    skinny=True (the streaming steps): a 16-bit product that skinny_plan routes goes to gemm_nt_skinny instead, a bf16 x 3 product that
+    skinny_plan_x3 routes to gemm_nt_skinny_x3 when its tensors have that entry point's 16-byte alignment (a view that has not stays on
+    tcow_gemm_nt, whose kernel has a scalar path); exact fp32 never routes."""
     if skinny and is16(mode) and not tile:
         split = skinny_plan(A.shape[0], W.shape[0], A.shape[1])
         if split > 0:
             return gemm_nt_skinny(mode, A, W, out, bias=bias, row_scale=row_scale, resid=resid, act=act, aux=aux, bias2=bias2, row_scale2=row_scale2, split=split)
+    if skinny and mode == F32X3 and not tile and _aligned16(A, W, out, bias, resid, aux, bias2):
+        split = skinny_plan_x3(A.shape[0], W.shape[0], A.shape[1])
+        if split > 0:
+            return gemm_nt_skinny_x3(A, W, out, bias=bias, row_scale=row_scale, resid=resid, act=act, aux=aux, bias2=bias2, row_scale2=row_scale2, split=split)
     _need_cuda(A, W, out)
     lib, dm = _sel(mode)
     a = _gemm_args(dm, A, W, out, bias, row_scale, resid, act, aux, tile, bias2, row_scale2)
@@ -77,6 +83,11 @@ def gemm_nt(mode, A, W, out, bias=None, row_scale=None, resid=None, act=ACT_NONE
 
 
 SKINNY_SPLITS = (1, 2, 3, 4, 6, 8)
+
+
+def _aligned16(*ts):
+    """Every given tensor starts on a 16-byte boundary and, if 2-D, has a row pitch of whole 16 bytes (tcow_gemm_nt_skinny_x3's rule)."""
+    return all(t is None or (t.data_ptr() % 16 == 0 and (t.dim() < 2 or t.stride(0) * t.element_size() % 16 == 0)) for t in ts)
 
 
 def skinny_plan(M, N, K):
@@ -109,6 +120,43 @@ def gemm_nt_skinny(mode, A, W, out, bias=None, row_scale=None, resid=None, act=A
     nbytes = lib.tcow_gemm_nt_skinny_workspace_bytes(a.M, a.N, split)
     ws = workspace(nbytes, A.device, 'nt_skinny') if nbytes > 0 else None
     L.check(lib.tcow_gemm_nt_skinny(_stream(), ctypes.byref(a), split, _p(ws), ws.numel() if ws is not None else 0), 'tcow_gemm_nt_skinny', lib)
+    return out
+
+
+def skinny_plan_x3(M, N, K):
+    """THE routing rule of the bf16 x 3 skinny-M NT GEMM (host arithmetic only): 0 = use tcow_gemm_nt, else the split S >= 1 of
+    tcow_gemm_nt_skinny_x3.  Measured (profiles/gemm_skinny_x3.json and gemm_skinny_x3_small.json).
+    Routed: K % 64 == 0 and N % 4 == 0 (what the entry point accepts), fewer than 256 tiles of 128 x 128 and at most 512 tiles of 64 x 64 --
+    what the chip holds at once, two workgroups per CU; past that the 128 tile is as fast or faster (qkv at M = 1 201: 684 tiles, 33.2
+    against 30.9 us; fc1: 912 tiles, 47.1 against 39.2).
+    S: the largest of SKINNY_SPLITS that leaves every slice at least four 64-wide k-slices and keeps tiles x S within 256 workgroups for
+    K < 1536 and within 512 from K = 1536: fc2 (K = 3072) S = 8 at M = 301, 40.9 -> 18.7 us, and S = 2 at M = 1 201, 46.7 -> 42.2; proj at
+    M = 301 (60 tiles) S = 3, where the table's row is too noisy to rank the splits (all within the spread); every other K = 768 product of 180 tiles or more is fastest unsplit (its second launch and the slab pass
+    cost more than the shorter chain saves).  At M = 14 ... 30 (12 ... 48 tiles) the K = 768 products are flat over S and fc2 gains 3 x from S = 8.
+    Fewer than 8 tiles (toy nets) never split: an extrapolation, not measured -- such a step is bound by the host's launches, and a split
+    adds one."""
+    M, N, K = int(M), int(N), int(K)
+    if M < 1 or N < 1 or N % 4 or K < 64 or K % 64 or -(-M // 128) * -(-N // 128) >= 256:
+        return 0
+    tiles, nk = -(-M // 64) * -(-N // 64), K // 64
+    if tiles > 512:
+        return 0
+    if tiles < 8:
+        return 1
+    cap = 512 if nk >= 24 else 256
+    return max(s for s in SKINNY_SPLITS if s == 1 or (s <= nk // 4 and tiles * s <= cap))
+
+
+def gemm_nt_skinny_x3(A, W, out, bias=None, row_scale=None, resid=None, act=ACT_NONE, aux=None, bias2=None, row_scale2=None, split=1):
+    """gemm_nt(F32X3, ...) on 64 x 64 tiles with a deterministic split over K (tcow_gemm_nt_skinny_x3): f32 tensors, 16-byte aligned, K % 64 == 0.
+    split == 1 gives gemm_nt's bits; split > 1 takes its [split, M, N] f32 slabs from workspace(tag='nt_skinny'), the tag of gemm_nt_skinny."""
+    _need_cuda(A, W, out)
+    lib = L.lib()
+    split = int(split)
+    a = _gemm_args(F32X3, A, W, out, bias, row_scale, resid, act, aux, 0, bias2, row_scale2)
+    nbytes = lib.tcow_gemm_nt_skinny_workspace_bytes(a.M, a.N, split)
+    ws = workspace(nbytes, A.device, 'nt_skinny') if nbytes > 0 else None
+    L.check(lib.tcow_gemm_nt_skinny_x3(_stream(), ctypes.byref(a), split, _p(ws), ws.numel() if ws is not None else 0), 'tcow_gemm_nt_skinny_x3', lib)
     return out
 
 

@@ -245,8 +245,9 @@ class QueryMaskTracker(nn.Module):
     def stream(self, batch_size=1, queries_per_clip=1, graph=False, skinny_gemm=None):
         """Streaming inference (causal_attention 1 or 2, eval, CUDA): a SeekerStream of at most num_total_frames frames for `batch_size` clips with
         `queries_per_clip` query masks each; stream.step(rgb, query_mask) takes the next frames and returns their outputs (tcow_amd/stream.py).
-        skinny_gemm: the steps' 16-bit GEMMs of a few hundred rows run on 64 x 64 tiles with a split over K (ops.skinny_plan); None = the
-        measured default, stream.SKINNY_GEMM_DEFAULT."""
+        skinny_gemm: the steps' GEMMs of a few hundred rows run on 64 x 64 tiles with a split over K -- the 16-bit modes where ops.skinny_plan
+        routes them, 'bf16x3' where ops.skinny_plan_x3 does; exact 'fp32' has no such kernel.  None = the measured default of the precision,
+        stream.SKINNY_GEMM_DEFAULT (16-bit) / stream.SKINNY_GEMM_X3_DEFAULT (bf16x3)."""
         from .stream import SeekerStream
         return SeekerStream(self, batch_size, queries_per_clip, graph, skinny_gemm)
 

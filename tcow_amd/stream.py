@@ -13,8 +13,9 @@ clips x queries (the query mask changes every token's K / V), a pool rows = capa
 that is 332 MB per row in the 16-bit modes; at configs[3] (T = 60, 480x640) 2.65 GB; f32 twice that.
 
 What belongs to one step is a _Step, and it is all run_forward sees (its `stream` argument): pos, time_rows [B*T, D] (one row of the time table
-per (row, frame) of the step), attn_temporal(i, ...) and cls_row(i, ...) for block i, and skinny: whether the step's 16-bit GEMMs take the
-skinny-M entry point where ops.skinny_plan routes them (the skinny_gemm keyword of net.stream / net.stream_pool).  There are three forms, each a _Step subclass that holds
+per (row, frame) of the step), attn_temporal(i, ...) and cls_row(i, ...) for block i, and skinny: whether the step's GEMMs take the
+skinny-M entry points where ops.skinny_plan (16-bit modes) / ops.skinny_plan_x3 (bf16x3) route them (the skinny_gemm keyword of net.stream /
+net.stream_pool).  There are three forms, each a _Step subclass that holds
 its device tables and calls its own pair of ops entry points; step(), pool.step() and pool.step_ragged() each build the tables and construct
 their form, and nothing else asks which form a step has:
 
@@ -32,7 +33,7 @@ their inputs into the graph's static buffers, write t0 and the time rows (the st
 length, and one t0 scalar: the graph points into both) and replay.  No step synchronises the host except the one capture per chunk length.  A
 graph keeps the module's operand copies it was captured with alive; when the module replaces them (.cuda() / .to() on the same device,
 set_precision() with the same precision, a train-mode forward) the graphs are dropped and captured again.  Pool steps run eagerly and build a
-fresh step object per call.  With skinny_gemm the captured launches also point into the split-K workspace of ops.gemm_nt_skinny: the capture
+fresh step object per call.  With skinny_gemm the captured launches also point into the split-K workspace of ops.gemm_nt_skinny / ops.gemm_nt_skinny_x3 (one tag): the capture
 runs on the workspace that the eager step before it sized, and the graph's entry keeps that tensor (ops.workspace replaces, never resizes).
 """
 import torch
@@ -44,6 +45,14 @@ from ._lib import TcowError
 # 1.42 ms instead of 2.41 at configs[1] B = 1, 2.41 instead of 3.35 at configs[3] B = 1 and 2.60 instead of 3.24 at configs[1] B = 8, on / off
 # alternating in one run, each difference several times the off leg's own max - min.  False runs the steps on tcow_gemm_nt alone.
 SKINNY_GEMM_DEFAULT = True
+# The same keyword's default when the module's precision is 'bf16x3' (ops.gemm_nt_skinny_x3 where ops.skinny_plan_x3 routes).  True: measured
+# (profiles/stream_skinny_x3_latency.json) -- a one-frame bf16x3 step takes 1.94 ms instead of 4.28 at configs[1] B = 1,
+# 4.45 instead of 5.88 at configs[3] B = 1 and 5.17 instead of 6.06 at configs[1] B = 8, each difference above the off leg's own max - min.
+SKINNY_GEMM_X3_DEFAULT = True
+
+
+def _skinny_default(module):
+    return SKINNY_GEMM_X3_DEFAULT if module.gemm_mode == ops.F32X3 else SKINNY_GEMM_DEFAULT
 
 
 class _State:
@@ -223,7 +232,7 @@ class SeekerStream:
         self.Bc, self.Qs, self.B = Bc, Qs, Bc * Qs
         self.T = module.num_total_frames
         self.graph = bool(graph)
-        self.skinny_gemm = SKINNY_GEMM_DEFAULT if skinny_gemm is None else bool(skinny_gemm)
+        self.skinny_gemm = _skinny_default(module) if skinny_gemm is None else bool(skinny_gemm)
         self._st = _State(module, self.B, self.skinny_gemm)
         self.device = self._st.pos.device
         self._t0_dev = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -322,7 +331,7 @@ class SeekerStreamPool:
         self.module = module
         self.capacity = capacity
         self.T = module.num_total_frames
-        self.skinny_gemm = SKINNY_GEMM_DEFAULT if skinny_gemm is None else bool(skinny_gemm)
+        self.skinny_gemm = _skinny_default(module) if skinny_gemm is None else bool(skinny_gemm)
         self._st = _State(module, capacity, self.skinny_gemm)
         self.device = self._st.pos.device
         self._sig = _signature(module)

@@ -1,0 +1,263 @@
+"""GPU: the skinny-M NT GEMM in the bf16 x 3 arithmetic (tcow_gemm_nt_skinny_x3, csrc/gemm_nt_skinny_x3.hip), the f32 counterpart of
+test_gpu_gemm_skinny.py.  split == 1 against the 128 x 128 tile of gemm_x3.hip bit for bit; split > 1 exactly on operands whose hi / lo planes are
+known, in its fixed summation order, and through every epilogue against an f64 product; the refusals.  Operands, outputs and aux are f32.
+Tolerance against f64: 4e-5 of the reference's maximum, the 'f32x3' entry of GEMM_MODES in test_gpu_kernels.py."""
+import ctypes
+import types
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from test_gpu_kernels import GEMM_MODES
+
+pytestmark = pytest.mark.gpu
+
+SENT = 7.0
+TOL = dict(GEMM_MODES)['f32x3']
+assert TOL == 4e-5
+
+
+@pytest.fixture(scope='module', autouse=True)
+def _leave_no_scratch():
+    """ops.workspace is a process-wide, grow-only cache that other tests look at: this module leaves none of its split-K scratch in it."""
+    yield
+    from tcow_amd import ops as o
+    for k in [k for k in o._ws_cache if k[2] == 'nt_skinny']:
+        del o._ws_cache[k]
+
+
+@pytest.fixture(scope='module')
+def ops(cuda):
+    from tcow_amd import ops as o
+    return o
+
+
+def rel(a, b):
+    return float((a.double() - b.double()).abs().max() / (b.double().abs().max() + 1e-12))
+
+
+def _case(cuda, M, N, K, seed, hilo=False):
+    """Operands of one product.  A and the GELU' / multiplier tile are column slices of wider tensors (lda > K, ldaux > N).
+    hilo: x = h + l with h in {+-2, +-3} and l in {-3 .. 3} 2^-10 (bf16(x) = h and bf16(x - h) = l exactly), integer bias and residual."""
+    g = torch.Generator(device='cuda').manual_seed(seed)
+    c = types.SimpleNamespace(M=M, N=N, K=K)
+    if hilo:
+        ri = lambda *s: torch.randint(-3, 4, s, device=cuda, generator=g).float()
+        hl = lambda *s: (torch.randint(2, 4, s, device=cuda, generator=g).float() * (torch.randint(0, 2, s, device=cuda, generator=g).float() * 2 - 1)
+                         + ri(*s) / 1024.0)
+        c.A = hl(M, K + 8)[:, 8:]; c.W = hl(N, K)
+        c.bias = ri(N); c.resid = ri(M, N)
+    else:
+        c.A = torch.randn(M, K + 8, device=cuda, generator=g)[:, 8:]; c.W = torch.randn(N, K, device=cuda, generator=g) * 0.05
+        c.bias = torch.randn(N, device=cuda, generator=g); c.resid = torch.randn(M, N, device=cuda, generator=g)
+    c.rs = torch.rand(M, device=cuda, generator=g) + 0.5; c.rs[::7] = 0.0
+    c.pre = torch.randn(M, N + 8, device=cuda, generator=g)[:, 4:4 + N]
+    c.b2 = torch.randn(N, device=cuda, generator=g); c.rs2 = (torch.rand(M, device=cuda, generator=g) > 0.3).float()
+    c.ref0 = c.A.double() @ c.W.double().t()                          # computed once per case, never modified
+    return c
+
+
+def _forms(ops, c):
+    """The 16 epilogue combinations of test_gpu_gemm_skinny.py with f32 outputs throughout (its 'plain32' would repeat 'plain': the row scale
+    alone takes its place): (name, residual aliases the output, aux role, keywords)."""
+    b, rs, res, b2, rs2 = dict(bias=c.bias), dict(row_scale=c.rs), dict(resid=c.resid), dict(bias2=c.b2), dict(row_scale2=c.rs2)
+    return [
+        ('plain', False, None, {}),
+        ('bias', False, None, {**b}),
+        ('rs', False, None, {**rs}),
+        ('bias_rs', False, None, {**b, **rs}),
+        ('bias_res', False, None, {**b, **res}),
+        ('bias_rs_res', False, None, {**b, **rs, **res}),
+        ('alias_bias_res', True, None, {**b}),
+        ('alias_bias_rs_res', True, None, {**b, **rs}),
+        ('fold7', False, None, {**b, **rs, **res, **b2, **rs2}),
+        ('alias_fold7', True, None, {**b, **rs, **b2, **rs2}),
+        ('bias_b2', False, None, {**b, **b2}),
+        ('gelu_aux', False, 'out', {**b, 'act': ops.ACT_GELU}),
+        ('gelu', False, None, {**b, 'act': ops.ACT_GELU}),
+        ('dgelu', False, 'in', {'act': ops.ACT_DGELU}),
+        ('gelu_dsave', False, 'out', {**b, 'act': ops.ACT_GELU_DSAVE}),
+        ('mul_aux', False, 'in', {'act': ops.ACT_MUL_AUX}),
+    ]
+
+
+def _dgelu(x):
+    x = x.clone().requires_grad_(True)
+    return torch.autograd.grad(F.gelu(x).sum(), x)[0]
+
+
+def _reference(ops, c, alias, kw):
+    """(f64 output, f64 aux output or None) of one form."""
+    v = c.ref0
+    if 'bias' in kw:
+        v = v + c.bias.double()
+    if 'row_scale' in kw:
+        v = v * c.rs.double()[:, None]
+    act, aux = kw.get('act', ops.ACT_NONE), None
+    if act == ops.ACT_GELU:
+        aux, v = v, F.gelu(v)
+    elif act == ops.ACT_GELU_DSAVE:
+        aux, v = _dgelu(v), F.gelu(v)
+    elif act == ops.ACT_DGELU:
+        v = v * _dgelu(c.pre.double())
+    elif act == ops.ACT_MUL_AUX:
+        v = v * c.pre.double()
+    if 'bias2' in kw:
+        v = v + (c.rs2.double()[:, None] if 'row_scale2' in kw else 1.0) * c.b2.double()
+    if alias or 'resid' in kw:
+        v = v + c.resid.double()
+    return v, aux
+
+
+def _run(call, cuda, c, alias, auxrole, kw):
+    """One call into f32 sentinel buffers [M + 1, N + 8]: (output buffer, aux buffer or None)."""
+    M, N = c.M, c.N
+    ob = torch.full((M + 1, N + 8), SENT, device=cuda)
+    kw = dict(kw)
+    if alias:
+        ob[:M, :N] = c.resid
+        kw['resid'] = ob[:M, :N]
+    ab = None
+    if auxrole == 'out':
+        ab = torch.full((M + 1, N + 8), SENT, device=cuda)
+        kw['aux'] = ab[:M, :N]
+    elif auxrole == 'in':
+        kw['aux'] = c.pre
+    call(c.A, c.W, ob[:M, :N], **kw)
+    return ob, ab
+
+
+def _guards_ok(buf, M, N):
+    return buf is None or (bool((buf[M] == SENT).all()) and bool((buf[:, N:] == SENT).all()))
+
+
+# one partial tile, a ragged N, nk = 1, 2, 3 (nk = 1: a ring shorter than its two stages) and 9; the last: 24 x 24 = 576 workgroups, more than one round
+@pytest.mark.parametrize('M,N,K', [(1, 4, 64), (63, 60, 128), (64, 64, 64), (65, 68, 192), (301, 264, 576), (1480, 1536, 128)])
+def test_split_1_equals_the_128_tile_bit_for_bit(ops, cuda, M, N, K):
+    c = _case(cuda, M, N, K, M + N + K)
+    skinny = lambda A, W, out, **kw: ops.gemm_nt_skinny_x3(A, W, out, split=1, **kw)
+    tile128 = lambda A, W, out, **kw: ops.gemm_nt(ops.F32X3, A, W, out, **kw)
+    for name, alias, auxrole, kw in _forms(ops, c):
+        o1, a1 = _run(skinny, cuda, c, alias, auxrole, kw)
+        o0, a0 = _run(tile128, cuda, c, alias, auxrole, kw)
+        assert torch.equal(o1, o0), (name, rel(o1[:M, :N], o0[:M, :N]))
+        assert a1 is None or torch.equal(a1, a0), name
+        assert _guards_ok(o1, M, N) and _guards_ok(a1, M, N), name
+
+
+def _planes(x):
+    h = x.bfloat16().float()
+    return h.double(), (x - h).bfloat16().double()
+
+
+@pytest.mark.parametrize('M,N,K,splits', [(65, 68, 320, (1, 2, 3, 5)), (301, 72, 1024, (4, 8, 16))])
+def test_split_exact_on_hi_lo_operands(ops, cuda, M, N, K, splits):
+    """x = h + l with bf16(x) = h and bf16(x - h) = l exactly: every kept term (hi hi, hi lo, lo hi) is a multiple of 2^-10 and every partial sum
+    stays below 2^24 of those units up to K = 1 024, so the f32 output is hi_A hi_W^T + hi_A lo_W^T + lo_A hi_W^T exactly, in any order.  A
+    kernel that drops, doubles or swaps a plane, skips a k-slice or covers one twice differs (nk = 5: uneven slices, and S = nk)."""
+    c = _case(cuda, M, N, K, 3 * M + K, hilo=True)
+    (ah, al), (wh, wl) = _planes(c.A), _planes(c.W)
+    assert torch.equal(ah + al, c.A.double()) and torch.equal(wh + wl, c.W.double()) and bool((al != 0).any()) and bool((wl != 0).any())
+    want = ah @ wh.t() + ah @ wl.t() + al @ wh.t()
+    assert not torch.equal(want, c.ref0)                              # (the dropped lo lo term is visible)
+    for S in splits:
+        call = lambda A, W, out, **kw: ops.gemm_nt_skinny_x3(A, W, out, split=S, **kw)
+        ob, _ = _run(call, cuda, c, False, None, {})
+        assert torch.equal(ob[:M, :N].double(), want) and _guards_ok(ob, M, N), S
+        ob, _ = _run(call, cuda, c, False, None, dict(bias=c.bias, resid=c.resid))
+        assert torch.equal(ob[:M, :N].double(), want + c.bias.double() + c.resid.double()) and _guards_ok(ob, M, N), S
+
+
+@pytest.mark.parametrize('M,N,K,splits', [(65, 68, 320, (2, 3, 5)), (301, 72, 1024, (4, 8, 16))])
+def test_split_adds_the_slices_in_order(ops, cuda, M, N, K, splits):
+    """No epilogue operands: the result is p_0 + p_1 + ... + p_{S-1} added in that order in f32, p_s = the split == 1 product over the columns of
+    slice s; a second call gives the same bits."""
+    c = _case(cuda, M, N, K, M + 5 * K)
+    nk = K // 64
+    for S in splits:
+        want = None
+        for s in range(S):
+            k0, k1 = 64 * (s * nk // S), 64 * ((s + 1) * nk // S)
+            p = ops.gemm_nt_skinny_x3(c.A[:, k0:k1], c.W[:, k0:k1], torch.empty(M, N, device=cuda), split=1)
+            want = p if want is None else want + p
+        got = ops.gemm_nt_skinny_x3(c.A, c.W, torch.empty(M, N, device=cuda), split=S)
+        assert torch.equal(got, want), (S, rel(got, want))
+        again = ops.gemm_nt_skinny_x3(c.A, c.W, torch.empty(M, N, device=cuda), split=S)
+        assert torch.equal(again, got), S
+
+
+def test_split_every_epilogue_vs_f64(ops, cuda):
+    """Two shapes of different sizes back to back on one workspace, filled with NaN before each pair of calls: a slab element that no workgroup
+    wrote, or one left by the other call, would show."""
+    cases = [(_case(cuda, 301, 264, 576, 11), 3), (_case(cuda, 130, 768, 3072, 12), 8)]
+    lib = ops.L.lib()
+    need = max(lib.tcow_gemm_nt_skinny_workspace_bytes(c.M, c.N, S) for c, S in cases)
+    ws = ops.workspace(need, cuda, 'nt_skinny')
+    forms = [_forms(ops, c) for c, _ in cases]
+    for i in range(len(forms[0])):
+        ws[:ws.numel() // 4 * 4].view(torch.float32).fill_(float('nan'))
+        ran = []
+        for (c, S), fs in zip(cases, forms):
+            name, alias, auxrole, kw = fs[i]
+            call = lambda A, W, out, **k: ops.gemm_nt_skinny_x3(A, W, out, split=S, **k)
+            ran.append((c, S, name, alias, kw) + _run(call, cuda, c, alias, auxrole, kw))
+        assert ops.workspace(need, cuda, 'nt_skinny') is ws
+        for c, S, name, alias, kw, ob, ab in ran:
+            want, want_aux = _reference(ops, c, alias, kw)
+            err = rel(ob[:c.M, :c.N], want)
+            assert err < TOL, (name, S, err)
+            assert ab is None or rel(ab[:c.M, :c.N], want_aux) < TOL, (name, S)
+            assert _guards_ok(ob, c.M, c.N) and _guards_ok(ab, c.M, c.N), (name, S)
+
+
+def test_refusals_name_the_argument_and_launch_nothing(ops, cuda):
+    from tcow_amd import _lib as L
+    lib = L.lib()
+    M, N = 40, 64
+    A = torch.randn(M, 256, device=cuda); W = torch.randn(N, 256, device=cuda)
+    ws = torch.empty(8 * M * N * 4 + 16, dtype=torch.uint8, device=cuda)
+
+    def call(K=256, split=2, wsp=ws.data_ptr(), nbytes=None, dtype=L.TCOW_F32X3, ldc_extra=0):
+        buf = torch.full((M, N + 8), SENT, device=cuda)
+        out = buf[:, :N]
+        a = L.GemmArgs(M, N, K, dtype, A.data_ptr(), A.stride(0), W.data_ptr(), W.stride(0), out.data_ptr(), out.stride(0) + ldc_extra, 1, None, None, None, 0,
+                       L.ACT_NONE, None, 0, 0, None, None)
+        need = lib.tcow_gemm_nt_skinny_workspace_bytes(M, N, split)
+        rc = lib.tcow_gemm_nt_skinny_x3(ops._stream(), ctypes.byref(a), split, wsp, need if nbytes is None else nbytes)
+        torch.cuda.synchronize()
+        return rc, lib.tcow_last_error().decode(), bool((buf == SENT).all())
+
+    rc, _, untouched = call()
+    assert rc == 0 and not untouched                                              # the accepted call these are variations of
+    need2 = 2 * M * N * 4
+    assert ws.data_ptr() % 16 == 0
+    for kw, word in [(dict(split=0), 'split'), (dict(split=17), 'split'), (dict(split=5), 'split'), (dict(K=96, split=1), 'K=96'),
+                     (dict(wsp=None), 'workspace'), (dict(nbytes=need2 - 1), 'workspace'), (dict(wsp=ws.data_ptr() + 4), 'workspace'),
+                     (dict(dtype=L.TCOW_BF16), 'dtype'), (dict(dtype=L.TCOW_F32), 'dtype'), (dict(ldc_extra=-2), 'ldc')]:
+        rc, msg, untouched = call(**kw)
+        assert rc != 0 and word in msg and untouched, (kw, rc, msg)
+    with pytest.raises(L.TcowError, match='split'):
+        ops.gemm_nt_skinny_x3(A, W, torch.empty(M, N, device=cuda), split=5)
+    with pytest.raises(L.TcowError):
+        ops.gemm_nt_skinny(ops.F32X3, A, W, torch.empty(M, N, device=cuda), split=1)       # the 16-bit entry point still refuses this mode
+
+
+def test_gemm_nt_routes_only_what_the_entry_point_accepts(ops, cuda, monkeypatch):
+    """ops.gemm_nt(F32X3, skinny=True): a product whose N is no multiple of 4, or whose output pitch is not whole 16 bytes, stays on tcow_gemm_nt
+    (the 128 tile has a scalar path) instead of raising in the entry point; the aligned product next to it is routed.  Same bits either way."""
+    calls = []
+    real = ops.gemm_nt_skinny_x3
+    monkeypatch.setattr(ops, 'gemm_nt_skinny_x3', lambda *a, **kw: (calls.append(kw.get('split')), real(*a, **kw))[1])
+    M, K = 65, 128
+    for N, pitch, routed in [(68, 76, True), (68, 74, False), (70, 78, False)]:
+        c = _case(cuda, M, N, K, N + pitch)
+        outs = []
+        for skinny in (False, True):
+            buf = torch.full((M + 1, pitch), SENT, device=cuda)
+            ops.gemm_nt(ops.F32X3, c.A, c.W, buf[:M, :N], bias=c.bias, resid=c.resid, skinny=skinny)
+            outs.append(buf)
+        assert calls == ([1] if routed else []), (N, pitch, calls)
+        del calls[:]
+        assert torch.equal(outs[0], outs[1]) and _guards_ok(outs[1], M, N)
+        assert rel(outs[1][:M, :N], c.ref0 + c.bias.double() + c.resid.double()) < TOL

@@ -14,6 +14,9 @@
     python tools/dev_stream_latency.py --skinny --out profiles/stream_skinny_latency.json
                                         # one-frame steps at t0 = T - 1 with skinny_gemm=True against skinny_gemm=False (the code as it was before the
                                         # keyword existed), alternating in one run: configs[1] B = 1 and B = 8, configs[3] B = 1, eager and graph
+    python tools/dev_stream_latency.py --skinny --precision bf16x3 --reps 30 --out profiles/stream_skinny_x3_latency.json
+                                        # the same legs in precision='bf16x3' (ops.gemm_nt_skinny_x3 against tcow_gemm_nt with TCOW_F32X3)
+    --kprof / --kstats take --precision and --skinny-gemm on|off as well: the breakdown of a bf16x3 step with and without the flag
 
 Times are device events around each call after warm-up, profiler off.  A step at a given t0 is timed by setting the stream's host frame counter
 (the kernels then read t0 from the device scalar the step writes): the work of a step depends on t0, not on what the cache holds.  Synthetic
@@ -224,14 +227,14 @@ def ragged_leg(reps):
     return res
 
 
-def skinny_leg(reps):
-    """One-frame bf16 steps at t0 = T - 1, skinny_gemm on / off, eager and graph: the four streams of a config are stepped in turn `reps` times, one
+def skinny_leg(reps, precision='bf16'):
+    """One-frame steps (bf16, or `precision`) at t0 = T - 1, skinny_gemm on / off, eager and graph: the four streams of a config are stepped in turn `reps` times, one
     sample (one step between a pair of events) each per round.  The verdict of DESIGN.md section 9: the eager medians at configs[1] B = 1 and
     configs[3] B = 1 are lower with the flag by more than the off-leg's own max - min, and the B = 8 leg is not slower by more than that spread."""
     runs = []
     for name, B in (('configs1', 1), ('configs1', 8), ('configs3', 1)):
         T, H, W = CONFIGS[name]
-        net = build(T, H, W, 'bf16')
+        net = build(T, H, W, precision)
         rgb, qm = inputs(B, T, H, W)
         f = lambda x, t: x[:, :, t:t + 1]
         with torch.no_grad():
@@ -251,7 +254,7 @@ def skinny_leg(reps):
             for _ in range(reps):
                 for k, fn in legs.items():
                     samples[k].append(ev_time(fn, 1))
-        r = {'config': name, 'T': T, 'H': H, 'W': W, 'B': B, 'precision': 'bf16', 't0': T - 1, 'reps': reps}
+        r = {'config': name, 'T': T, 'H': H, 'W': W, 'B': B, 'precision': precision, 't0': T - 1, 'reps': reps}
         for k, v in samples.items():
             v = sorted(v)
             r[k + '_step_ms'] = {'median': v[len(v) // 2], 'min': v[0], 'max': v[-1]}
@@ -283,21 +286,21 @@ def cached_kernel_bytes(T, H, W, e=2, heads=12, D=768):
     return alg
 
 
-def kprof():
-    """One-frame bf16 steps at configs[3], t0 = 59, for a rocprofv3 kernel trace: KPROF_WARMUP steps that build the operand copies, then
-    KPROF_STEPS steady ones (--kstats keeps only those)."""
+def kprof(precision='bf16', skinny_gemm=None):
+    """One-frame steps (bf16, or `precision`) at configs[3], t0 = 59, for a rocprofv3 kernel trace: KPROF_WARMUP steps that build the operand
+    copies, then KPROF_STEPS steady ones (--kstats keeps only those)."""
     T, H, W = CONFIGS['configs3']
-    net = build(T, H, W, 'bf16')
+    net = build(T, H, W, precision)
     rgb, qm = inputs(1, T, H, W)
     with torch.no_grad():
-        st = net.stream(batch_size=1, graph=False)
+        st = net.stream(batch_size=1, graph=False, skinny_gemm=skinny_gemm)
         for _ in range(KPROF_WARMUP + KPROF_STEPS):
             st.frames_done = T - 1
             st.step(rgb[:, :, T - 1:T], qm[:, :, T - 1:T])
         torch.cuda.synchronize()
 
 
-def kstats(trace_csv, out):
+def kstats(trace_csv, out, precision='bf16', skinny_gemm=None):
     """Per-step kernel breakdown of the KPROF_STEPS profiled steps from rocprofv3's kernel-trace CSV: dispatches in start order, everything up to
     and including the KPROF_WARMUP-th STEP_LAST_KERNEL dropped, per-kernel totals divided by KPROF_STEPS."""
     import csv
@@ -312,8 +315,9 @@ def kstats(trace_csv, out):
         n, tot, mn = per.get(r['Kernel_Name'], (0, 0, None))
         per[r['Kernel_Name']] = (n + 1, tot + d, d if mn is None else min(mn, d))
     T, H, W = CONFIGS['configs3']
-    alg = cached_kernel_bytes(T, H, W)
-    lines = [f'# {KPROF_STEPS} one-frame bf16 stream steps at BASELINE configs[3] (T=60, 480x640, B=1), t0 = 59, after {KPROF_WARMUP} warm-up steps',
+    alg = cached_kernel_bytes(T, H, W, e=2 if precision in ('bf16', 'fp16') else 4)
+    flag = '' if skinny_gemm is None else f", skinny_gemm={'on' if skinny_gemm else 'off'}"
+    lines = [f'# {KPROF_STEPS} one-frame {precision} stream steps at BASELINE configs[3] (T=60, 480x640, B=1), t0 = 59{flag}, after {KPROF_WARMUP} warm-up steps',
              '# (rocprofv3 --kernel-trace; tools/dev_stream_latency.py --kprof, then --kstats on the kernel-trace CSV: the warm-up dispatches are dropped)',
              '#   us/step  launches/step   avg us   min us  kernel']
     total = 0
@@ -342,15 +346,18 @@ def main():
     ap.add_argument('--ragged', action='store_true', help='the ragged-step leg (eight sessions at configs1, chunk lengths 1, 1, 1, 1, 2, 2, 4, 8)')
     ap.add_argument('--skinny', action='store_true', help='skinny_gemm=True against False, one-frame steps at configs1 B = 1 / 8 and configs3 B = 1')
     ap.add_argument('--kstats', default=None, metavar='KERNEL_TRACE_CSV')
+    ap.add_argument('--precision', default='bf16', help="precision of the --skinny, --kprof and --kstats legs ('bf16' or 'bf16x3')")
+    ap.add_argument('--skinny-gemm', default=None, choices=['on', 'off'], help='the skinny_gemm keyword of the --kprof steps (default: the stream default)')
     ap.add_argument('--only', default=None, help='comma list of configs1_b1, configs1_b8, configs3_b1')
     a = ap.parse_args()
+    flag = None if a.skinny_gemm is None else a.skinny_gemm == 'on'
     if a.kstats:
-        kstats(a.kstats, a.out)
+        kstats(a.kstats, a.out, a.precision, flag)
         return
     if not torch.cuda.is_available():
         raise SystemExit('dev_stream_latency.py needs a GPU')
     if a.kprof:
-        kprof()
+        kprof(a.precision, flag)
         return
     if a.pool:
         out = {'device': torch.cuda.get_device_name(0), 'pool': pool_leg(a.reps)}
@@ -369,7 +376,7 @@ def main():
                 json.dump(out, f, indent=1)
         return
     if a.skinny:
-        out = {'device': torch.cuda.get_device_name(0), 'skinny': skinny_leg(a.reps)}
+        out = {'device': torch.cuda.get_device_name(0), 'skinny': skinny_leg(a.reps, a.precision)}
         print(json.dumps(out['skinny']), flush=True)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

@@ -257,7 +257,21 @@ int tcow_attn_spatial_bwd(void* stream, const tcow_attn_shape* shape, const void
  *   causal 1 or 2, T_total <= TCOW_STREAM_MAX_FRAMES, n_slots >= 1, 1 <= n <= F.
  * tcow_cls_ragged: x [F*S, D] f32, cls_cache [n_slots, D]; per session r: t0_rows[r] == 0: slot 0 of every frame of the session <- slot 0 of
  *   its frame first_rows[r], and that row -> cls_cache[slot_rows[r]]; t0_rows[r] > 0: slot 0 of every frame of the session <- cls_cache[slot].
- *   A slot outside [0, n_slots) writes NaN and touches no cache row. */
+ *   A slot outside [0, n_slots) writes NaN and touches no cache row.
+ *
+ * A paged pool (SeekerStreamPool with page_frames = P): the K / V cache of a block is a heap of n_pages pages of P frames,
+ * k_pages / v_pages [n_pages, S-1, heads, P, 64], and a page id is valid in every block's arrays alike.  Session r of a step brings row r of
+ * page_rows [n, pages_per_session] (device int32): entry q is the page that holds its frames q*P .. q*P+P-1, so cache position kt of
+ * (session r, slot s >= 1, head h) is the 64 elements at (((page_rows[r][kt / P]*(S-1) + (s-1))*heads + h)*P + kt % P)*64.
+ * tcow_attn_temporal_ragged_paged_fwd: tcow_attn_temporal_ragged_fwd with that addressing and nothing else changed (one wave per (flat frame,
+ *   slot, head), the same per-frame body): out, and the pages gathered back into [T_total, 64] runs, are bit-identical to the ragged entry
+ *   point on contiguous caches with the same contents.  Before a wave touches a page it checks every entry it would dereference: a frame at
+ *   t = t0 + j needs page_rows[r][0 .. t / P] inside [0, n_pages); entries beyond t / P are never read.  A frame with such an entry outside
+ *   the heap, or one that the ragged entry point would refuse (t0 < 0, t0 + c > T_total, j outside [0, c)), writes NaN to its own rows of out
+ *   and touches no page.  No wave reads a cache position that the launch writes.  Two sessions of one launch that name the same page are
+ *   UNDEFINED, as two rows that name one slot are above.  P a power of two, 1 <= P <= TCOW_STREAM_MAX_FRAMES; n_pages >= 1;
+ *   pages_per_session * P >= T_total; causal 1 or 2, T_total <= TCOW_STREAM_MAX_FRAMES, 1 <= n <= F.  The cls rows stay per slot
+ *   (tcow_cls_ragged). */
 #define TCOW_STREAM_MAX_FRAMES 1024
 int tcow_attn_temporal_cached_fwd(void* stream, const tcow_attn_shape* chunk, int T_total, const int* t0_dev, const void* qkv, void* k_cache,
                                   void* v_cache, void* out);
@@ -270,6 +284,9 @@ int tcow_attn_temporal_ragged_fwd(void* stream, const tcow_attn_shape* step, int
                                   void* out);
 int tcow_cls_ragged(void* stream, int n, int F, int S, int D, float* x, float* cls_cache, int n_slots, const int* t0_rows, const int* slot_rows,
                     const int* first_rows, const int* c_rows);
+int tcow_attn_temporal_ragged_paged_fwd(void* stream, const tcow_attn_shape* step, int n, int T_total, int n_pages, int page_frames, int pages_per_session,
+                                        const int* t0_rows, const int* page_rows, const int* first_rows, const int* c_rows, const int* row_of_frame,
+                                        const void* qkv, void* k_pages, void* v_pages, void* out);
 
 /* ------------------------------------------------------------------------------------------- token glue
  * tcow_im2col: cat([rgb (B,3,T,H,W), query (B,1,T,H,W)]) (mask_tracker.py:107-108), optional (rgb-0.45)/0.225

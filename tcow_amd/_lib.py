@@ -100,6 +100,7 @@ SIGNATURES = {
     'tcow_cls_pool': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     'tcow_attn_temporal_ragged_fwd': (_i, [_vp, _ash, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'tcow_cls_ragged': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    'tcow_attn_temporal_ragged_paged_fwd': (_i, [_vp, _ash, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'tcow_im2col': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     'tcow_gather_frames': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'tcow_resize_aa': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp]),

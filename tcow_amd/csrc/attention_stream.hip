@@ -17,6 +17,11 @@
 // tcow_attn_temporal_ragged_fwd / tcow_cls_ragged (SeekerStreamPool.step_ragged): sessions that bring different numbers of frames to one step.
 // The frames lie flat in session order; the attention kernel runs one wave per (flat frame, slot, head) on the per-frame body it shares with
 // temporal_cached_kernel (temporal_query_frame), so a long chunk spreads over as many waves as it has frames.
+//
+// tcow_attn_temporal_ragged_paged_fwd (a paged SeekerStreamPool, stream_pool(page_frames=P)): the ragged kernel on a cache that is a heap of
+// pages of P frames, [n_pages, S-1, heads, P, 64]; a session's row of the page table names the page of its frames q*P .. q*P+P-1.  Where a
+// cached key lives is all that differs: temporal_query_frame takes that as a small functor (ContiguousKeys / PagedKeys), so the four kernels
+// keep one body and agree bit for bit.
 #include <math.h>
 
 #include "attention_common.h"
@@ -51,11 +56,33 @@ template <> struct StreamVec<float> {
 
 __device__ __forceinline__ void copy16(void* dst, const void* src) { *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src); }
 
+// Where cache position kt of the wave's (session, token slot, head) lives in a block's K / V array `base` (const or not): the address of the
+// lane's 16 bytes of that line.  The one thing in which the contiguous and the paged kernels differ.  In two steps: page(kt), which EVERY lane
+// of the wave calls together (a paged lookup may be a lane shuffle), then keys(base, page, kt) by the lanes that load or store.
+struct ContiguousKeys {             // [slots, S-1, heads, T_total, 64]: one run of whole lines from cbase (the lane's channel slice included)
+    struct NoPage {};
+    size_t cbase;
+    __device__ __forceinline__ NoPage page(int) const { return NoPage{}; }
+    template <typename P> __device__ __forceinline__ P operator()(P base, NoPage, int kt) const { return base + cbase + (size_t)kt * ATT_HD; }
+};
+struct PagedKeys {                  // [n_pages, S-1, heads, P, 64], P = 1 << lgP: page pages[kt / P], line kt % P of the (slot, head) run at `line`
+    const int* pages;               // the session's row of the page table (entries 0 .. kt / P checked by the caller)
+    size_t page_stride, line;       // (S-1) * heads * P * 64; ((s-1) * heads + h) * P * 64 + the lane's channel slice
+    int lgP;
+    int mine;                       // pages[lane], as the caller's check loaded it (lanes beyond the last checked entry: anything)
+    bool wide;                      // the wave's keys reach entries >= 64: more entries than lanes, look them up in memory
+    __device__ __forceinline__ int page(int kt) const { return wide ? pages[kt >> lgP] : __shfl(mine, kt >> lgP, 64); }
+    template <typename P> __device__ __forceinline__ P operator()(P base, int pg, int kt) const {
+        return base + ((size_t)pg * page_stride + line + (size_t)(kt & ((1 << lgP) - 1)) * ATT_HD);
+    }
+};
+
 // One query frame of a temporal stream step, shared by every kernel of this file so that they agree bit for bit: chunk frame j (flat frame
-// fb + j of the step's rows, fb = the chunk's first flat frame) stands at t = t0 + j and attends to keys 0 .. t, keys < t0 from the cache line
-// run at cbase, keys t0 .. t from the step's qkv rows at flat frame fb + (kt - t0).  Every lane of the wave calls it; lane group 0 stores.
-template <typename T>
-__device__ __forceinline__ void temporal_query_frame(const T* qkv, const T* kc, const T* vc, T* out, size_t cbase, int fb, int j, int t0, int S, int s, int D,
+// fb + j of the step's rows, fb = the chunk's first flat frame) stands at t = t0 + j and attends to keys 0 .. t, keys < t0 from the cache at
+// keys(kt) (each lane group looks up its own key: a batch of G * ST_U keys may span pages), keys t0 .. t from the step's qkv rows at flat
+// frame fb + (kt - t0).  Every lane of the wave calls it; lane group 0 stores.
+template <typename T, typename Keys>
+__device__ __forceinline__ void temporal_query_frame(const T* qkv, const T* kc, const T* vc, T* out, const Keys keys, int fb, int j, int t0, int S, int s, int D,
                                                      int col, int grp) {
     constexpr int VEC = StreamVec<T>::VEC, LPR = ATT_HD / VEC, G = 64 / LPR;
     const long ld3 = 3L * D;
@@ -71,9 +98,10 @@ __device__ __forceinline__ void temporal_query_frame(const T* qkv, const T* kc, 
 #pragma unroll
         for (int u = 0; u < ST_U; ++u) {
             const int kt = k0 + u * G + grp;
+            const auto pg = keys.page(kt <= t ? kt : t);        // (every lane, ahead of the branch)
             if (kt <= t) {
-                const T* kp = kt < t0 ? kc + cbase + (size_t)kt * ATT_HD : qkv + ((long)(fb + kt - t0) * S + s) * ld3 + D + col;
-                const T* vp = kt < t0 ? vc + cbase + (size_t)kt * ATT_HD : qkv + ((long)(fb + kt - t0) * S + s) * ld3 + 2 * D + col;
+                const T* kp = kt < t0 ? keys(kc, pg, kt) : qkv + ((long)(fb + kt - t0) * S + s) * ld3 + D + col;
+                const T* vp = kt < t0 ? keys(vc, pg, kt) : qkv + ((long)(fb + kt - t0) * S + s) * ld3 + 2 * D + col;
                 StreamVec<T>::ld(kp, kv[u]);
                 StreamVec<T>::ld(vp, vv[u]);
             } else {
@@ -152,14 +180,14 @@ __global__ __launch_bounds__(64 * ST_WAVES) void temporal_cached_kernel(int B, i
         for (int j = grp; j < c; j += G) StreamVec<T>::st(out + ((long)(b * c + j) * S + s) * D + col, z);
         return;
     }
-    const size_t cbase = ((((size_t)slot * (S - 1) + (s - 1)) * heads + h) * T_total) * ATT_HD + sub * VEC;
+    const ContiguousKeys keys{((((size_t)slot * (S - 1) + (s - 1)) * heads + h) * T_total) * ATT_HD + sub * VEC};
     // append the chunk's keys / values: cache[t0 + j] = chunk row j (bit copies)
     for (int j = grp; j < c; j += G) {
         const T* src = qkv + ((long)(b * c + j) * S + s) * ld3 + col;
-        copy16(kc + cbase + (size_t)(t0 + j) * ATT_HD, src + D);
-        copy16(vc + cbase + (size_t)(t0 + j) * ATT_HD, src + 2 * D);
+        copy16(keys(kc, keys.page(t0 + j), t0 + j), src + D);
+        copy16(keys(vc, keys.page(t0 + j), t0 + j), src + 2 * D);
     }
-    for (int j = 0; j < c; ++j) temporal_query_frame<T>(qkv, kc, vc, out, cbase, b * c, j, t0, S, s, D, col, grp);
+    for (int j = 0; j < c; ++j) temporal_query_frame<T>(qkv, kc, vc, out, keys, b * c, j, t0, S, s, D, col, grp);
 }
 
 // One wave per (flat frame f, token slot s, head h) of a ragged step: n sessions, session r with c_rows[r] frames at flat frames
@@ -204,14 +232,84 @@ __global__ __launch_bounds__(64 * ST_WAVES) void temporal_ragged_kernel(int n, i
         }
         return;
     }
-    const size_t cbase = ((((size_t)slot * (S - 1) + (s - 1)) * heads + h) * T_total) * ATT_HD + sub * VEC;
+    const ContiguousKeys keys{((((size_t)slot * (S - 1) + (s - 1)) * heads + h) * T_total) * ATT_HD + sub * VEC};
     if (grp == 0) {
         // append this frame's key / value: cache[t0 + j] = the frame's own row (bit copies)
         const T* src = qkv + ((long)f * S + s) * (3L * D) + col;
-        copy16(kc + cbase + (size_t)(t0 + j) * ATT_HD, src + D);
-        copy16(vc + cbase + (size_t)(t0 + j) * ATT_HD, src + 2 * D);
+        copy16(keys(kc, keys.page(t0 + j), t0 + j), src + D);
+        copy16(keys(vc, keys.page(t0 + j), t0 + j), src + 2 * D);
     }
-    temporal_query_frame<T>(qkv, kc, vc, out, cbase, first, j, t0, S, s, D, col, grp);
+    temporal_query_frame<T>(qkv, kc, vc, out, keys, first, j, t0, S, s, D, col, grp);
+}
+
+// temporal_ragged_kernel on a paged cache: the K / V array of a block is [n_pages, S-1, heads, P, 64] with P = 1 << lgP frames per page, and
+// session r brings row r of the page table page_rows [n, pps]: entry q is the page of its frames q*P .. q*P+P-1.  Cache position kt of
+// (session r, token slot s, head h) is line kt % P of the (s-1, h) run of page page_rows[r][kt / P] (PagedKeys).  One wave per (flat frame f,
+// token slot s, head h), the append of the frame's own K / V line and the per-frame body exactly as in temporal_ragged_kernel.
+// Before it touches any cache line the wave checks every table entry it would dereference: pages 0 .. (t0 + j) / P of its session must lie in
+// [0, n_pages) (t0 + j < T_total <= pps * P, which the launcher checked: the entries exist).  A bad entry, like a bad row of the ragged kernel,
+// writes NaN to this frame's own output row and touches no page.  The check loads entry `lane` into every lane; while the wave's keys reach
+// entries < 64 only, a lane group's lookup is a shuffle from those (one load less in the wave's chain of dependent loads, which is what bounds
+// this kernel at a few tens of frames), otherwise a load from the table.
+// INVARIANT: no wave reads a cache position that this launch writes.  The launch writes positions t0 .. t0+c-1 of a session (in the pages its
+// table row names for them); a wave reads positions < t0 of its own session's pages only and takes keys t0 .. t from the step's qkv rows.  The
+// pages of two sessions of one launch are distinct: a page in two sessions' rows is the host's error, as a slot in two rows is in the kernels
+// above (the pool's allocator never hands a page out twice).
+template <typename T>
+__global__ __launch_bounds__(64 * ST_WAVES) void temporal_ragged_paged_kernel(int n, int F, int S, int D, int heads, int T_total, int n_pages, int lgP, int pps,
+                                                                             const int* __restrict__ t0_rows, const int* __restrict__ page_rows,
+                                                                             const int* __restrict__ first_rows, const int* __restrict__ c_rows,
+                                                                             const int* __restrict__ row_of_frame, const T* __restrict__ qkv,
+                                                                             T* __restrict__ kc, T* __restrict__ vc, T* __restrict__ out) {
+    constexpr int VEC = StreamVec<T>::VEC, LPR = ATT_HD / VEC;
+    const int lane = threadIdx.x & 63, grp = lane / LPR, sub = lane - grp * LPR;
+    const long item = (long)blockIdx.x * ST_WAVES + (threadIdx.x >> 6);
+    if (item >= (long)F * S * heads) return;
+    const int h = (int)(item % heads);
+    const long fs = item / heads;
+    const int s = (int)(fs % S), f = (int)(fs / S);
+    // (f is the same in every lane of the wave: the session's entries stay scalars)
+    const int r = __builtin_amdgcn_readfirstlane(row_of_frame[f]);
+    const bool bad_r = r < 0 || r >= n;             // (a table entry outside the step names no session: nothing of a session is read)
+    const int rr = bad_r ? 0 : r;
+    const int t0 = __builtin_amdgcn_readfirstlane(t0_rows[rr]);
+    const int first = __builtin_amdgcn_readfirstlane(first_rows[rr]);
+    const int c = __builtin_amdgcn_readfirstlane(c_rows[rr]);
+    const int j = f - first;
+    const int col = h * ATT_HD + sub * VEC;
+    const int* pages = page_rows + (size_t)rr * pps;
+    bool bad = bad_r || t0 < 0 || c < 1 || t0 > T_total - c || j < 0 || j >= c || first < 0 || first > F - c;
+    int mine = 0;                                   // entry `lane` of the session's row, kept for PagedKeys::page
+    if (!bad) {
+        // (bad is the same in every lane; 0 <= t0 + j < T_total here, so entries 0 .. (t0 + j) >> lgP are inside the session's table row)
+        bool off = false;
+        for (int q = lane; q <= (t0 + j) >> lgP; q += 64) {
+            const int p = pages[q];
+            off |= p < 0 || p >= n_pages;
+            if (q == lane) mine = p;
+        }
+        bad = __any(off);
+    }
+    if (s == 0 || bad) {
+        // slot 0: zero, as in the pool kernel.  A bad row or page writes NaN to this frame's own output row and touches no page.
+        if (grp == 0) {
+            float z[VEC];
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) z[e] = bad ? __builtin_nanf("") : 0.f;
+            StreamVec<T>::st(out + ((long)f * S + s) * D + col, z);
+        }
+        return;
+    }
+    const size_t run = (size_t)ATT_HD << lgP;       // the P lines of one (token slot, head) of a page
+    const PagedKeys keys{pages, (size_t)(S - 1) * heads * run, ((size_t)(s - 1) * heads + h) * run + sub * VEC, lgP, mine, ((t0 + j) >> lgP) >= 64};
+    const int own = keys.page(t0 + j);              // (every lane, ahead of the branch)
+    if (grp == 0) {
+        // append this frame's key / value: position t0 + j of the session = the frame's own row (bit copies)
+        const T* src = qkv + ((long)f * S + s) * (3L * D) + col;
+        copy16(keys(kc, own, t0 + j), src + D);
+        copy16(keys(vc, own, t0 + j), src + 2 * D);
+    }
+    temporal_query_frame<T>(qkv, kc, vc, out, keys, first, j, t0, S, s, D, col, grp);
 }
 
 // causal_attention == 1 across chunks, for one session and 4 channels: `base` is slot 0 of the session's first frame of this step (these 4
@@ -338,6 +436,36 @@ int tcow_attn_temporal_ragged_fwd(void* stream, const tcow_attn_shape* step, int
     else
         hipLaunchKernelGGL(temporal_ragged_kernel<float>, grid, block, 0, (hipStream_t)stream, n, s.T, s.S, s.D, s.heads, T_total, n_slots, t0_rows, slot_rows,
                            first_rows, c_rows, row_of_frame, (const float*)qkv, (float*)k_cache, (float*)v_cache, (float*)out);
+    TCOW_CHECK_LAUNCH();
+    return TCOW_OK;
+}
+
+int tcow_attn_temporal_ragged_paged_fwd(void* stream, const tcow_attn_shape* step, int n, int T_total, int n_pages, int page_frames, int pages_per_session,
+                                        const int* t0_rows, const int* page_rows, const int* first_rows, const int* c_rows, const int* row_of_frame,
+                                        const void* qkv, void* k_pages, void* v_pages, void* out) {
+    const char* who = "tcow_attn_temporal_ragged_paged_fwd";
+    TCOW_CHECK_ARG(step != nullptr, "%s: null shape", who);
+    const tcow_attn_shape& s = *step;
+    if (const int err = check_temporal_args(who, s, 1, T_total, 1)) return err;                // (pages, not slots: n_pages is checked below)
+    TCOW_CHECK_ARG(s.B == 1 && n > 0 && n <= s.T, "%s: a ragged step is one row of F frames of 1 <= n <= F sessions (B=%d F=%d n=%d)", who, s.B, s.T, n);
+    TCOW_CHECK_ARG(page_frames >= 1 && page_frames <= TCOW_STREAM_MAX_FRAMES && (page_frames & (page_frames - 1)) == 0,
+                   "%s: page_frames=%d must be a power of two in [1, %d]", who, page_frames, TCOW_STREAM_MAX_FRAMES);
+    TCOW_CHECK_ARG(n_pages >= 1, "%s: n_pages=%d must be >= 1", who, n_pages);
+    TCOW_CHECK_ARG(pages_per_session >= 1 && (long)pages_per_session * page_frames >= T_total,
+                   "%s: pages_per_session=%d x page_frames=%d does not cover T_total=%d", who, pages_per_session, page_frames, T_total);
+    TCOW_CHECK_ARG(t0_rows && page_rows && first_rows && c_rows && row_of_frame && qkv && k_pages && v_pages && out, "%s: null pointer", who);
+    int lgP = 0;
+    while ((1 << lgP) < page_frames) ++lgP;
+    const long items = (long)s.T * s.S * s.heads;
+    const dim3 grid((unsigned)cdiv(items, ST_WAVES)), block(64 * ST_WAVES);
+    if (s.dtype == TCOW_BF16)
+        hipLaunchKernelGGL(temporal_ragged_paged_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, n, s.T, s.S, s.D, s.heads, T_total, n_pages, lgP,
+                           pages_per_session, t0_rows, page_rows, first_rows, c_rows, row_of_frame, (const bf16_t*)qkv, (bf16_t*)k_pages, (bf16_t*)v_pages,
+                           (bf16_t*)out);
+    else
+        hipLaunchKernelGGL(temporal_ragged_paged_kernel<float>, grid, block, 0, (hipStream_t)stream, n, s.T, s.S, s.D, s.heads, T_total, n_pages, lgP,
+                           pages_per_session, t0_rows, page_rows, first_rows, c_rows, row_of_frame, (const float*)qkv, (float*)k_pages, (float*)v_pages,
+                           (float*)out);
     TCOW_CHECK_LAUNCH();
     return TCOW_OK;
 }

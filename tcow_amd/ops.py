@@ -367,7 +367,7 @@ def _ragged_tables(who, n, F, t0_rows, slot_rows, first_rows, c_rows, row_of_fra
     """What a host can check of a ragged step's tables: on the device, int32, one entry per session (per frame: row_of_frame)."""
     for name, t, want in (('t0_rows', t0_rows, n), ('slot_rows', slot_rows, n), ('first_rows', first_rows, n), ('c_rows', c_rows, n),
                           ('row_of_frame', row_of_frame, F)):
-        if t is None and name == 'row_of_frame':
+        if t is None and name in ('row_of_frame', 'slot_rows'):         # (cls_ragged has no frame table, the paged attention no slot table)
             continue
         _need_cuda(t)
         if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != want or not t.is_contiguous():
@@ -387,6 +387,25 @@ def attn_temporal_ragged(mode, n, F, S, D, heads, causal, T_total, n_slots, t0_r
     L.check(lib.tcow_attn_temporal_ragged_fwd(_stream(), sh, int(n), int(T_total), int(n_slots), t0_rows.data_ptr(), slot_rows.data_ptr(),
                                               first_rows.data_ptr(), c_rows.data_ptr(), row_of_frame.data_ptr(), qkv.data_ptr(), k_cache.data_ptr(),
                                               v_cache.data_ptr(), out.data_ptr()), 'tcow_attn_temporal_ragged_fwd', lib)
+    return out
+
+
+def attn_temporal_ragged_paged(mode, n, F, S, D, heads, causal, T_total, n_pages, page_frames, t0_rows, page_rows, first_rows, c_rows, row_of_frame, qkv,
+                               k_pages, v_pages, out):
+    """attn_temporal_ragged on a paged cache: k_pages / v_pages [n_pages, S-1, heads, page_frames, 64], and instead of a slot session r brings row r
+    of page_rows (int32 device tensor [n, pages_per_session]): entry q is the page of its frames q * page_frames .. + page_frames - 1.
+    Bit-identical to attn_temporal_ragged on contiguous caches of the same contents (see tcow_attn_temporal_ragged_paged_fwd)."""
+    lib, sh = _stream_attn(mode, 1, F, S, D, heads, causal, qkv, k_pages, v_pages, out, page_rows)
+    _ragged_tables('attn_temporal_ragged_paged', n, F, t0_rows, None, first_rows, c_rows, row_of_frame)
+    if page_rows.dtype != torch.int32 or page_rows.dim() != 2 or page_rows.shape[0] != n or page_rows.shape[1] < 1 or not page_rows.is_contiguous():
+        raise L.TcowError(f'attn_temporal_ragged_paged: page_rows must be a contiguous int32 tensor of n = {n} rows of pages_per_session entries, got '
+                          f'{page_rows.dtype} {tuple(page_rows.shape)}')
+    if qkv.shape[0] != F * S or out.shape[0] != F * S:
+        raise L.TcowError(f'attn_temporal_ragged_paged: qkv / out must have F * S = {F * S} rows, got {qkv.shape[0]} / {out.shape[0]}')
+    L.check(lib.tcow_attn_temporal_ragged_paged_fwd(_stream(), sh, int(n), int(T_total), int(n_pages), int(page_frames), int(page_rows.shape[1]),
+                                                    t0_rows.data_ptr(), page_rows.data_ptr(), first_rows.data_ptr(), c_rows.data_ptr(),
+                                                    row_of_frame.data_ptr(), qkv.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), out.data_ptr()),
+            'tcow_attn_temporal_ragged_paged_fwd', lib)
     return out
 
 

@@ -251,11 +251,14 @@ class QueryMaskTracker(nn.Module):
         from .stream import SeekerStream
         return SeekerStream(self, batch_size, queries_per_clip, graph, skinny_gemm)
 
-    def stream_pool(self, capacity, skinny_gemm=None):
+    def stream_pool(self, capacity, skinny_gemm=None, page_frames=None, pages=None):
         """Streaming inference for up to `capacity` live sessions that started at different moments: a SeekerStreamPool whose step(ids, rgb,
-        query_mask) advances any subset of the open sessions, each at its own frame, in one Seeker step (tcow_amd/stream.py)."""
+        query_mask) advances any subset of the open sessions, each at its own frame, in one Seeker step (tcow_amd/stream.py).
+        page_frames=P (a power of two): a paged pool -- the K / V caches are `pages` pages of P frames (default capacity * ceil(T / P), which cannot
+        run out; lower it to the memory budget), a session holds only the pages its frames so far have filled and close() / reset() return them;
+        a step that would need more pages than are free raises TcowError and moves nothing.  Same outputs, bit for bit.  None: one full cache per slot."""
         from .stream import SeekerStreamPool
-        return SeekerStreamPool(self, capacity, skinny_gemm)
+        return SeekerStreamPool(self, capacity, skinny_gemm, page_frames, pages)
 
     def param_list(self):
         """Fixed order of the parameters the autograd.Function sees.  Cached: walking ~250 module attributes costs 0.4 ms per call.  .to() /
@@ -333,6 +336,6 @@ class Seeker(nn.Module):
         """See QueryMaskTracker.stream."""
         return self.seeker.stream(batch_size, queries_per_clip, graph, skinny_gemm)
 
-    def stream_pool(self, capacity, skinny_gemm=None):
+    def stream_pool(self, capacity, skinny_gemm=None, page_frames=None, pages=None):
         """See QueryMaskTracker.stream_pool."""
-        return self.seeker.stream_pool(capacity, skinny_gemm)
+        return self.seeker.stream_pool(capacity, skinny_gemm, page_frames, pages)

@@ -15,7 +15,7 @@ that is 332 MB per row in the 16-bit modes; at configs[3] (T = 60, 480x640) 2.65
 What belongs to one step is a _Step, and it is all run_forward sees (its `stream` argument): pos, time_rows [B*T, D] (one row of the time table
 per (row, frame) of the step), attn_temporal(i, ...) and cls_row(i, ...) for block i, and skinny: whether the step's GEMMs take the
 skinny-M entry points where ops.skinny_plan (16-bit modes) / ops.skinny_plan_x3 (bf16x3) route them (the skinny_gemm keyword of net.stream /
-net.stream_pool).  There are three forms, each a _Step subclass that holds
+net.stream_pool).  There are three forms (a fourth for paged pools, below), each a _Step subclass that holds
 its device tables and calls its own pair of ops entry points; step(), pool.step() and pool.step_ragged() each build the tables and construct
 their form, and nothing else asks which form a step has:
 
@@ -27,6 +27,21 @@ their form, and nothing else asks which form a step has:
   session that catches up while its neighbours advance by one).  The F = sum of the c_i frames lie flat in session order and run as ONE row
   of F frames; ragged_tables() gives every session its t0, slot, first flat frame and chunk length and every frame its session
   (tcow_attn_temporal_ragged_fwd, one wave per frame, not per session, and tcow_cls_ragged).
+
+A paged pool (net.stream_pool(capacity, page_frames=P, pages=N)): a contiguous pool reserves a whole stream's cache per slot, whether its session
+is at frame 2, at frame 59 or closed.  With page_frames the K / V caches of a block are a heap of N pages of P frames (_PagedState:
+[N, S-1, heads, P, 64], a page id valid in every block alike), a session owns only the pages its frames so far have filled (PageAllocator: host
+side, lowest free page first, grows when t0 + c crosses a multiple of P), and close() / reset() give them back; the cls rows stay per slot.  The
+pool is then sized in memory (pages), and `capacity` only bounds the number of open sessions.  pages defaults to capacity * ceil(T / P), which
+cannot run out; with fewer, a step that needs more pages than are free raises TcowError before anything is launched or any counter or page
+moves.  Both step() and step_ragged() of a paged pool run a fourth form:
+
+  _PagedRaggedStep: the _RaggedStep tables plus page_rows [n, ceil(T / P)], the sessions' pages in frame order, sent in the same host-to-device
+  copy (tcow_attn_temporal_ragged_paged_fwd: the ragged kernel with "page page_rows[r][kt / P], line kt % P" for "slot, line kt"; tcow_cls_ragged).
+
+Where a key lives does not enter the arithmetic, so a paged pool gives the bits of the contiguous pool.  A one-frame step costs between nothing measurable
+and 0.13 ms more than on the contiguous pool (profiles/stream_paged_latency.json; P = 8 is the recommendation, P = 1 the
+dearest): the keywords are off by default.  SeekerStream stays contiguous.
 
 graph=True (SeekerStream): the first step of each chunk length c runs eagerly and captures the step as a torch.cuda.CUDAGraph; later steps copy
 their inputs into the graph's static buffers, write t0 and the time rows (the stream keeps one _StreamStep with static time rows per chunk
@@ -40,6 +55,8 @@ import torch
 
 from . import engine, ops
 from ._lib import TcowError
+
+MAX_FRAMES = 1024       # TCOW_STREAM_MAX_FRAMES of include/tcow_hip.h
 
 # Default of the skinny_gemm keyword.  True: measured (profiles/stream_skinny_latency.json) -- a one-frame bf16 step takes
 # 1.42 ms instead of 2.41 at configs[1] B = 1, 2.41 instead of 3.35 at configs[3] B = 1 and 2.60 instead of 3.24 at configs[1] B = 8, on / off
@@ -59,13 +76,16 @@ class _State:
     """What lives as long as a stream or a pool of `rows` query rows: per block the K / V caches [rows, S-1, heads, T, 64] in the mode's storage
     type and one f32 cls row per query row, and the effective pos table and time table [T, D]."""
 
+    def _kv_shape(self, depth, rows, g):
+        return (depth, rows, g['S'] - 1, g['heads'], self.T_total, 64)
+
     def __init__(self, module, rows, skinny=False):
         self.skinny = bool(skinny)                              # every step built on this state carries it (_Step.skinny)
         g = module.geometry(rows)
         dev = module.vit.pos_embed.device
         cdt = ops.tdtype(module.mode)                           # (bf16x3 stores f32, like fp32)
         self.T_total, self.n_slots, self.D = module.num_total_frames, rows, g['D']
-        shape = (module.network_depth, rows, g['S'] - 1, g['heads'], self.T_total, 64)
+        shape = self._kv_shape(module.network_depth, rows, g)
         self.k_cache = torch.empty(shape, dtype=cdt, device=dev)
         self.v_cache = torch.empty(shape, dtype=cdt, device=dev)
         self.cls_cache = torch.empty(module.network_depth, rows, g['D'], dtype=torch.float32, device=dev)
@@ -75,6 +95,20 @@ class _State:
     @property
     def nbytes(self):
         return sum(t.numel() * t.element_size() for t in (self.k_cache, self.v_cache, self.cls_cache))
+
+
+class _PagedState(_State):
+    """The state of a paged pool: per block the K / V caches are a heap of n_pages pages of P frames, [n_pages, S-1, heads, P, 64], of which a
+    session owns those its frames so far have filled (PageAllocator; a page id is valid in every block's arrays alike); the cls rows stay one per
+    slot [rows, D], and `rows` = capacity only bounds the number of open sessions.  A session's row of the page table has pps = ceil(T / P) entries."""
+
+    def __init__(self, module, rows, skinny, page_frames, n_pages):
+        self.P, self.n_pages = page_frames, n_pages
+        self.pps = -(-module.num_total_frames // page_frames)
+        super().__init__(module, rows, skinny)
+
+    def _kv_shape(self, depth, rows, g):
+        return (depth, self.n_pages, g['S'] - 1, g['heads'], self.P, 64)
 
 
 class _Step:
@@ -120,6 +154,17 @@ class _RaggedStep(_Step):
 
     def cls_row(self, i, R2, B, T, S):
         ops.cls_ragged(R2, self.tables[0].numel(), T, S, self.state.cls_cache[i], self.state.n_slots, *self.tables[:4])
+
+
+class _PagedRaggedStep(_RaggedStep):
+    """A ragged step on a _PagedState.  tables: those of _RaggedStep (the slot still names the session's cls row) and page_rows (device int32
+    [n, pps]): the pages of every session in frame order, -1 where it owns none yet (the kernel reads only the entries of frames <= t)."""
+
+    def attn_temporal(self, i, amode, B, T, S, D, heads, ca, QKV, O):
+        st = self.state
+        t0_rows, _, first_rows, c_rows, row_of_frame, page_rows = self.tables
+        ops.attn_temporal_ragged_paged(amode, t0_rows.numel(), T, S, D, heads, ca, st.T_total, st.n_pages, st.P, t0_rows, page_rows, first_rows, c_rows,
+                                       row_of_frame, QKV, st.k_cache[i], st.v_cache[i], O)
 
 
 def check_streamable(module):
@@ -212,6 +257,63 @@ def check_range(who, ids, t0s, cs, T):
         if t0 + c > T:
             raise TcowError(f'{who}: session {sid}: frames {t0}..{t0 + c - 1} run past the last frame {T - 1} of the stream '
                             f'(num_total_frames = {T}); reset() or close() it')
+
+
+def page_plan(capacity, T, page_frames, pages):
+    """The page_frames / pages keywords of stream_pool for a pool of `capacity` sessions of T frames -> (P, n_pages), or (None, None) for the
+    contiguous pool (page_frames None).  P must be a power of two in 1 .. TCOW_STREAM_MAX_FRAMES; pages defaults to capacity * ceil(T / P), with
+    which no step can run out of pages."""
+    if page_frames is None:
+        if pages is not None:
+            raise TcowError(f'stream_pool: pages ({pages}) given without page_frames: only a paged pool is sized in pages')
+        return None, None
+    P = int(page_frames)
+    if P != page_frames or P < 1 or P > MAX_FRAMES or P & (P - 1):
+        raise TcowError(f'stream_pool: page_frames ({page_frames}) must be a power of two in 1 .. {MAX_FRAMES}')
+    n_pages = capacity * -(-T // P) if pages is None else int(pages)
+    if n_pages < 1 or (pages is not None and n_pages != pages):
+        raise TcowError(f'stream_pool: pages ({pages}) must be an integer >= 1')
+    return P, n_pages
+
+
+class PageAllocator:
+    """Which pages of a paged pool each session owns: plain Python, no device.  Pages 0 .. n_pages-1 hold P frames each; a session that has
+    `frames` frames owns ceil(frames / P) pages, in frame order (entry q holds its frames q*P .. q*P+P-1).  Deterministic: grow() hands out the
+    lowest free page first, session by session in the order given, as open() takes the lowest free slot."""
+
+    def __init__(self, n_pages, page_frames):
+        self.n_pages, self.P = int(n_pages), int(page_frames)
+        self._free = list(range(self.n_pages))                  # ascending
+        self._pages = {}                                        # session -> its pages in frame order
+
+    @property
+    def free(self):
+        return len(self._free)
+
+    def pages_of(self, sid):
+        return tuple(self._pages.get(sid, ()))
+
+    def missing(self, sid, frames):
+        """Pages the session lacks to hold `frames` frames: more than 0 only when the frames cross a page boundary."""
+        return max(0, -(-int(frames) // self.P) - len(self._pages.get(sid, ())))
+
+    def grow(self, sids, frames):
+        """Every session sids[k] gets the pages it lacks to hold frames[k] frames.  All or nothing: if the free pages do not cover the sum, raises
+        TcowError (pages needed and free named) and nothing has moved.  Returns each session's pages."""
+        need = sum(self.missing(sid, f) for sid, f in zip(sids, frames))
+        if need > len(self._free):
+            raise TcowError(f'stream_pool: out of pages: this step needs {need} more page(s) of {self.P} frame(s), {len(self._free)} of '
+                            f'{self.n_pages} are free; close() or reset() a session, or open the pool with more pages')
+        for sid, f in zip(sids, frames):
+            k = self.missing(sid, f)
+            if k:
+                self._pages.setdefault(sid, []).extend(self._free[:k])
+                del self._free[:k]
+        return [self.pages_of(sid) for sid in sids]
+
+    def release(self, sid):
+        """The session's pages are free again (a session without pages: nothing happens)."""
+        self._free = sorted(self._free + self._pages.pop(sid, []))
 
 
 def _zero_mask(rows, rgb):
@@ -318,21 +420,27 @@ class SeekerStream:
 
 
 class SeekerStreamPool:
-    """net.stream_pool(capacity, skinny_gemm) of Seeker / QueryMaskTracker: up to `capacity` live sessions (one clip and one query mask each) that stand at
-    different frames, stepped together; see the module docstring.  open() -> id, step(ids, rgb, query_mask) (one chunk length for all) or
-    step_ragged(ids, rgbs, query_masks) (a chunk length per session), close(id)."""
+    """net.stream_pool(capacity, skinny_gemm, page_frames, pages) of Seeker / QueryMaskTracker: up to `capacity` live sessions (one clip and one query
+    mask each) that stand at different frames, stepped together; see the module docstring.  open() -> id, step(ids, rgb, query_mask) (one chunk
+    length for all) or step_ragged(ids, rgbs, query_masks) (a chunk length per session), close(id).  page_frames=P: a paged pool, whose K / V
+    memory is `pages` pages of P frames shared by the sessions (pages_total, pages_free, pages_of(id)); its outputs are bit-identical to the
+    contiguous pool's."""
 
-    def __init__(self, module, capacity, skinny_gemm=None):
+    def __init__(self, module, capacity, skinny_gemm=None, page_frames=None, pages=None):
         module = getattr(module, 'seeker', module)
         capacity = int(capacity)
         if capacity < 1:
             raise TcowError(f'stream_pool: capacity ({capacity}) must be >= 1')
+        self.page_frames, n_pages = page_plan(capacity, module.num_total_frames, page_frames, pages)
         check_streamable(module)
         self.module = module
         self.capacity = capacity
         self.T = module.num_total_frames
         self.skinny_gemm = _skinny_default(module) if skinny_gemm is None else bool(skinny_gemm)
-        self._st = _State(module, capacity, self.skinny_gemm)
+        if self.page_frames is None:
+            self._st, self._alloc = _State(module, capacity, self.skinny_gemm), None
+        else:
+            self._st, self._alloc = _PagedState(module, capacity, self.skinny_gemm, self.page_frames, n_pages), PageAllocator(n_pages, self.page_frames)
         self.device = self._st.pos.device
         self._sig = _signature(module)
         self._slot = {}                 # open session id -> cache slot
@@ -341,8 +449,27 @@ class SeekerStreamPool:
 
     @property
     def cache_bytes(self):
-        """Device bytes of the K / V caches and the cls rows of all `capacity` slots."""
+        """Device bytes of the K / V caches and the cls rows of all `capacity` slots (a paged pool: of all its pages and the cls rows)."""
         return self._st.nbytes
+
+    def _paged(self):
+        if self._alloc is None:
+            raise TcowError('stream_pool: this pool is contiguous (opened without page_frames): it has no pages')
+        return self._alloc
+
+    @property
+    def pages_total(self):
+        """Pages of a paged pool."""
+        return self._paged().n_pages
+
+    @property
+    def pages_free(self):
+        """Pages of a paged pool that no session owns."""
+        return self._paged().free
+
+    def pages_of(self, sid):
+        """The pages the session owns, in frame order: ceil(frames it was stepped to / page_frames) of them."""
+        return self._paged().pages_of(self._known(sid))
 
     def _known(self, sid):
         if sid not in self._slot:
@@ -361,16 +488,20 @@ class SeekerStreamPool:
         return sid
 
     def close(self, sid):
-        """End the session; its slot is free for the next open()."""
+        """End the session; its slot is free for the next open() (and in a paged pool its pages for any session)."""
         self._known(sid)
         del self._slot[sid], self._done[sid]
+        if self._alloc is not None:
+            self._alloc.release(sid)
 
     def frames_done(self, sid):
         return self._done[self._known(sid)]
 
     def reset(self, sid):
-        """Put the session back at frame 0 (it keeps its slot)."""
+        """Put the session back at frame 0 (it keeps its slot; in a paged pool it gives its pages back)."""
         self._done[self._known(sid)] = 0
+        if self._alloc is not None:
+            self._alloc.release(sid)
 
     def _checked(self, who, ids, rgbs, qms, per):
         """Every check of a step (`who`), before anything is launched or any counter moves.  rgbs / qms: one tensor of all sessions, or (per) a list
@@ -384,6 +515,9 @@ class SeekerStreamPool:
             cs = [_check_inputs(who, m, self.device, len(ids), len(ids), rgbs, qms)] * len(ids)
         t0s = [self._done[sid] for sid in ids]
         check_range(who, ids, t0s, cs, self.T)
+        if self._alloc is not None:
+            # the last check, and the only thing of a refused step that could have moved: the pages of frames up to t0 + c_i - 1 (all or nothing)
+            self._alloc.grow(ids, [t0 + c for t0, c in zip(t0s, cs)])
         return ids, t0s, cs
 
     def _run(self, step, ids, cs, rgb, qm):
@@ -399,6 +533,8 @@ class SeekerStreamPool:
         frames of each -> (mask logits (n, Co, c, H, W) f32, flags (n, c, F) or None) in the order of `ids`, owned by the caller.  Every check
         runs before anything is launched: a refused step leaves every session where it was."""
         ids, t0s, cs = self._checked('stream_pool.step', ids, rgb, query_mask, False)
+        if self._alloc is not None:
+            return self._step_paged(ids, t0s, cs, rgb, query_mask)
         st, c = self._st, cs[0]
         with torch.no_grad(), torch.cuda.device(self.device):
             t0_rows = torch.tensor(t0s, dtype=torch.int32, device=self.device)
@@ -406,6 +542,36 @@ class SeekerStreamPool:
             frames = (t0_rows[:, None] + torch.arange(c, dtype=torch.int32, device=self.device)[None, :]).reshape(-1)
             step = _PoolStep(st, st.time.index_select(0, frames), t0_rows, slot_rows)         # [n*c, D]: row r*c + j = time row t0_rows[r] + j
             return self._run(step, ids, cs, rgb.to(torch.float32).contiguous(), None if query_mask is None else query_mask.to(torch.float32).contiguous())
+
+    def _ragged_form(self, ids, t0s, cs):
+        """The step object of a ragged step (inside no_grad on the pool's device) and every session's first flat frame.  A paged pool sends the
+        sessions' page rows in the same host-to-device copy as the other tables."""
+        n, st = len(ids), self._st
+        tab = ragged_tables(t0s, [self._slot[sid] for sid in ids], cs)
+        F = len(tab['frames'])
+        # all tables in one host-to-device copy: [t0 | slot | first | c] per session, [row_of_frame | frames] per flat frame, [pages] per session
+        flat = tab['t0'] + tab['slot'] + tab['first'] + tab['c'] + tab['row_of_frame'] + tab['frames']
+        if self._alloc is not None:
+            for sid in ids:
+                own = self._alloc.pages_of(sid)
+                flat += list(own) + [-1] * (st.pps - len(own))
+        dev = torch.tensor(flat, dtype=torch.int32).to(self.device)
+        time_rows = st.time.index_select(0, dev[4 * n + F:4 * n + 2 * F])               # [F, D]: flat frame f = time row t0 + j of its session
+        tables = (dev[0:n], dev[n:2 * n], dev[2 * n:3 * n], dev[3 * n:4 * n], dev[4 * n:4 * n + F])
+        if self._alloc is None:
+            return _RaggedStep(st, time_rows, *tables), tab['first']
+        return _PagedRaggedStep(st, time_rows, *tables, dev[4 * n + 2 * F:].view(n, st.pps)), tab['first']
+
+    def _step_paged(self, ids, t0s, cs, rgb, query_mask):
+        """step() of a paged pool: the ragged form with equal chunk lengths (bit-equal to the pool form), in and out in step()'s shapes."""
+        n, c = len(ids), cs[0]
+        # (n, C, c, H, W) -> (1, C, n*c, H, W): the frames flat in session order
+        flat = lambda x: x.to(torch.float32).transpose(0, 1).reshape(1, x.shape[1], n * c, *x.shape[3:]).contiguous()
+        with torch.no_grad(), torch.cuda.device(self.device):
+            step, _ = self._ragged_form(ids, t0s, cs)
+            out_mask, flags = self._run(step, ids, cs, flat(rgb), None if query_mask is None else flat(query_mask))
+            out_mask = out_mask.view(out_mask.shape[1], n, c, *out_mask.shape[3:]).transpose(0, 1).contiguous()
+        return out_mask, (None if flags is None else flags.reshape(n, c, -1))
 
     def step_ragged(self, ids, rgbs, query_masks=None):
         """ids: n distinct open sessions, at any phases; rgbs: n tensors (1, 3, c_i, H, W), the next c_i >= 1 frames of each session (the c_i need
@@ -416,22 +582,17 @@ class SeekerStreamPool:
         rgbs = list(rgbs)
         qms = None if query_masks is None else list(query_masks)
         ids, t0s, cs = self._checked('stream_pool.step_ragged', ids, rgbs, qms, True)
-        n, st = len(ids), self._st
-        tab = ragged_tables(t0s, [self._slot[sid] for sid in ids], cs)
-        F = len(tab['frames'])
+        n = len(ids)
         with torch.no_grad(), torch.cuda.device(self.device):
-            # all six tables in one host-to-device copy: [t0 | slot | first | c] per session, [row_of_frame | frames] per flat frame
-            dev = torch.tensor(tab['t0'] + tab['slot'] + tab['first'] + tab['c'] + tab['row_of_frame'] + tab['frames'], dtype=torch.int32).to(self.device)
-            step = _RaggedStep(st, st.time.index_select(0, dev[4 * n + F:]),              # [F, D]: flat frame f = time row t0 + j of its session
-                               dev[0:n], dev[n:2 * n], dev[2 * n:3 * n], dev[3 * n:4 * n], dev[4 * n:4 * n + F])
+            step, first = self._ragged_form(ids, t0s, cs)
             rgb32 = rgbs[0].to(torch.float32).contiguous() if n == 1 else torch.cat([r.to(torch.float32) for r in rgbs], 2)
             if qms is not None and all(q is not None for q in qms):
                 qm32 = qms[0].to(torch.float32).contiguous() if n == 1 else torch.cat([q.to(torch.float32) for q in qms], 2)
             else:
                 qm32 = _zero_mask(1, rgb32)
-                for q, f0, c in zip(qms or (), tab['first'], cs):
+                for q, f0, c in zip(qms or (), first, cs):
                     if q is not None:
                         qm32[:, :, f0:f0 + c] = q
             out_mask, flags = self._run(step, ids, cs, rgb32, qm32)
-        masks = [out_mask[:, :, f0:f0 + c] for f0, c in zip(tab['first'], cs)]
-        return masks, (None if flags is None else [flags[:, f0:f0 + c] for f0, c in zip(tab['first'], cs)])
+        masks = [out_mask[:, :, f0:f0 + c] for f0, c in zip(first, cs)]
+        return masks, (None if flags is None else [flags[:, f0:f0 + c] for f0, c in zip(first, cs)])

@@ -109,49 +109,43 @@ long tcow_gemm_nt_skinny_workspace_bytes(int M, int N, int split) {
     return (long)split * M * N * 4;
 }
 
-int tcow_gemm_nt_skinny(void* stream, const tcow_gemm_args* a, int split, void* workspace, long workspace_bytes) {
-    TCOW_CHECK_ARG(a != nullptr, "tcow_gemm_nt_skinny: null args");
-    TCOW_CHECK_ARG(a->dtype == TCOW_BF16, "tcow_gemm_nt_skinny: dtype %d is not served (the 16-bit mode only; TCOW_F32 and TCOW_F32X3 go to tcow_gemm_nt)", a->dtype);
-    TCOW_CHECK_ARG(a->M > 0 && a->N > 0 && a->K > 0, "tcow_gemm_nt_skinny: bad shape M=%d N=%d K=%d", a->M, a->N, a->K);
-    TCOW_CHECK_ARG(a->A && a->W && a->C, "tcow_gemm_nt_skinny: null operand");
-    TCOW_CHECK_ARG((a->act != TCOW_ACT_DGELU && a->act != TCOW_ACT_GELU_DSAVE && a->act != TCOW_ACT_MUL_AUX) || a->aux, "tcow_gemm_nt_skinny: this activation needs aux");
-    TCOW_CHECK_ARG(a->act >= TCOW_ACT_NONE && a->act <= TCOW_ACT_MUL_AUX, "tcow_gemm_nt_skinny: unknown activation %d", a->act);
-    TCOW_CHECK_ARG(a->bias2 || !a->row_scale2, "tcow_gemm_nt_skinny: row_scale2 without bias2");
-    TCOW_CHECK_ARG(a->K % 64 == 0, "tcow_gemm_nt_skinny: K=%d must be a multiple of 64", a->K);
-    TCOW_CHECK_ARG(a->lda % 8 == 0 && a->ldw % 8 == 0, "tcow_gemm_nt_skinny: lda/ldw must be multiples of 8 elements");
-    TCOW_CHECK_ARG(a->ldc % 4 == 0 && a->N % 4 == 0, "tcow_gemm_nt_skinny: N and ldc must be multiples of 4");
-    TCOW_CHECK_ARG((!a->resid || a->ldr % 4 == 0) && (!a->aux || a->ldaux % 4 == 0), "tcow_gemm_nt_skinny: ldr / ldaux must be multiples of 4");
-    TCOW_CHECK_ARG(split >= 1 && split <= 16, "tcow_gemm_nt_skinny: split=%d must be 1 .. 16", split);
-    TCOW_CHECK_ARG(split <= a->K / 64, "tcow_gemm_nt_skinny: split=%d exceeds the K/64 = %d k-slices of K=%d", split, a->K / 64, a->K);
+// What both entry points ask of a call, in one place; the dtype, the operand pitches and alignment are each entry point's own.
+static int check_skinny_args(const char* who, const tcow_gemm_args* a, int split, void* ws, long ws_bytes) {
+    TCOW_CHECK_ARG(a != nullptr, "%s: null args", who);
+    TCOW_CHECK_ARG(a->M > 0 && a->N > 0 && a->K > 0, "%s: bad shape M=%d N=%d K=%d", who, a->M, a->N, a->K);
+    TCOW_CHECK_ARG(a->A && a->W && a->C, "%s: null operand", who);
+    TCOW_CHECK_ARG((a->act != TCOW_ACT_DGELU && a->act != TCOW_ACT_GELU_DSAVE && a->act != TCOW_ACT_MUL_AUX) || a->aux, "%s: this activation needs aux", who);
+    TCOW_CHECK_ARG(a->act >= TCOW_ACT_NONE && a->act <= TCOW_ACT_MUL_AUX, "%s: unknown activation %d", who, a->act);
+    TCOW_CHECK_ARG(a->bias2 || !a->row_scale2, "%s: row_scale2 without bias2", who);
+    TCOW_CHECK_ARG(a->K % 64 == 0, "%s: K=%d must be a multiple of 64", who, a->K);
+    TCOW_CHECK_ARG(a->ldc % 4 == 0 && a->N % 4 == 0, "%s: N and ldc must be multiples of 4 (N=%d ldc=%ld)", who, a->N, a->ldc);
+    TCOW_CHECK_ARG((!a->resid || a->ldr % 4 == 0) && (!a->aux || a->ldaux % 4 == 0), "%s: ldr / ldaux must be multiples of 4", who);
+    TCOW_CHECK_ARG(split >= 1 && split <= 16, "%s: split=%d must be 1 .. 16", who, split);
+    TCOW_CHECK_ARG(split <= a->K / 64, "%s: split=%d exceeds the K/64 = %d k-slices of K=%d", who, split, a->K / 64, a->K);
     const long need = tcow_gemm_nt_skinny_workspace_bytes(a->M, a->N, split);
-    TCOW_CHECK_ARG(need == 0 || workspace != nullptr, "tcow_gemm_nt_skinny: workspace is NULL (split=%d needs %ld bytes)", split, need);
-    TCOW_CHECK_ARG(workspace_bytes >= need, "tcow_gemm_nt_skinny: workspace too small (workspace_bytes %ld < %ld)", workspace_bytes, need);
-    TCOW_CHECK_ARG(need == 0 || ((uintptr_t)workspace & 15) == 0, "tcow_gemm_nt_skinny: workspace must be 16-byte aligned");
-    return tcow_gemm_nt_skinny_bf16((hipStream_t)stream, a, split, (float*)workspace);
+    TCOW_CHECK_ARG(need == 0 || ws != nullptr, "%s: workspace is NULL (split=%d needs %ld bytes)", who, split, need);
+    TCOW_CHECK_ARG(ws_bytes >= need, "%s: workspace too small (workspace_bytes %ld < %ld)", who, ws_bytes, need);
+    TCOW_CHECK_ARG(need == 0 || ((uintptr_t)ws & 15) == 0, "%s: workspace must be 16-byte aligned", who);
+    return TCOW_OK;
+}
+
+// (a wrong dtype is reported before anything else about the arguments, as it always was; a null `a` is check_skinny_args's to refuse)
+int tcow_gemm_nt_skinny(void* stream, const tcow_gemm_args* a, int split, void* workspace, long workspace_bytes) {
+    TCOW_CHECK_ARG(!a || a->dtype == TCOW_BF16, "tcow_gemm_nt_skinny: dtype %d is not served (the 16-bit mode only; TCOW_F32 and TCOW_F32X3 go to tcow_gemm_nt)", a->dtype);
+    if (const int rc = check_skinny_args("tcow_gemm_nt_skinny", a, split, workspace, workspace_bytes)) return rc;
+    TCOW_CHECK_ARG(a->lda % 8 == 0 && a->ldw % 8 == 0, "tcow_gemm_nt_skinny: lda/ldw must be multiples of 8 elements");
+    return tcow_gemm_nt_skinny_launch_bf16((hipStream_t)stream, a, split, (float*)workspace);
 }
 
 // ---- the same for the bf16 x 3 arithmetic on f32 operands (gemm_nt_skinny_x3.hip); exact f32 has no skinny kernel
 int tcow_gemm_nt_skinny_x3(void* stream, const tcow_gemm_args* a, int split, void* workspace, long workspace_bytes) {
-    TCOW_CHECK_ARG(a != nullptr, "tcow_gemm_nt_skinny_x3: null args");
-    TCOW_CHECK_ARG(a->dtype == TCOW_F32X3, "tcow_gemm_nt_skinny_x3: dtype %d is not served (TCOW_F32X3 only; TCOW_BF16 goes to tcow_gemm_nt_skinny, TCOW_F32 to tcow_gemm_nt)", a->dtype);
-    TCOW_CHECK_ARG(a->M > 0 && a->N > 0 && a->K > 0, "tcow_gemm_nt_skinny_x3: bad shape M=%d N=%d K=%d", a->M, a->N, a->K);
-    TCOW_CHECK_ARG(a->A && a->W && a->C, "tcow_gemm_nt_skinny_x3: null operand");
-    TCOW_CHECK_ARG((a->act != TCOW_ACT_DGELU && a->act != TCOW_ACT_GELU_DSAVE && a->act != TCOW_ACT_MUL_AUX) || a->aux, "tcow_gemm_nt_skinny_x3: this activation needs aux");
-    TCOW_CHECK_ARG(a->act >= TCOW_ACT_NONE && a->act <= TCOW_ACT_MUL_AUX, "tcow_gemm_nt_skinny_x3: unknown activation %d", a->act);
-    TCOW_CHECK_ARG(a->bias2 || !a->row_scale2, "tcow_gemm_nt_skinny_x3: row_scale2 without bias2");
-    TCOW_CHECK_ARG(a->K % 64 == 0, "tcow_gemm_nt_skinny_x3: K=%d must be a multiple of 64", a->K);
+    TCOW_CHECK_ARG(!a || a->dtype == TCOW_F32X3, "tcow_gemm_nt_skinny_x3: dtype %d is not served (TCOW_F32X3 only; TCOW_BF16 goes to tcow_gemm_nt_skinny, TCOW_F32 to tcow_gemm_nt)", a->dtype);
+    if (const int rc = check_skinny_args("tcow_gemm_nt_skinny_x3", a, split, workspace, workspace_bytes)) return rc;
     TCOW_CHECK_ARG(a->lda >= a->K && a->ldw >= a->K && a->lda % 4 == 0 && a->ldw % 4 == 0, "tcow_gemm_nt_skinny_x3: lda/ldw must be multiples of 4 elements and at least K");
-    TCOW_CHECK_ARG(a->ldc >= a->N && a->ldc % 4 == 0 && a->N % 4 == 0, "tcow_gemm_nt_skinny_x3: N and ldc must be multiples of 4 (N=%d ldc=%ld)", a->N, a->ldc);
-    TCOW_CHECK_ARG((!a->resid || a->ldr % 4 == 0) && (!a->aux || a->ldaux % 4 == 0), "tcow_gemm_nt_skinny_x3: ldr / ldaux must be multiples of 4");
+    TCOW_CHECK_ARG(a->ldc >= a->N, "tcow_gemm_nt_skinny_x3: ldc=%ld must be at least N=%d", a->ldc, a->N);
     TCOW_CHECK_ARG((((uintptr_t)a->A | (uintptr_t)a->W | (uintptr_t)a->C | (uintptr_t)a->bias | (uintptr_t)a->resid | (uintptr_t)a->aux | (uintptr_t)a->bias2) & 15) == 0,
                    "tcow_gemm_nt_skinny_x3: A, W, C, bias, resid, aux and bias2 must be 16-byte aligned");
-    TCOW_CHECK_ARG(split >= 1 && split <= 16, "tcow_gemm_nt_skinny_x3: split=%d must be 1 .. 16", split);
-    TCOW_CHECK_ARG(split <= a->K / 64, "tcow_gemm_nt_skinny_x3: split=%d exceeds the K/64 = %d k-slices of K=%d", split, a->K / 64, a->K);
-    const long need = tcow_gemm_nt_skinny_workspace_bytes(a->M, a->N, split);
-    TCOW_CHECK_ARG(need == 0 || workspace != nullptr, "tcow_gemm_nt_skinny_x3: workspace is NULL (split=%d needs %ld bytes)", split, need);
-    TCOW_CHECK_ARG(workspace_bytes >= need, "tcow_gemm_nt_skinny_x3: workspace too small (workspace_bytes %ld < %ld)", workspace_bytes, need);
-    TCOW_CHECK_ARG(need == 0 || ((uintptr_t)workspace & 15) == 0, "tcow_gemm_nt_skinny_x3: workspace must be 16-byte aligned");
-    return tcow_gemm_nt_skinny_x3_launch((hipStream_t)stream, a, split, (float*)workspace);
+    return tcow_gemm_nt_skinny_launch_x3((hipStream_t)stream, a, split, (float*)workspace);
 }
 
 static const int kColsumParts = 64 * 24 * 2;   // >= nz * tiles_k * 2 partial rows of the fused bias gradient (nz <= 64, K <= 3072)

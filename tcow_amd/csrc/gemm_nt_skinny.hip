@@ -2,29 +2,23 @@
 // gemm_bf16.hip starts 18 ... 72 workgroups on 256 CUs and the launch takes one workgroup's serial walk over K.
 //
 //   gemm_nt_skinny_kernel         64 x 64 output tile, 4 waves as 2 x 2 with one 32 x 32 accumulator each, K in 64-element slices through a ring of
-//                                 LDS stages (16 KiB each) filled by direct-to-LDS loads.  A workgroup is (tile, slice s of S): it walks the k-slices
-//                                 [s nk / S, (s + 1) nk / S).  S == 1: the shared epilogue (epi_rows<EpiAny>).  S > 1: the raw f32 partial goes to slab
-//                                 s of the workspace [S, M, N].
-//   gemm_nt_skinny_reduce_kernel  S > 1 only, a second launch: v = slab[0]; v += slab[1]; ... in slice order, then epi_row_apply<EpiAny>.
+//                                 LDS stages (16 KiB each) filled by direct-to-LDS loads.  The work items, the split over K, its slabs and the
+//                                 reduce launch are those of gemm_nt_skinny.h.  S == 1: the shared epilogue (epi_rows<EpiAny>); the reduce of
+//                                 S > 1: epi_row_apply<EpiAny>.
 //
 // The arithmetic of an output element is that of gemm_nt_bf16_kernel: the same MFMA, the same k elements per lane half (chunk c = 2 ks + hi), K ascending.
-// S == 1 therefore gives the 128 tile's bits; S > 1 is a fixed function of the inputs (no atomics, no arrival order).
-// The kernel boundary makes the slabs visible: workgroups do not communicate inside a launch.
-#include "common.h"
-#include "internal.h"
+// S == 1 therefore gives the 128 tile's bits.
 #include "gemm_nt_common.h"
+#include "gemm_nt_skinny.h"
 
 namespace {
 
-constexpr int SK_BM = 64, SK_BN = 64, SK_BK = 64;
 constexpr int SK_TILE = SK_BM * 128;          // 8 KiB per operand per stage
 constexpr int SK_STAGE = 2 * SK_TILE;         // 16 KiB
-constexpr int SK_CT_LD = 68;                  // f32 epilogue tile: 64 rows x 68 floats = 17 KiB (rows 4 apart land 16 banks apart)
 
 struct SkinnyParams {
-    NtParams nt;
-    int split;            // S
-    float* slab;          // [S, M, N] f32 (S > 1)
+    NtParams p;           // (p.tiles_m / p.tiles_n / p.band unused: the work items are sk's)
+    SkinnySplit sk;
 };
 
 // Ring of NS stages.  Slice i lives in stage i % NS; NS - 1 slices are in flight in front of the one being multiplied.  Per iteration: a counted
@@ -34,22 +28,16 @@ struct SkinnyParams {
 template <int NS>
 __global__ __launch_bounds__(256) void gemm_nt_skinny_kernel(SkinnyParams sp) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const NtParams& p = sp.nt;
+    const NtParams& p = sp.p;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
     const int l31 = lane & 31, hi = lane >> 5;
 
-    const int S = sp.split;
-    const int nblk = p.tiles_m * p.tiles_n * S;
-    const int pid = xcd_remap(blockIdx.x, nblk);
-    const int tile = pid / S, s = pid - tile * S;
-    const int pm = tile / p.tiles_n, pn = tile - pm * p.tiles_n;
-    const int m0 = pm * SK_BM, n0 = pn * SK_BN;
-    const int nk = p.K / SK_BK;
-    const int k0 = (int)((long)s * nk / S), k1 = (int)((long)(s + 1) * nk / S);
-    const int n = k1 - k0;                         // >= 1: S <= nk
+    const int S = sp.sk.split;
+    const SkinnyItem w = skinny_item(sp.sk, p.K);
+    const int m0 = w.m0, n0 = w.n0, s = w.s, k0 = w.k0, n = w.n;
 
     const int c4 = (tid & 15) * 4, gn = n0 + c4;   // epilogue: 16 threads x 4 columns per row, 16 rows per pass
     const bool col_ok = gn < p.N;                  // N % 4 == 0
@@ -128,7 +116,7 @@ __global__ __launch_bounds__(256) void gemm_nt_skinny_kernel(SkinnyParams sp) {
     if (S == 1) {
         epi_rows<4>(p, ct, SK_CT_LD, b4, m0 + (tid >> 4), tid >> 4, 16, c4, gn);
     } else {
-        float* dst = sp.slab + (size_t)s * p.M * p.N;
+        float* dst = sp.sk.slab + (size_t)s * p.M * p.N;
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
             const int row = (tid >> 4) + it * 16, gm = m0 + row;
@@ -137,50 +125,25 @@ __global__ __launch_bounds__(256) void gemm_nt_skinny_kernel(SkinnyParams sp) {
     }
 }
 
-// One thread per (row, 4 columns).  The residual may alias the f32 output: a thread reads its residual element (epi_row_fetch) before it stores it.
-__global__ __launch_bounds__(256) void gemm_nt_skinny_reduce_kernel(SkinnyParams sp) {
-    const NtParams& p = sp.nt;
-    const int n4 = p.N >> 2;
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long)p.M * n4) return;
-    const int gm = (int)(idx / n4), gn = (int)(idx - (long)gm * n4) * 4;
-    const size_t slab_stride = (size_t)p.M * p.N;
-    const float* src = sp.slab + (size_t)gm * p.N + gn;
-    const EpiRow o = epi_row_fetch<EpiAny>(p, gm, gn, true);
-    const float4 b4 = p.bias ? ld4(p.bias + gn) : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 v = ld4(src);
-    for (int s = 1; s < sp.split; ++s) {
-        const float4 t = ld4(src + (size_t)s * slab_stride);
-        v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
-    }
-    epi_row_apply<EpiAny>(p, o, v, b4, gm, gn);
-}
+// The reduce kernel's epilogue.  The residual may alias the f32 output: a thread reads its residual element (epi_row_fetch) before it stores it.
+struct SkinnyEpi {
+    EpiRow o;
+    __device__ SkinnyEpi(const NtParams& p, int gm, int gn) : o(epi_row_fetch<EpiAny>(p, gm, gn, true)) {}
+    __device__ void operator()(const NtParams& p, float4 v, float4 b4, int gm, int gn) const { epi_row_apply<EpiAny>(p, o, v, b4, gm, gn); }
+};
 
 }  // namespace
 
 // (validated by tcow_gemm_nt_skinny, api.cpp)
-int tcow_gemm_nt_skinny_bf16(hipStream_t stream, const tcow_gemm_args* a, int split, float* slab) {
+int tcow_gemm_nt_skinny_launch_bf16(hipStream_t stream, const tcow_gemm_args* a, int split, float* slab) {
     SkinnyParams sp;
-    sp.nt = nt_params_from_args(a);
-    sp.nt.tiles_m = cdiv(a->M, SK_BM); sp.nt.tiles_n = cdiv(a->N, SK_BN);
-    sp.split = split; sp.slab = slab;
-    const long blocks = (long)sp.nt.tiles_m * sp.nt.tiles_n * split;
-    TCOW_CHECK_ARG(blocks < (1L << 31), "tcow_gemm_nt_skinny: M=%d N=%d split=%d give too many workgroups", a->M, a->N, split);
+    sp.p = nt_params_from_args(a);
+    sp.sk = skinny_split(a, split, slab);
     // Ring depth (profiles/gemm_skinny.json; the depth does not change the arithmetic).  Up to two workgroups per CU: four stages, the loads of three
     // k-slices in flight per workgroup -- 8.9 -> 6.8 us (qkv), 9.3 -> 7.1 (proj), 9.7 -> 7.8 (fc1) at M = 301 against two stages.  More workgroups
     // than that: two stages (32 KiB, five workgroups per CU), the co-resident workgroups hide the latency and a deep ring only takes their LDS --
     // fc1 at M = 1 201 (912 workgroups) 15.1 us on two stages, 17.1 on three, 18.8 on four.
-    typedef void (*Kern)(SkinnyParams);
-    const int ns = blocks > 512 ? 2 : 4;
-    const Kern k = ns == 2 ? gemm_nt_skinny_kernel<2> : gemm_nt_skinny_kernel<4>;
-    const int lds = ns * SK_STAGE;                 // >= 32 KiB: holds the 17 KiB epilogue tile
-    tcow_ensure_lds(reinterpret_cast<const void*>(k), lds);
-    hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(256), lds, stream, sp);
-    TCOW_CHECK_LAUNCH();
-    if (split > 1) {
-        const long threads = (long)a->M * (a->N / 4);
-        hipLaunchKernelGGL(gemm_nt_skinny_reduce_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, sp);
-        TCOW_CHECK_LAUNCH();
-    }
-    return TCOW_OK;
+    const int ns = skinny_blocks(sp.sk) > 512 ? 2 : 4;      // (ns * SK_STAGE >= 32 KiB: holds the 17 KiB epilogue tile)
+    return skinny_launch("tcow_gemm_nt_skinny", stream, sp, ns == 2 ? gemm_nt_skinny_kernel<2> : gemm_nt_skinny_kernel<4>, ns * SK_STAGE,
+                         gemm_nt_skinny_reduce_kernel<SkinnyParams, SkinnyEpi>);
 }

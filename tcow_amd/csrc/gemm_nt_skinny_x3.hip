@@ -4,32 +4,26 @@
 //
 //   gemm_nt_skinny_x3_kernel         64 x 64 output tile, 4 waves as 2 x 2 with one 32 x 32 accumulator each, K in 64-element slices through a ring
 //                                    of two LDS stages (32 KiB each: 64 rows x 256 B per operand) filled by direct-to-LDS f32 loads.  A lane reads its 8
-//                                    consecutive k values as two 16-byte reads and splits them in registers (split2, gemm_f32.h).  A workgroup is
-//                                    (tile, slice s of S): it walks the k-slices [s nk / S, (s + 1) nk / S).  S == 1: f32_epilogue_store4.  S > 1:
-//                                    the raw f32 partial goes to slab s of the workspace [S, M, N].
-//   gemm_nt_skinny_x3_reduce_kernel  S > 1 only, a second launch: v = slab[0]; v += slab[1]; ... in slice order, then f32_epilogue_store4.
+//                                    consecutive k values as two 16-byte reads and splits them in registers (split2, gemm_f32.h).  The work items, the
+//                                    split over K, its slabs and the reduce launch are those of gemm_nt_skinny.h; the epilogue of S == 1 and of the
+//                                    reduce is f32_epilogue_store4.
 //
 // The arithmetic of an output element is that of gemm_x3_body: the same split, per 16-wide k chunk the three MFMAs b_hi a_lo, b_lo a_hi, b_hi a_hi
 // in that order (B fragment first: the accumulators hold C^T), the same k elements per lane half (k = 16 ks + 8 hi + e), K ascending from a zero
-// accumulator.  S == 1 therefore gives the 128 tile's bits; S > 1 is a fixed function of the inputs (no atomics, no arrival order).  The kernel
-// boundary makes the slabs visible: workgroups do not communicate inside a launch.
+// accumulator.  S == 1 therefore gives the 128 tile's bits.
 #include "gemm_f32.h"
-#include "gemm_glds.h"
+#include "gemm_nt_skinny.h"
 
 namespace {
 
-constexpr int SX_BM = 64, SX_BN = 64, SX_BK = 64;
-constexpr int SX_ROW = SX_BK * 4;             // 256 B: an f32 row of a stage is one LDS bank row
-constexpr int SX_TILE = SX_BM * SX_ROW;       // 16 KiB per operand per stage
+constexpr int SX_ROW = SK_BK * 4;             // 256 B: an f32 row of a stage is one LDS bank row
+constexpr int SX_TILE = SK_BM * SX_ROW;       // 16 KiB per operand per stage
 constexpr int SX_STAGE = 2 * SX_TILE;         // 32 KiB
 constexpr int SX_NS = 2;                      // ring stages: 64 KiB, two workgroups per CU (a four-stage ring measured no better)
-constexpr int SX_CT_LD = 68;                  // f32 epilogue tile: 64 rows x 68 floats = 17 KiB
 
 struct SkinnyX3Params {
-    F32Params p;          // (p.slab / p.kps unused: the split is the three fields below)
-    int tiles_m, tiles_n;
-    int split;            // S
-    float* slab;          // [S, M, N] f32 (S > 1)
+    F32Params p;          // (p.slab / p.kps unused: the split is sk's)
+    SkinnySplit sk;
 };
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -62,15 +56,9 @@ __global__ __launch_bounds__(256) void gemm_nt_skinny_x3_kernel(SkinnyX3Params s
     const int wm = wave >> 1, wn = wave & 1;
     const int l31 = lane & 31, hi = lane >> 5;
 
-    const int S = sp.split;
-    const int nblk = sp.tiles_m * sp.tiles_n * S;
-    const int pid = xcd_remap(blockIdx.x, nblk);
-    const int tile = pid / S, s = pid - tile * S;
-    const int pm = tile / sp.tiles_n, pn = tile - pm * sp.tiles_n;
-    const int m0 = pm * SX_BM, n0 = pn * SX_BN;
-    const int nk = p.K / SX_BK;
-    const int k0 = (int)((long)s * nk / S), k1 = (int)((long)(s + 1) * nk / S);
-    const int n = k1 - k0;                         // >= 1: S <= nk
+    const int S = sp.sk.split;
+    const SkinnyItem w = skinny_item(sp.sk, p.K);
+    const int m0 = w.m0, n0 = w.n0, s = w.s, k0 = w.k0, n = w.n;
 
     const int c4 = (tid & 15) * 4, gn = n0 + c4;   // epilogue: 16 threads x 4 columns per row, 16 rows per pass
     const bool col_ok = gn < p.N;                  // N % 4 == 0
@@ -86,16 +74,16 @@ __global__ __launch_bounds__(256) void gemm_nt_skinny_x3_kernel(SkinnyX3Params s
         const int c = (lane & 15) ^ (r & 15);
         int gm = m0 + r; gm = gm < p.M ? gm : p.M - 1;
         int gw = n0 + r; gw = gw < p.N ? gw : p.N - 1;
-        a_src[j] = p.A + (size_t)gm * p.sai + (size_t)k0 * SX_BK + c * 4;
-        w_src[j] = p.B + (size_t)gw * p.sbj + (size_t)k0 * SX_BK + c * 4;
+        a_src[j] = p.A + (size_t)gm * p.sai + (size_t)k0 * SK_BK + c * 4;
+        w_src[j] = p.B + (size_t)gw * p.sbj + (size_t)k0 * SK_BK + c * 4;
     }
     auto issue = [&](int i) {
         char* sa = smem + (i % SX_NS) * SX_STAGE;
         char* sw = sa + SX_TILE;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            glds16(a_src[j] + (size_t)i * SX_BK, sa + (wave * 4 + j) * 1024);
-            glds16(w_src[j] + (size_t)i * SX_BK, sw + (wave * 4 + j) * 1024);
+            glds16(a_src[j] + (size_t)i * SK_BK, sa + (wave * 4 + j) * 1024);
+            glds16(w_src[j] + (size_t)i * SK_BK, sw + (wave * 4 + j) * 1024);
         }
     };
 
@@ -148,56 +136,32 @@ __global__ __launch_bounds__(256) void gemm_nt_skinny_x3_kernel(SkinnyX3Params s
     float* ct = reinterpret_cast<float*>(smem);
 #pragma unroll
     for (int g = 0; g < 4; ++g)
-        *reinterpret_cast<float4*>(ct + (wm * 32 + l31) * SX_CT_LD + wn * 32 + 8 * g + 4 * hi) = make_float4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
+        *reinterpret_cast<float4*>(ct + (wm * 32 + l31) * SK_CT_LD + wn * 32 + 8 * g + 4 * hi) = make_float4(acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]);
     __syncthreads();
     if (!col_ok) return;
-    float* dst = S == 1 ? nullptr : sp.slab + (size_t)s * p.M * p.N;
+    float* dst = S == 1 ? nullptr : sp.sk.slab + (size_t)s * p.M * p.N;
 #pragma unroll 1
     for (int it = 0; it < 4; ++it) {
         const int row = (tid >> 4) + it * 16, gm = m0 + row;
         if (gm >= p.M) break;
-        const float4 x = *reinterpret_cast<const float4*>(ct + row * SX_CT_LD + c4);
+        const float4 x = *reinterpret_cast<const float4*>(ct + row * SK_CT_LD + c4);
         if (dst) st4(dst + (size_t)gm * p.N + gn, x);
         else f32_epilogue_store4(p, gm, gn, x, b4);
     }
 }
 
-// One thread per (row, 4 columns).  The residual may alias the output: f32_epilogue_store4 reads the thread's residual element before it stores it.
-__global__ __launch_bounds__(256) void gemm_nt_skinny_x3_reduce_kernel(SkinnyX3Params sp) {
-    const F32Params& p = sp.p;
-    const int n4 = p.N >> 2;
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long)p.M * n4) return;
-    const int gm = (int)(idx / n4), gn = (int)(idx - (long)gm * n4) * 4;
-    const size_t slab_stride = (size_t)p.M * p.N;
-    const float* src = sp.slab + (size_t)gm * p.N + gn;
-    const float4 b4 = p.bias ? ld4(p.bias + gn) : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 v = ld4(src);
-    for (int s = 1; s < sp.split; ++s) {
-        const float4 t = ld4(src + (size_t)s * slab_stride);
-        v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
-    }
-    f32_epilogue_store4(p, gm, gn, v, b4);
-}
+// The reduce kernel's epilogue.  The residual may alias the output: f32_epilogue_store4 reads the thread's residual element before it stores it.
+struct SkinnyX3Epi {
+    __device__ SkinnyX3Epi(const F32Params&, int, int) {}
+    __device__ void operator()(const F32Params& p, float4 v, float4 b4, int gm, int gn) const { f32_epilogue_store4(p, gm, gn, v, b4); }
+};
 
 }  // namespace
 
-// (validated by tcow_gemm_nt_skinny_x3, api.cpp)
-int tcow_gemm_nt_skinny_x3_launch(hipStream_t stream, const tcow_gemm_args* a, int split, float* slab) {
+// (validated by tcow_gemm_nt_skinny_x3, api.cpp)  The ring's 64 KiB hold the 17 KiB epilogue tile.
+int tcow_gemm_nt_skinny_launch_x3(hipStream_t stream, const tcow_gemm_args* a, int split, float* slab) {
     SkinnyX3Params sp;
-    sp.p = f32_params_nt(a, SX_BK);
-    sp.tiles_m = cdiv(a->M, SX_BM); sp.tiles_n = cdiv(a->N, SX_BN);
-    sp.split = split; sp.slab = slab;
-    const long blocks = (long)sp.tiles_m * sp.tiles_n * split;
-    TCOW_CHECK_ARG(blocks < (1L << 31), "tcow_gemm_nt_skinny_x3: M=%d N=%d split=%d give too many workgroups", a->M, a->N, split);
-    const int lds = SX_NS * SX_STAGE;              // 64 KiB: holds the 17 KiB epilogue tile
-    tcow_ensure_lds(reinterpret_cast<const void*>(gemm_nt_skinny_x3_kernel), lds);
-    hipLaunchKernelGGL(gemm_nt_skinny_x3_kernel, dim3((unsigned)blocks), dim3(256), lds, stream, sp);
-    TCOW_CHECK_LAUNCH();
-    if (split > 1) {
-        const long threads = (long)a->M * (a->N / 4);
-        hipLaunchKernelGGL(gemm_nt_skinny_x3_reduce_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, sp);
-        TCOW_CHECK_LAUNCH();
-    }
-    return TCOW_OK;
+    sp.p = f32_params_nt(a, SK_BK);
+    sp.sk = skinny_split(a, split, slab);
+    return skinny_launch("tcow_gemm_nt_skinny_x3", stream, sp, gemm_nt_skinny_x3_kernel, SX_NS * SX_STAGE, gemm_nt_skinny_reduce_kernel<SkinnyX3Params, SkinnyX3Epi>);
 }

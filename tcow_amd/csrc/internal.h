@@ -11,8 +11,8 @@ int tcow_gemm_nt_bf16(hipStream_t stream, const tcow_gemm_args* a);             
 bool tcow_gemm_nt_c2_ok(const tcow_gemm_args* a);                                                   // gemm_nt_c2.hip
 int tcow_gemm_nt_bf16_c2(hipStream_t stream, const tcow_gemm_args* a);
 int tcow_nt_band_for(const tcow_gemm_args* a, int tiles_n, int tile);                               // gemm_bf16.hip
-int tcow_gemm_nt_skinny_bf16(hipStream_t stream, const tcow_gemm_args* a, int split, float* slab);  // gemm_nt_skinny.hip
-int tcow_gemm_nt_skinny_x3_launch(hipStream_t stream, const tcow_gemm_args* a, int split, float* slab);  // gemm_nt_skinny_x3.hip
+int tcow_gemm_nt_skinny_launch_bf16(hipStream_t stream, const tcow_gemm_args* a, int split, float* slab);  // gemm_nt_skinny.hip
+int tcow_gemm_nt_skinny_launch_x3(hipStream_t stream, const tcow_gemm_args* a, int split, float* slab);    // gemm_nt_skinny_x3.hip
 int tcow_gemm_nt_f32(hipStream_t stream, const tcow_gemm_args* a);                                  // gemm_f32.hip
 int tcow_gemm_nt_x3(hipStream_t stream, const tcow_gemm_args* a);                                   // gemm_x3.hip
 

@@ -67,14 +67,13 @@ def gemm_nt(mode, A, W, out, bias=None, row_scale=None, resid=None, act=ACT_NONE
     skinny=True (the streaming steps): a 16-bit product that skinny_plan routes goes to gemm_nt_skinny instead, a bf16 x 3 product that
     skinny_plan_x3 routes to gemm_nt_skinny_x3 when its tensors have that entry point's 16-byte alignment (a view that has not stays on
     tcow_gemm_nt, whose kernel has a scalar path); exact fp32 never routes."""
-    if skinny and is16(mode) and not tile:
-        split = skinny_plan(A.shape[0], W.shape[0], A.shape[1])
+    if skinny and not tile:
+        shape = A.shape[0], W.shape[0], A.shape[1]
+        x3 = mode == F32X3 and _aligned16(A, W, out, bias, resid, aux, bias2)
+        split = skinny_plan(*shape) if is16(mode) else skinny_plan_x3(*shape) if x3 else 0
         if split > 0:
-            return gemm_nt_skinny(mode, A, W, out, bias=bias, row_scale=row_scale, resid=resid, act=act, aux=aux, bias2=bias2, row_scale2=row_scale2, split=split)
-    if skinny and mode == F32X3 and not tile and _aligned16(A, W, out, bias, resid, aux, bias2):
-        split = skinny_plan_x3(A.shape[0], W.shape[0], A.shape[1])
-        if split > 0:
-            return gemm_nt_skinny_x3(A, W, out, bias=bias, row_scale=row_scale, resid=resid, act=act, aux=aux, bias2=bias2, row_scale2=row_scale2, split=split)
+            kw = dict(bias=bias, row_scale=row_scale, resid=resid, act=act, aux=aux, bias2=bias2, row_scale2=row_scale2, split=split)
+            return gemm_nt_skinny(mode, A, W, out, **kw) if is16(mode) else gemm_nt_skinny_x3(A, W, out, **kw)
     _need_cuda(A, W, out)
     lib, dm = _sel(mode)
     a = _gemm_args(dm, A, W, out, bias, row_scale, resid, act, aux, tile, bias2, row_scale2)
@@ -108,19 +107,24 @@ def skinny_plan(M, N, K):
     return allowed[-1]
 
 
-def gemm_nt_skinny(mode, A, W, out, bias=None, row_scale=None, resid=None, act=ACT_NONE, aux=None, bias2=None, row_scale2=None, split=1):
-    """gemm_nt on 64 x 64 tiles with a deterministic split over K (tcow_gemm_nt_skinny; the 16-bit modes only).  split > 1 takes its [split, M, N]
-    f32 slabs from workspace(tag='nt_skinny')."""
+def _skinny_call(entry, mode, A, W, out, bias, row_scale, resid, act, aux, bias2, row_scale2, split):
+    """What both skinny entry points do: `entry` of the mode's library on the arguments of gemm_nt, its slabs from workspace(tag='nt_skinny')."""
     _need_cuda(A, W, out)
-    if not is16(mode):
-        raise L.TcowError('gemm_nt_skinny: the 16-bit modes only (fp32 and bf16x3 products go through gemm_nt)')
     lib, dm = _sel(mode)
     split = int(split)
     a = _gemm_args(dm, A, W, out, bias, row_scale, resid, act, aux, 0, bias2, row_scale2)
     nbytes = lib.tcow_gemm_nt_skinny_workspace_bytes(a.M, a.N, split)
     ws = workspace(nbytes, A.device, 'nt_skinny') if nbytes > 0 else None
-    L.check(lib.tcow_gemm_nt_skinny(_stream(), ctypes.byref(a), split, _p(ws), ws.numel() if ws is not None else 0), 'tcow_gemm_nt_skinny', lib)
+    L.check(getattr(lib, entry)(_stream(), ctypes.byref(a), split, _p(ws), ws.numel() if ws is not None else 0), entry, lib)
     return out
+
+
+def gemm_nt_skinny(mode, A, W, out, bias=None, row_scale=None, resid=None, act=ACT_NONE, aux=None, bias2=None, row_scale2=None, split=1):
+    """gemm_nt on 64 x 64 tiles with a deterministic split over K (tcow_gemm_nt_skinny; the 16-bit modes only).  split > 1 takes its [split, M, N]
+    f32 slabs from workspace(tag='nt_skinny')."""
+    if not is16(mode):
+        raise L.TcowError('gemm_nt_skinny: the 16-bit modes only (fp32 and bf16x3 products go through gemm_nt)')
+    return _skinny_call('tcow_gemm_nt_skinny', mode, A, W, out, bias, row_scale, resid, act, aux, bias2, row_scale2, split)
 
 
 def skinny_plan_x3(M, N, K):
@@ -150,14 +154,7 @@ def skinny_plan_x3(M, N, K):
 def gemm_nt_skinny_x3(A, W, out, bias=None, row_scale=None, resid=None, act=ACT_NONE, aux=None, bias2=None, row_scale2=None, split=1):
     """gemm_nt(F32X3, ...) on 64 x 64 tiles with a deterministic split over K (tcow_gemm_nt_skinny_x3): f32 tensors, 16-byte aligned, K % 64 == 0.
     split == 1 gives gemm_nt's bits; split > 1 takes its [split, M, N] f32 slabs from workspace(tag='nt_skinny'), the tag of gemm_nt_skinny."""
-    _need_cuda(A, W, out)
-    lib = L.lib()
-    split = int(split)
-    a = _gemm_args(F32X3, A, W, out, bias, row_scale, resid, act, aux, 0, bias2, row_scale2)
-    nbytes = lib.tcow_gemm_nt_skinny_workspace_bytes(a.M, a.N, split)
-    ws = workspace(nbytes, A.device, 'nt_skinny') if nbytes > 0 else None
-    L.check(lib.tcow_gemm_nt_skinny_x3(_stream(), ctypes.byref(a), split, _p(ws), ws.numel() if ws is not None else 0), 'tcow_gemm_nt_skinny_x3', lib)
-    return out
+    return _skinny_call('tcow_gemm_nt_skinny_x3', F32X3, A, W, out, bias, row_scale, resid, act, aux, bias2, row_scale2, split)
 
 
 _ws_cache = {}

@@ -1,8 +1,12 @@
-"""CPU: the routing rule of the skinny-M NT GEMM (ops.skinny_plan, host arithmetic only) and its two entry points in the C ABI."""
+"""CPU: the routing rules of the skinny-M NT GEMMs (ops.skinny_plan for the 16-bit modes, ops.skinny_plan_x3 for bf16 x 3; host arithmetic
+only), their entry points in the C ABI and the Python surface around them."""
 import ctypes
+import inspect
 import json
 import os
 import re
+
+import pytest
 
 from conftest import ROOT
 
@@ -91,10 +95,88 @@ def test_abi_14_declares_the_two_entry_points():
 
 def test_public_keyword_and_default():
     """net.stream / net.stream_pool take skinny_gemm; its default is the measured constant of tcow_amd/stream.py."""
-    import inspect
     from tcow_amd import ops, seeker, stream
     for cls in (seeker.QueryMaskTracker, seeker.Seeker):
         for name in ('stream', 'stream_pool'):
             assert inspect.signature(getattr(cls, name)).parameters['skinny_gemm'].default is None
     assert isinstance(stream.SKINNY_GEMM_DEFAULT, bool)
     assert inspect.signature(ops.gemm_nt).parameters['skinny'].default is False
+
+
+def test_abi_14_declares_the_x3_entry_point():
+    from tcow_amd import _lib
+    hdr = open(os.path.join(ROOT, 'include', 'tcow_hip.h')).read()
+    assert int(re.search(r'#define\s+TCOW_ABI_VERSION\s+(\d+)', hdr).group(1)) == 14 and _lib.ABI_VERSION == 14
+    assert re.search(r'int\s+tcow_gemm_nt_skinny_x3\(void\* stream, const tcow_gemm_args\* args, int split, void\* workspace, long workspace_bytes\);', hdr)
+    i, l, vp = ctypes.c_int, ctypes.c_long, ctypes.c_void_p
+    assert _lib.SIGNATURES['tcow_gemm_nt_skinny_x3'] == (i, [vp, ctypes.POINTER(_lib.GemmArgs), i, vp, l])
+    assert _lib.SIGNATURES['tcow_gemm_nt_skinny'] == (i, [vp, ctypes.POINTER(_lib.GemmArgs), i, vp, l])       # (unchanged)
+    for fmt in ('bf16', 'fp16'):
+        lib = _lib.lib(fmt)
+        assert lib.tcow_version() == 14
+        assert hasattr(lib, 'tcow_gemm_nt_skinny_x3')
+
+
+def test_plan_x3_properties():
+    from tcow_amd import ops
+    plan = ops.skinny_plan_x3
+    for N, K in WEIGHTS:
+        assert plan(27090, N, K) == 0                                  # the clip and training shapes stay on tcow_gemm_nt
+    for K in (96, 100, 767, 32, 1):
+        assert plan(301, 768, K) == 0                                  # K the entry point refuses
+    for M, N in [(2048, 2048), (128 * 256, 128), (4000, 1024)]:
+        assert -(-M // 128) * -(-N // 128) >= 256 and plan(M, N, 768) == 0
+    for M in list(range(1, 4200, 37)) + STREAM_M + [14, 28, 30]:
+        for N, K in WEIGHTS + [(128, 128), (512, 128), (128, 512), (4, 64), (768, 64)]:
+            S = plan(M, N, K)
+            assert S == 0 or S in ops.SKINNY_SPLITS, (M, N, K, S)
+            assert S <= K // 64, (M, N, K, S)
+    assert plan(1, 4, 64) in (0, 1)                                    # one k-slice cannot be split
+    for N in (766, 770, 3 * 15 * 15):
+        assert plan(301, N, 768) == 0                                  # N the entry point refuses (an odd patch size: a head of 3 P^2 columns)
+    for M in (14, 28, 30):
+        for N, K in [(128, 128), (384, 128), (512, 128), (128, 512)]:
+            assert plan(M, N, K) in (0, 1)                             # K <= 512 never splits (tests/test_gpu_stream_skinny.py, the d128 net)
+
+
+def test_plan_x3_reproduces_the_measured_table():
+    """profiles/gemm_skinny_x3.json (tools/dev_gemm_skinny.py --x3) states per shape what the measurement asks of the rule: 'route' false =
+    tcow_gemm_nt holds the shape; true = the skinny entry point with one of 'accept', the splits within the best one's spread."""
+    from tcow_amd import ops
+    rows = json.load(open(os.path.join(ROOT, 'profiles', 'gemm_skinny_x3.json')))['shapes']
+    assert len(rows) == 12 and {(r['M'], r['N'], r['K']) for r in rows} == {(M, N, K) for M in STREAM_M for N, K in WEIGHTS}
+    for r in rows:
+        S = ops.skinny_plan_x3(r['M'], r['N'], r['K'])
+        if r['route']:
+            assert S in r['accept'], (r['M'], r['N'], r['K'], S, r['accept'])
+        else:
+            assert S == 0, (r['M'], r['N'], r['K'], S)
+
+
+def test_plan_x3_reproduces_the_small_net_table():
+    """profiles/gemm_skinny_x3_small.json (the same tool with --rows 14,30): the four weight shapes at the row counts of a 32 x 48-pixel net's steps."""
+    from tcow_amd import ops
+    rows = json.load(open(os.path.join(ROOT, 'profiles', 'gemm_skinny_x3_small.json')))['shapes']
+    assert {(r['M'], r['N'], r['K']) for r in rows} == {(M, N, K) for M in (14, 30) for N, K in WEIGHTS}
+    for r in rows:
+        S = ops.skinny_plan_x3(r['M'], r['N'], r['K'])
+        assert (S in r['accept']) if r['route'] else S == 0, (r['M'], r['N'], r['K'], S, r['accept'])
+
+
+def test_the_16_bit_entry_point_and_gemm_nt_are_unchanged(monkeypatch):
+    import torch
+    from tcow_amd import _lib, ops
+    x = torch.zeros(64, 64)
+    monkeypatch.setattr(ops, '_need_cuda', lambda *ts: None)           # (the mode is refused before anything touches the device)
+    for mode in (ops.F32X3, ops.F32):
+        with pytest.raises(_lib.TcowError, match='16-bit modes only'):
+            ops.gemm_nt_skinny(mode, x, x, x, split=1)
+    assert str(inspect.signature(ops.gemm_nt)) == ('(mode, A, W, out, bias=None, row_scale=None, resid=None, act=0, aux=None, tile=0, bias2=None, '
+                                                   'row_scale2=None, skinny=False)')
+    assert list(inspect.signature(ops.gemm_nt_skinny_x3).parameters) == ['A', 'W', 'out', 'bias', 'row_scale', 'resid', 'act', 'aux', 'bias2', 'row_scale2', 'split']
+    assert inspect.signature(ops.gemm_nt_skinny_x3).parameters['split'].default == 1
+
+
+def test_default_constant():
+    from tcow_amd import stream
+    assert isinstance(stream.SKINNY_GEMM_X3_DEFAULT, bool) and isinstance(stream.SKINNY_GEMM_DEFAULT, bool)

@@ -16,7 +16,7 @@ tests/test_gemm_skinny_host.py::test_plan_reproduces_the_measured_table holds th
     python tools/dev_gemm_skinny.py --x3 --out profiles/gemm_skinny_x3.json
 
 --x3: the same harness for precision='bf16x3' -- f32 operands and outputs, tcow_gemm_nt with TCOW_F32X3 against ops.gemm_nt_skinny_x3, the rule
-ops.skinny_plan_x3 (tests/test_gemm_skinny_x3_host.py).
+ops.skinny_plan_x3 (tests/test_gemm_skinny_host.py::test_plan_x3_reproduces_the_measured_table).
 
     python tools/dev_gemm_skinny.py --x3 --rows 14,30 --out profiles/gemm_skinny_x3_small.json
 

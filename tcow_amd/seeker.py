@@ -115,6 +115,37 @@ class _Backbone(nn.Module):                      # vision_tf.py:27-66
 _DEPTH_GEOMETRY = {12: (768, 12), 18: (896, 14), 24: (1024, 16)}      # vit.py:424-449
 
 
+class ParamLayout:
+    """THE order of QueryMaskTracker.param_list(), by name: the list is built from it and the engine indexes the list through it.
+
+        cls, pos, time, patch_w, patch_b | depth x block | norm_w, norm_b, head_w, head_b [, flags_w, flags_b]
+
+    A block is (weight, bias) of each of `subs` in order; ix[name] is the weight's offset inside the block (bias: + 1), at(i, name) its index
+    in the whole list, block(i) the block's slice, blocks(lo, hi) the indices of blocks lo .. hi-1, embed those in front of the blocks."""
+    cls, pos, time, patch_w, patch_b = embed = range(5)
+    # sub-module of a _Block behind each name; a joint_space_time block has no temporal half (vit.py:135-153)
+    MODULES = dict(tn=lambda b: b.temporal_norm1, tqkv=lambda b: b.temporal_attn.qkv, tproj=lambda b: b.temporal_attn.proj, tfc=lambda b: b.temporal_fc,
+                   n1=lambda b: b.norm1, qkv=lambda b: b.attn.qkv, proj=lambda b: b.attn.proj, n2=lambda b: b.norm2, fc1=lambda b: b.mlp.fc1,
+                   fc2=lambda b: b.mlp.fc2)
+
+    def __init__(self, divided, depth, flags):
+        self.subs = (('tn', 'tqkv', 'tproj', 'tfc') if divided else ()) + ('n1', 'qkv', 'proj', 'n2', 'fc1', 'fc2')
+        self.ix = {name: 2 * k for k, name in enumerate(self.subs)}
+        self.per_block, self.depth = 2 * len(self.subs), depth
+        end = 5 + depth * self.per_block
+        self.norm_w, self.norm_b, self.head_w, self.head_b, self.flags_w, self.flags_b = range(end, end + 6)
+        self.count = end + (6 if flags else 4)
+
+    def at(self, i, name, bias=0):
+        return 5 + i * self.per_block + self.ix[name] + bias
+
+    def blocks(self, lo, hi):
+        return range(5 + lo * self.per_block, 5 + hi * self.per_block)
+
+    def block(self, i):
+        return slice(5 + i * self.per_block, 5 + (i + 1) * self.per_block)
+
+
 # ----------------------------------------------------------------------------------------------- the module
 
 class QueryMaskTracker(nn.Module):
@@ -177,6 +208,7 @@ class QueryMaskTracker(nn.Module):
         self.tracker_backbone = _Backbone(img_size=(frame_height, frame_width), patch=patch_size,
                                           in_chans=self.input_channels, dim=embed_dim, depth=network_depth,
                                           mlp_ratio=4, num_frames=num_total_frames, divided=(attention_type == 'divided_space_time'))
+        self.layout = ParamLayout(attention_type == 'divided_space_time', network_depth, flag_channels > 0)
         self.use_feature_dim = embed_dim
         self.tracker_post_linear = nn.Linear(embed_dim, output_channels * patch_size * patch_size)
         if flag_channels > 0:
@@ -275,17 +307,16 @@ class QueryMaskTracker(nn.Module):
         self.__dict__.pop('_param_list_cache', None)
 
     def _param_list_uncached(self):
-        v = self.vit
+        v, lay = self.vit, self.layout                 # (the order is ParamLayout's: its docstring states it)
         ps = [v.cls_token, v.pos_embed, v.time_embed, v.patch_embed.proj.weight, v.patch_embed.proj.bias]
-        for b in v.blocks:                   # (order = engine._layout)
-            if self.attention_type == 'divided_space_time':
-                ps += [b.temporal_norm1.weight, b.temporal_norm1.bias, b.temporal_attn.qkv.weight, b.temporal_attn.qkv.bias,
-                       b.temporal_attn.proj.weight, b.temporal_attn.proj.bias, b.temporal_fc.weight, b.temporal_fc.bias]
-            ps += [b.norm1.weight, b.norm1.bias, b.attn.qkv.weight, b.attn.qkv.bias, b.attn.proj.weight, b.attn.proj.bias,
-                   b.norm2.weight, b.norm2.bias, b.mlp.fc1.weight, b.mlp.fc1.bias, b.mlp.fc2.weight, b.mlp.fc2.bias]
+        for b in v.blocks:
+            for name in lay.subs:
+                sub = lay.MODULES[name](b)
+                ps += [sub.weight, sub.bias]
         ps += [v.norm.weight, v.norm.bias, self.tracker_post_linear.weight, self.tracker_post_linear.bias]
         if self.flag_channels > 0:
             ps += [self.flag_post_linear.weight, self.flag_post_linear.bias]
+        assert len(ps) == lay.count
         return ps
 
     # ---- forward

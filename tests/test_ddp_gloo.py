@@ -2,6 +2,7 @@
 import os
 import socket
 
+import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
@@ -137,54 +138,73 @@ def test_group_sizes_spec():
     assert group_sizes(12, '5,5,2') == group_sizes(12, None) or 'TCOW_DDP_GROUP' in os.environ
 
 
-def test_backward_publishes_only_finished_buckets():
-    """CPU guard on engine.run_backward's ordering (the GPU tests check the values): every publish() of a block group must come after the
-    flush_pending() that issues the group's deferred weight-gradient GEMMs and LayerNorm folds, the late fold bucket after
-    finish_fold_group(), and `return grads` after grad_hook.finish().  Checked on the function's AST: for each publish call the nearest
-    preceding statement that touches `pending` / `ln_jobs` work must be the flush."""
-    import ast
-    import inspect
-    from tcow_amd import engine
-    src = inspect.getsource(engine.run_backward)
-    tree = ast.parse(src)
-    fn = tree.body[0]
-    calls = []                                       # (lineno, name) of the calls that matter, in source order, nested defs excluded
-    class V(ast.NodeVisitor):
-        def visit_FunctionDef(self, node):
-            if node is fn:
-                self.generic_visit(node)
-        def visit_Call(self, node):
-            f = node.func
-            name = f.id if isinstance(f, ast.Name) else (f.attr if isinstance(f, ast.Attribute) else None)
-            if name in ('publish', 'flush_pending', 'finish_fold_group', 'finish', 'linear_bwd', 'layernorm_bwd'):
-                calls.append((node.lineno, name))
-            self.generic_visit(node)
-    V().visit(tree)
-    calls.sort()
-    names = [n for _, n in calls]
-    pubs = [i for i, n in enumerate(names) if n == 'publish']
-    assert len(pubs) == 3                                                   # block groups above the bottom one, the late fold bucket, the bottom group
-    # (1) group publish inside the block loop: the last deferred producer before it is followed by a flush
-    i = pubs[0]
-    last_producer = max(j for j in range(i) if names[j] in ('linear_bwd', 'layernorm_bwd'))
-    assert 'flush_pending' in names[last_producer:i], names
-    # (2) the late bucket: behind finish_fold_group()
-    assert names[pubs[1] - 1] == 'finish_fold_group', names
-    # (3) the bottom bucket, then the drain, then nothing else
-    assert names[pubs[2] + 1:] == ['finish'], names
-    ret = [n.lineno for n in ast.walk(fn) if isinstance(n, ast.Return) and isinstance(n.value, ast.Name) and n.value.id == 'grads']
-    assert ret and ret[-1] > calls[-1][0]
-    # the bottom group's own weight gradients: the block loop's flush happens for i == 0 too (group_lo[0] == 0), before the loop ends
-    assert 'if group_lo[i] == i or len(pending) + 8 > tn_group_max:' in src
+def _bucket_tags(depth, spec, fold):
+    """The tags engine.run_backward publishes, in order: 'g<lowest block>' of every group above the bottom one from the top down, the late
+    fold bucket, the bottom group."""
+    from tcow_amd.engine import group_sizes
+    tags, hi = [], depth
+    for gs in group_sizes(depth, spec):
+        hi -= gs
+        if hi > 0:
+            tags.append('g%d' % hi)
+    return tags + (['fold'] if fold else []) + ['g0']
 
 
-def test_hook_sees_complete_buckets_with_a_fake_engine_run():
-    """The same ordering, dynamically: run engine.run_backward's bucket bookkeeping with stub ops and a recording hook is not possible without
-    the GPU library, so this drives GradSync the way the backward does and checks that finish() leaves nothing pending before gradients are
-    handed out (single process: the hook is a no-op but its state machine still runs)."""
+# gradients that torch ops write (a copy_ of a reduced table), not a library call; model.norm.* stay None without norm_embeddings
+_TORCH_WRITTEN = ('model.cls_token', 'model.patch_embed.proj.bias', 'flag_post_linear.bias', 'model.norm.weight', 'model.norm.bias')
+
+
+@pytest.mark.parametrize('precision,spec', [(p, s) for p in ('bf16', 'fp32') for s in ('1', '2,1', '3')] + [('fp16', '2,1')])
+def test_backward_publishes_only_finished_buckets(precision, spec, monkeypatch):
+    """CPU guard on engine.run_backward's ordering (the GPU tests check the values): the real backward on CPU tensors with a recording library
+    and a recording hook (tests/engine_trace.py).  bf16 / fp16 fold the temporal projection (late bucket), fp32 does not; fp16 with an active
+    hook makes publish() undo the loss scale."""
+    import engine_trace as kit
+    monkeypatch.setenv('TCOW_DDP_GROUP', spec)
+    trace = kit.install(monkeypatch)
+    net = kit.make_net(precision)
+    m = kit.train_step(net, hook=kit.RecordingHook(trace), trace=trace)
+    ev = list(trace.events)
+    fold = precision != 'fp32'
+    pubs = [(k, e[1], e[2]) for k, e in enumerate(ev) if e[0] == 'publish']
+    touches = lambda e, lo, hi: e[0] == 'call' and any(lo <= p < hi for p in e[2])
+    # the buckets come in the order g<top> ..., 'fold', 'g0'; the drain is the last event, right behind the bottom bucket
+    assert [t for _, t, _ in pubs] == _bucket_tags(kit.DEPTH, spec, fold)
+    assert ev[-1] == ('finish',) and ev[pubs[-1][0] + 1:] == [('finish',)]
+    assert sum(e[0] == 'finish' for e in ev) == 1
+    assert m.pending_inv_scale is None                                      # (fp16: the hook is active, so publish() unscaled every bucket itself)
+    for k, tag, (lo, hi) in pubs:
+        # a published bucket is finished: no library call receives a pointer into it any more
+        late = [e[1] for e in ev[k + 1:] if touches(e, lo, hi)]
+        assert not late, (tag, late)
+        before = [e[1] for e in ev[:k] if touches(e, lo, hi)]
+        if tag == 'fold':
+            # the late bucket: right behind the four batched launches of _GradBuckets.finish_late, all of which write into it
+            assert [e[1] for e in ev[k - 4:k]] == ['tcow_sgemm_x3_batched'] * 4 and all(touches(e, lo, hi) for e in ev[k - 4:k])
+        else:
+            # a block group (the bottom one included): its deferred weight-gradient GEMMs and LayerNorm folds were flushed before
+            assert 'tcow_gemm_tn_grouped' in before and 'tcow_layernorm_fold' in before, (tag, before)
+    # every parameter's gradient lies in exactly one published bucket, and a library call wrote into it before that bucket went out
+    names = {id(p): n for n, p in net.named_parameters()}
+    for p in m.param_list():
+        name, gr = names[id(p)], p.grad
+        if gr is None:
+            assert name.endswith(('model.norm.weight', 'model.norm.bias')), name
+            continue
+        a = gr.data_ptr()
+        home = [k for k, _, (lo, hi) in pubs if lo <= a and a + gr.numel() * 4 <= hi]
+        assert len(home) == 1, (name, home)
+        written = any(touches(e, a, a + gr.numel() * 4) for e in ev[:home[0]])
+        assert written or name.endswith(_TORCH_WRITTEN), name
+
+
+def test_hook_sees_complete_buckets_with_a_fake_engine_run(monkeypatch):
+    """The same ordering with the real hook: engine.run_backward on CPU tensors (tests/engine_trace.py) drives a GradSync of one rank, and
+    finish() leaves nothing pending before gradients are handed out (single process: the hook is a no-op but its state machine still runs)."""
+    import engine_trace as kit
     from tcow_amd import ddp
+    trace = kit.install(monkeypatch)
     sync = ddp.GradSync(1, force=False)
-    for tag in ('g7', 'g2', 'fold', 'g0'):
-        sync(tag, torch.ones(3))
-    sync.finish()
+    m = kit.train_step(kit.make_net('bf16'), hook=sync)
+    assert any(c[0] == 'tcow_gemm_tn_grouped' for c in trace.calls) and all(p.grad is not None for p in m.param_list()[:5])
     assert sync.pending == [] and sync.deferred == [] and sync.steps == 1

@@ -134,3 +134,13 @@ __host__ __device__ __forceinline__ constexpr int crow32(int r, int hi) { return
 void tcow_ensure_lds(const void* kernel, int bytes);
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+// workgroups of a grid-stride launch: one per `per_block` items, at least 1 and at most 4096
+static inline int gs_blocks(long total, int per_block = 256) { long b = (total + per_block - 1) / per_block; return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b)); }
+
+// ---- storage-type dispatch of an entry point: TCOW_DISPATCH_STORAGE(dtype, [&](auto t) { using T = decltype(t); launch<T>(...); }) calls the generic
+// callable with a bf16_t for TCOW_BF16 and a float for TCOW_F32; any other dtype sets "<entry point>: unknown dtype %d" and returns
+// TCOW_ERR_INVALID_ARG from the entry point.  The callable only launches: TCOW_CHECK_LAUNCH() follows the macro, in the entry point whose name it reports.
+#define TCOW_DISPATCH_STORAGE(dtype, ...)                                                                                         \
+    do { auto launch__ = __VA_ARGS__;                                                                                             \
+         if ((dtype) == TCOW_BF16) launch__(bf16_t{}); else if ((dtype) == TCOW_F32) launch__(float{});                           \
+         else { tcow_set_error("%s: unknown dtype %d", __func__, (dtype)); return TCOW_ERR_INVALID_ARG; } } while (0)

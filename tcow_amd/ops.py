@@ -419,7 +419,8 @@ def cls_ragged(x, n, F, S, cls_cache, n_slots, t0_rows, slot_rows, first_rows, c
 
 def im2col(mode, rgb, query, P, pretrained_norm, out):
     B, _, T, H, W = rgb.shape
-    L.check(_sel(mode)[0].tcow_im2col(_stream(), _sel(mode)[1], B, T, H, W, P, rgb.data_ptr(), query.data_ptr(), int(pretrained_norm), out.data_ptr()), 'tcow_im2col', _sel(mode)[0])
+    lib, dm = _sel(mode)
+    L.check(lib.tcow_im2col(_stream(), dm, B, T, H, W, P, rgb.data_ptr(), query.data_ptr(), int(pretrained_norm), out.data_ptr()), 'tcow_im2col', lib)
     return out
 
 
@@ -460,7 +461,6 @@ def photometric(frames, frame_idx, rect, order, factors, taps, gray):
     """frames (3,Tv,H,W) f32 CUDA tensor in [0, 1], frame_idx int32 CUDA table, rect = (y0, x0, h, w) -> (3,Tc,h,w) f32: ColorJitter adjustments
     `order` (list of 0 brightness / 1 contrast / 2 saturation / 3 hue, may be empty) with `factors` = (brightness, contrast, saturation, hue),
     5-tap blur with the normalised `taps` (None: no blur), grayscale fold (see tcow_photometric)."""
-    import ctypes
     _need_cuda(frames, frame_idx)
     if frames.dtype != torch.float32 or not frames.is_contiguous() or frames.dim() != 4 or frames.shape[0] != 3:
         raise L.TcowError('photometric: contiguous (3, Tv, H, W) f32 frames expected')
@@ -484,7 +484,8 @@ def photometric(frames, frame_idx, rect, order, factors, taps, gray):
 def im2col_channels(mode, src, P, normalise, out):
     """src (B,C,T,H,W) f32 -> out [B*T*S, C*P*P] (see tcow_im2col_channels)."""
     B, C, T, H, W = src.shape
-    L.check(_sel(mode)[0].tcow_im2col_channels(_stream(), _sel(mode)[1], B, T, H, W, P, C, src.data_ptr(), int(normalise), out.data_ptr()), 'tcow_im2col_channels', _sel(mode)[0])
+    lib, dm = _sel(mode)
+    L.check(lib.tcow_im2col_channels(_stream(), dm, B, T, H, W, P, C, src.data_ptr(), int(normalise), out.data_ptr()), 'tcow_im2col_channels', lib)
     return out
 
 
@@ -508,12 +509,14 @@ def cls_merge(x, B, T, S, mode, backward=False, cast_mode=None, cast_out=None, c
 
 
 def unpatchify_pool_fwd(mode, pm, BT, Hp, Wp, P, C, st, pooled):
-    L.check(_sel(mode)[0].tcow_unpatchify_pool_fwd(_stream(), _sel(mode)[1], BT, Hp, Wp, P, C, st, pm.data_ptr(), pooled.data_ptr()), 'tcow_unpatchify_pool_fwd', _sel(mode)[0])
+    lib, dm = _sel(mode)
+    L.check(lib.tcow_unpatchify_pool_fwd(_stream(), dm, BT, Hp, Wp, P, C, st, pm.data_ptr(), pooled.data_ptr()), 'tcow_unpatchify_pool_fwd', lib)
     return pooled
 
 
 def unpatchify_pool_bwd(mode, dpooled, BT, Hp, Wp, P, C, st, dpm):
-    L.check(_sel(mode)[0].tcow_unpatchify_pool_bwd(_stream(), _sel(mode)[1], BT, Hp, Wp, P, C, st, dpooled.data_ptr(), dpm.data_ptr()), 'tcow_unpatchify_pool_bwd', _sel(mode)[0])
+    lib, dm = _sel(mode)
+    L.check(lib.tcow_unpatchify_pool_bwd(_stream(), dm, BT, Hp, Wp, P, C, st, dpooled.data_ptr(), dpm.data_ptr()), 'tcow_unpatchify_pool_bwd', lib)
     return dpm
 
 
@@ -553,7 +556,8 @@ def scale_unless_one(x, scale):
 
 def scale_cast(mode, src, row_scale, dst):
     rows, D = src.shape
-    L.check(_sel(mode)[0].tcow_scale_cast(_stream(), _sel(mode)[1], rows, D, src.data_ptr(), src.stride(0), _p(row_scale), dst.data_ptr(), dst.stride(0)), 'tcow_scale_cast', _sel(mode)[0])
+    lib, dm = _sel(mode)
+    L.check(lib.tcow_scale_cast(_stream(), dm, rows, D, src.data_ptr(), src.stride(0), _p(row_scale), dst.data_ptr(), dst.stride(0)), 'tcow_scale_cast', lib)
     return dst
 
 
@@ -571,18 +575,19 @@ def droppath_rows(u, keep_p, mask0, B, T, S):
 
 def cast_transpose(mode, W, Wc=None, Wt=None):
     N, K = W.shape
-    L.check(_sel(mode)[0].tcow_cast_transpose(_stream(), _sel(mode)[1], N, K, W.data_ptr(), _p(Wc), _p(Wt)), 'tcow_cast_transpose', _sel(mode)[0])
+    lib, dm = _sel(mode)
+    L.check(lib.tcow_cast_transpose(_stream(), dm, N, K, W.data_ptr(), _p(Wc), _p(Wt)), 'tcow_cast_transpose', lib)
 
 
 def cast_transpose_batched(mode, table, n, total_tiles):
     """One launch for all operand copies; `table` is the uint8 device tensor of tcow_cast_desc records (see tcow_cast_transpose_batched)."""
-    L.check(_sel(mode)[0].tcow_cast_transpose_batched(_stream(), _sel(mode)[1], table.data_ptr(), int(n), int(total_tiles)), 'tcow_cast_transpose_batched', _sel(mode)[0])
+    lib, dm = _sel(mode)
+    L.check(lib.tcow_cast_transpose_batched(_stream(), dm, table.data_ptr(), int(n), int(total_tiles)), 'tcow_cast_transpose_batched', lib)
 
 
-def mask_loss(logits, target, channel, pixel_w=None, frame_w=None, weighted_aot=False, aot_loss=0.8, topk_frac=1.0,
-              loss_weight=1.0, loss_out=None, total=None, dlogits=None, focal=False):
-    """Channel `channel` of the TCOW mask objective on (BQ, C, T, H, W) f32 logits / targets (see tcow_mask_loss):
-    writes loss_out[0], adds loss_weight * loss to total[0] and d(loss)/d(logits) into dlogits[:, channel]."""
+def _mask_loss_args(lib, ws_tag, logits, target, channel, pixel_w, frame_w, weighted_aot, aot_loss, topk_frac, loss_weight, loss_out, total, dlogits, focal):
+    """The tcow_mask_loss_args record of channel `channel` of (BQ, C, T, H, W) f32 logits / targets, after the tensor checks; its workspace is the
+    pinned one tagged ws_tag, sized for this job (the 4 B / pixel bit-pattern image only when the radix select runs)."""
     _need_cuda(logits, target, pixel_w, frame_w, loss_out, total, dlogits)
     BQ, C, T, H, W = logits.shape
     for t in (logits, target, dlogits):
@@ -593,14 +598,20 @@ def mask_loss(logits, target, channel, pixel_w=None, frame_w=None, weighted_aot=
         raise L.TcowError('mask_loss: pixel_w must be a contiguous f32 tensor with one weight per pixel')
     if frame_w is not None and (frame_w.dtype != torch.float32 or not frame_w.is_contiguous() or frame_w.numel() != n_frames):
         raise L.TcowError('mask_loss: frame_w must be a contiguous f32 tensor with one weight per frame')
-    lib = L.lib()
-    nb = lib.tcow_mask_loss_workspace_bytes_for(n_frames, frame_len, float(topk_frac), float(aot_loss))
-    ws = workspace(nb, logits.device, 'mask_loss')
+    ws = workspace(lib.tcow_mask_loss_workspace_bytes_for(n_frames, frame_len, float(topk_frac), float(aot_loss)), logits.device, ws_tag)
     off = channel * T * frame_len * 4
-    a = L.MaskLossArgs(n_frames, frame_len, T, logits.data_ptr() + off, C * T * frame_len, target.data_ptr() + off, C * T * frame_len,
-                       _p(pixel_w), _p(frame_w), 1 if weighted_aot else 0, float(aot_loss), float(topk_frac), float(loss_weight),
-                       loss_out.data_ptr(), _p(total), (dlogits.data_ptr() + off) if dlogits is not None else None,
-                       C * T * frame_len, ws.data_ptr(), ws.numel(), 1 if focal else 0)
+    return L.MaskLossArgs(n_frames, frame_len, T, logits.data_ptr() + off, C * T * frame_len, target.data_ptr() + off, C * T * frame_len,
+                          _p(pixel_w), _p(frame_w), 1 if weighted_aot else 0, float(aot_loss), float(topk_frac), float(loss_weight),
+                          loss_out.data_ptr(), _p(total), (dlogits.data_ptr() + off) if dlogits is not None else None,
+                          C * T * frame_len, ws.data_ptr(), ws.numel(), 1 if focal else 0)
+
+
+def mask_loss(logits, target, channel, pixel_w=None, frame_w=None, weighted_aot=False, aot_loss=0.8, topk_frac=1.0,
+              loss_weight=1.0, loss_out=None, total=None, dlogits=None, focal=False):
+    """Channel `channel` of the TCOW mask objective on (BQ, C, T, H, W) f32 logits / targets (see tcow_mask_loss):
+    writes loss_out[0], adds loss_weight * loss to total[0] and d(loss)/d(logits) into dlogits[:, channel]."""
+    lib = L.lib()
+    a = _mask_loss_args(lib, 'mask_loss', logits, target, channel, pixel_w, frame_w, weighted_aot, aot_loss, topk_frac, loss_weight, loss_out, total, dlogits, focal)
     L.check(lib.tcow_mask_loss(_stream(), ctypes.byref(a)), 'tcow_mask_loss')
     return loss_out
 
@@ -608,27 +619,11 @@ def mask_loss(logits, target, channel, pixel_w=None, frame_w=None, weighted_aot=
 def mask_loss_channels(logits, target, jobs, aot_loss=0.8, topk_frac=1.0, total=None, dlogits=None, focal=False):
     """Several channels of the TCOW mask objective in ONE set of launches (tcow_mask_loss_batch).  jobs: up to 4 tuples
     (channel, pixel_w | None, frame_w | None, weighted_aot, loss_weight, loss_out[1]); `total` receives sum_j loss_weight_j * loss_j in job order."""
-    _need_cuda(logits, target, total, dlogits)
-    BQ, C, T, H, W = logits.shape
-    for t in (logits, target, dlogits):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.shape != logits.shape):
-            raise L.TcowError('mask_loss: logits / target / dlogits must be contiguous f32 tensors of one shape')
-    n_frames, frame_len = BQ * T, H * W
     lib = L.lib()
-    nb = lib.tcow_mask_loss_workspace_bytes_for(n_frames, frame_len, float(topk_frac), float(aot_loss))      # (the 4 B / pixel bit-pattern image only when the radix select runs)
     arr = (L.MaskLossArgs * len(jobs))()
     for i, (channel, pixel_w, frame_w, weighted_aot, loss_weight, loss_out) in enumerate(jobs):
-        _need_cuda(pixel_w, frame_w, loss_out)
-        if pixel_w is not None and (pixel_w.dtype != torch.float32 or not pixel_w.is_contiguous() or pixel_w.numel() != n_frames * frame_len):
-            raise L.TcowError('mask_loss: pixel_w must be a contiguous f32 tensor with one weight per pixel')
-        if frame_w is not None and (frame_w.dtype != torch.float32 or not frame_w.is_contiguous() or frame_w.numel() != n_frames):
-            raise L.TcowError('mask_loss: frame_w must be a contiguous f32 tensor with one weight per frame')
-        ws = workspace(nb, logits.device, 'mask_loss%d' % i)             # every job of a batch needs its own workspace
-        off = channel * T * frame_len * 4
-        arr[i] = L.MaskLossArgs(n_frames, frame_len, T, logits.data_ptr() + off, C * T * frame_len, target.data_ptr() + off, C * T * frame_len,
-                                _p(pixel_w), _p(frame_w), 1 if weighted_aot else 0, float(aot_loss), float(topk_frac), float(loss_weight),
-                                loss_out.data_ptr(), _p(total), (dlogits.data_ptr() + off) if dlogits is not None else None,
-                                C * T * frame_len, ws.data_ptr(), ws.numel(), 1 if focal else 0)
+        arr[i] = _mask_loss_args(lib, 'mask_loss%d' % i, logits, target, channel, pixel_w, frame_w, weighted_aot, aot_loss, topk_frac, loss_weight, loss_out, total,
+                                 dlogits, focal)            # (every job of a batch needs its own workspace)
     L.check(lib.tcow_mask_loss_batch(_stream(), arr, len(jobs)), 'tcow_mask_loss_batch')
 
 
@@ -644,6 +639,12 @@ def iou_counts(logits, target):
     return out
 
 
+def _mask_outputs(B, Q, T, H, W, dev):
+    """What both mask builders write: query_mask (B,Q,1,T,H,W) f32, target (B,Q,3,T,H,W) f32, snitch_occl_by_ptr (B,Q,1,T,H,W) u8, counts int32 [1 + 2Q]."""
+    return (torch.empty(B, Q, 1, T, H, W, dtype=torch.float32, device=dev), torch.empty(B, Q, 3, T, H, W, dtype=torch.float32, device=dev),
+            torch.empty(B, Q, 1, T, H, W, dtype=torch.uint8, device=dev), torch.empty(1 + 2 * Q, dtype=torch.int32, device=dev))
+
+
 def build_masks(segm, div_segm, query_idx, front_idx, cont_idx, query_time):
     """segm (B,1,T,H,W) u8, div_segm (B,M,T,H,W) u8, query_idx (B,Q) int32, front_idx / cont_idx (B,Q,T) int32 (-1 = none).
     Returns query_mask (B,Q,1,T,H,W) f32, target (B,Q,3,T,H,W) f32, snitch_occl_by_ptr (B,Q,1,T,H,W) u8, counts int32 [1 + 2Q]
@@ -653,9 +654,7 @@ def build_masks(segm, div_segm, query_idx, front_idx, cont_idx, query_time):
     M = div_segm.shape[1]; Q = query_idx.shape[1]
     if segm.dtype != torch.uint8 or div_segm.dtype != torch.uint8 or not segm.is_contiguous() or not div_segm.is_contiguous():
         raise L.TcowError('build_masks: segmentation maps must be contiguous uint8 tensors')
-    dev = segm.device
-    qm = torch.empty(B, Q, 1, T, H, W, dtype=torch.float32, device=dev); tg = torch.empty(B, Q, 3, T, H, W, dtype=torch.float32, device=dev)
-    pt = torch.empty(B, Q, 1, T, H, W, dtype=torch.uint8, device=dev); counts = torch.empty(1 + 2 * Q, dtype=torch.int32, device=dev)
+    qm, tg, pt, counts = _mask_outputs(B, Q, T, H, W, segm.device)
     qi = query_idx.to(torch.int32).contiguous(); fi = front_idx.to(torch.int32).contiguous(); ci = cont_idx.to(torch.int32).contiguous()
     L.check(L.lib().tcow_build_masks(_stream(), B, Q, M, T, H * W, int(query_time), segm.data_ptr(), div_segm.data_ptr(), qi.data_ptr(), fi.data_ptr(),
                                      ci.data_ptr(), qm.data_ptr(), tg.data_ptr(), pt.data_ptr(), counts.data_ptr()), 'tcow_build_masks')
@@ -678,8 +677,7 @@ def build_query_masks(segm, div_segm, occl_fracs, dag, sel, query_time, front_oc
     dev = segm.device
     of = occl_fracs.to(torch.float32).contiguous(); dg = dag.to(torch.float32).contiguous(); sl = sel.contiguous()
     n = B * Q * T
-    qm = torch.empty(B, Q, 1, T, H, W, dtype=torch.float32, device=dev); tg = torch.empty(B, Q, 3, T, H, W, dtype=torch.float32, device=dev)
-    pt = torch.empty(B, Q, 1, T, H, W, dtype=torch.uint8, device=dev); counts = torch.empty(1 + 2 * Q, dtype=torch.int32, device=dev)
+    qm, tg, pt, counts = _mask_outputs(B, Q, T, H, W, dev)
     idx = torch.empty(B * Q + 2 * n, dtype=torch.int32, device=dev)
     ids = torch.empty(B, Q, T, 2, dtype=torch.uint8, device=dev)
     fl = torch.empty(2, B, Q, T, 3, dtype=torch.float32, device=dev)         # flags | sel_occl_fracs (one allocation)

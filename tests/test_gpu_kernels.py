@@ -519,6 +519,34 @@ def test_flags_casts(ops, cuda):
     assert torch.equal(dh, (src * rs[:, None]).half())
 
 
+@pytest.mark.parametrize('mname', ['f32', 'bf16', 'fp16'])
+@pytest.mark.parametrize('edge,shapes', [(64, [(64, 128), (128, 64)]), (32, [(48, 40), (33, 65)])])
+def test_cast_transpose_batched(ops, cuda, mname, edge, shapes):
+    """tcow_cast_transpose_batched called directly, with the table bytes built as tcow_amd/operands.py builds them: both tile edges (64 when every
+    N and K is a multiple of 64, else 32 with edge tiles), two records for the bisection, one record without Wc and one without Wt.  The copies
+    are W and its transpose cast to the mode's storage type bit for bit (torch's cast and f2bf both round to nearest even); an output that is
+    null in the table is not written."""
+    import struct
+    from tcow_amd import _lib
+    mode, dt = _mode(ops, mname)
+    g = torch.Generator(device='cuda').manual_seed(edge)
+    rec, tiles, outs = [], 0, []
+    for i, (N, K) in enumerate(shapes):
+        W = torch.randn(N, K, device=cuda, generator=g)
+        Wc = torch.full((N, K), 7.0, device=cuda, dtype=dt); Wt = torch.full((K, N), 7.0, device=cuda, dtype=dt)
+        in_c, in_t = i != 0, i != 1                                     # record 0 has no Wc, record 1 no Wt
+        rec.append(struct.pack('<QQQiiii', W.data_ptr(), Wc.data_ptr() if in_c else 0, Wt.data_ptr() if in_t else 0, N, K, tiles, edge))
+        tiles += ((N + edge - 1) // edge) * ((K + edge - 1) // edge)
+        outs.append((W, Wc, Wt, in_c, in_t))
+    assert len(rec[0]) == int(_lib.lib().tcow_cast_desc_bytes())
+    table = torch.frombuffer(bytearray(b''.join(rec)), dtype=torch.uint8).to(cuda)
+    ops.cast_transpose_batched(mode, table, len(rec), tiles)
+    torch.cuda.synchronize()
+    for W, Wc, Wt, in_c, in_t in outs:
+        assert torch.equal(Wc, W.to(dt) if in_c else torch.full_like(Wc, 7.0))
+        assert torch.equal(Wt, W.t().contiguous().to(dt) if in_t else torch.full_like(Wt, 7.0))
+
+
 def test_layernorm_deferred_fold_is_bit_identical(ops, cuda):
     """layernorm_bwd(..., defer=jobs) + layernorm_fold(jobs) (one launch for several LayerNorm calls: tcow_layernorm_fold) vs the immediate fold:
     the same partial tables through the same reduction -- dgamma, dbeta and the fused column sum bit for bit; with and without accumulation."""

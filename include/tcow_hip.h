@@ -172,7 +172,9 @@ int tcow_sgemm_x3_batched(void* stream, int n, const tcow_sgemm* problems);
  * dx_cast (may be NULL) additionally receives dtype(dx * cast_row_scale[row]) (scale NULL = 1): the operand of the
  * input-gradient GEMM that consumes this gradient next, without a separate tcow_scale_cast pass.
  * colsum_out (may be NULL; needs dgamma / dbeta) (+)= sum_rows colsum_row_scale[row] * dx[row] (scale NULL = 1) in f32: the bias gradient
- * of the Linear layer whose output fed this norm's residual stream under a row mask (temporal_fc.bias, vit.py:146,174-176). */
+ * of the Linear layer whose output fed this norm's residual stream under a row mask (temporal_fc.bias, vit.py:146,174-176).
+ * Rows are read and written four elements at a time: D and every row stride (ldx, ldy; lddy, lddres when dres is given, lddx, lddx_cast when
+ * dx_cast is given) must be multiples of 4, else TCOW_ERR_INVALID_ARG. */
 int tcow_layernorm_fwd(void* stream, int dtype, int rows, int D, const float* x, long ldx, const float* gamma,
                        const float* beta, float eps, void* y, long ldy, float* mean, float* rstd);
 long tcow_layernorm_bwd_workspace_bytes(int D);

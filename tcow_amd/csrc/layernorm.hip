@@ -231,6 +231,11 @@ int tcow_layernorm_bwd(void* stream, int dtype, int rows, int D, const void* dy,
                        const float* colsum_row_scale, float* colsum_out) {
     TCOW_CHECK_ARG(rows > 0 && D > 0 && D % 4 == 0 && D <= 64 * 4 * LN_MAXV, "tcow_layernorm_bwd: bad D=%d", D);
     TCOW_CHECK_ARG(dy && x && mean && rstd && gamma && dx, "tcow_layernorm_bwd: null pointer");
+    // (every row is read and written in 4-element vectors: 16 bytes of f32, 8 bytes of 16-bit storage)
+    TCOW_CHECK_ARG(lddy % 4 == 0, "tcow_layernorm_bwd: dy stride %ld must be a multiple of 4", lddy);
+    TCOW_CHECK_ARG(ldx % 4 == 0, "tcow_layernorm_bwd: x stride %ld must be a multiple of 4", ldx);
+    TCOW_CHECK_ARG(!dres || lddres % 4 == 0, "tcow_layernorm_bwd: dres stride %ld must be a multiple of 4", lddres);
+    TCOW_CHECK_ARG(lddx % 4 == 0, "tcow_layernorm_bwd: dx stride %ld must be a multiple of 4", lddx);
     TCOW_CHECK_ARG(!dx_cast || lddx_cast % 4 == 0, "tcow_layernorm_bwd: dx_cast stride must be a multiple of 4");
     const bool want_param_grads = dgamma != nullptr || dbeta != nullptr;
     TCOW_CHECK_ARG(!want_param_grads || (dgamma && dbeta && workspace && workspace_bytes >= tcow_layernorm_bwd_workspace_bytes(D)),

@@ -159,13 +159,14 @@ __device__ __forceinline__ void epi_row_apply(const NtParams& p, const EpiRow& o
         if (p.aux) st4(p.aux + (size_t)gm * p.ldaux + gn, v);
         v = gelu4(v);
     } else if (act == TCOW_ACT_DGELU) {
-        v = dgelu4(v, o.ext);
+        v = dgelu4(v, E::res(p) ? ld4(p.aux + (size_t)gm * p.ldaux + gn) : o.ext);      // (with a residual, o.ext holds the residual: the aux tile is read here)
     } else if (act == TCOW_ACT_GELU_DSAVE) {
         float4 g, d; gelu_both4(v, g, d);
         st4(p.aux + (size_t)gm * p.ldaux + gn, d);
         v = g;
     } else if (act == TCOW_ACT_MUL_AUX) {
-        v.x *= o.ext.x; v.y *= o.ext.y; v.z *= o.ext.z; v.w *= o.ext.w;
+        const float4 ax = E::res(p) ? ld4(p.aux + (size_t)gm * p.ldaux + gn) : o.ext;
+        v.x *= ax.x; v.y *= ax.y; v.z *= ax.z; v.w *= ax.w;
     }
     if (E::b2(p)) { const float4 c4 = ld4(p.bias2 + gn); v.x = fmaf(o.rs2, c4.x, v.x); v.y = fmaf(o.rs2, c4.y, v.y); v.z = fmaf(o.rs2, c4.z, v.z); v.w = fmaf(o.rs2, c4.w, v.w); }
     if (E::res(p)) { v.x += o.ext.x; v.y += o.ext.y; v.z += o.ext.z; v.w += o.ext.w; }

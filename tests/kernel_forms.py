@@ -1,4 +1,4 @@
-"""Helpers shared by test_gpu_layernorm_forms.py and test_gpu_glue_forms.py: outputs that live inside larger buffers pre-filled with a sentinel, so
+"""Helpers shared by test_gpu_layernorm_forms.py, test_gpu_glue_forms.py and test_gpu_gemm_nt.py: outputs that live inside larger buffers pre-filled with a sentinel, so
 that a kernel form which writes a dead lane, a pad column or a row past the end is seen (NaN for floats: it also poisons any result that read it)."""
 import torch
 
@@ -11,8 +11,8 @@ def bits(t):
 
 
 def guarded(rows, cols, pitch, dtype, device):
-    """([rows + 1, pitch] buffer of NaN, its [:rows, :cols] view): pitch - cols pad columns and one spare row."""
-    assert pitch > cols
+    """([rows + 1, pitch] buffer of NaN, its [:rows, :cols] view): pitch - cols pad columns (none for a dense pitch) and one spare row."""
+    assert pitch >= cols
     buf = torch.full((rows + 1, pitch), NAN, dtype=dtype, device=device)
     return buf, buf[:rows, :cols]
 

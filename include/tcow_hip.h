@@ -308,6 +308,18 @@ int tcow_im2col(void* stream, int dtype, int B, int T, int H, int W, int P, cons
  * embedding then splits into ONE rgb GEMM per clip (C = 3) plus a K = P*P mask-channel GEMM per query (C = 1). */
 int tcow_im2col_channels(void* stream, int dtype, int B, int T, int H, int W, int P, int C, const float* src,
                          int normalise, void* out);
+/* The adjoints of the two gathers above (the gradient of the frames and of the query mask).  The patch stride is the patch size, so every pixel
+ * sits in exactly one (row, column) of the patch matrix:
+ *   dst[b, c, t, hp*P + py, wp*P + px] = dA[(b*T + t)*S + 1 + hp*Wp + wp, c*P*P + py*P + px] * k_c * s
+ * with k_c = 1 / 0.225f on normalised rgb channels (an f32 division, as in the forward), 1 elsewhere, and s = *inv_scale (a device f32 scalar, read on the
+ * device: the inverse of a power-of-two loss scale) or 1 when inv_scale is NULL.  dA: f32 [B*T*S, lda], lda >= 4*P*P (C*P*P), lda % 4 == 0; its slot-0
+ * rows are never read.  Every element of an output is written exactly once: no atomics, nothing to clear first.
+ * d_rgb f32 (B,3,T,H,W) and d_query f32 (B,1,T,H,W): either may be NULL -- that gradient is not wanted, its columns are not read and nothing is written
+ * for it; both NULL is refused.  The channels form writes dst f32 (B,C,T,H,W) from the first C*P*P columns. */
+int tcow_col2im(void* stream, int B, int T, int H, int W, int P, const float* dA, long lda, float* d_rgb, float* d_query,
+                int pretrained_norm, const float* inv_scale);
+int tcow_col2im_channels(void* stream, int B, int T, int H, int W, int P, int C, const float* dA, long lda, int normalise,
+                         const float* inv_scale, float* dst);
 /* Input-pipeline gather (data/augs.py:150-203: frame sub-sampling, centre / random crop, horizontal flip, NEAREST resize composed into
  * index tables by tcow_amd/augs.py): out[c,t,y,x] = src[c, frame_idx[t], src_y[y], src_x[x]]; src (C,Tv,H,W), out (C,Tc,h,w), elements of
  * elem_bytes = 1 (uint8 segmentation / masks) or 4 (f32 frames); index tables are device int32 arrays with in-range entries. */

@@ -108,7 +108,9 @@ SIGNATURES = {
     'tcow_photometric': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, ctypes.POINTER(ctypes.c_int), _f, _f, _f, _f, _i, ctypes.POINTER(ctypes.c_float), _i,
                          _vp, _l, _vp]),
     'tcow_im2col_channels': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
-    'tcow_embed_fwd': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'tcow_col2im': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _l, _vp, _vp, _i, _vp]),
+    'tcow_col2im_channels': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _l, _i, _vp, _vp]),
+    'tcow_embed_fwd': (_i,[_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'tcow_embed_bwd': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i]),
     'tcow_cls_merge': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i]),
     'tcow_cls_merge_bwd_cast': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _l, _vp]),

@@ -34,6 +34,32 @@ __global__ void im2col_kernel(int B, int T_, int H, int W, int P, int Crgb, int 
     }
 }
 
+// ------------------------------------------------------------------------------------------ col2im
+// The adjoint of im2col_kernel.  The patch stride is the patch size, so every pixel sits in exactly one (row, column) of the patch matrix: a permutation
+// with a scale, no sums.  Walks the matrix side in order, as im2col_kernel does (16 bytes per thread, whole rows of 4 * (c1 - c0) * P * P bytes
+// contiguous), and writes the images in pieces of P * 4 bytes.  Channels c0 <= c < c1 only: c < Crgb goes to channel c of d_rgb (B,Crgb,T,H,W), the rest to
+// channel c - Crgb of d_qm (B,Cq,T,H,W); the slot-0 rows of dA are never read.  Channels below Cnorm take the 1 / 0.225 of the forward's normalisation (an
+// f32 division, as there); *inv_scale (device scalar, may be NULL) undoes a power-of-two loss scale on the way.
+__global__ void col2im_kernel(int B, int T_, int H, int W, int P, int Crgb, int Cq, int c0, int c1, int Cnorm, const float* __restrict__ dA, long lda,
+                              const float* __restrict__ inv_scale, float* __restrict__ d_rgb, float* __restrict__ d_qm) {
+    const int Hp = H / P, Wp = W / P, N = Hp * Wp, S = N + 1, PP = P * P;
+    const int q4 = (c1 - c0) * PP / 4;
+    const long total = (long)B * T_ * N * q4;
+    const float s = inv_scale ? *inv_scale : 1.0f;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long prow = i / q4; const int k = c0 * PP + (int)(i - prow * q4) * 4;
+        const int n = (int)(prow % N); const long bt = prow / N; const int t = (int)(bt % T_); const int b = (int)(bt / T_);
+        const int hp = n / Wp, wp = n - hp * Wp;
+        const int c = k / PP, rem = k - c * PP, py = rem / P, px = rem - py * P;
+        const int y = hp * P + py, x = wp * P + px;
+        float4 v = ld4(dA + (bt * S + 1 + n) * lda + k);
+        v.x *= s; v.y *= s; v.z *= s; v.w *= s;
+        if (c < Cnorm) { v.x /= 0.225f; v.y /= 0.225f; v.z /= 0.225f; v.w /= 0.225f; }
+        if (c < Crgb) st4(d_rgb + ((((size_t)b * Crgb + c) * T_ + t) * H + y) * W + x, v);
+        else st4(d_qm + ((((size_t)b * Cq + (c - Crgb)) * T_ + t) * H + y) * W + x, v);
+    }
+}
+
 // ------------------------------------------------------------------------------------------ embeddings
 // x[b,t,s,:] = (s == 0) ? cls + pos[0] : x + pos[s] + time[t]      (vision_tf.py:99-138; f32 residual stream)
 __global__ void embed_fwd_kernel(int B, int T_, int S, int D, float* __restrict__ x, const float* __restrict__ cls, const float* __restrict__ pos,
@@ -192,7 +218,31 @@ int tcow_im2col_channels(void* stream, int dtype, int B, int T_, int H, int W, i
     return TCOW_OK;
 }
 
-int tcow_embed_fwd(void* stream, int B, int T_, int S, int D, float* x, const float* cls, const float* pos, const float* time_embed) {
+int tcow_col2im(void* stream, int B, int T_, int H, int W, int P, const float* dA, long lda, float* d_rgb, float* d_query, int pretrained_norm,
+                const float* inv_scale) {
+    TCOW_CHECK_ARG(B > 0 && T_ > 0 && H > 0 && W > 0 && P > 0 && P % 4 == 0 && H % P == 0 && W % P == 0, "tcow_col2im: bad geometry B=%d T=%d H=%d W=%d P=%d", B, T_, H, W, P);
+    TCOW_CHECK_ARG(lda >= 4L * P * P && lda % 4 == 0, "tcow_col2im: lda=%ld must be a multiple of 4 and at least 4 * P * P = %d", lda, 4 * P * P);
+    TCOW_CHECK_ARG(dA && (d_rgb || d_query), "tcow_col2im: null pointer (dA, or both outputs)");
+    const int c0 = d_rgb ? 0 : 3, c1 = d_query ? 4 : 3;
+    const long total = (long)B * T_ * ((H / P) * (W / P)) * ((c1 - c0) * P * P / 4);
+    hipLaunchKernelGGL(col2im_kernel, dim3(gs_blocks(total)), dim3(256), 0, (hipStream_t)stream, B, T_, H, W, P, 3, 1, c0, c1, pretrained_norm ? 3 : 0, dA, lda, inv_scale,
+                       d_rgb, d_query);
+    TCOW_CHECK_LAUNCH();
+    return TCOW_OK;
+}
+
+int tcow_col2im_channels(void* stream, int B, int T_, int H, int W, int P, int C, const float* dA, long lda, int normalise, const float* inv_scale, float* dst) {
+    TCOW_CHECK_ARG(B > 0 && T_ > 0 && C > 0 && H > 0 && W > 0 && P > 0 && P % 4 == 0 && H % P == 0 && W % P == 0,
+                   "tcow_col2im_channels: bad geometry B=%d T=%d H=%d W=%d P=%d C=%d", B, T_, H, W, P, C);
+    TCOW_CHECK_ARG(lda >= (long)C * P * P && lda % 4 == 0, "tcow_col2im_channels: lda=%ld must be a multiple of 4 and at least C * P * P = %ld", lda, (long)C * P * P);
+    TCOW_CHECK_ARG(dA && dst, "tcow_col2im_channels: null pointer");
+    const long total = (long)B * T_ * ((H / P) * (W / P)) * (C * P * P / 4);
+    hipLaunchKernelGGL(col2im_kernel, dim3(gs_blocks(total)), dim3(256), 0, (hipStream_t)stream, B, T_, H, W, P, C, 0, 0, C, normalise ? C : 0, dA, lda, inv_scale, dst, dst);
+    TCOW_CHECK_LAUNCH();
+    return TCOW_OK;
+}
+
+int tcow_embed_fwd(void* stream, int B, int T_, int S, int D, float* x,const float* cls, const float* pos, const float* time_embed) {
     TCOW_CHECK_ARG(B > 0 && T_ > 0 && S > 1 && D % 4 == 0 && x && cls && pos && time_embed, "tcow_embed_fwd: bad arguments");
     hipLaunchKernelGGL(embed_fwd_kernel, dim3(gs_blocks((long)B * T_ * S * D / 4)), dim3(256), 0, (hipStream_t)stream, B, T_, S, D, x, cls, pos, time_embed);
     TCOW_CHECK_LAUNCH();

@@ -28,7 +28,7 @@ that produces dR1.  (The f32 parity modes keep the reference's op order.)
 How the file reads.  run_forward and run_backward are drivers.  Both build a _Ctx (the step's modes, geometry, attention shapes, allocation
 and operand look-ups) and address the parameters through module.layout (seeker.ParamLayout), never by position.  The forward walks
 _patch_embed, _embed, one _block_forward_* per block and _heads_forward; the backward walks _heads_backward (which chooses the binary16 loss
-scale, _loss_scale), one _block_backward_* per block and _embed_backward.  Where a parameter gradient lands, when its weight-gradient GEMM is
+scale, _loss_scale), one _block_backward_* per block, _embed_backward and -- when the frames or the query mask require grad -- _input_backward.  Where a parameter gradient lands, when its weight-gradient GEMM is
 launched and when its bucket goes to the data-parallel hook is all in _GradBuckets, whose docstring states the ordering rules;
 tests/test_ddp_gloo.py and tests/test_engine_host.py check them, and the launch schedule call for call, on the CPU.
 """
@@ -739,7 +739,9 @@ def _block_backward_divided(c, bk, i, q, st, dp, mask0, next_scale, dR3, G3):
 
 
 def _embed_backward(c, bk, sv, gX, Gpe):
-    """Embeddings (cls, pos, time) and patch embedding from gX [M,D] f32; Gpe = its operand copy * mask0 from block 0's LayerNorm backward."""
+    """Embeddings (cls, pos, time) and patch embedding from gX [M,D] f32; Gpe = its operand copy * mask0 from block 0's LayerNorm backward.
+    -> Gsum, the operand copy of gX summed over each clip's queries (shared rgb; None otherwise), which _input_backward takes as well."""
+    Gsum = None
     g, lay, grads, mask0 = c.g, c.lay, bk.grads, sv['mask0']
     B, T, S, D = g['B'], g['T'], g['S'], g['D']
     dpos_eff = grads[lay.pos][0] if sv['pos_idx'] is None else c.E(S, D, dtype=f32)
@@ -764,10 +766,47 @@ def _embed_backward(c, bk, sv, gX, Gpe):
     else:
         ops.gemm_tn(c.gmode, Gpe, sv['A_pe'], dWpe)
     grads[lay.patch_b].copy_(dtime_eff.sum(0))       # bias gradient = sum over all patch rows
+    return Gsum
+
+
+def _input_backward(c, bk, sv, G, want_rgb, want_qm, Gsum=None):
+    """Gradients of the frames and of the query mask -> (d_rgb or None, d_qm or None), f32 in the shapes of the inputs.  The patch embedding is
+    X = A W_pe^T with A = im2col(cat[rgb, mask]), so dA = G W_pe with the operand G of the patch-embed weight gradient (dR0 * mask0: the cls rows take
+    no part) and the transposed operand copy of W_pe the forward already made; col2im, the adjoint of im2col, is a permutation (ops.col2im).  Only
+    the rows of W_pe^T whose channels are wanted are multiplied.  G carries the binary16 loss scale, so dA does: col2im multiplies it out (exact, a
+    power of two, read on the device) whether or not the parameter buckets stay scaled for the optimizer -- these gradients go back through autograd
+    at once.  Runs behind publish('g0'): no bucket is touched, and a data-parallel all-reduce of the last bucket overlaps the two launches."""
+    module, g = c.module, c.g
+    B, T, S, M, P = g['B'], g['T'], g['S'], g['M'], g['P']
+    H, W, PP = g['Hp'] * P, g['Wp'] * P, P * P
+    Wt = c.Wt(bk.params[c.lay.patch_w])                                 # [4 P^2, D], channel-major rows (vit.py:233)
+    norm, inv = module.tracker_pretrained, bk.inv_gscale
+    if not isinstance(sv['A_pe'], tuple):
+        dA = c.E(M, 4 * PP, dtype=f32)
+        lo, hi = (0 if want_rgb else 3) * PP, (4 if want_qm else 3) * PP
+        ops.gemm_nt(c.gmode, G, Wt[lo:hi], dA[:, lo:hi])
+        d_rgb = c.E(B, 3, T, H, W, dtype=f32) if want_rgb else None
+        d_qm = c.E(B, 1, T, H, W, dtype=f32) if want_qm else None
+        ops.col2im(dA, B, T, H, W, P, norm, d_rgb, d_qm, inv_scale=inv)
+        return d_rgb, d_qm
+    # shared rgb: a clip's frames feed all its queries, so their gradient is the sum over the queries -- taken on the operand (Gsum), before the product
+    d_rgb = d_qm = None
+    if want_rgb:
+        Bc = Gsum.shape[0] // (T * S)
+        dA_rgb = c.E(Bc * T * S, 3 * PP, dtype=f32)
+        ops.gemm_nt(c.gmode, Gsum, Wt[:3 * PP], dA_rgb)
+        d_rgb = ops.col2im_channels(dA_rgb, P, norm, c.E(Bc, 3, T, H, W, dtype=f32), inv_scale=inv)
+    if want_qm:
+        dA_m = c.E(M, PP, dtype=f32)
+        ops.gemm_nt(c.gmode, G, Wt[3 * PP:], dA_m)
+        d_qm = ops.col2im_channels(dA_m, P, False, c.E(B, 1, T, H, W, dtype=f32), inv_scale=inv)
+    return d_rgb, d_qm
 
 
 def run_backward(module, sv, params, d_mask, d_flags):
-    """-> the parameter gradients, in the order of `params` (None where a parameter takes no part), every bucket published."""
+    """-> the parameter gradients, in the order of `params` (None where a parameter takes no part), every bucket published.
+    sv['want_inputs'] = (frames, query mask), set by SeekerFunction.forward: which input gradients are wanted as well; they are left in
+    sv['d_inputs'] (None where not wanted)."""
     c = _Ctx(module, sv['g'], sv['X_final'].device, True)
     have_flags = module.flag_channels > 0 and d_flags is not None and d_flags.numel() > 0
     bk = _GradBuckets(c, params, have_flags)
@@ -779,9 +818,11 @@ def run_backward(module, sv, params, d_mask, d_flags):
         dR, G = block_backward(c, bk, i, params[c.lay.block(i)], sv['blocks'][i], sv['dps'][i], sv['mask0'], next_scale, dR, G)
         bk.end_block(i, sv)
     bk.finish_late()
-    _embed_backward(c, bk, sv, dR, G)
+    Gsum = _embed_backward(c, bk, sv, dR, G)
     bk.publish('g0', bk.flat)
     module.pending_inv_scale = bk.inv_gscale if bk.defer_unscale else None
+    want_rgb, want_qm = sv.get('want_inputs', (False, False))
+    sv['d_inputs'] = _input_backward(c, bk, sv, G, want_rgb, want_qm, Gsum) if want_rgb or want_qm else (None, None)
     if bk.hook is not None and hasattr(bk.hook, 'finish'):
         # The collectives launched above were overlapped with the remaining backward compute; they must be complete (in
         # stream order) before autograd copies the bucket views into param.grad, so the hook is drained here.
@@ -794,9 +835,11 @@ class SeekerFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, module, rgb, qm, *params):
-        need = any(ctx.needs_input_grad[3:])
+        need = any(ctx.needs_input_grad[1:])      # a parameter, the frames (1) or the query mask (2)
         ctx.set_materialize_grads(False)      # an unused output (e.g. output_flags in Kubric training) arrives as None, not zeros
         out_mask, flags, sv = run_forward(module, rgb, qm, params, save=need)
+        if sv is not None:
+            sv['want_inputs'] = (ctx.needs_input_grad[1], ctx.needs_input_grad[2])
         ctx.module = module
         ctx.sv = sv
         ctx.params = params
@@ -807,6 +850,7 @@ class SeekerFunction(torch.autograd.Function):
         if ctx.sv is None:
             raise ops.L.TcowError('backward called on a forward that did not save activations')
         grads = run_backward(ctx.module, ctx.sv, ctx.params, d_mask, d_flags)
+        d_rgb, d_qm = ctx.sv['d_inputs']
         ctx.sv = None
         out = []
         persistent = getattr(ctx.module, 'persistent_grads', False)
@@ -820,4 +864,4 @@ class SeekerFunction(torch.autograd.Function):
                 out.append(None)
             else:
                 out.append(gr)
-        return (None, None, None, *out)
+        return (None, d_rgb, d_qm, *out)

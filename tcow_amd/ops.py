@@ -489,6 +489,38 @@ def im2col_channels(mode, src, P, normalise, out):
     return out
 
 
+def _col2im_operand(who, dA, rows, cols, inv_scale):
+    if inv_scale is not None and (inv_scale.dtype != torch.float32 or inv_scale.numel() != 1):
+        raise L.TcowError(f'{who}: inv_scale must be one f32 element on the device, got {inv_scale.dtype} {tuple(inv_scale.shape)}')
+    if dA.dtype != torch.float32 or dA.dim() != 2 or dA.stride(1) != 1 or dA.shape[0] != rows or dA.shape[1] < cols:
+        raise L.TcowError(f'{who}: dA must be an f32 matrix of {rows} rows and at least {cols} columns with unit column stride, got {dA.dtype} {tuple(dA.shape)}')
+
+
+def _col2im_image(who, name, t, shape):
+    if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous()):
+        raise L.TcowError(f'{who}: {name} must be a contiguous f32 tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}')
+
+
+def col2im(dA, B, T, H, W, P, pretrained_norm, d_rgb, d_query, inv_scale=None):
+    """The adjoint of im2col: dA f32 [B*T*S, >= 4*P*P] (a row pitch of its own is fine) -> d_rgb (B,3,T,H,W) / d_query (B,1,T,H,W) f32, either may be
+    None (not wanted: not written); inv_scale: device f32 scalar multiplied in, or None (see tcow_col2im)."""
+    _need_cuda(dA, d_rgb, d_query, inv_scale)
+    _col2im_operand('col2im', dA, B * T * ((H // P) * (W // P) + 1), 4 * P * P, inv_scale)
+    _col2im_image('col2im', 'd_rgb', d_rgb, (B, 3, T, H, W)); _col2im_image('col2im', 'd_query', d_query, (B, 1, T, H, W))
+    L.check(L.lib().tcow_col2im(_stream(), B, T, H, W, P, dA.data_ptr(), dA.stride(0), _p(d_rgb), _p(d_query), int(pretrained_norm), _p(inv_scale)), 'tcow_col2im')
+    return d_rgb, d_query
+
+
+def col2im_channels(dA, P, normalise, dst, inv_scale=None):
+    """dA f32 [B*T*S, >= C*P*P] -> dst (B,C,T,H,W) f32 (see tcow_col2im_channels)."""
+    _need_cuda(dA, dst, inv_scale)
+    B, C, T, H, W = dst.shape
+    _col2im_operand('col2im_channels', dA, B * T * ((H // P) * (W // P) + 1), C * P * P, inv_scale)
+    _col2im_image('col2im_channels', 'dst', dst, (B, C, T, H, W))
+    L.check(L.lib().tcow_col2im_channels(_stream(), B, T, H, W, P, C, dA.data_ptr(), dA.stride(0), int(normalise), _p(inv_scale), dst.data_ptr()), 'tcow_col2im_channels')
+    return dst
+
+
 def embed_fwd(x, B, T, S, cls, pos, time_embed):
     L.check(L.lib().tcow_embed_fwd(_stream(), B, T, S, x.shape[1], x.data_ptr(), cls.data_ptr(), pos.data_ptr(), time_embed.data_ptr()), 'tcow_embed_fwd')
     return x

@@ -15,7 +15,9 @@
 typedef _Float16 tcow_h16;
 #define TCOW_MFMA_32x32x16_H16 __builtin_amdgcn_mfma_f32_32x32x16_f16
 #define TCOW_MFMA_32x32x16_H16_ASM "v_mfma_f32_32x32x16_f16"
+#define TCOW_MFMA_16x16x32_H16 __builtin_amdgcn_mfma_f32_16x16x32_f16
 #else
+#define TCOW_MFMA_16x16x32_H16 __builtin_amdgcn_mfma_f32_16x16x32_bf16
 typedef __bf16 tcow_h16;
 #define TCOW_MFMA_32x32x16_H16 __builtin_amdgcn_mfma_f32_32x32x16_bf16
 #define TCOW_MFMA_32x32x16_H16_ASM "v_mfma_f32_32x32x16_bf16"

@@ -5,13 +5,24 @@
 // (8 consecutive m for one column) are gathered with the LDS transpose read ds_read_b64_tr_b16:
 // within a 16-lane group lane 4r+c supplies the address of row r / 4-element column quad c of a [4][16]
 // block and receives column (lane&15), rows 0..3 (verified on hardware, profiles/r01_hw_probe.txt).
-// LDS rows are 256 B (128 columns); 16-byte chunk c of row r sits at chunk position c ^ ((r&3)<<2) so the four
-// rows a half-wave touches per read fall into four different 64-byte bank segments.
+//
+// Two kernels, two fragment shapes:
+//   128-tile kernel (gemm_tn_bf16_kernel; small shapes): 32x32x16 MFMAs, a fragment is 32 columns x 16 tokens (lane l: tokens 8 (l >> 5) ... + 7).
+//     LDS rows are 256 B (128 columns); 16-byte chunk c of row r sits at chunk position c ^ ((r&3)<<2) so the four rows a half-wave touches
+//     per read fall into four different 64-byte bank segments.
+//   256-tile kernels (tn256_body; every weight of the training step): 16x16x32 MFMAs, a fragment is 16 columns x 32 tokens (lane l: column
+//     l & 15, tokens 8 (l >> 4) ... + 7), one "lo" + one "hi" transpose read each.  A half-wave then touches EIGHT rows, {b ... b+3, b+8 ... b+11},
+//     32 bytes of each: the image of the 512-byte rows is c ^ ((r&3)<<2) ^ (((r>>3)&1)<<1), eight different 32-byte bank segments
+//     (gemm_tn_layout.h: the image, the loads' source permutation, the read addresses; checked lane by lane on the CPU by
+//     tools/tn_layout_check.cpp).  X is the A operand and dY the B operand, so a lane's four accumulators of a 16 x 16 block are four
+//     consecutive k of one n: the slab store is one 16-byte store per block.  The f32 sums group 32 tokens per MFMA.
 #include <stdlib.h>
+#include <type_traits>
 
 #include "common.h"
 #include "internal.h"
 #include "gemm_glds.h"
+#include "gemm_tn_layout.h"
 
 namespace {
 
@@ -173,11 +184,13 @@ constexpr int T2_STAGE = 2 * T2_TILE;
 constexpr int T2_LDS = 2 * T2_STAGE;            // 128 KiB
 
 // one workgroup of the 256-tile weight-gradient GEMM `p`: pid = slice * tiles + tile
-// SCHED = 1 (round 4): the stage's ONE wait + barrier sits between the third and the fourth k-step instead of at the stage end: the fourth
-// k-step's fragments are in registers by then, so its MFMAs run right behind the barrier while the NEXT stage's first fragments are read and the
-// stage after next is requested into the buffer this stage has just released -- no stage boundary at which all eight waves wait for the barrier,
-// then for their first transpose reads, with the matrix pipe idle.  (The round-3 order -- wait + barrier at the stage end -- is gone: 553-566 vs 504 us per block.)
-// SCHED = 2: the interleaved loop further down, for whole tiles with 32-bit offsets (tn_whole).
+// Both SCHED values run ONE stage loop (further down): four blocks of 16 MFMAs per stage, the next block's transpose reads one behind each MFMA, and
+// the stage's ONE wait + barrier between the third and the fourth block instead of at the stage end: the fourth block's fragments are in registers
+// by then, so its MFMAs run right behind the barrier while the NEXT stage's first fragments are read and the stage after next is requested into
+// the buffer this stage has just released -- no stage boundary at which all eight waves wait for the barrier, then for their first transpose
+// reads, with the matrix pipe idle.  (The round-3 order -- wait + barrier at the stage end -- is gone: 553-566 vs 504 us per block.)
+// SCHED = 2, for whole tiles with 32-bit offsets (tn_whole): every stage by buffer loads, issued one behind every second MFMA of the fourth block.
+// SCHED = 1: the general addressing (edge tiles, 64-bit offsets); the stage after next is requested in one piece behind the barrier.
 template <int SCHED>
 __device__ __forceinline__ void tn256_body(const TnParams& p, const int pid, char* smem) {
     const int tid = threadIdx.x, lane = tid & 63;
@@ -191,22 +204,23 @@ __device__ __forceinline__ void tn256_body(const TnParams& p, const int pid, cha
     const int mend = (mbeg + p.mps < p.M) ? mbeg + p.mps : p.M;
 
     // direct-to-LDS loads: a wave-load covers 2 tile rows x 512 B; wave w issues wave-loads 4w..4w+3 of each operand per stage
-    const int lrow = lane >> 5, cl = lane & 31;
+    const int lrow = lane >> 5;
     const bf16_t* zero = reinterpret_cast<const bf16_t*>(&g_zero16);
-    int ycol[2], xcol[2];                                         // source column of this lane for even / odd wave-loads (row & 3 differs)
+    int ycol[2], xcol[2];                                         // source column of this lane for even / odd wave-loads (the row's swizzle differs)
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
-        const int r3 = (e << 1) | lrow;                            // (tile row) & 3 for wave-load q with q & 1 == e
-        const int sc = cl ^ (r3 << 2);
+        const int sc = tnl_load_chunk(wave, e, lane);              // rows 8 wave + 2 j + lrow: the swizzle depends on j through j & 1 only
         ycol[e] = n0 + sc * 8; xcol[e] = k0 + sc * 8;
     }
-    f32x16 acc[4][2];
+    // accumulators of 16x16x32 MFMAs with X as the A and dY as the B operand: acc[i][j] is the block of columns n = 16 i ... + 15 and
+    // k = 16 j ... + 15 of the wave's 128 x 64, lane l holding n = l & 15 and the FOUR CONSECUTIVE k = 4 (l >> 4) ... + 3 -- one 16-byte store each
+    f32x4 acc[8][4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < 8; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+        for (int j = 0; j < 4; ++j)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+            for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
 
     auto issue = [&](int mt, int stage) {
         char* sy = smem + stage * T2_STAGE;
@@ -240,19 +254,12 @@ __device__ __forceinline__ void tn256_body(const TnParams& p, const int pid, cha
         TCOW_BUFFER_GLDS16(yv1, srd_y, sy + 3 * ry, dy + 3072); TCOW_BUFFER_GLDS16(xv1, srd_x, sx + 3 * rx, dx + 3072);
     };
     // transpose-read addressing (constant over the loop)
-    const int q16 = lane & 15, g16 = (lane >> 4) & 1, hi = lane >> 5;
-    const int rr = 8 * hi + (q16 >> 2);
-    int y_off[4], x_off[2];
+    // (gemm_tn_layout.h: the "lo" read of the fragment of 16 columns, first MFMA step; "hi" and the second step are immediate offsets)
+    int y_off[8], x_off[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int cy = wm * 128 + i * 32 + 16 * g16 + 4 * (q16 & 3);
-        y_off[i] = rr * T2_ROWB + ((((cy >> 3) ^ ((q16 >> 2) << 2))) << 4) + (cy & 7) * 2;
-    }
+    for (int i = 0; i < 8; ++i) y_off[i] = tnl_read_off(lane, wm * 128 + i * 16, 0);
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int cx = wn * 64 + j * 32 + 16 * g16 + 4 * (q16 & 3);
-        x_off[j] = rr * T2_ROWB + ((((cx >> 3) ^ ((q16 >> 2) << 2))) << 4) + (cx & 7) * 2;
-    }
+    for (int j = 0; j < 4; ++j) x_off[j] = tnl_read_off(lane, wn * 64 + j * 16, 0);
 
     // column-sum duty (bias gradient): column cs_col of the dY tile, rows [cs_r0, cs_r1) of every stage; the tiles_k workgroups
     // that share a dY tile split its 64 rows between them, and each between its two thread halves
@@ -262,13 +269,13 @@ __device__ __forceinline__ void tn256_body(const TnParams& p, const int pid, cha
     const int cs_lo = pk * p.rows_per_pk, cs_hi = (cs_lo + p.rows_per_pk < T2_MC) ? cs_lo + p.rows_per_pk : T2_MC;
     const int cs_chunk = tid & 31, cs_rg = tid >> 5;
     float csum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    // (a macro, expanded in both stage loops: as a lambda the same text compiles to different address arithmetic)
+    // (a macro: as a lambda the same text compiles to different address arithmetic)
 #define TN_COLSUM(sy)                                                                                                              \
     if (p.bias_part) {                                                                                                             \
         _Pragma("unroll") for (int u = 0; u < 4; ++u) {                                                                            \
             const int r = cs_lo + cs_rg + 16 * u;                                                                                  \
             if (r < cs_hi) {                                                                                                       \
-                const uint4 v = *reinterpret_cast<const uint4*>((sy) + r * T2_ROWB + ((cs_chunk ^ ((r & 3) << 2)) << 4));          \
+                const uint4 v = *reinterpret_cast<const uint4*>((sy) + tnl_colsum_off(r, cs_chunk));                               \
                 csum[0] += bflo(v.x); csum[1] += bfhi(v.x); csum[2] += bflo(v.y); csum[3] += bfhi(v.y);                            \
                 csum[4] += bflo(v.z); csum[5] += bfhi(v.z); csum[6] += bflo(v.w); csum[7] += bfhi(v.w);                            \
             }                                                                                                                      \
@@ -294,115 +301,120 @@ __device__ __forceinline__ void tn256_body(const TnParams& p, const int pid, cha
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
-    // Transpose reads software-pipelined by hand, as in the NT kernels: the 12 ds_read_b64_tr_b16 of k-step ks+1 are issued
-    // before the 8 MFMAs of k-step ks (inline asm + counted lgkmcnt; hipcc alone waits for each group right before its use).
+    // The stage loop.  A stage (64 token rows) is two MFMA steps of 32 tokens; a step is 8 dY x 4 X fragments = 32 MFMAs, issued as two blocks of
+    // 16: block P multiplies the step's dY fragments 0-3 (set FY[0]), block Q its fragments 4-7 (FY[1]), both with the step's four X fragments
+    // (FX[xb], double-buffered over steps).  A block's MFMAs run X-fragment-major, so its first four need one X fragment and its dY set.
+    // A 16-MFMA block is as long as an 8-MFMA k-step of the 32x32x16 loop this one replaces, and the four blocks of a stage keep that loop's frame:
+    // ONE wait + barrier per stage, between the third and the fourth block; the fourth block carries the 8 buffer loads of the stage after next
+    // (into the buffer the barrier has released) and reads its fragments from the NEXT stage.
+    // Transpose reads (inline asm, counted lgkmcnt: hipcc knows nothing of them): ONE behind each of the first 12 MFMAs of a block, 24 per step.
+    //   P issues   X2 X3 (this step, used by its own MFMAs 8.. and 12..), then FY[1] 0-3 (this step, for Q)
+    //   Q issues   X0 of the next step (other FX set), FY[0] 0-3 of the next step, X1 of the next step
+    // each as a "lo" and a "hi" read.  Reads return in order, so "at most n outstanding" names the fragment an MFMA is about to use; the n below
+    // are (reads issued so far) - (reads up to and including that fragment).
     typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     const uint32_t lds0 = (uint32_t)(uintptr_t)(LDS_PTR(char))smem;
-    uint32_t ya[4], xa[2];
+    uint32_t ya[8], xa[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) ya[i] = lds0 + (uint32_t)y_off[i];
+    for (int i = 0; i < 8; ++i) ya[i] = lds0 + (uint32_t)y_off[i];
 #pragma unroll
-    for (int j = 0; j < 2; ++j) xa[j] = lds0 + (uint32_t)x_off[j];
-    u32x2 fyl[2][4], fyh[2][4], fxl[2][2], fxh[2][2];
-#define TCOW_TRR(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(off))
-#define TCOW_TN_READ(buf, ks, so)                                                                                          \
-    do {                                                                                                                   \
-        _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                                    \
-            TCOW_TRR(fxl[buf][j], xa[j] + (so), T2_TILE + (ks) * 16 * T2_ROWB);                                            \
-            TCOW_TRR(fxh[buf][j], xa[j] + (so), T2_TILE + (ks) * 16 * T2_ROWB + 4 * T2_ROWB);                              \
-        }                                                                                                                  \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                                    \
-            TCOW_TRR(fyl[buf][i], ya[i] + (so), (ks) * 16 * T2_ROWB);                                                      \
-            TCOW_TRR(fyh[buf][i], ya[i] + (so), (ks) * 16 * T2_ROWB + 4 * T2_ROWB);                                        \
-        }                                                                                                                  \
-    } while (0)
-#define TCOW_TN_FRAG(lo, hi) __builtin_bit_cast(bf16x8, (u32x4){(lo).x, (lo).y, (hi).x, (hi).y})
-#define TCOW_TN_MFMA8(buf)                                                                                                 \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                          \
-        _Pragma("unroll") for (int j = 0; j < 2; ++j)                                                                      \
-            acc[i][j] = TCOW_MFMA_32x32x16_H16(TCOW_TN_FRAG(fyl[buf][i], fyh[buf][i]), TCOW_TN_FRAG(fxl[buf][j], fxh[buf][j]), acc[i][j], 0, 0, 0)
-
-    if (nmt > 0) TCOW_TN_READ(0, 0, 0u);
-    if constexpr (SCHED == 2) {
-        // Every k-step as ONE block: its 8 MFMAs with the NEXT k-step's 12 transpose reads behind the first six of them (two each), the waits
-        // counted per fragment -- issued as a burst before the MFMAs, the reads of all 8 waves queue up at the LDS while the MFMA pipe idles,
-        // and then the LDS idles under the MFMAs: reads-only 30 us + MFMAs-only 60 us = 92 us measured with the loads off, no overlap at all
-        // (profiles/r04_ubench_tn_ab.txt).  The fourth k-step also carries the 8 buffer loads of stage it+2, one behind each MFMA.
+    for (int j = 0; j < 4; ++j) xa[j] = lds0 + (uint32_t)(T2_TILE + x_off[j]);
+    u32x2 fyl[2][4], fyh[2][4], fxl[2][4], fxh[2][4];
+    constexpr int STEPB = TNL_STEP * T2_ROWB;                        // bytes from the first MFMA step of a stage to the second
+#define TN_SB __builtin_amdgcn_sched_barrier(0)
+#define TN_TRR(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(off)); TN_SB
+#define TN_RXL(xb, j, OFF) TN_TRR(fxl[xb][j], xa[j], (OFF))
+#define TN_RXH(xb, j, OFF) TN_TRR(fxh[xb][j], xa[j], (OFF) + TNL_HI)
+#define TN_RYL(h, i, OFF) TN_TRR(fyl[h][i], ya[4 * (h) + (i)], (OFF))
+#define TN_RYH(h, i, OFF) TN_TRR(fyh[h][i], ya[4 * (h) + (i)], (OFF) + TNL_HI)
+#define TN_FRAG(lo, hi) __builtin_bit_cast(bf16x8, (u32x4){(lo).x, (lo).y, (hi).x, (hi).y})
+#define TN_WAIT(n) asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory"); TN_SB
+#define TN_MF(h, xb, i, j)                                                                                                                  \
+    acc[4 * (h) + (i)][j] = TCOW_MFMA_16x16x32_H16(TN_FRAG(fxl[xb][j], fxh[xb][j]), TN_FRAG(fyl[h][i], fyh[h][i]), acc[4 * (h) + (i)][j], 0, 0, 0); TN_SB
 #define TN_NOP do { } while (0)
-#define TN_MF(cur, i, j) acc[i][j] = TCOW_MFMA_32x32x16_H16(TCOW_TN_FRAG(fyl[cur][i], fyh[cur][i]), TCOW_TN_FRAG(fxl[cur][j], fxh[cur][j]), acc[i][j], 0, 0, 0); \
-                    __builtin_amdgcn_sched_barrier(0)
-#define TN_BLK(cur, nxt, OFFK, son, W0, B0, B1, B2, B3, B4, B5, B6, B7)                                                                  \
-    do {                                                                                                                                 \
-        asm volatile("s_waitcnt lgkmcnt(" #W0 ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0);                     \
-        TN_MF(cur, 0, 0); TCOW_TRR(fxl[nxt][0], xa[0] + (son), T2_TILE + (OFFK)); TCOW_TRR(fxh[nxt][0], xa[0] + (son), T2_TILE + (OFFK) + 4 * T2_ROWB); B0; \
-        TN_MF(cur, 0, 1); TCOW_TRR(fxl[nxt][1], xa[1] + (son), T2_TILE + (OFFK)); TCOW_TRR(fxh[nxt][1], xa[1] + (son), T2_TILE + (OFFK) + 4 * T2_ROWB); B1; \
-        TN_MF(cur, 1, 0); TCOW_TRR(fyl[nxt][0], ya[0] + (son), (OFFK)); TCOW_TRR(fyh[nxt][0], ya[0] + (son), (OFFK) + 4 * T2_ROWB); B2;              \
-        TN_MF(cur, 1, 1); TCOW_TRR(fyl[nxt][1], ya[1] + (son), (OFFK)); TCOW_TRR(fyh[nxt][1], ya[1] + (son), (OFFK) + 4 * T2_ROWB); B3;              \
-        asm volatile("s_waitcnt lgkmcnt(10)" ::: "memory"); __builtin_amdgcn_sched_barrier(0);    /* the previous block's fy[2] */ \
-        TN_MF(cur, 2, 0); TCOW_TRR(fyl[nxt][2], ya[2] + (son), (OFFK)); TCOW_TRR(fyh[nxt][2], ya[2] + (son), (OFFK) + 4 * T2_ROWB); B4;              \
-        TN_MF(cur, 2, 1); TCOW_TRR(fyl[nxt][3], ya[3] + (son), (OFFK)); TCOW_TRR(fyh[nxt][3], ya[3] + (son), (OFFK) + 4 * T2_ROWB); B5;              \
-        asm volatile("s_waitcnt lgkmcnt(12)" ::: "memory"); __builtin_amdgcn_sched_barrier(0);    /* ... and its fy[3] */  \
-        TN_MF(cur, 3, 0); B6;                                                                                                            \
-        TN_MF(cur, 3, 1); B7;                                                                                                            \
+    // block P of the step at byte offset OFF of the stage: 12 reads of block Q (X0, Y0 Y1 Y2 Y3, X1) are outstanding at most on entry
+#define TN_BLK_P(xb, OFF)                                                                                                                   \
+    do {                                                                                                                                    \
+        TN_WAIT(8); TN_MF(0, xb, 0, 0); TN_RXL(xb, 2, OFF);                              /* X0, Y0 */                                        \
+        TN_WAIT(7); TN_MF(0, xb, 1, 0); TN_RXH(xb, 2, OFF);                              /* Y1 */                                            \
+        TN_WAIT(6); TN_MF(0, xb, 2, 0); TN_RXL(xb, 3, OFF);                              /* Y2 */                                            \
+        TN_WAIT(5); TN_MF(0, xb, 3, 0); TN_RXH(xb, 3, OFF);                              /* Y3 */                                            \
+        TN_WAIT(4); TN_MF(0, xb, 0, 1); TN_RYL(1, 0, OFF);                               /* X1: all of block Q's */                          \
+        TN_MF(0, xb, 1, 1); TN_RYH(1, 0, OFF);                                                                                              \
+        TN_MF(0, xb, 2, 1); TN_RYL(1, 1, OFF);                                                                                              \
+        TN_MF(0, xb, 3, 1); TN_RYH(1, 1, OFF);                                                                                              \
+        TN_WAIT(6); TN_MF(0, xb, 0, 2); TN_RYL(1, 2, OFF);                               /* X2: 2 of this block's 8 */                       \
+        TN_MF(0, xb, 1, 2); TN_RYH(1, 2, OFF);                                                                                              \
+        TN_MF(0, xb, 2, 2); TN_RYL(1, 3, OFF);                                                                                              \
+        TN_MF(0, xb, 3, 2); TN_RYH(1, 3, OFF);                                                                                              \
+        TN_WAIT(8); TN_MF(0, xb, 0, 3);                                                  /* X3: 4 of this block's 12 */                      \
+        TN_MF(0, xb, 1, 3); TN_MF(0, xb, 2, 3); TN_MF(0, xb, 3, 3);                                                                         \
     } while (0)
-        for (int it = 0; it < nmt; ++it) {
-            const int stage = it & 1;
-            const uint32_t so = (uint32_t)stage * T2_STAGE;
-            const char* sy = smem + stage * T2_STAGE;
-            TN_BLK(0, 1, 1 * 16 * T2_ROWB, so, 4, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP);
-            TN_BLK(1, 0, 2 * 16 * T2_ROWB, so, 4, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP);
-            TN_BLK(0, 1, 3 * 16 * T2_ROWB, so, 4, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP);
-            TN_COLSUM(sy)
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            __syncthreads();
-            {
-                const int mt2 = mbeg + (it + 2) * T2_MC;
-                const bool more = it + 2 < nmt;
-                const uint32_t dy = lds_base + so + wave * 4096, dx = dy + T2_TILE;
-                const uint32_t by = (uint32_t)((long)(mt2 + wave * 8) * p.ldy * 2), bx = (uint32_t)((long)(mt2 + wave * 8) * p.ldx * 2);
-                const uint32_t yw0 = more ? yv0 : 0x80000000u, yw1 = more ? yv1 : 0x80000000u;     // (the per-lane offset is the range-checked one)
-                const uint32_t xw0 = more ? xv0 : 0x80000000u, xw1 = more ? xv1 : 0x80000000u;
-                const uint32_t ry = (uint32_t)(2 * p.ldy * 2), rx = (uint32_t)(2 * p.ldx * 2);
-                const uint32_t sn = so ^ (uint32_t)T2_STAGE;
-                TN_BLK(1, 0, 0, sn, 0, TCOW_BUFFER_GLDS16(yw0, srd_y, by, dy), TCOW_BUFFER_GLDS16(xw0, srd_x, bx, dx), TCOW_BUFFER_GLDS16(yw1, srd_y, by + ry, dy + 1024),
-                       TCOW_BUFFER_GLDS16(xw1, srd_x, bx + rx, dx + 1024), TCOW_BUFFER_GLDS16(yw0, srd_y, by + 2 * ry, dy + 2048), TCOW_BUFFER_GLDS16(xw0, srd_x, bx + 2 * rx, dx + 2048),
-                       TCOW_BUFFER_GLDS16(yw1, srd_y, by + 3 * ry, dy + 3072), TCOW_BUFFER_GLDS16(xw1, srd_x, bx + 3 * rx, dx + 3072));
-            }
+    // block Q: block P's 12 reads (X2, X3, Y0 Y1 Y2 Y3 of FY[1]) are outstanding at most on entry.  NOFF: byte offset of the NEXT step from the
+    // stage that ya / xa point to; nb: the FX set of that step; L0 ... L7: the load slots, behind every second MFMA.
+#define TN_BLK_Q(xb, nb, NOFF, L0, L1, L2, L3, L4, L5, L6, L7)                                                                              \
+    do {                                                                                                                                    \
+        TN_WAIT(6); TN_MF(1, xb, 0, 0); TN_RXL(nb, 0, NOFF);                             /* X2, X3, Y0 */                                    \
+        TN_WAIT(5); TN_MF(1, xb, 1, 0); TN_RXH(nb, 0, NOFF); L0; TN_SB;                  /* Y1 */                                            \
+        TN_WAIT(4); TN_MF(1, xb, 2, 0); TN_RYL(0, 0, NOFF);                              /* Y2 */                                            \
+        TN_WAIT(3); TN_MF(1, xb, 3, 0); TN_RYH(0, 0, NOFF); L1; TN_SB;                   /* Y3: all of block P's */                          \
+        TN_MF(1, xb, 0, 1); TN_RYL(0, 1, NOFF);                                                                                             \
+        TN_MF(1, xb, 1, 1); TN_RYH(0, 1, NOFF); L2; TN_SB;                                                                                  \
+        TN_MF(1, xb, 2, 1); TN_RYL(0, 2, NOFF);                                                                                             \
+        TN_MF(1, xb, 3, 1); TN_RYH(0, 2, NOFF); L3; TN_SB;                                                                                  \
+        TN_MF(1, xb, 0, 2); TN_RYL(0, 3, NOFF);                                                                                             \
+        TN_MF(1, xb, 1, 2); TN_RYH(0, 3, NOFF); L4; TN_SB;                                                                                  \
+        TN_MF(1, xb, 2, 2); TN_RXL(nb, 1, NOFF);                                                                                            \
+        TN_MF(1, xb, 3, 2); TN_RXH(nb, 1, NOFF); L5; TN_SB;                                                                                 \
+        TN_MF(1, xb, 0, 3); TN_MF(1, xb, 1, 3); L6; TN_SB;                                                                                  \
+        TN_MF(1, xb, 2, 3); TN_MF(1, xb, 3, 3); L7; TN_SB;                                                                                  \
+    } while (0)
+
+    if (nmt > 0) {       // what block Q of a stage before the first would have issued
+        TN_RXL(0, 0, 0); TN_RXH(0, 0, 0);
+        TN_RYL(0, 0, 0); TN_RYH(0, 0, 0); TN_RYL(0, 1, 0); TN_RYH(0, 1, 0); TN_RYL(0, 2, 0); TN_RYH(0, 2, 0); TN_RYL(0, 3, 0); TN_RYH(0, 3, 0);
+        TN_RXL(0, 1, 0); TN_RXH(0, 1, 0);
+    }
+    for (int it = 0; it < nmt; ++it) {
+        const int stage = it & 1;
+        const uint32_t so = (uint32_t)stage * T2_STAGE;
+        const char* sy = smem + stage * T2_STAGE;
+        TN_BLK_P(0, 0);
+        TN_BLK_Q(0, 1, STEPB, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP);
+        TN_BLK_P(1, STEPB);
+        TN_COLSUM(sy)
+        // this wave's loads of stage it+1 (requested a whole stage ago) have landed, its reads of this stage are back (the fourth block's
+        // fragments are in registers): behind the barrier the buffer of this stage is free and stage it+1 is visible
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __syncthreads();
+        {
+            const uint32_t flip = stage ? (uint32_t)(-T2_STAGE) : (uint32_t)T2_STAGE;       // the read addresses move to the next stage
+#pragma unroll
+            for (int i = 0; i < 8; ++i) ya[i] += flip;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) xa[j] += flip;
         }
-#undef TN_BLK
-#undef TN_MF
-#undef TN_NOP
-    } else
-    if constexpr (SCHED == 1) {
-        for (int it = 0; it < nmt; ++it) {
-            const int stage = it & 1;
-            const uint32_t so = (uint32_t)stage * T2_STAGE;
-            const char* sy = smem + stage * T2_STAGE;
-            TCOW_TN_READ(1, 1, so);
-            asm volatile("s_waitcnt lgkmcnt(12)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            TCOW_TN_MFMA8(0);
-            TCOW_TN_READ(0, 2, so);
-            asm volatile("s_waitcnt lgkmcnt(12)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            TCOW_TN_MFMA8(1);
-            TCOW_TN_READ(1, 3, so);
-            asm volatile("s_waitcnt lgkmcnt(12)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            TCOW_TN_MFMA8(0);
-            TN_COLSUM(sy)
-            // this wave's loads of stage it+1 (requested a whole stage ago) have landed, its reads of this stage are back (the fourth k-step's
-            // fragments are in registers): behind the barrier the buffer of this stage is free and stage it+1 is visible
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            __syncthreads();
+        TN_SB;
+        if constexpr (SCHED == 2) {
+            // (every stage through the buffer loads: the host picks this variant for whole tiles and 32-bit offsets only)
+            const int mt2 = mbeg + (it + 2) * T2_MC;
+            const bool more = it + 2 < nmt;
+            const uint32_t dy = lds_base + so + wave * 4096, dx = dy + T2_TILE;
+            const uint32_t by = (uint32_t)((long)(mt2 + wave * 8) * p.ldy * 2), bx = (uint32_t)((long)(mt2 + wave * 8) * p.ldx * 2);
+            const uint32_t yw0 = more ? yv0 : 0x80000000u, yw1 = more ? yv1 : 0x80000000u;     // (the per-lane offset is the range-checked one)
+            const uint32_t xw0 = more ? xv0 : 0x80000000u, xw1 = more ? xv1 : 0x80000000u;
+            const uint32_t ry = (uint32_t)(2 * p.ldy * 2), rx = (uint32_t)(2 * p.ldx * 2);
+            TN_BLK_Q(1, 0, 0, TCOW_BUFFER_GLDS16(yw0, srd_y, by, dy), TCOW_BUFFER_GLDS16(xw0, srd_x, bx, dx), TCOW_BUFFER_GLDS16(yw1, srd_y, by + ry, dy + 1024),
+                     TCOW_BUFFER_GLDS16(xw1, srd_x, bx + rx, dx + 1024), TCOW_BUFFER_GLDS16(yw0, srd_y, by + 2 * ry, dy + 2048), TCOW_BUFFER_GLDS16(xw0, srd_x, bx + 2 * rx, dx + 2048),
+                     TCOW_BUFFER_GLDS16(yw1, srd_y, by + 3 * ry, dy + 3072), TCOW_BUFFER_GLDS16(xw1, srd_x, bx + 3 * rx, dx + 3072));
+        } else {
             if (it + 2 < nmt) issue_stage(it + 2, stage);
-            if (it + 1 < nmt) TCOW_TN_READ(0, 0, so ^ (uint32_t)T2_STAGE);
-            __builtin_amdgcn_sched_barrier(0);
-            TCOW_TN_MFMA8(1);
+            TN_SB;
+            TN_BLK_Q(1, 0, 0, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP);
         }
     }
-    // (SCHED = 2: the last stage's fourth k-step has requested fragments of a stage that does not exist into set 0.  The wait re-defines those
+    // (The last stage's fourth block has requested fragments of a stage that does not exist into X0, X1 of set 0 and FY[0].  The wait re-defines those
     // registers, so that hipcc -- which knows nothing of reads issued by asm statements -- cannot hand them to the code behind the loop before the
     // data is in: see the same note in gemm_nt_c2.hip, where exactly that corrupted tiles)
     asm volatile("s_waitcnt lgkmcnt(0)"
@@ -410,11 +422,19 @@ __device__ __forceinline__ void tn256_body(const TnParams& p, const int pid, cha
                    "+v"(fyh[0][0]), "+v"(fyh[0][1]), "+v"(fyh[0][2]), "+v"(fyh[0][3])
                  :: "memory");
     __builtin_amdgcn_sched_barrier(0);
-#undef TCOW_TRR
+#undef TN_BLK_Q
+#undef TN_BLK_P
+#undef TN_NOP
+#undef TN_MF
+#undef TN_WAIT
+#undef TN_FRAG
+#undef TN_RYH
+#undef TN_RYL
+#undef TN_RXH
+#undef TN_RXL
+#undef TN_TRR
+#undef TN_SB
 #undef TN_COLSUM
-#undef TCOW_TN_READ
-#undef TCOW_TN_FRAG
-#undef TCOW_TN_MFMA8
     if (p.bias_part) {
         // fold the sixteen row groups (the operand stages are dead: the loop ended on a barrier): red[rg][256 columns]
         float* red = reinterpret_cast<float*>(smem);
@@ -433,20 +453,26 @@ __device__ __forceinline__ void tn256_body(const TnParams& p, const int pid, cha
         __syncthreads();
     }
 
+    // slab store: a lane's four accumulators of a block are four consecutive k of one n -- 16 bytes, 32 stores per wave.  (K is a multiple of 8,
+    // so a piece of four is whole or absent; SCHED = 2 has whole tiles only.  A slab that is not 16-byte aligned gets the same values one by one.)
     float* out = p.slab + (size_t)z * p.N * p.K;
-    const int l31 = lane & 31;
+    const int ln = lane & 15, lk = 4 * (lane >> 4);
+    auto store = [&](auto vec) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < 8; ++i) {
+            const int gn = n0 + wm * 128 + i * 16 + ln;
+            if (SCHED != 2 && gn >= p.N) continue;
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int gk = k0 + wn * 64 + j * 32 + l31;
-            if (gk >= p.K) continue;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int gn = n0 + wm * 128 + i * 32 + crow32(r, hi);
-                if (gn < p.N) out[(size_t)gn * p.K + gk] = acc[i][j][r];
+            for (int j = 0; j < 4; ++j) {
+                const int gk = k0 + wn * 64 + j * 16 + lk;
+                if (SCHED != 2 && gk >= p.K) continue;
+                float* dst = out + (size_t)gn * p.K + gk;
+                if constexpr (decltype(vec)::value) *reinterpret_cast<f32x4*>(dst) = acc[i][j];
+                else { dst[0] = acc[i][j][0]; dst[1] = acc[i][j][1]; dst[2] = acc[i][j][2]; dst[3] = acc[i][j][3]; }
             }
         }
+    };
+    if ((reinterpret_cast<uintptr_t>(out) & 15) == 0) store(std::true_type{}); else store(std::false_type{});
 }
 
 template <int SCHED>
@@ -488,9 +514,9 @@ bool tcow_tn_use_256(int M, int N, int K) {
     return M >= 4096 && N >= 256 && K >= 256 && tiles >= 9 && tiles <= 256;
 }
 
-// Stage loop of the 256-tile weight-gradient kernel (tn256_body): whole 256-tiles with 32-bit byte offsets take the interleaved loop (SCHED = 2 --
-// the transpose reads of the next k-step and the next stage's requests spread between the MFMAs of every k-step, the loads as buffer loads with
-// scalar row offsets), anything else the general one (SCHED = 1: the same wait / barrier placement, general addressing).
+// Loads of the 256-tile weight-gradient kernel (tn256_body): whole 256-tiles with 32-bit byte offsets take SCHED = 2 (the next stage's requests
+// spread between the MFMAs of the stage's fourth block, as buffer loads with scalar row offsets), anything else the general SCHED = 1 (the same
+// stage loop, general addressing).
 static bool tn_whole(int M, int N, int K, long ldy, long ldx) { return N % T2 == 0 && K % T2 == 0 && (long)M * ldy < (1L << 29) && (long)M * ldx < (1L << 29); }
 
 // launch parameters of one weight gradient on output tiles of `tile` (TN_T with mc = TN_MC token rows per stage, or T2 with T2_MC), `splits` token slices requested

@@ -18,6 +18,8 @@ all: $(LIB) $(LIB16)
 # attention_bf16.hip includes its three kernel families (attention_bf16_*.inc): one translation unit
 ATTN_INC := $(wildcard $(CSRC)/attention_bf16_*.inc)
 $(OBJ)/attention_bf16.hip.o $(OBJ16)/attention_bf16.hip.o: $(ATTN_INC)
+# gemm_tn_bf16.hip includes its two kernels (gemm_tn_128.inc, gemm_tn_256.inc): one translation unit
+$(OBJ)/gemm_tn_bf16.hip.o $(OBJ16)/gemm_tn_bf16.hip.o: $(wildcard $(CSRC)/gemm_tn_*.inc)
 $(OBJ)/attention_bf16.hip.o: EXTRA := -fno-honor-nans -fno-slp-vectorize
 $(OBJ)/%.hip.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/tcow_hip.h
 	@mkdir -p $(OBJ)

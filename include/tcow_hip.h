@@ -126,7 +126,11 @@ int tcow_prof_attn_end(double* ms4, double* flops4, double* bytes4, long* launch
  * dY, X: `dtype` row-major (ldy, ldx in elements).  The M (token) dimension is split across workgroups;
  * partial tiles go to `workspace` (f32, tcow_gemm_tn_workspace_bytes) and are reduced deterministically.
  * If bias_grad != NULL it also receives (+)= column sums of dY (autograd of nn.Linear.bias).
- * accumulate != 0 adds into dW / bias_grad instead of overwriting. */
+ * accumulate != 0 adds into dW / bias_grad instead of overwriting.
+ * tcow_gemm_tn_workspace_bytes is the same for every dtype (one buffer serves a module in any precision) and covers two regions, both at fixed
+ * offsets however large a buffer is passed (csrc/gemm_tn_plan.h): from byte 0 the slab, one f32 image [N][K] of dW per token slice, with room for
+ * one slice more than any dtype's kernel asks for; 224 bytes behind it the bias table of 3072 rows of N floats (partial column sums of dY that the
+ * slab fold sums on the side, or the scratch of a separate column-sum launch), and 32 unused bytes. */
 long tcow_gemm_tn_workspace_bytes(int M, int N, int K);
 int tcow_gemm_tn(void* stream, int dtype, int M, int N, int K, const void* dY, long ldy, const void* X,
                  long ldx, float* dW, long lddw, float* bias_grad, int accumulate, void* workspace,
@@ -135,7 +139,7 @@ int tcow_gemm_tn(void* stream, int dtype, int M, int N, int K, const void* dY, l
 /* The same for several Linear layers at once (the weight gradients of one transformer block, train.py:98's backward through
  * vit.py:50-61,74-76,146): in bf16 mode, problems that share M run as ONE grid with a common, much smaller number of token slices
  * (see gemm_tn_bf16.hip: gemm_tn_bf16_256_group_kernel; the more tiles a group has, the fewer slices fill the chip: five for one ViT-B block,
- * two for four blocks -- tcow_tn_group_slices); otherwise the call is a loop over tcow_gemm_tn.  Results are identical in
+ * two for four blocks -- tcow_tn_group_plan, csrc/gemm_tn_plan.h); otherwise the call is a loop over tcow_gemm_tn.  Results are identical in
  * meaning to n calls of tcow_gemm_tn (f32 summation order over the token slices differs). */
 typedef struct {
     int M, N, K;

@@ -148,92 +148,42 @@ int tcow_gemm_nt_skinny_x3(void* stream, const tcow_gemm_args* a, int split, voi
     return tcow_gemm_nt_skinny_launch_x3((hipStream_t)stream, a, split, (float*)workspace);
 }
 
-static const int kColsumParts = 64 * 24 * 2;   // >= nz * tiles_k * 2 partial rows of the fused bias gradient (nz <= 64, K <= 3072)
-
-// number of token-dimension slices used by the weight-gradient GEMMs (both dtypes): ~2 workgroups per CU, a multiple of
-// 8 so that every XCD owns the same number of slices (gemm_tn_bf16_kernel pins slice z to XCD z % 8), >= 256 tokens each.
-static int tcow_tn_splits(int M, int N, int K, int tile_outputs) {
-    const int tiles = cdiv(N, tile_outputs) * cdiv(K, tile_outputs);
-    int s = ((cdiv(512, tiles) + 7) / 8) * 8;
-    const int max_s = M / 256;
-    if (s > max_s) s = max_s >= 8 ? (max_s / 8) * 8 : max_s;
-    if (s < 1) s = 1;
-    if (s > 64) s = 64;
-    return s;
-}
-
-long tcow_gemm_tn_workspace_bytes(int M, int N, int K) {
-    const int s_bf = tcow_tn_splits(M, N, K, 128), s_f = tcow_tn_splits(M, N, K, 64), s_big = tcow_tn_splits_256(M, N, K);
-    int s = s_bf > s_f ? s_bf : s_f;
-    if (s_big > s) s = s_big;
-    if (tcow_tn_splits_x3(M, N, K) > s) s = tcow_tn_splits_x3(M, N, K);
-    return ((long)(s + 1) * N * K + (long)kColsumParts * N) * 4 + 256;
-}
+// ---- weight gradients.  Every number below -- kernel, slices, how the bias gradient is produced, workspace offsets -- is the plan's (gemm_tn_plan.h).
+long tcow_gemm_tn_workspace_bytes(int M, int N, int K) { return tcow_tn_workspace_total(M, N, K); }
 
 int tcow_gemm_tn(void* stream, int dtype, int M, int N, int K, const void* dY, long ldy, const void* X, long ldx, float* dW, long lddw,
                  float* bias_grad, int accumulate, void* workspace, long workspace_bytes) {
     TCOW_CHECK_ARG(M > 0 && N > 0 && K > 0 && dY && X && dW && workspace, "tcow_gemm_tn: bad arguments");
-    TCOW_CHECK_ARG(workspace_bytes >= tcow_gemm_tn_workspace_bytes(M, N, K), "tcow_gemm_tn: workspace too small (%ld < %ld)", workspace_bytes,
-                   tcow_gemm_tn_workspace_bytes(M, N, K));
-    float* slab = (float*)workspace;
-    float* part = slab + (size_t)(workspace_bytes / 4 - (long)kColsumParts * N - 8);
-    int rc;
-    if (dtype == TCOW_BF16) {
-        const int splits = tcow_tn_use_256(M, N, K) ? tcow_tn_splits_256(M, N, K) : tcow_tn_splits(M, N, K, 128);
-        int nz = 0, nparts = 0;
-        const bool fuse_bias = bias_grad != nullptr && (long)splits * ((K + 127) / 128) * 2 <= kColsumParts;
-        rc = tcow_gemm_tn_bf16((hipStream_t)stream, M, N, K, (const bf16_t*)dY, ldy, (const bf16_t*)X, ldx, slab, splits, &nz, fuse_bias ? part : nullptr, &nparts);
-        if (rc) return rc;
-        rc = tcow_launch_slab_reduce((hipStream_t)stream, slab, nz, (long)N * K, N, K, dW, lddw, accumulate, fuse_bias ? part : nullptr, nparts, N, bias_grad);
-        if (rc) return rc;
-        if (fuse_bias) return TCOW_OK;
-    } else if (dtype == TCOW_F32 || dtype == TCOW_F32X3) {
-        // f32 storage: the bias gradient's column-sum partials first, their fold rides on the weight gradient's slab fold (one launch instead of two per Linear)
-        int nparts = 0;
-        if (bias_grad) {
-            rc = tcow_launch_colsum_partials((hipStream_t)stream, TCOW_F32, dY, ldy, M, N, part, 64, &nparts);      // (5.4 TB/s averaged over the step's shapes; 256 slices measured the same and a dearer fold)
-            if (rc) return rc;
-        }
-        if (dtype == TCOW_F32) rc = tcow_gemm_tn_f32((hipStream_t)stream, M, N, K, (const float*)dY, ldy, (const float*)X, ldx, dW, lddw, accumulate, slab, tcow_tn_splits(M, N, K, 64),
-                                                     bias_grad ? part : nullptr, nparts, bias_grad);
-        else rc = tcow_gemm_tn_x3((hipStream_t)stream, M, N, K, (const float*)dY, ldy, (const float*)X, ldx, dW, lddw, accumulate, slab, tcow_tn_splits_x3(M, N, K),
-                                  bias_grad ? part : nullptr, nparts, bias_grad);
-        return rc;
-    } else {
-        tcow_set_error("tcow_gemm_tn: unknown dtype %d", dtype);
-        return TCOW_ERR_INVALID_ARG;
-    }
-    if (bias_grad) {
-        rc = tcow_launch_colsum((hipStream_t)stream, dtype == TCOW_BF16 ? TCOW_BF16 : TCOW_F32, dY, ldy, M, N, bias_grad, accumulate, part, 64);
-        if (rc) return rc;
-    }
-    return TCOW_OK;
+    const TnPlan pl = tcow_tn_plan(dtype, M, N, K, ldy, ldx, bias_grad != nullptr);
+    TCOW_CHECK_ARG(workspace_bytes >= pl.total, "tcow_gemm_tn: workspace too small (%ld < %ld)", workspace_bytes, pl.total);
+    TCOW_CHECK_ARG(pl.kernel != TN_KNONE, "tcow_gemm_tn: unknown dtype %d", dtype);
+    hipStream_t st = (hipStream_t)stream;
+    float* slab = (float*)((char*)workspace + pl.slab_off);
+    float* table = (float*)((char*)workspace + pl.table_off);
+    int rc = TCOW_OK, nparts = pl.table_rows;
+    if (pl.bias == TN_BIAS_PARTIALS) rc = tcow_launch_colsum_partials(st, TCOW_F32, dY, ldy, M, N, table, TN_COLSUM_PARTS, &nparts);
+    if (rc) return rc;
+    if (dtype == TCOW_BF16) rc = tcow_gemm_tn_bf16(st, pl, M, N, K, (const bf16_t*)dY, ldy, (const bf16_t*)X, ldx, slab, pl.bias == TN_BIAS_FUSED ? table : nullptr);
+    else if (dtype == TCOW_F32) rc = tcow_gemm_tn_f32(st, pl, M, N, K, (const float*)dY, ldy, (const float*)X, ldx, slab);
+    else rc = tcow_gemm_tn_x3(st, pl, M, N, K, (const float*)dY, ldy, (const float*)X, ldx, slab);
+    if (rc) return rc;
+    const bool folded = pl.bias == TN_BIAS_FUSED || pl.bias == TN_BIAS_PARTIALS;      // the table's fold rides on the slab fold
+    rc = tcow_launch_slab_reduce(st, slab, pl.nz, (long)N * K, N, K, dW, lddw, accumulate, folded ? table : nullptr, nparts, N, bias_grad);
+    if (rc || pl.bias != TN_BIAS_COLSUM) return rc;
+    return tcow_launch_colsum(st, TCOW_BF16, dY, ldy, M, N, bias_grad, accumulate, table, TN_COLSUM_PARTS);
 }
 
 // ---- grouped weight gradients
-static long tn_group_bytes(int n, const tcow_tn_problem* pr, int nz) {
-    long b = 256;
-    for (int i = 0; i < n; ++i) b += ((long)nz * pr[i].N * pr[i].K + (long)nz * ((pr[i].K + 255) / 256) * 2 * pr[i].N) * 4 + 64;
-    return b;
-}
-
 int tcow_gemm_tn_group_max(void) { return TCOW_TN_GROUP_MAX; }
-
-long tcow_gemm_tn_grouped_workspace_bytes(int dtype, int n, const tcow_tn_problem* pr) {
-    if (n <= 0 || pr == nullptr) return 0;
-    long single = 0;
-    for (int i = 0; i < n; ++i) { const long b = tcow_gemm_tn_workspace_bytes(pr[i].M, pr[i].N, pr[i].K); if (b > single) single = b; }
-    if (dtype == TCOW_BF16 && tcow_tn_group_ok(n, pr)) { const long g = tn_group_bytes(n, pr, tcow_tn_group_slices(n, pr) + 1); if (g > single) single = g; }
-    return single;
-}
+long tcow_gemm_tn_grouped_workspace_bytes(int dtype, int n, const tcow_tn_problem* pr) { return n <= 0 || pr == nullptr ? 0 : tcow_tn_group_plan(dtype, n, pr).total; }
 
 int tcow_gemm_tn_grouped(void* stream, int dtype, int n, const tcow_tn_problem* pr, void* workspace, long workspace_bytes) {
     TCOW_CHECK_ARG(n > 0 && pr && workspace, "tcow_gemm_tn_grouped: bad arguments");
-    TCOW_CHECK_ARG(workspace_bytes >= tcow_gemm_tn_grouped_workspace_bytes(dtype, n, pr), "tcow_gemm_tn_grouped: workspace too small (%ld < %ld)", workspace_bytes,
-                   tcow_gemm_tn_grouped_workspace_bytes(dtype, n, pr));
+    const TnGroupPlan pl = tcow_tn_group_plan(dtype, n, pr);
+    TCOW_CHECK_ARG(workspace_bytes >= pl.total, "tcow_gemm_tn_grouped: workspace too small (%ld < %ld)", workspace_bytes, pl.total);
     for (int i = 0; i < n; ++i)
         TCOW_CHECK_ARG(pr[i].M > 0 && pr[i].N > 0 && pr[i].K > 0 && pr[i].dY && pr[i].X && pr[i].dW, "tcow_gemm_tn_grouped: bad problem %d", i);
-    if (!(dtype == TCOW_BF16 && tcow_tn_group_ok(n, pr))) {
+    if (!pl.grouped) {
         for (int i = 0; i < n; ++i) {
             const int rc = tcow_gemm_tn(stream, dtype, pr[i].M, pr[i].N, pr[i].K, pr[i].dY, pr[i].ldy, pr[i].X, pr[i].ldx, pr[i].dW, pr[i].lddw, pr[i].bias_grad,
                                         pr[i].accumulate, workspace, workspace_bytes);
@@ -241,35 +191,26 @@ int tcow_gemm_tn_grouped(void* stream, int dtype, int n, const tcow_tn_problem* 
         }
         return TCOW_OK;
     }
-    const int nz_req = tcow_tn_group_slices(n, pr);
-    float* slabs[TCOW_TN_GROUP_MAX]; float* parts[TCOW_TN_GROUP_MAX]; int nparts[TCOW_TN_GROUP_MAX];          // (tcow_tn_group_ok: n <= TCOW_TN_GROUP_MAX)
-    char* w = (char*)workspace;
-    for (int i = 0; i < n; ++i) {
-        slabs[i] = (float*)w; w += (long)(nz_req + 1) * pr[i].N * pr[i].K * 4;
-        parts[i] = pr[i].bias_grad ? (float*)w : nullptr; w += (long)(nz_req + 1) * ((pr[i].K + 255) / 256) * 2 * pr[i].N * 4 + 64;
-        // ONE token slice (a group whose tiles fill whole rounds of the chip by themselves: five ViT-B blocks = 765 tiles): nothing to fold, so the
-        // kernel writes a dense, non-accumulating weight gradient straight into its destination -- no slab image written, re-read and copied
-        // (2 x 177 MB per five-block group); only the bias-gradient partials still go through the fold launch
-        if (nz_req == 1 && !pr[i].accumulate && pr[i].lddw == pr[i].K && tcow_fold_vec_ok(pr[i].dW, (long)pr[i].N * pr[i].K, pr[i].K, pr[i].dW, pr[i].lddw))
-            slabs[i] = pr[i].dW;
-    }
-    int nz = 0;
-    int rc = tcow_gemm_tn_bf16_group((hipStream_t)stream, n, pr, nz_req, slabs, parts, &nz, nparts);
-    if (rc) return rc;
+    constexpr int G = TCOW_TN_GROUP_MAX;          // (a plan that groups has n <= G)
+    float* slabs[G]; float* parts[G];
     bool vec = true;
-    for (int i = 0; i < n; ++i) vec = vec && tcow_fold_vec_ok(slabs[i], (long)pr[i].N * pr[i].K, pr[i].K, pr[i].dW, pr[i].lddw);
+    for (int i = 0; i < n; ++i) {
+        slabs[i] = pl.p[i].in_place ? pr[i].dW : (float*)((char*)workspace + pl.p[i].slab_off);
+        parts[i] = pr[i].bias_grad ? (float*)((char*)workspace + pl.p[i].table_off) : nullptr;
+        vec = vec && tcow_fold_vec_ok(slabs[i], (long)pr[i].N * pr[i].K, pr[i].K, pr[i].dW, pr[i].lddw);
+    }
+    int rc = tcow_gemm_tn_bf16_group((hipStream_t)stream, pl, n, pr, slabs, parts);
+    if (rc) return rc;
     if (vec) {       // one fold launch for the whole group
-        constexpr int G = TCOW_TN_GROUP_MAX;
-        long rows[G], cols[G], ldo[G]; int acc[G]; float* outs[G]; float* bouts[G]; const float* cparts[G]; const float* cslabs[G];
+        long rows[G], cols[G], ldo[G]; int acc[G], nparts[G]; float* outs[G]; float* bouts[G];
         for (int i = 0; i < n; ++i) {
-            rows[i] = pr[i].N; cols[i] = pr[i].K; ldo[i] = pr[i].lddw; acc[i] = pr[i].accumulate; outs[i] = pr[i].dW; bouts[i] = pr[i].bias_grad;
-            cparts[i] = parts[i]; cslabs[i] = slabs[i]; if (!parts[i]) nparts[i] = 0;
+            rows[i] = pr[i].N; cols[i] = pr[i].K; ldo[i] = pr[i].lddw; acc[i] = pr[i].accumulate; outs[i] = pr[i].dW; bouts[i] = pr[i].bias_grad; nparts[i] = pl.p[i].table_rows;
         }
-        return tcow_launch_slab_reduce_group((hipStream_t)stream, n, cslabs, nz, rows, cols, outs, ldo, acc, cparts, nparts, bouts);
+        return tcow_launch_slab_reduce_group((hipStream_t)stream, n, slabs, pl.nz, rows, cols, outs, ldo, acc, parts, nparts, bouts);
     }
     for (int i = 0; i < n; ++i) {
-        rc = tcow_launch_slab_reduce((hipStream_t)stream, slabs[i], nz, (long)pr[i].N * pr[i].K, pr[i].N, pr[i].K, pr[i].dW, pr[i].lddw, pr[i].accumulate,
-                                     parts[i], parts[i] ? nparts[i] : 0, pr[i].N, pr[i].bias_grad);
+        rc = tcow_launch_slab_reduce((hipStream_t)stream, slabs[i], pl.nz, (long)pr[i].N * pr[i].K, pr[i].N, pr[i].K, pr[i].dW, pr[i].lddw, pr[i].accumulate,
+                                     parts[i], pl.p[i].table_rows, pr[i].N, pr[i].bias_grad);
         if (rc) return rc;
     }
     return TCOW_OK;

@@ -8,8 +8,7 @@
 
 namespace {
 
-constexpr int FT = 64;   // tile edge
-constexpr int FK = 16;   // k-slice
+// (FT = 64: tile edge, FK = 16: k-slice -- gemm_tile_sizes.h)
 constexpr int FLD = FT + 4;
 
 __device__ __forceinline__ void load_tile(const float* __restrict__ P, long s_row, long s_k, int row0, int nrows, int k0, int kend,
@@ -94,12 +93,9 @@ int tcow_gemm_nt_f32(hipStream_t stream, const tcow_gemm_args* a) {
     return TCOW_OK;
 }
 
-int tcow_gemm_tn_f32(hipStream_t stream, int M, int N, int K, const float* dY, long ldy, const float* X, long ldx, float* dW, long lddw,
-                     int accumulate, float* slab, int splits, const float* bias_part, int bias_nparts, float* bias_out) {
-    int kps = cdiv(M, splits); kps = ((kps + FK - 1) / FK) * FK;
-    const int nz = cdiv(M, kps);
-    const F32Params p = f32_params_plain(N, K, M, dY, 1, ldy, X, 1, ldx, kps, slab);      // output [N,K], contraction over tokens
-    hipLaunchKernelGGL(gemm_f32_kernel, dim3(cdiv(K, FT), cdiv(N, FT), nz), dim3(256), 0, stream, p);
+int tcow_gemm_tn_f32(hipStream_t stream, const TnPlan& pl, int M, int N, int K, const float* dY, long ldy, const float* X, long ldx, float* slab) {
+    const F32Params p = f32_params_plain(N, K, M, dY, 1, ldy, X, 1, ldx, pl.mps, slab);      // output [N,K], contraction over tokens
+    hipLaunchKernelGGL(gemm_f32_kernel, dim3(pl.tiles_k, pl.tiles_n, pl.nz), dim3(256), 0, stream, p);
     TCOW_CHECK_LAUNCH();
-    return tcow_launch_slab_reduce(stream, slab, nz, (long)N * K, N, K, dW, lddw, accumulate, bias_part, bias_nparts, N, bias_out);
+    return TCOW_OK;
 }

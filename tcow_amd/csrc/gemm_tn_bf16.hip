@@ -1,21 +1,12 @@
-// bf16 weight-gradient GEMM (gfx950):  gemm_tn_bf16 : dW[N,K] += dY[M,N]^T . X[M,K], the token dimension split across workgroups.
-//
-// slab[z][N][K] = sum over token rows of slice z of dY[m][n] * X[m][k].
-// Both operands have the contraction index (token row m) as their slow dimension, so the MFMA fragments
-// (8 consecutive m for one column) are gathered with the LDS transpose read ds_read_b64_tr_b16:
-// within a 16-lane group lane 4r+c supplies the address of row r / 4-element column quad c of a [4][16]
-// block and receives column (lane&15), rows 0..3 (verified on hardware, profiles/r01_hw_probe.txt).
-//
-// Two kernels, two fragment shapes:
-//   128-tile kernel (gemm_tn_bf16_kernel; small shapes): 32x32x16 MFMAs, a fragment is 32 columns x 16 tokens (lane l: tokens 8 (l >> 5) ... + 7).
-//     LDS rows are 256 B (128 columns); 16-byte chunk c of row r sits at chunk position c ^ ((r&3)<<2) so the four rows a half-wave touches
-//     per read fall into four different 64-byte bank segments.
-//   256-tile kernels (tn256_body; every weight of the training step): 16x16x32 MFMAs, a fragment is 16 columns x 32 tokens (lane l: column
-//     l & 15, tokens 8 (l >> 4) ... + 7), one "lo" + one "hi" transpose read each.  A half-wave then touches EIGHT rows, {b ... b+3, b+8 ... b+11},
-//     32 bytes of each: the image of the 512-byte rows is c ^ ((r&3)<<2) ^ (((r>>3)&1)<<1), eight different 32-byte bank segments
-//     (gemm_tn_layout.h: the image, the loads' source permutation, the read addresses; checked lane by lane on the CPU by
-//     tools/tn_layout_check.cpp).  X is the A operand and dY the B operand, so a lane's four accumulators of a 16 x 16 block are four
-//     consecutive k of one n: the slab store is one 16-byte store per block.  The f32 sums group 32 tokens per MFMA.
+// 16-bit weight-gradient GEMM (gfx950):  dW[N,K] += dY[M,N]^T . X[M,K], the token dimension split across workgroups:
+// slab[z][N][K] = sum over token rows of slice z of dY[m][n] * X[m][k];  the slabs are folded by reduce.hip.
+// Both operands have the contraction index (token row m) as their slow dimension, so the MFMA fragments (consecutive m for one column) are
+// gathered with the LDS transpose read ds_read_b64_tr_b16: within a 16-lane group lane 4r+c supplies the address of row r / 4-element column
+// quad c of a [4][16] block and receives column (lane&15), rows 0..3 (verified on hardware, profiles/r01_hw_probe.txt).
+// Two kernels with two fragment shapes, one included file each, compiled as ONE translation unit: gemm_tn_128.inc (gemm_tn_bf16_kernel, small shapes)
+// and gemm_tn_256.inc (tn256_body: gemm_tn_bf16_256_kernel<SCHED> for one problem, gemm_tn_bf16_256_group_kernel<SCHED> for a group in one grid).
+// Which kernel runs on how many token slices, and where slab and bias table lie, is the host plan's to say (gemm_tn_plan.h); the launchers below
+// turn a plan into kernel parameters and a grid.
 #include <stdlib.h>
 #include <type_traits>
 
@@ -26,9 +17,6 @@
 
 namespace {
 
-constexpr int TN_T = 128;                 // output tile edge (n and k)
-constexpr int TN_MC = 32;                 // token rows per LDS stage: 32 KiB of LDS, 4 workgroups/CU (64 rows, 2 workgroups/CU: 5-25 % behind, profiles/r01_gemm_tn_ab.txt)
-
 __device__ uint4 g_zero16 = {0u, 0u, 0u, 0u};
 
 struct TnParams {
@@ -36,498 +24,21 @@ struct TnParams {
     const bf16_t* dY; long ldy;
     const bf16_t* X; long ldx;
     float* slab;
-    int tiles_n, tiles_k, mps, nz;   // mps: token rows per slice (multiple of TN_MC); nz slices
+    int tiles_n, tiles_k, mps, nz;   // mps: token rows per slice (multiple of the stage); nz slices
     float* bias_part;                // optional [nz][tiles_k][2][N] partial column sums of dY (bias gradient)
-    int rows_per_pk;                 // LDS rows of each 64-row stage summed by the workgroup with k-tile index pk
+    int rows_per_pk;                 // LDS rows of each stage summed by the workgroup with k-tile index pk
 };
-
-__device__ __forceinline__ bf16x8 tr_frag(const char* tile, int off0) {
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(tile + off0));
-    const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(tile + off0 + 4 * 256));
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-    const s16x8 v = __builtin_shufflevector(lo, hi4, 0, 1, 2, 3, 4, 5, 6, 7);
-    return __builtin_bit_cast(bf16x8, v);
-}
-
-__global__ __launch_bounds__(256, 4) void gemm_tn_bf16_kernel(TnParams p) {
-    constexpr int MC = TN_MC, TILE_BYTES_ = MC * 256, STAGE_BYTES_ = 2 * TILE_BYTES_;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    // XCD-aware placement: blocks are dispatched round-robin over the 8 XCDs (private L2s).  All output tiles of one token
-    // slice z read the same dY / X rows, so slice z is pinned to XCD z % 8: its rows are fetched from HBM once per XCD-resident
-    // slice instead of once per XCD (measured: FETCH_SIZE 4-8x the algorithmic bytes with the naive order).
-    const int ntile = p.tiles_n * p.tiles_k;
-    const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    const int z = xcd + 8 * (idx / ntile), tile = idx % ntile;
-    if (z >= p.nz) return;
-    const int pn = tile / p.tiles_k, pk = tile - pn * p.tiles_k;
-    const int n0 = pn * TN_T, k0 = pk * TN_T;
-    const int mbeg = z * p.mps;
-    const int mend = (mbeg + p.mps < p.M) ? mbeg + p.mps : p.M;
-
-    // direct-to-LDS loads: wave-load q (16 per operand per stage) covers tile rows 4q..4q+3 x 256 B.
-    const int lrow = lane >> 4;
-    const int schunk = (lane & 15) ^ (lrow << 2);
-    int ncol = n0 + schunk * 8; const bool n_ok = ncol < p.N;     // N, K multiples of 8 -> whole chunk in or out
-    int kcol = k0 + schunk * 8; const bool k_ok = kcol < p.K;
-    const bf16_t* zero = reinterpret_cast<const bf16_t*>(&g_zero16);
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    auto issue = [&](int mt, int stage) {
-        char* sy = smem + stage * STAGE_BYTES_;
-        char* sx = sy + TILE_BYTES_;
-#pragma unroll
-        for (int j = 0; j < MC / 16; ++j) {
-            const int q = wave * (MC / 16) + j;
-            const int gm = mt + q * 4 + lrow;
-            const bool ok = gm < mend;
-            const bf16_t* ys = (ok && n_ok) ? p.dY + (size_t)gm * p.ldy + ncol : zero;
-            const bf16_t* xs = (ok && k_ok) ? p.X + (size_t)gm * p.ldx + kcol : zero;
-            glds16(ys, sy + q * 1024);
-            glds16(xs, sx + q * 1024);
-        }
-    };
-
-    // transpose-read addressing (constant over the loop)
-    const int q16 = lane & 15, g16 = (lane >> 4) & 1, hi = lane >> 5;
-    int y_off[2], x_off[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int cy = wm * 64 + i * 32 + 16 * g16 + 4 * (q16 & 3);
-        const int cx = wn * 64 + i * 32 + 16 * g16 + 4 * (q16 & 3);
-        const int rr = 8 * hi + (q16 >> 2);
-        y_off[i] = rr * 256 + ((((cy >> 3) ^ ((q16 >> 2) << 2))) << 4) + (cy & 7) * 2;
-        x_off[i] = rr * 256 + ((((cx >> 3) ^ ((q16 >> 2) << 2))) << 4) + (cx & 7) * 2;
-    }
-
-    // column-sum duty of this thread: column cs_col of the dY tile, LDS rows [cs_r0, cs_r1) of every stage
-    const int cs_col = tid & 127;
-    const int cs_lo = pk * p.rows_per_pk, cs_hi = (cs_lo + p.rows_per_pk < MC) ? cs_lo + p.rows_per_pk : MC;
-    const int cs_mid = cs_lo + (cs_hi - cs_lo + 1) / 2;
-    const int cs_r0 = (tid >> 7) ? cs_mid : cs_lo, cs_r1 = (tid >> 7) ? cs_hi : (cs_mid < cs_hi ? cs_mid : cs_hi);
-    float colsum = 0.f;
-
-    const int nmt = (mend - mbeg + MC - 1) / MC;
-    if (nmt > 0) {
-        issue(mbeg, 0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    }
-    for (int it = 0; it < nmt; ++it) {
-        const int stage = it & 1;
-        if (it + 1 < nmt) issue(mbeg + (it + 1) * MC, stage ^ 1);
-        const char* sy = smem + stage * STAGE_BYTES_;
-        const char* sx = sy + TILE_BYTES_;
-#pragma unroll
-        for (int ks = 0; ks < MC / 16; ++ks) {
-            bf16x8 fy[2], fx[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                fy[i] = tr_frag(sy, y_off[i] + ks * 16 * 256);
-                fx[i] = tr_frag(sx, x_off[i] + ks * 16 * 256);
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[i][j] = TCOW_MFMA_32x32x16_H16(fy[i], fx[j], acc[i][j], 0, 0, 0);
-        }
-        if (p.bias_part) {
-            // bias gradient = column sums of dY: the dY stage is already in LDS; the tiles_k workgroups that share it split
-            // its 64 rows between them (and each between its two thread halves), so the extra work is a few LDS reads each.
-#pragma unroll 4
-            for (int r = cs_r0; r < cs_r1; ++r) {
-                const int off = r * 256 + ((((cs_col >> 3) ^ ((r & 3) << 2))) << 4) + (cs_col & 7) * 2;
-                colsum += bf2f(*reinterpret_cast<const bf16_t*>(sy + off));
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    }
-    if (p.bias_part && n0 + cs_col < p.N)
-        p.bias_part[(((size_t)z * p.tiles_k + pk) * 2 + (tid >> 7)) * p.N + n0 + cs_col] = colsum;
-
-    float* out = p.slab + (size_t)z * p.N * p.K;
-    const int l31 = lane & 31;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int gk = k0 + wn * 64 + j * 32 + l31;
-            if (gk >= p.K) continue;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int gn = n0 + wm * 64 + i * 32 + crow32(r, hi);
-                if (gn < p.N) out[(size_t)gn * p.K + gk] = acc[i][j][r];
-            }
-        }
-}
-
-// ---- 256 x 256 output tile, 8 waves (2 x 4, 128 x 64 each), 64 token rows per stage, two stages = 128 KiB, one workgroup per CU.
-// The 128-tile kernel above is bound by the global->LDS stream (a loads-only build takes 70 % of its time,
-// profiles/r01_gemm_variants.txt); this tile moves half the bytes per FLOP.  Workgroups = tiles x slices <= 256 (one round):
-// workgroup ids are handed out so that each XCD owns a contiguous range of (slice, tile) pairs, i.e. at most two token slices.
-constexpr int T2 = 256;
-constexpr int T2_MC = 64;
-constexpr int T2_ROWB = T2 * 2;                 // 512 B per LDS row
-constexpr int T2_TILE = T2_MC * T2_ROWB;        // 32 KiB per operand per stage
-constexpr int T2_STAGE = 2 * T2_TILE;
-constexpr int T2_LDS = 2 * T2_STAGE;            // 128 KiB
-
-// one workgroup of the 256-tile weight-gradient GEMM `p`: pid = slice * tiles + tile
-// Both SCHED values run ONE stage loop (further down): four blocks of 16 MFMAs per stage, the next block's transpose reads one behind each MFMA, and
-// the stage's ONE wait + barrier between the third and the fourth block instead of at the stage end: the fourth block's fragments are in registers
-// by then, so its MFMAs run right behind the barrier while the NEXT stage's first fragments are read and the stage after next is requested into
-// the buffer this stage has just released -- no stage boundary at which all eight waves wait for the barrier, then for their first transpose
-// reads, with the matrix pipe idle.  (The round-3 order -- wait + barrier at the stage end -- is gone: 553-566 vs 504 us per block.)
-// SCHED = 2, for whole tiles with 32-bit offsets (tn_whole): every stage by buffer loads, issued one behind every second MFMA of the fourth block.
-// SCHED = 1: the general addressing (edge tiles, 64-bit offsets); the stage after next is requested in one piece behind the barrier.
-template <int SCHED>
-__device__ __forceinline__ void tn256_body(const TnParams& p, const int pid, char* smem) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 2, wn = wave & 3;
-    const int ntile = p.tiles_n * p.tiles_k;
-    const int z = pid / ntile, tile = pid - z * ntile;
-    const int pn = tile / p.tiles_k, pk = tile - pn * p.tiles_k;
-    const int n0 = pn * T2, k0 = pk * T2;
-    const int mbeg = z * p.mps;
-    const int mend = (mbeg + p.mps < p.M) ? mbeg + p.mps : p.M;
-
-    // direct-to-LDS loads: a wave-load covers 2 tile rows x 512 B; wave w issues wave-loads 4w..4w+3 of each operand per stage
-    const int lrow = lane >> 5;
-    const bf16_t* zero = reinterpret_cast<const bf16_t*>(&g_zero16);
-    int ycol[2], xcol[2];                                         // source column of this lane for even / odd wave-loads (the row's swizzle differs)
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-        const int sc = tnl_load_chunk(wave, e, lane);              // rows 8 wave + 2 j + lrow: the swizzle depends on j through j & 1 only
-        ycol[e] = n0 + sc * 8; xcol[e] = k0 + sc * 8;
-    }
-    // accumulators of 16x16x32 MFMAs with X as the A and dY as the B operand: acc[i][j] is the block of columns n = 16 i ... + 15 and
-    // k = 16 j ... + 15 of the wave's 128 x 64, lane l holding n = l & 15 and the FOUR CONSECUTIVE k = 4 (l >> 4) ... + 3 -- one 16-byte store each
-    f32x4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
-
-    auto issue = [&](int mt, int stage) {
-        char* sy = smem + stage * T2_STAGE;
-        char* sx = sy + T2_TILE;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int q = wave * 4 + j;
-            const int gm = mt + q * 2 + lrow;
-            const bool ok = gm < mend;
-            const bf16_t* ys = (ok && ycol[j & 1] < p.N) ? p.dY + (size_t)gm * p.ldy + ycol[j & 1] : zero;
-            const bf16_t* xs = (ok && xcol[j & 1] < p.K) ? p.X + (size_t)gm * p.ldx + xcol[j & 1] : zero;
-            glds16(ys, sy + q * 1024);
-            glds16(xs, sx + q * 1024);
-        }
-    };
-    const bool interior = n0 + T2 <= p.N && k0 + T2 <= p.K;
-    // The fast path as buffer loads: descriptor + ONE per-lane byte offset per operand and row parity + a scalar row offset -- no vector
-    // arithmetic per load, rows past M read as zeros.  (inline asm: hipcc does not count these loads; every wait in the loop is explicit.)
-    const i32x4_ srd_y = make_srd(p.dY, ((long)(p.M - 1) * p.ldy + p.N) * 2), srd_x = make_srd(p.X, ((long)(p.M - 1) * p.ldx + p.K) * 2);
-    const uint32_t yv0 = (uint32_t)(lrow * p.ldy + ycol[0]) * 2u, yv1 = (uint32_t)(lrow * p.ldy + ycol[1]) * 2u;
-    const uint32_t xv0 = (uint32_t)(lrow * p.ldx + xcol[0]) * 2u, xv1 = (uint32_t)(lrow * p.ldx + xcol[1]) * 2u;
-    const bool small32 = (long)p.M * p.ldy < (1L << 29) && (long)p.M * p.ldx < (1L << 29);
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(LDS_PTR(char))smem;
-    auto issue_fast = [&](int mt, int stage) {
-        const uint32_t dy = lds_base + stage * T2_STAGE + wave * 4096, dx = dy + T2_TILE;
-        const uint32_t sy = (uint32_t)((long)(mt + wave * 8) * p.ldy * 2), sx = (uint32_t)((long)(mt + wave * 8) * p.ldx * 2);
-        const uint32_t ry = (uint32_t)(2 * p.ldy * 2), rx = (uint32_t)(2 * p.ldx * 2);
-        TCOW_BUFFER_GLDS16(yv0, srd_y, sy, dy); TCOW_BUFFER_GLDS16(xv0, srd_x, sx, dx);
-        TCOW_BUFFER_GLDS16(yv1, srd_y, sy + ry, dy + 1024); TCOW_BUFFER_GLDS16(xv1, srd_x, sx + rx, dx + 1024);
-        TCOW_BUFFER_GLDS16(yv0, srd_y, sy + 2 * ry, dy + 2048); TCOW_BUFFER_GLDS16(xv0, srd_x, sx + 2 * rx, dx + 2048);
-        TCOW_BUFFER_GLDS16(yv1, srd_y, sy + 3 * ry, dy + 3072); TCOW_BUFFER_GLDS16(xv1, srd_x, sx + 3 * rx, dx + 3072);
-    };
-    // transpose-read addressing (constant over the loop)
-    // (gemm_tn_layout.h: the "lo" read of the fragment of 16 columns, first MFMA step; "hi" and the second step are immediate offsets)
-    int y_off[8], x_off[4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) y_off[i] = tnl_read_off(lane, wm * 128 + i * 16, 0);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) x_off[j] = tnl_read_off(lane, wn * 64 + j * 16, 0);
-
-    // column-sum duty (bias gradient): column cs_col of the dY tile, rows [cs_r0, cs_r1) of every stage; the tiles_k workgroups
-    // that share a dY tile split its 64 rows between them, and each between its two thread halves
-    // (thread t sums the eight columns of 16-byte chunk t & 31 over rows cs_lo + (t >> 5), + 16, ...: at most four b128 reads per stage instead
-    // of up to 32 two-byte ones; the sixteen row groups are folded through LDS once, after the loop)
-    const int cs_col = tid & 255;
-    const int cs_lo = pk * p.rows_per_pk, cs_hi = (cs_lo + p.rows_per_pk < T2_MC) ? cs_lo + p.rows_per_pk : T2_MC;
-    const int cs_chunk = tid & 31, cs_rg = tid >> 5;
-    float csum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    // (a macro: as a lambda the same text compiles to different address arithmetic)
-#define TN_COLSUM(sy)                                                                                                              \
-    if (p.bias_part) {                                                                                                             \
-        _Pragma("unroll") for (int u = 0; u < 4; ++u) {                                                                            \
-            const int r = cs_lo + cs_rg + 16 * u;                                                                                  \
-            if (r < cs_hi) {                                                                                                       \
-                const uint4 v = *reinterpret_cast<const uint4*>((sy) + tnl_colsum_off(r, cs_chunk));                               \
-                csum[0] += bflo(v.x); csum[1] += bfhi(v.x); csum[2] += bflo(v.y); csum[3] += bfhi(v.y);                            \
-                csum[4] += bflo(v.z); csum[5] += bfhi(v.z); csum[6] += bflo(v.w); csum[7] += bfhi(v.w);                            \
-            }                                                                                                                      \
-        }                                                                                                                          \
-    }
-
-    const int nmt = (mend - mbeg + T2_MC - 1) / T2_MC;
-    auto issue_stage = [&](int st_, int buf_) {
-        const int mt = mbeg + st_ * T2_MC;
-        if (interior && small32 && (mt + T2_MC <= mend || mend == p.M)) issue_fast(mt, buf_); else issue(mt, buf_);
-    };
-    if constexpr (SCHED == 2) {
-        // (every stage through the buffer loads: the host picks this variant for whole tiles and 32-bit offsets only)
-        if (nmt > 0) {
-            issue_fast(mbeg, 0);
-            if (nmt > 1) { issue_fast(mbeg + T2_MC, 1); asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); }
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-        }
-    } else if (nmt > 0) {
-        issue(mbeg, 0);
-        if (nmt > 1) { issue_stage(1, 1); asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); }      // stage 1 (8 loads per wave) stays in flight
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    }
-    // The stage loop.  A stage (64 token rows) is two MFMA steps of 32 tokens; a step is 8 dY x 4 X fragments = 32 MFMAs, issued as two blocks of
-    // 16: block P multiplies the step's dY fragments 0-3 (set FY[0]), block Q its fragments 4-7 (FY[1]), both with the step's four X fragments
-    // (FX[xb], double-buffered over steps).  A block's MFMAs run X-fragment-major, so its first four need one X fragment and its dY set.
-    // A 16-MFMA block is as long as an 8-MFMA k-step of the 32x32x16 loop this one replaces, and the four blocks of a stage keep that loop's frame:
-    // ONE wait + barrier per stage, between the third and the fourth block; the fourth block carries the 8 buffer loads of the stage after next
-    // (into the buffer the barrier has released) and reads its fragments from the NEXT stage.
-    // Transpose reads (inline asm, counted lgkmcnt: hipcc knows nothing of them): ONE behind each of the first 12 MFMAs of a block, 24 per step.
-    //   P issues   X2 X3 (this step, used by its own MFMAs 8.. and 12..), then FY[1] 0-3 (this step, for Q)
-    //   Q issues   X0 of the next step (other FX set), FY[0] 0-3 of the next step, X1 of the next step
-    // each as a "lo" and a "hi" read.  Reads return in order, so "at most n outstanding" names the fragment an MFMA is about to use; the n below
-    // are (reads issued so far) - (reads up to and including that fragment).
-    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    const uint32_t lds0 = (uint32_t)(uintptr_t)(LDS_PTR(char))smem;
-    uint32_t ya[8], xa[4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ya[i] = lds0 + (uint32_t)y_off[i];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) xa[j] = lds0 + (uint32_t)(T2_TILE + x_off[j]);
-    u32x2 fyl[2][4], fyh[2][4], fxl[2][4], fxh[2][4];
-    constexpr int STEPB = TNL_STEP * T2_ROWB;                        // bytes from the first MFMA step of a stage to the second
-#define TN_SB __builtin_amdgcn_sched_barrier(0)
-#define TN_TRR(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(off)); TN_SB
-#define TN_RXL(xb, j, OFF) TN_TRR(fxl[xb][j], xa[j], (OFF))
-#define TN_RXH(xb, j, OFF) TN_TRR(fxh[xb][j], xa[j], (OFF) + TNL_HI)
-#define TN_RYL(h, i, OFF) TN_TRR(fyl[h][i], ya[4 * (h) + (i)], (OFF))
-#define TN_RYH(h, i, OFF) TN_TRR(fyh[h][i], ya[4 * (h) + (i)], (OFF) + TNL_HI)
-#define TN_FRAG(lo, hi) __builtin_bit_cast(bf16x8, (u32x4){(lo).x, (lo).y, (hi).x, (hi).y})
-#define TN_WAIT(n) asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory"); TN_SB
-#define TN_MF(h, xb, i, j)                                                                                                                  \
-    acc[4 * (h) + (i)][j] = TCOW_MFMA_16x16x32_H16(TN_FRAG(fxl[xb][j], fxh[xb][j]), TN_FRAG(fyl[h][i], fyh[h][i]), acc[4 * (h) + (i)][j], 0, 0, 0); TN_SB
-#define TN_NOP do { } while (0)
-    // block P of the step at byte offset OFF of the stage: 12 reads of block Q (X0, Y0 Y1 Y2 Y3, X1) are outstanding at most on entry
-#define TN_BLK_P(xb, OFF)                                                                                                                   \
-    do {                                                                                                                                    \
-        TN_WAIT(8); TN_MF(0, xb, 0, 0); TN_RXL(xb, 2, OFF);                              /* X0, Y0 */                                        \
-        TN_WAIT(7); TN_MF(0, xb, 1, 0); TN_RXH(xb, 2, OFF);                              /* Y1 */                                            \
-        TN_WAIT(6); TN_MF(0, xb, 2, 0); TN_RXL(xb, 3, OFF);                              /* Y2 */                                            \
-        TN_WAIT(5); TN_MF(0, xb, 3, 0); TN_RXH(xb, 3, OFF);                              /* Y3 */                                            \
-        TN_WAIT(4); TN_MF(0, xb, 0, 1); TN_RYL(1, 0, OFF);                               /* X1: all of block Q's */                          \
-        TN_MF(0, xb, 1, 1); TN_RYH(1, 0, OFF);                                                                                              \
-        TN_MF(0, xb, 2, 1); TN_RYL(1, 1, OFF);                                                                                              \
-        TN_MF(0, xb, 3, 1); TN_RYH(1, 1, OFF);                                                                                              \
-        TN_WAIT(6); TN_MF(0, xb, 0, 2); TN_RYL(1, 2, OFF);                               /* X2: 2 of this block's 8 */                       \
-        TN_MF(0, xb, 1, 2); TN_RYH(1, 2, OFF);                                                                                              \
-        TN_MF(0, xb, 2, 2); TN_RYL(1, 3, OFF);                                                                                              \
-        TN_MF(0, xb, 3, 2); TN_RYH(1, 3, OFF);                                                                                              \
-        TN_WAIT(8); TN_MF(0, xb, 0, 3);                                                  /* X3: 4 of this block's 12 */                      \
-        TN_MF(0, xb, 1, 3); TN_MF(0, xb, 2, 3); TN_MF(0, xb, 3, 3);                                                                         \
-    } while (0)
-    // block Q: block P's 12 reads (X2, X3, Y0 Y1 Y2 Y3 of FY[1]) are outstanding at most on entry.  NOFF: byte offset of the NEXT step from the
-    // stage that ya / xa point to; nb: the FX set of that step; L0 ... L7: the load slots, behind every second MFMA.
-#define TN_BLK_Q(xb, nb, NOFF, L0, L1, L2, L3, L4, L5, L6, L7)                                                                              \
-    do {                                                                                                                                    \
-        TN_WAIT(6); TN_MF(1, xb, 0, 0); TN_RXL(nb, 0, NOFF);                             /* X2, X3, Y0 */                                    \
-        TN_WAIT(5); TN_MF(1, xb, 1, 0); TN_RXH(nb, 0, NOFF); L0; TN_SB;                  /* Y1 */                                            \
-        TN_WAIT(4); TN_MF(1, xb, 2, 0); TN_RYL(0, 0, NOFF);                              /* Y2 */                                            \
-        TN_WAIT(3); TN_MF(1, xb, 3, 0); TN_RYH(0, 0, NOFF); L1; TN_SB;                   /* Y3: all of block P's */                          \
-        TN_MF(1, xb, 0, 1); TN_RYL(0, 1, NOFF);                                                                                             \
-        TN_MF(1, xb, 1, 1); TN_RYH(0, 1, NOFF); L2; TN_SB;                                                                                  \
-        TN_MF(1, xb, 2, 1); TN_RYL(0, 2, NOFF);                                                                                             \
-        TN_MF(1, xb, 3, 1); TN_RYH(0, 2, NOFF); L3; TN_SB;                                                                                  \
-        TN_MF(1, xb, 0, 2); TN_RYL(0, 3, NOFF);                                                                                             \
-        TN_MF(1, xb, 1, 2); TN_RYH(0, 3, NOFF); L4; TN_SB;                                                                                  \
-        TN_MF(1, xb, 2, 2); TN_RXL(nb, 1, NOFF);                                                                                            \
-        TN_MF(1, xb, 3, 2); TN_RXH(nb, 1, NOFF); L5; TN_SB;                                                                                 \
-        TN_MF(1, xb, 0, 3); TN_MF(1, xb, 1, 3); L6; TN_SB;                                                                                  \
-        TN_MF(1, xb, 2, 3); TN_MF(1, xb, 3, 3); L7; TN_SB;                                                                                  \
-    } while (0)
-
-    if (nmt > 0) {       // what block Q of a stage before the first would have issued
-        TN_RXL(0, 0, 0); TN_RXH(0, 0, 0);
-        TN_RYL(0, 0, 0); TN_RYH(0, 0, 0); TN_RYL(0, 1, 0); TN_RYH(0, 1, 0); TN_RYL(0, 2, 0); TN_RYH(0, 2, 0); TN_RYL(0, 3, 0); TN_RYH(0, 3, 0);
-        TN_RXL(0, 1, 0); TN_RXH(0, 1, 0);
-    }
-    for (int it = 0; it < nmt; ++it) {
-        const int stage = it & 1;
-        const uint32_t so = (uint32_t)stage * T2_STAGE;
-        const char* sy = smem + stage * T2_STAGE;
-        TN_BLK_P(0, 0);
-        TN_BLK_Q(0, 1, STEPB, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP);
-        TN_BLK_P(1, STEPB);
-        TN_COLSUM(sy)
-        // this wave's loads of stage it+1 (requested a whole stage ago) have landed, its reads of this stage are back (the fourth block's
-        // fragments are in registers): behind the barrier the buffer of this stage is free and stage it+1 is visible
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __syncthreads();
-        {
-            const uint32_t flip = stage ? (uint32_t)(-T2_STAGE) : (uint32_t)T2_STAGE;       // the read addresses move to the next stage
-#pragma unroll
-            for (int i = 0; i < 8; ++i) ya[i] += flip;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) xa[j] += flip;
-        }
-        TN_SB;
-        if constexpr (SCHED == 2) {
-            // (every stage through the buffer loads: the host picks this variant for whole tiles and 32-bit offsets only)
-            const int mt2 = mbeg + (it + 2) * T2_MC;
-            const bool more = it + 2 < nmt;
-            const uint32_t dy = lds_base + so + wave * 4096, dx = dy + T2_TILE;
-            const uint32_t by = (uint32_t)((long)(mt2 + wave * 8) * p.ldy * 2), bx = (uint32_t)((long)(mt2 + wave * 8) * p.ldx * 2);
-            const uint32_t yw0 = more ? yv0 : 0x80000000u, yw1 = more ? yv1 : 0x80000000u;     // (the per-lane offset is the range-checked one)
-            const uint32_t xw0 = more ? xv0 : 0x80000000u, xw1 = more ? xv1 : 0x80000000u;
-            const uint32_t ry = (uint32_t)(2 * p.ldy * 2), rx = (uint32_t)(2 * p.ldx * 2);
-            TN_BLK_Q(1, 0, 0, TCOW_BUFFER_GLDS16(yw0, srd_y, by, dy), TCOW_BUFFER_GLDS16(xw0, srd_x, bx, dx), TCOW_BUFFER_GLDS16(yw1, srd_y, by + ry, dy + 1024),
-                     TCOW_BUFFER_GLDS16(xw1, srd_x, bx + rx, dx + 1024), TCOW_BUFFER_GLDS16(yw0, srd_y, by + 2 * ry, dy + 2048), TCOW_BUFFER_GLDS16(xw0, srd_x, bx + 2 * rx, dx + 2048),
-                     TCOW_BUFFER_GLDS16(yw1, srd_y, by + 3 * ry, dy + 3072), TCOW_BUFFER_GLDS16(xw1, srd_x, bx + 3 * rx, dx + 3072));
-        } else {
-            if (it + 2 < nmt) issue_stage(it + 2, stage);
-            TN_SB;
-            TN_BLK_Q(1, 0, 0, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP, TN_NOP);
-        }
-    }
-    // (The last stage's fourth block has requested fragments of a stage that does not exist into X0, X1 of set 0 and FY[0].  The wait re-defines those
-    // registers, so that hipcc -- which knows nothing of reads issued by asm statements -- cannot hand them to the code behind the loop before the
-    // data is in: see the same note in gemm_nt_c2.hip, where exactly that corrupted tiles)
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(fxl[0][0]), "+v"(fxl[0][1]), "+v"(fxh[0][0]), "+v"(fxh[0][1]), "+v"(fyl[0][0]), "+v"(fyl[0][1]), "+v"(fyl[0][2]), "+v"(fyl[0][3]),
-                   "+v"(fyh[0][0]), "+v"(fyh[0][1]), "+v"(fyh[0][2]), "+v"(fyh[0][3])
-                 :: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-#undef TN_BLK_Q
-#undef TN_BLK_P
-#undef TN_NOP
-#undef TN_MF
-#undef TN_WAIT
-#undef TN_FRAG
-#undef TN_RYH
-#undef TN_RYL
-#undef TN_RXH
-#undef TN_RXL
-#undef TN_TRR
-#undef TN_SB
-#undef TN_COLSUM
-    if (p.bias_part) {
-        // fold the sixteen row groups (the operand stages are dead: the loop ended on a barrier): red[rg][256 columns]
-        float* red = reinterpret_cast<float*>(smem);
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 8; ++e) red[cs_rg * 256 + cs_chunk * 8 + e] = csum[e];
-        __syncthreads();
-        if (n0 + cs_col < p.N) {
-            float t = 0.f;
-            if (tid < 256) {
-#pragma unroll
-                for (int g = 0; g < 16; ++g) t += red[g * 256 + cs_col];
-            }
-            p.bias_part[(((size_t)z * p.tiles_k + pk) * 2 + (tid >> 8)) * p.N + n0 + cs_col] = t;      // (the second half-row of the table stays zero)
-        }
-        __syncthreads();
-    }
-
-    // slab store: a lane's four accumulators of a block are four consecutive k of one n -- 16 bytes, 32 stores per wave.  (K is a multiple of 8,
-    // so a piece of four is whole or absent; SCHED = 2 has whole tiles only.  A slab that is not 16-byte aligned gets the same values one by one.)
-    float* out = p.slab + (size_t)z * p.N * p.K;
-    const int ln = lane & 15, lk = 4 * (lane >> 4);
-    auto store = [&](auto vec) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int gn = n0 + wm * 128 + i * 16 + ln;
-            if (SCHED != 2 && gn >= p.N) continue;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int gk = k0 + wn * 64 + j * 16 + lk;
-                if (SCHED != 2 && gk >= p.K) continue;
-                float* dst = out + (size_t)gn * p.K + gk;
-                if constexpr (decltype(vec)::value) *reinterpret_cast<f32x4*>(dst) = acc[i][j];
-                else { dst[0] = acc[i][j][0]; dst[1] = acc[i][j][1]; dst[2] = acc[i][j][2]; dst[3] = acc[i][j][3]; }
-            }
-        }
-    };
-    if ((reinterpret_cast<uintptr_t>(out) & 15) == 0) store(std::true_type{}); else store(std::false_type{});
-}
-
-template <int SCHED>
-__global__ __launch_bounds__(512, 2) void gemm_tn_bf16_256_kernel(TnParams p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    tn256_body<SCHED>(p, xcd_remap(blockIdx.x, gridDim.x), smem);
-}
-
-// Grouped launch: the weight gradients of ONE transformer block (7 Linear layers, 153 tiles of 256 x 256 at ViT-B) as one grid.  Launched
-// one by one, a 768 x 768 weight has 9 tiles and needs 28 token slices to fill the chip -- 66 MB of f32 partials written and read back per
-// GEMM (11.5 GB per training step), a fold launch each, and a ramp / tail per launch.  Together the tiles fill three rounds with FIVE slices:
-// every workgroup walks 5 418 token rows, the partials shrink 5x and one launch replaces seven.
-struct TnGroup { int n; int first[TCOW_TN_GROUP_MAX + 1]; TnParams p[TCOW_TN_GROUP_MAX]; };
-template <int SCHED>
-__global__ __launch_bounds__(512, 2) void gemm_tn_bf16_256_group_kernel(TnGroup g) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int pid = xcd_remap(blockIdx.x, gridDim.x);
-    int k = 0;
-    while (k + 1 < g.n && pid >= g.first[k + 1]) ++k;           // workgroup-uniform
-    const TnParams p = g.p[k];
-    tn256_body<SCHED>(p, pid - g.first[k], smem);
-}
 
 }  // namespace
 
-// slices for the 256-tile kernel: as many as fit one round of workgroups (<= 256), at least 256 token rows each
-int tcow_tn_splits_256(int M, int N, int K) {
-    const int tiles = cdiv(N, T2) * cdiv(K, T2);
-    int s = 256 / tiles;
-    const int max_s = M / 256;
-    if (s > max_s) s = max_s;
-    if (s > 64) s = 64;
-    if (s < 1) s = 1;
-    return s;
-}
-bool tcow_tn_use_256(int M, int N, int K) {
-    const int tiles = cdiv(N, T2) * cdiv(K, T2);
-    // (a 768 x 768 weight = 9 tiles x 28 slices still wins 12 % over the 128-tile kernel despite the larger slab fold)
-    return M >= 4096 && N >= 256 && K >= 256 && tiles >= 9 && tiles <= 256;
-}
+#include "gemm_tn_128.inc"
+#include "gemm_tn_256.inc"
 
-// Loads of the 256-tile weight-gradient kernel (tn256_body): whole 256-tiles with 32-bit byte offsets take SCHED = 2 (the next stage's requests
-// spread between the MFMAs of the stage's fourth block, as buffer loads with scalar row offsets), anything else the general SCHED = 1 (the same
-// stage loop, general addressing).
-static bool tn_whole(int M, int N, int K, long ldy, long ldx) { return N % T2 == 0 && K % T2 == 0 && (long)M * ldy < (1L << 29) && (long)M * ldx < (1L << 29); }
-
-// launch parameters of one weight gradient on output tiles of `tile` (TN_T with mc = TN_MC token rows per stage, or T2 with T2_MC), `splits` token slices requested
-static TnParams tn_params(int M, int N, int K, const bf16_t* dY, long ldy, const bf16_t* X, long ldx, float* slab, float* bias_part, int splits, int tile, int mc) {
+static TnParams tn_params(const TnPlan& pl, int M, int N, int K, const void* dY, long ldy, const void* X, long ldx, float* slab, float* bias_part) {
     TnParams p;
-    p.M = M; p.N = N; p.K = K; p.dY = dY; p.ldy = ldy; p.X = X; p.ldx = ldx; p.slab = slab;
-    p.tiles_n = cdiv(N, tile); p.tiles_k = cdiv(K, tile);
-    p.mps = ((cdiv(M, splits) + 63) / 64) * 64;
-    p.nz = cdiv(M, p.mps);
-    p.bias_part = bias_part;
-    p.rows_per_pk = cdiv(mc, p.tiles_k);
+    p.M = M; p.N = N; p.K = K; p.dY = (const bf16_t*)dY; p.ldy = ldy; p.X = (const bf16_t*)X; p.ldx = ldx; p.slab = slab;
+    p.tiles_n = pl.tiles_n; p.tiles_k = pl.tiles_k; p.mps = pl.mps; p.nz = pl.nz;
+    p.bias_part = bias_part; p.rows_per_pk = pl.rows_per_pk;
     return p;
 }
 template <typename P>
@@ -536,67 +47,25 @@ static void tn_launch_256(void (*kernel)(P), int grid, hipStream_t stream, const
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), T2_LDS, stream, p);
 }
 
-int tcow_gemm_tn_bf16(hipStream_t stream, int M, int N, int K, const bf16_t* dY, long ldy, const bf16_t* X, long ldx, float* slab, int splits,
-                      int* nz_out, float* bias_part, int* bias_parts_out) {
+int tcow_gemm_tn_bf16(hipStream_t stream, const TnPlan& pl, int M, int N, int K, const bf16_t* dY, long ldy, const bf16_t* X, long ldx, float* slab, float* bias_part) {
     TCOW_CHECK_ARG(N % 8 == 0 && K % 8 == 0 && ldy % 8 == 0 && ldx % 8 == 0, "tcow_gemm_tn(bf16): N, K, ldy, ldx must be multiples of 8");
-    const bool big = tcow_tn_use_256(M, N, K);
-    const TnParams p = big ? tn_params(M, N, K, dY, ldy, X, ldx, slab, bias_part, splits, T2, T2_MC) : tn_params(M, N, K, dY, ldy, X, ldx, slab, bias_part, splits, TN_T, TN_MC);
-    *nz_out = p.nz;
-    if (bias_parts_out) *bias_parts_out = p.nz * p.tiles_k * 2;
-    if (big) {
-        tn_launch_256(tn_whole(M, N, K, ldy, ldx) ? gemm_tn_bf16_256_kernel<2> : gemm_tn_bf16_256_kernel<1>, p.nz * p.tiles_n * p.tiles_k, stream, p);
-    } else {
-        const dim3 grid(8 * cdiv(p.nz, 8) * p.tiles_n * p.tiles_k);
-        hipLaunchKernelGGL(gemm_tn_bf16_kernel, grid, dim3(256), 2 * 2 * TN_MC * 256, stream, p);
-    }
+    const TnParams p = tn_params(pl, M, N, K, dY, ldy, X, ldx, slab, bias_part);
+    if (pl.kernel == TN_K128) hipLaunchKernelGGL(gemm_tn_bf16_kernel, dim3(8 * cdiv(p.nz, 8) * p.tiles_n * p.tiles_k), dim3(256), 2 * 2 * TN_MC * 256, stream, p);
+    else tn_launch_256(pl.kernel == TN_K256_S2 ? gemm_tn_bf16_256_kernel<2> : gemm_tn_bf16_256_kernel<1>, p.nz * p.tiles_n * p.tiles_k, stream, p);
     TCOW_CHECK_LAUNCH();
     return TCOW_OK;
 }
 
-// ---- grouped weight-gradient launch (see gemm_tn_bf16_256_group_kernel).  All problems share M and the slice count nz.
-bool tcow_tn_group_ok(int n, const tcow_tn_problem* pr) {
-    if (n < 2 || n > TCOW_TN_GROUP_MAX) return false;
-    for (int i = 0; i < n; ++i) {
-        if (pr[i].M != pr[0].M || !tcow_tn_use_256(pr[i].M, pr[i].N, pr[i].K)) return false;
-        if (pr[i].N % 8 || pr[i].K % 8 || pr[i].ldy % 8 || pr[i].ldx % 8) return false;
-    }
-    return true;
-}
-// common slice count: the cheapest one under  cost(s) = 1 / (fill of whole rounds of 256 workgroups) + 0.044 s  -- every slice writes and re-reads
-// one f32 image of all the group's weights: slab store + fold measured at 22 % of the loop time with five slices (profiles/r04_ubench_tn_ab.txt,
-// r04_step_kernel_stats.txt).  One ViT-B block (153 tiles): 5 slices (765 workgroups = 2.99 rounds); four blocks (612 tiles): 2 slices
-// (1224 workgroups = 4.78 rounds, 60 % less slab traffic for 4 % more tail).  >= 256 token rows per slice.
-int tcow_tn_group_slices(int n, const tcow_tn_problem* pr) {
-    int tiles = 0;
-    for (int i = 0; i < n; ++i) tiles += cdiv(pr[i].N, T2) * cdiv(pr[i].K, T2);
-    int max_s = pr[0].M / 256; if (max_s > 64) max_s = 64; if (max_s < 1) max_s = 1;
-    int best = 1; double best_cost = 1e30;
-    for (int s = 1; s <= max_s; ++s) {
-        const int wg = s * tiles, rounds = cdiv(wg, 256);
-        const double cost = (rounds * 256.0) / (double)wg + 0.044 * s;
-        if (cost < best_cost - 1e-9) { best_cost = cost; best = s; }
-    }
-    return best;
-}
-int tcow_gemm_tn_bf16_group(hipStream_t stream, int n, const tcow_tn_problem* pr, int nz_req, float* const* slabs, float* const* bias_parts, int* nz_out,
-                            int* bias_nparts) {
+// grouped launch (gemm_tn_bf16_256_group_kernel): all problems share M and the slice count
+int tcow_gemm_tn_bf16_group(hipStream_t stream, const TnGroupPlan& pl, int n, const tcow_tn_problem* pr, float* const* slabs, float* const* bias_parts) {
     TnGroup g;
     g.n = n;
-    int first = 0, nz = 0;
     for (int i = 0; i < n; ++i) {
-        TnParams& p = g.p[i];
-        p = tn_params(pr[i].M, pr[i].N, pr[i].K, (const bf16_t*)pr[i].dY, pr[i].ldy, (const bf16_t*)pr[i].X, pr[i].ldx, slabs[i], bias_parts[i], nz_req, T2, T2_MC);
-        nz = p.nz;
-        bias_nparts[i] = p.nz * p.tiles_k * 2;
-        g.first[i] = first;
-        first += p.nz * p.tiles_n * p.tiles_k;
+        g.p[i] = tn_params(pl.p[i], pr[i].M, pr[i].N, pr[i].K, pr[i].dY, pr[i].ldy, pr[i].X, pr[i].ldx, slabs[i], bias_parts[i]);
+        g.first[i] = pl.p[i].first;
     }
-    g.first[n] = first;
-    for (int i = n + 1; i <= TCOW_TN_GROUP_MAX; ++i) g.first[i] = first;
-    *nz_out = nz;
-    bool whole = true;
-    for (int i = 0; i < n; ++i) whole = whole && tn_whole(pr[i].M, pr[i].N, pr[i].K, pr[i].ldy, pr[i].ldx);
-    tn_launch_256(whole ? gemm_tn_bf16_256_group_kernel<2> : gemm_tn_bf16_256_group_kernel<1>, first, stream, g);
+    for (int i = n; i <= TCOW_TN_GROUP_MAX; ++i) g.first[i] = pl.workgroups;
+    tn_launch_256(pl.kernel == TN_K256_S2 ? gemm_tn_bf16_256_group_kernel<2> : gemm_tn_bf16_256_group_kernel<1>, pl.workgroups, stream, g);
     TCOW_CHECK_LAUNCH();
     return TCOW_OK;
 }

@@ -1,6 +1,6 @@
-// LDS image of the 256-tile weight-gradient GEMM (gemm_tn_bf16.hip, tn256_body): where the direct-to-LDS loads put a stage, and where the transpose
+// LDS image of the 256-tile weight-gradient GEMM (gemm_tn_256.inc, tn256_body): where the direct-to-LDS loads put a stage, and where the transpose
 // reads of the 16x16x32 MFMA operands and the column-sum reads find it.  Plain constexpr functions of integers, shared by the kernel and by the
-// host program tools/tn_layout_check.cpp, which enumerates every lane of every load and read (tests/test_gpu_gemm_tn_k32.py runs it on the CPU).
+// host program tools/tn_layout_check.cpp, which enumerates every lane of every load and read (tests/test_gemm_tn_plan_host.py runs it on the CPU).
 //
 // One operand tile of a stage is [64 token rows][256 columns] of 16-bit elements: 512-byte rows of 32 chunks of 16 bytes.  Chunk c of row r sits
 // at chunk position c ^ tnl_swz(r).  A 16x16x32 operand fragment is 16 columns x 32 tokens, lane l holding column l & 15 and tokens

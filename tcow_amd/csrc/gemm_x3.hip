@@ -17,8 +17,7 @@
 
 namespace {
 
-constexpr int XT = 128;              // tile edge
-constexpr int XK = 32;               // k-slice
+// (XT = 128: tile edge, XK = 32: k-slice -- gemm_tile_sizes.h)
 constexpr int XP = 80;               // LDS row pitch in bytes (32 bf16 + 16 B pad)
 constexpr int XPLANE = XT * XP;      // 10 KiB per plane
 
@@ -295,29 +294,14 @@ int tcow_gemm_nt_x3(hipStream_t stream, const tcow_gemm_args* a) {
     return TCOW_OK;
 }
 
-// token-dimension slices of the weight-gradient form: as many as keep tiles x slices within ONE round of 3 workgroups per CU
-// (the vector loaders fit 168 registers and 40 KiB of LDS), at least 256 tokens each
-int tcow_tn_splits_x3(int M, int N, int K) {
-    const int tiles = cdiv(N, XT) * cdiv(K, XT);
-    int s = (3 * 256) / tiles;
-    const int max_s = M / 256;
-    if (s > max_s) s = max_s;
-    if (s > 64) s = 64;
-    if (s < 1) s = 1;
-    return s;
-}
-
-int tcow_gemm_tn_x3(hipStream_t stream, int M, int N, int K, const float* dY, long ldy, const float* X, long ldx, float* dW, long lddw,
-                    int accumulate, float* slab, int splits, const float* bias_part, int bias_nparts, float* bias_out) {
-    int kps = cdiv(M, splits); kps = ((kps + XK - 1) / XK) * XK;
-    const int nz = cdiv(M, kps);
-    const F32Params p = f32_params_plain(N, K, M, dY, 1, ldy, X, 1, ldx, kps, slab);      // output [N,K], contraction over tokens
+int tcow_gemm_tn_x3(hipStream_t stream, const TnPlan& pl, int M, int N, int K, const float* dY, long ldy, const float* X, long ldx, float* slab) {
+    const F32Params p = f32_params_plain(N, K, M, dY, 1, ldy, X, 1, ldx, pl.mps, slab);      // output [N,K], contraction over tokens
     const bool vec = ((reinterpret_cast<uintptr_t>(dY) | reinterpret_cast<uintptr_t>(X)) & 15) == 0 && ((ldy | ldx | N | K) & 3) == 0;
-    const dim3 grid(cdiv(K, XT) * cdiv(N, XT), nz);
+    const dim3 grid(pl.tiles_k * pl.tiles_n, pl.nz);
     if (vec) hipLaunchKernelGGL(gemm_x3_kernel<LD_RVEC>, grid, dim3(256), 0, stream, p);
     else hipLaunchKernelGGL(gemm_x3_kernel<LD_ANY>, grid, dim3(256), 0, stream, p);
     TCOW_CHECK_LAUNCH();
-    return tcow_launch_slab_reduce(stream, slab, nz, (long)N * K, N, K, dW, lddw, accumulate, bias_part, bias_nparts, N, bias_out);       // (bias partials of tcow_launch_colsum_partials ride on the fold)
+    return TCOW_OK;
 }
 
 // ---- tcow_sgemm_x3_batched: C = A B for up to 24 small f32 problems in one launch; every operand is addressed by (row stride, k stride),

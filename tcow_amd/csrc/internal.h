@@ -2,8 +2,8 @@
 // each, included by the defining file and by every caller.  (The attention back ends take a SeqDesc: attention_common.h declares them.)
 #pragma once
 #include "common.h"
+#include "gemm_tn_plan.h"      // TCOW_TN_GROUP_MAX, TnPlan, TnGroupPlan: the host rules of the weight-gradient GEMMs
 
-constexpr int TCOW_TN_GROUP_MAX = 40;     // problems of one grouped weight-gradient launch (five divided space-time blocks: 35-40 problems; TnGroup = 3.7 KiB, below the 4 KiB kernel-argument limit)
 constexpr int TCOW_LN_FOLD_MAX = 16;      // jobs of one tcow_layernorm_fold launch
 
 // ---- NT GEMM back ends (forward / input gradient)
@@ -16,20 +16,12 @@ int tcow_gemm_nt_skinny_launch_x3(hipStream_t stream, const tcow_gemm_args* a, i
 int tcow_gemm_nt_f32(hipStream_t stream, const tcow_gemm_args* a);                                  // gemm_f32.hip
 int tcow_gemm_nt_x3(hipStream_t stream, const tcow_gemm_args* a);                                   // gemm_x3.hip
 
-// ---- TN GEMM back ends (weight gradient), their slice planners and group predicates
-int tcow_gemm_tn_bf16(hipStream_t stream, int M, int N, int K, const bf16_t* dY, long ldy, const bf16_t* X, long ldx, float* slab, int splits, int* nz_out,
-                      float* bias_part, int* bias_parts_out);                                       // gemm_tn_bf16.hip
-int tcow_tn_splits_256(int M, int N, int K);
-bool tcow_tn_use_256(int M, int N, int K);
-bool tcow_tn_group_ok(int n, const tcow_tn_problem* pr);
-int tcow_tn_group_slices(int n, const tcow_tn_problem* pr);
-int tcow_gemm_tn_bf16_group(hipStream_t stream, int n, const tcow_tn_problem* pr, int nz_req, float* const* slabs, float* const* bias_parts, int* nz_out,
-                            int* bias_nparts);
-int tcow_gemm_tn_f32(hipStream_t stream, int M, int N, int K, const float* dY, long ldy, const float* X, long ldx, float* dW, long lddw, int accumulate,
-                     float* slab, int splits, const float* bias_part, int bias_nparts, float* bias_out);       // gemm_f32.hip
-int tcow_gemm_tn_x3(hipStream_t stream, int M, int N, int K, const float* dY, long ldy, const float* X, long ldx, float* dW, long lddw, int accumulate,
-                    float* slab, int splits, const float* bias_part, int bias_nparts, float* bias_out);        // gemm_x3.hip
-int tcow_tn_splits_x3(int M, int N, int K);
+// ---- TN GEMM back ends (weight gradient): each launches its kernel into the slab as the plan (gemm_tn_plan.h) says; tcow_gemm_tn issues the fold
+int tcow_gemm_tn_bf16(hipStream_t stream, const TnPlan& pl, int M, int N, int K, const bf16_t* dY, long ldy, const bf16_t* X, long ldx, float* slab,
+                      float* bias_part);                                                            // gemm_tn_bf16.hip
+int tcow_gemm_tn_bf16_group(hipStream_t stream, const TnGroupPlan& pl, int n, const tcow_tn_problem* pr, float* const* slabs, float* const* bias_parts);
+int tcow_gemm_tn_f32(hipStream_t stream, const TnPlan& pl, int M, int N, int K, const float* dY, long ldy, const float* X, long ldx, float* slab);      // gemm_f32.hip
+int tcow_gemm_tn_x3(hipStream_t stream, const TnPlan& pl, int M, int N, int K, const float* dY, long ldy, const float* X, long ldx, float* slab);       // gemm_x3.hip
 
 // ---- reduction launchers (reduce.hip)
 int tcow_launch_slab_reduce(hipStream_t stream, const float* slab, int nz, long slab_stride, long rows, long cols, float* out, long ldo, int accumulate,

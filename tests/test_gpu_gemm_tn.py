@@ -10,8 +10,8 @@ The guards.  Operands are the [:M, :N] / [:M, :K] views of buffers with >= 64 ro
 (ld = N + 8, K + 8), NaN pad columns: any over-read turns an accumulator into NaN.  dW is a view of an [N + 1, K + pad] buffer and
 bias_grad the head of an N + 8 buffer, both filled with the sentinel 7.0, which everything outside the view must keep.
 
-The shape comments give (kernel, splits requested, mps = token rows per slice, nz = slices, rows of the last slice) as tcow_tn_use_256,
-tcow_tn_splits_256, tcow_tn_splits, tn_params and tcow_tn_group_slices derive them at this commit."""
+The shape comments give (kernel, splits requested, mps = token rows per slice, nz = slices, rows of the last slice) of the host plan
+(tcow_amd/csrc/gemm_tn_plan.h: tcow_tn_plan, tcow_tn_group_plan).  They are asserted, shape by shape, on the CPU: tests/test_gemm_tn_plan_host.py."""
 import pytest
 import torch
 
@@ -232,7 +232,7 @@ def test_engine_form_two_halves_of_one_buffer(ops, cuda, refs, mname):
 # ---- 5: bias-table edges
 @pytest.mark.parametrize('mname', MODES16)
 @pytest.mark.parametrize('M,N,K', [(4096, 8, 4224),        # (128-tile, 16, 256, 16, 256): 33 k-tiles > 32 stage rows -> rows_per_pk = 1, the last k-tile sums no bias row; fused bias
-                                   (4096, 256, 16640),     # (256-tile SCHED 2, 3, 1408, 3, 1280): 65 k-tiles > 64 stage rows; fused bias (3 x 130 x 2 = 780 rows)
+                                   (4096, 256, 16640),     # (256-tile SCHED 2, 3, 1408, 3, 1280): 65 k-tiles of 256 > 64 stage rows; fused bias (3 x 65 x 2 = 390 table rows)
                                    (2048, 8, 24704)])      # (128-tile, 8, 256, 8, 256): 8 x 193 x 2 = 3088 > 3072 table rows -> un-fused bias (tcow_launch_colsum)
 def test_bias_table_edges(ops, cuda, refs, mname, M, N, K):
     mode, dt = _mode(ops, mname)
@@ -308,7 +308,7 @@ def _run_group(ops, dev, refs, mname, specs, what):
 
 
 GM = 4133
-# 30 tiles -> tcow_tn_group_slices = 8: (256-tile group SCHED 1 -- one problem is ragged --, 8, 576, 8, 101); all folds by the one group fold launch
+# 30 tiles -> the group plan asks for 8 slices: (256-tile group SCHED 1 -- one problem is ragged --, 8, 576, 8, 101); all folds by the one group fold launch
 GROUP_MIXED = [(GM, 768, 768, True, False, 'dense', 0), (GM, 776, 520, False, True, 'ld8', 0), (GM, 256, 2304, True, True, 'ld8', 0)]
 
 
@@ -329,7 +329,7 @@ def test_group_with_scalar_fold_member(ops, cuda, refs, mname):
 
 @pytest.mark.parametrize('mname', MODES16)
 def test_group_one_slice_direct_write(ops, cuda, refs, mname):
-    """7c: 64 + 64 + 64 + 64 = 256 tiles -> tcow_tn_group_slices = 1 (cost 1.044 against 1.088 for two slices): (256-tile group SCHED 2, 1, 4160, 1, 4133).
+    """7c: 64 + 64 + 64 + 64 = 256 tiles -> the group plan asks for 1 slice (cost 1.044 against 1.088 for two slices): (256-tile group SCHED 2, 1, 4160, 1, 4133).
     The plain problem and the one without bias_grad are written straight into dW (slab = dW, no fold blocks); accumulate = 1 and lddw = K + 8 go through a slab."""
     specs = [(GM, 2048, 2048, True, False, 'dense', 0), (GM, 1024, 4096, True, True, 'dense', 0), (GM, 4096, 1024, True, False, 'ld8', 0), (GM, 2048, 2048, False, False, 'dense', 1)]
     _run_group(ops, cuda, refs, mname, specs, '7c')

@@ -5,18 +5,13 @@ GPU tests (exact integers, the kit of test_gpu_gemm_tn.py: operands in {-3 ... 3
   2. the general path (SCHED = 1): an edge tile in n, and strided operands with an edge tile in k;
   3. the grouped launch, through the slab + fold path and through the in-place (one slice) path;
   4. full-range operands against the derived accumulation bound.
-CPU test:
-  5. the LDS image (tcow_amd/csrc/gemm_tn_layout.h) enumerated lane by lane by tools/tn_layout_check.cpp, built with the host compiler."""
-import os
-import shutil
-import subprocess
-
+That every shape here reaches the kernel form it was chosen for is asserted on the CPU by tests/test_gemm_tn_plan_host.py, which also holds the
+check of the LDS image (tools/tn_layout_check.cpp)."""
 import pytest
 import torch
 
 from test_gpu_gemm_tn import Out, _mode, _operands, _reference
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODES16 = ['bf16', 'fp16']
 TAILS = [1, 15, 16, 17, 31, 32, 33, 48, 63]
 
@@ -101,7 +96,7 @@ def _group(ops, dev, refs, mname, copies):
 @pytest.mark.gpu
 @pytest.mark.parametrize('mname', MODES16)
 def test_grouped_slab_and_fold(ops, cuda, refs, mname):
-    """768 x 768 and 2304 x 768 at M = 4113: 9 + 27 = 36 tiles; tcow_tn_group_slices picks 7 slices (252 workgroups, cost 1.016 + 0.308):
+    """768 x 768 and 2304 x 768 at M = 4113: 9 + 27 = 36 tiles; the group plan (tcow_tn_group_slices, gemm_tn_plan.h) picks 7 slices (252 workgroups, cost 1.016 + 0.308):
     mps = 640, the last slice has 273 rows = 4 stages + 17 rows; seven slabs per weight, folded by the group fold launch."""
     _group(ops, cuda, refs, mname, 1)
 
@@ -143,17 +138,3 @@ def test_full_range_operands(ops, cuda, mname):
     assert not bool(out.dW.isnan().any()) and bool((err_w <= bound_w).all()), f'dW: {int((err_w > bound_w).sum())} entries beyond the bound, worst ratio {float((err_w / bound_w).max())}'
     assert bool((err_b <= bound_b).all()), f'bias_grad: worst ratio {float((err_b / bound_b).max())}'
     assert out.guards_ok()
-
-
-# ---- 5 (CPU)
-def test_lds_layout_on_cpu(tmp_path):
-    """tools/tn_layout_check.cpp includes the header the kernel uses and checks, over all lanes, that the loads write every element of a stage once,
-    that every transpose read returns what the 16x16x32 operand layout demands, and that the transpose reads (per 32-lane half) and the 16-byte
-    column-sum reads (per 16-lane group) are free of bank conflicts."""
-    cxx = next((c for c in (os.environ.get('CXX'), 'c++', 'g++', 'clang++', '/opt/rocm/llvm/bin/clang++') if c and shutil.which(c)), None)
-    assert cxx, 'no host C++ compiler found'
-    exe = str(tmp_path / 'tn_layout_check')
-    subprocess.run([cxx, '-std=c++17', '-O1', '-I', os.path.join(ROOT, 'tcow_amd', 'csrc'), os.path.join(ROOT, 'tools', 'tn_layout_check.cpp'), '-o', exe],
-                   check=True, capture_output=True, text=True, timeout=300)
-    run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert run.returncode == 0 and run.stdout.strip().endswith('ok'), run.stdout + run.stderr

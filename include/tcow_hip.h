@@ -154,6 +154,23 @@ int tcow_gemm_tn_grouped(void* stream, int dtype, int n, const tcow_tn_problem* 
 /* most problems that run as one grid (more are accepted and run one by one): 40 = the weight gradients of five divided space-time blocks */
 int tcow_gemm_tn_group_max(void);
 
+/* Bias gradients without their weight gradients (a Linear whose weight is frozen and whose bias trains):  out[N] (f32) (+)= column sums of
+ * dY[M,N], for up to tcow_colsum_group_max() Linear layers in one call (two launches: the partial sums of all problems as one grid, their fold
+ * as one more).  dY: `dtype` row-major (TCOW_BF16 or TCOW_F32), lddy in elements; every dY is read once, in 16-byte loads, so with V = 8
+ * elements of 16-bit storage / 4 of f32:  N % V == 0, lddy % V == 0, lddy >= N and dY 16-byte aligned.  M >= 1; dY and out not NULL.
+ * accumulate != 0 adds into `out`.  Partial sums are f32, one row of N per 256 rows of dY (at most 64 rows), kept in `workspace` (f32,
+ * at least tcow_colsum_grouped_workspace_bytes(dtype, n, problems) bytes, no initialisation needed) and summed in a fixed order.
+ * Every refusal (TCOW_ERR_INVALID_ARG) happens before any launch: no output is touched. */
+typedef struct {
+    int M, N;
+    const void* dY; long lddy;
+    float* out;
+    int accumulate;
+} tcow_colsum_problem;
+long tcow_colsum_grouped_workspace_bytes(int dtype, int n, const tcow_colsum_problem* problems);
+int tcow_colsum_grouped(void* stream, int dtype, int n, const tcow_colsum_problem* problems, void* workspace, long workspace_bytes);
+int tcow_colsum_group_max(void);
+
 /* Small f32 products C[M,N] = A B for the folded temporal projection (W' = W_fc W_proj after every optimizer step;
  * dW_fc = dW' W_proj^T + db' b_proj^T, dW_proj = W_fc^T dW', db_proj = W_fc^T db' in the backward): up to 24 problems per launch on the split-bf16 arithmetic of TCOW_F32X3
  * (three bf16 MFMAs per product, ~5e-6 relative).  A(i,k) = A[i*sai + k*sak], B(j,k) = B[j*sbj + k*sbk] -- one stride of each operand

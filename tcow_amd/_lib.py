@@ -45,6 +45,11 @@ class TnProblem(ctypes.Structure):
                 ('dW', ctypes.c_void_p), ('lddw', ctypes.c_long), ('bias_grad', ctypes.c_void_p), ('accumulate', ctypes.c_int)]
 
 
+class ColsumProblem(ctypes.Structure):
+    _fields_ = [('M', ctypes.c_int), ('N', ctypes.c_int), ('dY', ctypes.c_void_p), ('lddy', ctypes.c_long), ('out', ctypes.c_void_p),
+                ('accumulate', ctypes.c_int)]
+
+
 class LnFoldJob(ctypes.Structure):
     _fields_ = [('part', ctypes.c_void_p), ('parts', ctypes.c_int), ('D', ctypes.c_int), ('dgamma', ctypes.c_void_p), ('dbeta', ctypes.c_void_p),
                 ('colsum_out', ctypes.c_void_p), ('accumulate', ctypes.c_int)]
@@ -83,6 +88,9 @@ SIGNATURES = {
     'tcow_gemm_tn_grouped_workspace_bytes': (_l, [_i, _i, _vp]),
     'tcow_gemm_tn_grouped': (_i, [_vp, _i, _i, _vp, _vp, _l]),
     'tcow_gemm_tn_group_max': (_i, []),
+    'tcow_colsum_grouped_workspace_bytes': (_l, [_i, _i, _vp]),
+    'tcow_colsum_grouped': (_i, [_vp, _i, _i, _vp, _vp, _l]),
+    'tcow_colsum_group_max': (_i, []),
     'tcow_sgemm_x3_batched': (_i, [_vp, _i, _vp]),
     'tcow_layernorm_fwd': (_i, [_vp, _i, _i, _i, _vp, _l, _vp, _vp, _f, _vp, _l, _vp, _vp]),
     'tcow_layernorm_bwd_workspace_bytes': (_l, [_i]),

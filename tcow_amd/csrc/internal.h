@@ -5,6 +5,7 @@
 #include "gemm_tn_plan.h"      // TCOW_TN_GROUP_MAX, TnPlan, TnGroupPlan: the host rules of the weight-gradient GEMMs
 
 constexpr int TCOW_LN_FOLD_MAX = 16;      // jobs of one tcow_layernorm_fold launch
+constexpr int TCOW_COLSUM_GROUP_MAX = TCOW_LN_FOLD_MAX;      // problems of one tcow_colsum_grouped call: one row-fold launch finishes them
 
 // ---- NT GEMM back ends (forward / input gradient)
 int tcow_gemm_nt_bf16(hipStream_t stream, const tcow_gemm_args* a);                                 // gemm_bf16.hip

@@ -167,37 +167,99 @@ __global__ __launch_bounds__(256) void row_reduce_group_kernel(RowReduceGroup g)
     row_reduce_body(blockIdx.x, j.part, j.nrows, j.ld, j.N, j.out, j.accumulate, j.N1, j.out2, j.N12, j.out3);
 }
 
-// column sums of Y[M,N] (bias gradient): thread = 4 consecutive columns, a block covers 128 columns x a row slice with
-// 8 row groups folded through LDS; partial rows go to `part` and tcow_launch_slab_reduce finishes.
-template <typename T>
-__global__ __launch_bounds__(256) void colsum_partial_kernel(const T* __restrict__ Y, long ldy, int M, int N, int rows_per_blk, float* __restrict__ part) {
-    __shared__ float4 red[8][32];
+// VW consecutive elements of a row as floats: ld4 (VW = 4), or one 16-byte load of eight 16-bit elements (VW = 8)
+template <int VW, typename T> __device__ __forceinline__ void ld_cols(const T* p, float (&v)[VW]) {
+    if constexpr (VW == 4) {
+        const float4 t = ld4(p);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else {
+        static_assert(VW == 8 && sizeof(T) == 2, "eight 16-bit elements or four of any type");
+        const uint4 u = *reinterpret_cast<const uint4*>(p);
+        v[0] = bflo(u.x); v[1] = bfhi(u.x); v[2] = bflo(u.y); v[3] = bfhi(u.y); v[4] = bflo(u.z); v[5] = bfhi(u.z); v[6] = bflo(u.w); v[7] = bfhi(u.w);
+    }
+}
+
+// column sums of Y[M,N] (bias gradient): thread = VW consecutive columns, workgroup (bx, by) covers 32 * VW columns x a row slice with
+// 8 row groups folded through LDS; partial rows go to `part` and tcow_launch_slab_reduce / a row fold finishes.
+template <typename T, int VW>
+__device__ __forceinline__ void colsum_partial_body(const int bx, const int by, const T* __restrict__ Y, long ldy, int M, int N, int rows_per_blk, float* __restrict__ part) {
+    __shared__ __attribute__((aligned(16))) float red[8][32][VW];
     const int cq = threadIdx.x & 31, rg = threadIdx.x >> 5;
-    const int c = blockIdx.x * 128 + cq * 4;
-    const int r0 = blockIdx.y * rows_per_blk;
+    const int c = bx * (32 * VW) + cq * VW;
+    const int r0 = by * rows_per_blk;
     const int r1 = (r0 + rows_per_blk < M) ? r0 + rows_per_blk : M;
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (c + 3 < N) {
+    float s[VW];
+#pragma unroll
+    for (int k = 0; k < VW; ++k) s[k] = 0.f;
+    if (c + VW - 1 < N) {
         // four row groups in flight per trip (one load per trip ran at the memory latency: 2.7 TB/s at N = 768 in the f32-storage modes' step)
         int r = r0 + rg;
         for (; r + 24 < r1; r += 32) {
-            const float4 v0 = ld4(Y + (size_t)r * ldy + c), v1 = ld4(Y + (size_t)(r + 8) * ldy + c), v2 = ld4(Y + (size_t)(r + 16) * ldy + c), v3 = ld4(Y + (size_t)(r + 24) * ldy + c);
-            s.x += (v0.x + v1.x) + (v2.x + v3.x); s.y += (v0.y + v1.y) + (v2.y + v3.y); s.z += (v0.z + v1.z) + (v2.z + v3.z); s.w += (v0.w + v1.w) + (v2.w + v3.w);
+            float v0[VW], v1[VW], v2[VW], v3[VW];
+            ld_cols<VW>(Y + (size_t)r * ldy + c, v0); ld_cols<VW>(Y + (size_t)(r + 8) * ldy + c, v1);
+            ld_cols<VW>(Y + (size_t)(r + 16) * ldy + c, v2); ld_cols<VW>(Y + (size_t)(r + 24) * ldy + c, v3);
+#pragma unroll
+            for (int k = 0; k < VW; ++k) s[k] += (v0[k] + v1[k]) + (v2[k] + v3[k]);
         }
-        for (; r < r1; r += 8) { const float4 v = ld4(Y + (size_t)r * ldy + c); s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
+        for (; r < r1; r += 8) {
+            float v[VW];
+            ld_cols<VW>(Y + (size_t)r * ldy + c, v);
+#pragma unroll
+            for (int k = 0; k < VW; ++k) s[k] += v[k];
+        }
     } else if (c < N) {
         for (int r = r0 + rg; r < r1; r += 8) {
             const T* p = Y + (size_t)r * ldy + c;
-            s.x += Elem<T>::ld(p); if (c + 1 < N) s.y += Elem<T>::ld(p + 1); if (c + 2 < N) s.z += Elem<T>::ld(p + 2);
+#pragma unroll
+            for (int k = 0; k < VW; ++k)
+                if (c + k < N) s[k] += Elem<T>::ld(p + k);
         }
     }
-    red[rg][cq] = s;
+#pragma unroll
+    for (int k = 0; k < VW; ++k) red[rg][cq][k] = s[k];
     __syncthreads();
     if (rg == 0 && c < N) {
-        for (int g = 1; g < 8; ++g) { const float4 v = red[g][cq]; s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
-        float* o = part + (size_t)blockIdx.y * N + c;
-        o[0] = s.x; if (c + 1 < N) o[1] = s.y; if (c + 2 < N) o[2] = s.z; if (c + 3 < N) o[3] = s.w;
+        for (int g = 1; g < 8; ++g) {
+#pragma unroll
+            for (int k = 0; k < VW; ++k) s[k] += red[g][cq][k];
+        }
+        float* o = part + (size_t)by * N + c;
+#pragma unroll
+        for (int k = 0; k < VW; ++k)
+            if (c + k < N) o[k] = s[k];
     }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void colsum_partial_kernel(const T* __restrict__ Y, long ldy, int M, int N, int rows_per_blk, float* __restrict__ part) {
+    colsum_partial_body<T, 4>(blockIdx.x, blockIdx.y, Y, ldy, M, N, rows_per_blk, part);
+}
+// the same for several matrices as ONE flat grid (tcow_colsum_grouped): job k owns workgroups [first[k], first[k + 1]), column blocks fastest;
+// every thread loads 16 bytes (the entry point has checked what that needs of N, ldy and the pointers)
+struct ColsumJob { const void* Y; float* part; long ldy; int M, N, rows_per_blk, nbx; };
+struct ColsumGroup { int n; int first[TCOW_COLSUM_GROUP_MAX + 1]; ColsumJob j[TCOW_COLSUM_GROUP_MAX]; };
+template <typename T>
+__global__ __launch_bounds__(256) void colsum_partial_group_kernel(ColsumGroup g) {
+    int k = 0;
+    while (k + 1 < g.n && (int)blockIdx.x >= g.first[k + 1]) ++k;          // workgroup-uniform
+    const ColsumJob& j = g.j[k];
+    const int b = (int)blockIdx.x - g.first[k];
+    colsum_partial_body<T, 16 / (int)sizeof(T)>(b % j.nbx, b / j.nbx, (const T*)j.Y, j.ldy, j.M, j.N, j.rows_per_blk, j.part);
+}
+
+// row slices of a column sum over M rows: one per 256 rows, at most max_parts, none of them empty
+inline int colsum_parts(int M, int max_parts, int* rows_per_blk) {
+    int parts = cdiv(M, 256); if (parts > max_parts) parts = max_parts; if (parts < 1) parts = 1;
+    *rows_per_blk = cdiv(M, parts);
+    return cdiv(M, *rows_per_blk);
+}
+// (the row slices of the f32-storage weight-gradient GEMM's own column-sum launch: with them the partial rows, and so a bias gradient, are the
+// same bits whether its Linear's weight gradient is computed or not; up to 112 rows tcow_launch_row_reduce_group adds them in that fold's order)
+constexpr int kColsumGroupMaxParts = TN_COLSUM_PARTS;
+// f32 elements of a problem's partial table inside the group's workspace (tables start on 16-byte boundaries)
+inline long colsum_table_floats(const tcow_colsum_problem& p) {
+    if (p.M < 1 || p.N < 1) return 0;
+    int rpb;
+    return ((long)colsum_parts(p.M, kColsumGroupMaxParts, &rpb) * p.N + 3) & ~3L;
 }
 
 }  // namespace
@@ -277,9 +339,8 @@ int tcow_launch_row_reduce_group(hipStream_t stream, int n, const float* const* 
 
 // the partial sums only: `part` [parts][N], returns the number of parts (the caller folds them -- with the weight-gradient slabs, in one launch)
 int tcow_launch_colsum_partials(hipStream_t stream, int dtype, const void* Y, long ldy, int M, int N, float* part, int max_parts, int* nparts) {
-    int parts = cdiv(M, 256); if (parts > max_parts) parts = max_parts; if (parts < 1) parts = 1;
-    const int rpb = cdiv(M, parts);
-    parts = cdiv(M, rpb);
+    int rpb;
+    const int parts = colsum_parts(M, max_parts, &rpb);
     if (dtype == TCOW_BF16)
         hipLaunchKernelGGL(colsum_partial_kernel<bf16_t>, dim3(cdiv(N, 128), parts), dim3(256), 0, stream, (const bf16_t*)Y, ldy, M, N, rpb, part);
     else
@@ -296,3 +357,57 @@ int tcow_launch_colsum(hipStream_t stream, int dtype, const void* Y, long ldy, i
     if (rc) return rc;
     return tcow_launch_slab_reduce(stream, part, parts, N, 1, N, out, N, accumulate, nullptr, 0, 0, nullptr);
 }
+
+extern "C" {
+
+int tcow_colsum_group_max(void) { return TCOW_COLSUM_GROUP_MAX; }
+
+long tcow_colsum_grouped_workspace_bytes(int dtype, int n, const tcow_colsum_problem* pr) {
+    (void)dtype;                    // (partial sums are f32 whatever the storage)
+    long total = 0;
+    for (int i = 0; pr && i < n; ++i) total += colsum_table_floats(pr[i]);
+    return total * 4;
+}
+
+int tcow_colsum_grouped(void* stream, int dtype, int n, const tcow_colsum_problem* pr, void* workspace, long workspace_bytes) {
+    constexpr int G = TCOW_COLSUM_GROUP_MAX;
+    TCOW_CHECK_ARG(dtype == TCOW_BF16 || dtype == TCOW_F32, "tcow_colsum_grouped: unknown dtype %d", dtype);
+    TCOW_CHECK_ARG(n >= 1 && n <= G, "tcow_colsum_grouped: 1 .. %d problems per call (got %d)", G, n);
+    TCOW_CHECK_ARG(pr && workspace, "tcow_colsum_grouped: null pointer (problems or workspace)");
+    const int vw = dtype == TCOW_BF16 ? 8 : 4;              // elements of one 16-byte load
+    for (int i = 0; i < n; ++i) {
+        const tcow_colsum_problem& p = pr[i];
+        TCOW_CHECK_ARG(p.dY && p.out, "tcow_colsum_grouped: null pointer in problem %d (dY or out)", i);
+        TCOW_CHECK_ARG(p.M >= 1, "tcow_colsum_grouped: problem %d has M=%d rows, at least 1 is needed", i, p.M);
+        TCOW_CHECK_ARG(p.N >= 1 && p.N % vw == 0, "tcow_colsum_grouped: N=%d of problem %d must be a multiple of %d", p.N, i, vw);
+        TCOW_CHECK_ARG(p.lddy >= p.N, "tcow_colsum_grouped: lddy=%ld of problem %d is below N=%d", p.lddy, i, p.N);
+        TCOW_CHECK_ARG(p.lddy % vw == 0 && reinterpret_cast<uintptr_t>(p.dY) % 16 == 0,
+                       "tcow_colsum_grouped: dY of problem %d must be 16-byte aligned with lddy a multiple of %d", i, vw);
+    }
+    const long need = tcow_colsum_grouped_workspace_bytes(dtype, n, pr);
+    TCOW_CHECK_ARG(workspace_bytes >= need, "tcow_colsum_grouped: workspace too small (%ld < %ld)", workspace_bytes, need);
+    ColsumGroup g;
+    g.n = n;
+    const float* part[G]; int nrows[G]; long ld[G]; int N1[G], zero[G], acc[G]; float* out[G]; float* none[G];
+    float* table = static_cast<float*>(workspace);
+    int first = 0;
+    for (int i = 0; i < n; ++i) {
+        const tcow_colsum_problem& p = pr[i];
+        ColsumJob& j = g.j[i];
+        j.Y = p.dY; j.part = table; j.ldy = p.lddy; j.M = p.M; j.N = p.N;
+        nrows[i] = colsum_parts(p.M, kColsumGroupMaxParts, &j.rows_per_blk);
+        j.nbx = cdiv(p.N, 32 * vw);
+        g.first[i] = first;
+        first += j.nbx * nrows[i];
+        part[i] = table; ld[i] = p.N; N1[i] = p.N; zero[i] = 0; acc[i] = p.accumulate ? 1 : 0; out[i] = p.out; none[i] = nullptr;
+        table += colsum_table_floats(p);
+    }
+    for (int i = n; i < G; ++i) g.j[i] = g.j[0];
+    for (int i = n; i <= G; ++i) g.first[i] = first;
+    if (dtype == TCOW_BF16) hipLaunchKernelGGL(colsum_partial_group_kernel<bf16_t>, dim3(first), dim3(256), 0, (hipStream_t)stream, g);
+    else hipLaunchKernelGGL(colsum_partial_group_kernel<float>, dim3(first), dim3(256), 0, (hipStream_t)stream, g);
+    TCOW_CHECK_LAUNCH();
+    return tcow_launch_row_reduce_group((hipStream_t)stream, n, part, nrows, ld, N1, out, zero, none, zero, none, acc);
+}
+
+}  // extern "C"

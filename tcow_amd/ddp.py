@@ -89,7 +89,9 @@ def first_contact(device=None, timeout_s=None, group=None):
 class GradSync:
     """Bucketed, overlapped gradient averaging. Attach with `module.grad_hook = sync`: engine.run_backward calls it once
     per completed bucket and drains it (`finish()`) before handing the gradients to autograd, so after `loss.backward()`
-    every param.grad is already the mean over ranks."""
+    every param.grad is already the mean over ranks.
+    Frozen parameters (requires_grad False) are in no bucket, and a bucket without a trainable parameter is not published at all: every rank must
+    freeze the SAME set, or the ranks' collectives differ in number or size.  Nothing checks this."""
 
     def __init__(self, world_size=None, group=None, overlap=None, bucket_dtype='f32', force=False):
         """overlap: launch each bucket's all-reduce as soon as the backward has produced it (default; `TCOW_DDP_OVERLAP=0` or

@@ -29,7 +29,8 @@ How the file reads.  run_forward and run_backward are drivers.  Both build a _Ct
 and operand look-ups) and address the parameters through module.layout (seeker.ParamLayout), never by position.  The forward walks
 _patch_embed, _embed, one _block_forward_* per block and _heads_forward; the backward walks _heads_backward (which chooses the binary16 loss
 scale, _loss_scale), one _block_backward_* per block, _embed_backward and -- when the frames or the query mask require grad -- _input_backward.  Where a parameter gradient lands, when its weight-gradient GEMM is
-launched and when its bucket goes to the data-parallel hook is all in _GradBuckets, whose docstring states the ordering rules;
+launched and when its bucket goes to the data-parallel hook is all in _GradBuckets, whose docstring states the ordering rules, rule 5 what
+requires_grad_(False) takes out of the backward (lowest_block: where the chain stops; tests/test_frozen_host.py);
 tests/test_ddp_gloo.py and tests/test_engine_host.py check them, and the launch schedule call for call, on the CPU.
 """
 import os
@@ -248,7 +249,7 @@ class _Ctx:
 # ---------------------------------------------------------------------------------------------------------------------------------- forward
 
 def _patch_embed(c, rgb, qm, params, sv):
-    """Patch embedding (vit.py:233-241) -> X [M,D] f32; the im2col operand(s) are kept for the weight gradient."""
+    """Patch embedding (vit.py:233-241) -> X [M,D] f32; the im2col operand(s) are kept for the weight gradient (sv None: nobody wants them)."""
     module, g, lay = c.module, c.g, c.lay
     T, S, D, M, P = g['T'], g['S'], g['D'], g['M'], g['P']
     Kpe = module.input_channels * P * P
@@ -416,8 +417,23 @@ def _heads_forward(c, X, params, sv):
     return out_mask, flags
 
 
-def run_forward(module, rgb, qm, params, save, stream=None):
+def lowest_block(lay, frozen, want_inputs):
+    """The stopping rule of a backward with frozen parameters: k, the lowest block that holds a wanted parameter -- 0 when an embedding parameter
+    or an input gradient is wanted, lay.depth when nothing at or below the top block is.  The backward runs blocks depth-1 .. k and nothing below;
+    the forward keeps no activations of the blocks below k."""
+    if any(want_inputs) or any(j not in frozen for j in lay.embed):
+        return 0
+    for i in range(lay.depth):
+        if any(j not in frozen for j in lay.blocks(i, i + 1)):
+            return i
+    return lay.depth
+
+
+def run_forward(module, rgb, qm, params, save, stream=None, frozen=frozenset(), want_inputs=(False, False)):
     """-> (mask logits, flags, saved activations or None).
+    frozen, want_inputs (training): the indices of the parameters whose gradient is NOT wanted and which input gradients (frames, query mask) are,
+    as SeekerFunction.forward reads them; they hold for this forward's backward (sv['frozen'], sv['want_inputs'], sv['k'] = lowest_block()) and
+    decide what is saved, never what is computed.
     stream (inference only): one stream step, built by tcow_amd/stream.py -- rgb / qm then hold the step's T = rgb.shape[2] frames
     per row, and the schedule differs in three places: the embeddings (stream.pos, and stream.time_rows [B*T, D], one row of the time table per
     (row, frame)), the temporal attention (stream.attn_temporal: against the block's K / V cache, which it extends) and, for
@@ -428,12 +444,17 @@ def run_forward(module, rgb, qm, params, save, stream=None):
     c = _Ctx(module, g, rgb.device, save, stream)
     mask0, dps = _row_vectors(module, g, module.training, stream_step=stream is not None)
     sv = {'g': g, 'blocks': [], 'mask0': mask0, 'dps': dps} if save else None
-    X = _patch_embed(c, rgb, qm, params, sv)
+    k = lowest_block(c.lay, frozen, want_inputs) if save else 0
+    if save:
+        sv.update(frozen=frozen, want_inputs=tuple(want_inputs), k=k)
+    X = _patch_embed(c, rgb, qm, params, sv if save and (c.lay.patch_w not in frozen or any(want_inputs)) else None)
     _embed(c, X, params, sv)
     block_forward = _block_forward_joint if c.joint else _block_forward_divided
+    below = _Ctx(module, g, rgb.device, False, stream) if k > 0 else None      # the blocks under the lowest wanted parameter run as in inference
     for i in range(module.network_depth):
-        st = {} if save else None
-        X = block_forward(c, i, params[c.lay.block(i)], X, dps[i], mask0, st)
+        keep = save and i >= k
+        st = {} if keep else None
+        X = block_forward(c if keep or not save else below, i, params[c.lay.block(i)], X, dps[i], mask0, st)
         if save:
             sv['blocks'].append(st)
     out_mask, flags = _heads_forward(c, X, params, sv)
@@ -482,12 +503,21 @@ class _GradBuckets:
     3. publish(tag, flat) hands a FINISHED bucket to module.grad_hook: no launch writes into it afterwards.  The order is 'g<bottom block>'
        of every group above the bottom one, straight behind its flush; 'fold', behind the four batched products of finish_late(); 'g0',
        behind the embedding gradients (run_backward); then the hook's finish(), and nothing after it.
-    4. The loss scale (inv_gscale, set by _heads_backward) is undone by publish(), unless defer_unscale leaves it to the optimizer."""
+    4. The loss scale (inv_gscale, set by _heads_backward) is undone by publish(), unless defer_unscale leaves it to the optimizer.
+    5. Frozen parameters (`frozen`: the indices whose gradient is not wanted; k = lowest_block()).  A bucket holds views for wanted parameters
+       only, grads[j] stays None for the others, and a bucket without a wanted parameter is neither allocated nor published.  The chain stops
+       below block k, so block k is the bottom block of its group: its bucket goes out as 'g<k>' (k = depth, heads only: 'g<depth>'), and the
+       groups wholly below k never appear.  linear_bwd queues a Linear's weight-gradient GEMM only when its weight is wanted (bias frozen: without a
+       bias gradient) and a column sum (`colsums`, one tcow_colsum_grouped call per flush) when only its bias is; a LayerNorm with both
+       parameters frozen computes neither (ln_targets), one with one of them wanted sends the other to scratch -- the kernel has no form for one.
+       Scratch is c.E(...), never a bucket.  Nothing here looks at the frozen set to choose the loss scale or who undoes it."""
 
-    def __init__(self, c, params, have_flags):
+    def __init__(self, c, params, have_flags, frozen=frozenset(), k=0):
         module, lay = c.module, c.lay
         self.c, self.params, self.hook = c, params, module.grad_hook
         self.grads = [None] * len(params)
+        self.want, self.k = [j not in frozen for j in range(len(params))], k
+        self.colsums = []                                               # (dY, db): bias gradients of Linear layers whose weight is frozen
         self.inv_gscale = None
         # Who undoes the loss scale.  With a data-parallel hook every finished bucket is multiplied back before the hook sees it (ranks choose their
         # own scales).  Without one (or with one that says it is not `active`: a GradSync of one rank), and with a live FusedAdamWClip(module=net)
@@ -514,7 +544,7 @@ class _GradBuckets:
         hi = lay.depth
         for gs in group_sizes(lay.depth):
             for j in range(hi - gs, hi):
-                self.group_lo[j] = hi - gs
+                self.group_lo[j] = max(hi - gs, k)
             hi -= gs
         # The folded projection's three gradients per block come out of small products that are worth batching over ALL blocks (a launch of three
         # 768^3 problems is pure latency: 35 us whether it carries 3 problems or 12): the late bucket (57 MB at ViT-B), finished once after block 0.
@@ -527,8 +557,12 @@ class _GradBuckets:
         self.flat = self.group_bucket(self.group_lo[lay.depth - 1], lay.depth, heads)
 
     def bucket(self, indices):
-        """A flat buffer for the given parameters; persistent_grads: the same storage every step (see QueryMaskTracker.persistent_grads)."""
+        """A flat buffer for those of the given parameters that are wanted, None when none is; persistent_grads: the same storage every step (see
+        QueryMaskTracker.persistent_grads)."""
         params, dev = self.params, self.c.dev
+        indices = [j for j in indices if self.want[j]]
+        if not indices:
+            return None
         total = sum(params[j].numel() for j in indices)
         alloc = lambda: torch.empty(total, dtype=f32, device=dev)
         flat = self.c.opnd.buffer(('gbuf', indices[0], total, str(dev)), alloc) if getattr(self.c.module, 'persistent_grads', False) else alloc()
@@ -545,22 +579,45 @@ class _GradBuckets:
         return self.bucket((list(lay.embed) if lo == 0 else []) + [j for j in lay.blocks(lo, hi) if j not in self.late] + list(heads))
 
     def publish(self, tag, flat):
+        if flat is None:                                                # (no wanted parameter in this bucket: it does not exist)
+            return
         if self.inv_gscale is not None and not self.defer_unscale:
             flat.mul_(self.inv_gscale)
         if self.hook is not None:
             self.hook(tag, flat)
 
+    def wants(self, *indices):
+        return any(self.want[j] for j in indices)
+
     def linear_bwd(self, idx_w, dY, Xin, defer=False):
-        """dW, db of the Linear at params[idx_w], [idx_w + 1] whose output-gradient operand is dY [M,N] and input operand Xin [M,K]."""
+        """dW, db of the Linear at params[idx_w], [idx_w + 1] whose output-gradient operand is dY [M,N] and input operand Xin [M,K]; a frozen one
+        is None and not computed: without the weight there is no GEMM, its bias gradient is a column sum of dY."""
         dW, db = self.grads[idx_w], self.grads[idx_w + 1]
-        if defer:
+        if dW is None:
+            if db is not None and defer:
+                self.colsums.append((dY, db))
+            elif db is not None:
+                ops.colsum_grouped(self.c.mode, [(dY, db)])
+        elif defer:
             self.pending.append((dY, Xin, dW.reshape(dW.shape[0], -1), db))
         else:
             ops.gemm_tn(self.c.gmode, dY, Xin, dW.reshape(dW.shape[0], -1), bias_grad=db)
 
+    def ln_targets(self, idx_w):
+        """(dgamma, dbeta) to pass to the backward of the LayerNorm at params[idx_w], [idx_w + 1]: (None, None) when both are frozen (no partial table,
+        no fold); with one of them wanted the other is scratch."""
+        dg, db = self.grads[idx_w], self.grads[idx_w + 1]
+        if dg is None and db is None:
+            return None, None
+        D = self.params[idx_w].numel()
+        return dg if dg is not None else self.c.E(D, dtype=f32), db if db is not None else self.c.E(D, dtype=f32)
+
     def queue_fold(self, i, dY, O):
-        """Block i's folded projection: dW' = dY'^T O, db' into persistent temporaries, turned into the three real gradients by finish_late()."""
-        c, D = self.c, self.c.g['D']
+        """Block i's folded projection: dW' = dY'^T O, db' into persistent temporaries, turned into the three real gradients by finish_late();
+        nothing when none of the three is wanted."""
+        c, D, lay = self.c, self.c.g['D'], self.c.lay
+        if not self.wants(lay.at(i, 'tproj'), lay.at(i, 'tproj', 1), lay.at(i, 'tfc')):
+            return
         tW, tb = c.opnd.buffer(('foldtmp', i, str(c.dev)), lambda: (torch.empty(D, D, dtype=f32, device=c.dev), torch.empty(D, dtype=f32, device=c.dev)))
         self.pending.append((dY, O, tW, tb))
         self.fold_jobs.append((i, tW, tb))
@@ -569,6 +626,9 @@ class _GradBuckets:
         if self.pending:
             ops.gemm_tn_grouped(self.c.gmode, self.pending)
             self.pending.clear()
+        if self.colsums:
+            ops.colsum_grouped(self.c.mode, self.colsums)
+            self.colsums.clear()
         if self.ln_jobs:
             ops.layernorm_fold(self.ln_jobs)
 
@@ -591,20 +651,25 @@ class _GradBuckets:
         for (i, tW, tb) in self.fold_jobs:
             fc, pw, pb = lay.at(i, 'tfc'), lay.at(i, 'tproj'), lay.at(i, 'tproj', 1)
             wfc, wp, bp = params[fc].detach(), params[pw].detach(), params[pb].detach()
-            nt_.append((tW, wp.t(), grads[fc]))
-            r1_.append((tb.view(-1, 1), bp.view(1, -1), grads[fc]))
-            tn_.append((wfc.t(), tW, grads[pw]))
-            gv_.append((wfc.t(), tb.view(-1, 1), grads[pb].view(-1, 1)))
-        for c0 in range(0, len(nt_), 24):
-            ops.sgemm_batched(nt_[c0:c0 + 24]); ops.sgemm_batched(r1_[c0:c0 + 24], accumulate=True)
-            ops.sgemm_batched(tn_[c0:c0 + 24]); ops.sgemm_batched(gv_[c0:c0 + 24])
+            if grads[fc] is not None:
+                nt_.append((tW, wp.t(), grads[fc]))
+                r1_.append((tb.view(-1, 1), bp.view(1, -1), grads[fc]))
+            if grads[pw] is not None:
+                tn_.append((wfc.t(), tW, grads[pw]))
+            if grads[pb] is not None:
+                gv_.append((wfc.t(), tb.view(-1, 1), grads[pb].view(-1, 1)))
+        for c0 in range(0, max(len(nt_), len(tn_), len(gv_)), 24):       # (wanted outputs only: a list may be shorter than the others, or empty)
+            for lst, acc in ((nt_, False), (r1_, True), (tn_, False), (gv_, False)):
+                if lst[c0:c0 + 24]:
+                    ops.sgemm_batched(lst[c0:c0 + 24], accumulate=acc)
         self.fold_jobs.clear()
         if self.late_flat is not None:
             self.publish('fold', self.late_flat)
 
 
 def _heads_backward(c, bk, sv, params, d_mask, d_flags, have_flags):
-    """Mask head (mask_tracker.py:113-132), flags head and final norm, from the seeds to dX [M,D] f32; chooses the loss scale on the way."""
+    """Mask head (mask_tracker.py:113-132), flags head and final norm, from the seeds to dX [M,D] f32; chooses the loss scale on the way.
+    -> None when only head parameters are wanted: then nothing is launched behind the wanted head products."""
     module, g, lay, mode, dev = c.module, c.g, c.lay, c.mode, c.dev
     B, T, S, D, M, P = g['B'], g['T'], g['S'], g['D'], g['M'], g['P']
     Co = module.output_channels
@@ -631,23 +696,32 @@ def _heads_backward(c, bk, sv, params, d_mask, d_flags, have_flags):
     dPm = c.E(M, Co * P * P)
     ops.unpatchify_pool_bwd(mode, dpooled, B * T, g['Hp'], g['Wp'], P, Co, sv['stp'], dPm)
     bk.linear_bwd(lay.head_w, dPm, sv['Fm'])
-    # gradient w.r.t. the features that feed both heads, always f32: dFeat = dPm . Whead (+ flags adjoint)
-    dFeat = c.E(M, D, dtype=f32)
-    ops.gemm_nt(c.gmode, dPm, c.Wt(params[lay.head_w]), dFeat)
+    # heads only: no block runs (bk.k == depth) and the final norm, where it takes part, is frozen too -- nothing below the head products is wanted
+    below = bk.k < lay.depth or (module.norm_embeddings and bk.wants(lay.norm_w, lay.norm_b))
+    dFeat = None
+    if below:
+        # gradient w.r.t. the features that feed both heads, always f32: dFeat = dPm . Whead (+ flags adjoint)
+        dFeat = c.E(M, D, dtype=f32)
+        ops.gemm_nt(c.gmode, dPm, c.Wt(params[lay.head_w]), dFeat)
     if have_flags:
         # flags head adjoint (F x D, once per step; only the plugin path ever asks for it, pipeline.py:238)
         df = d_flags.to(f32).reshape(B * T, -1).contiguous()
-        meanf = sv['feat32'].reshape(B * T, S, D)[:, 1:, :].float().mean(dim=1)
-        dmean = torch.empty(B * T, D, dtype=f32, device=dev)
-        ops.sgemm_batched([(df.t(), meanf, bk.grads[lay.flags_w])])             # dWf = df^T mean(features)   (library kernel: no vendor BLAS on the path)
-        ops.sgemm_batched([(df, params[lay.flags_w].detach(), dmean)])
-        bk.grads[lay.flags_b].copy_(df.sum(0))
-        dFeat.reshape(B * T, S, D)[:, 1:, :] += (dmean / float(S - 1))[:, None, :]
+        if bk.grads[lay.flags_w] is not None:
+            meanf = sv['feat32'].reshape(B * T, S, D)[:, 1:, :].float().mean(dim=1)
+            ops.sgemm_batched([(df.t(), meanf, bk.grads[lay.flags_w])])         # dWf = df^T mean(features)   (library kernel: no vendor BLAS on the path)
+        if below:
+            dmean = torch.empty(B * T, D, dtype=f32, device=dev)
+            ops.sgemm_batched([(df, params[lay.flags_w].detach(), dmean)])
+        if bk.grads[lay.flags_b] is not None:
+            bk.grads[lay.flags_b].copy_(df.sum(0))
+        if below:
+            dFeat.reshape(B * T, S, D)[:, 1:, :] += (dmean / float(S - 1))[:, None, :]
     # (without a flags gradient flag_post_linear.* keep grad None, like the reference where pipeline.py:157 drops them)
-    if not module.norm_embeddings:
+    if not below or not module.norm_embeddings:
         return dFeat     # model.norm takes no part when norm_embeddings is False (vision_tf.py:152): its grads stay None
     dX = c.E(M, D, dtype=f32)
-    ops.layernorm_bwd(ops.F32, dFeat, sv['X_final'], sv['muf'], sv['rsf'], params[lay.norm_w].detach(), None, dX, bk.grads[lay.norm_w], bk.grads[lay.norm_b])
+    dgamma, dbeta = bk.ln_targets(lay.norm_w)
+    ops.layernorm_bwd(ops.F32, dFeat, sv['X_final'], sv['muf'], sv['rsf'], params[lay.norm_w].detach(), None, dX, dgamma, dbeta)
     return dX
 
 
@@ -667,7 +741,8 @@ def _mlp_backward(c, bk, i, q, st, dp, dR3, G3):
     bk.linear_bwd(lay.at(i, 'fc1'), dpre, st['Wn'], defer=True)
     dR2 = c.E(M, D, dtype=f32)
     G2 = c.E(M, D)                           # operand copy of dR2 * row scale: written by the LayerNorm backward, its slot-0 rows redone by the cls adjoint
-    ops.layernorm_bwd(c.mode, dWn, st['R2'], st['mu2'], st['rs2'], q[ix['n2']].detach(), dR3, dR2, bk.grads[lay.at(i, 'n2')], bk.grads[lay.at(i, 'n2', 1)],
+    dgamma, dbeta = bk.ln_targets(lay.at(i, 'n2'))
+    ops.layernorm_bwd(c.mode, dWn, st['R2'], st['mu2'], st['rs2'], q[ix['n2']].detach(), dR3, dR2, dgamma, dbeta,
                       dx_cast=G2, cast_scale=st['rs_s'], defer=bk.ln_jobs)
     return dR2, G2
 
@@ -696,8 +771,13 @@ def _attn_backward(c, bk, i, q, st, dp, mask0, next_scale, dR2, G2):
     dR1 = c.E(M, D, dtype=f32)
     G1 = c.E(M, D)                           # bf16(dR1 * row scale), written by the same LayerNorm backward pass
     # folded: G1 = bf16(dR1 * mask0 * dp_t) = dY' of the folded projection; its bias b_fc sees dR1 * mask0: summed here, in f32
-    extra = dict(cast_scale=dp['t0'], colsum_out=bk.grads[lay.at(i, 'tfc', 1)], colsum_scale=mask0) if c.fold else dict(cast_scale=next_scale if c.joint else mask0)
-    ops.layernorm_bwd(c.mode, dV, st['R1'], st['mu1'], st['rs1'], q[ix['n1']].detach(), dR2, dR1, bk.grads[lay.at(i, 'n1')], bk.grads[lay.at(i, 'n1', 1)],
+    extra = dict(cast_scale=dp['t0']) if c.fold else dict(cast_scale=next_scale if c.joint else mask0)
+    dgamma, dbeta = bk.ln_targets(lay.at(i, 'n1'))
+    if c.fold and bk.grads[lay.at(i, 'tfc', 1)] is not None:
+        extra.update(colsum_out=bk.grads[lay.at(i, 'tfc', 1)], colsum_scale=mask0)
+        if dgamma is None:           # the column sum rides on the parameter-gradient pass: with n1 frozen that pass writes to scratch
+            dgamma, dbeta = c.E(D, dtype=f32), c.E(D, dtype=f32)
+    ops.layernorm_bwd(c.mode, dV, st['R1'], st['mu1'], st['rs1'], q[ix['n1']].detach(), dR2, dR1, dgamma, dbeta,
                       dx_cast=G1, defer=bk.ln_jobs, **extra)
     return dR1, G1
 
@@ -733,7 +813,8 @@ def _block_backward_divided(c, bk, i, q, st, dp, mask0, next_scale, dR3, G3):
     bk.linear_bwd(lay.at(i, 'tqkv'), dQKV, st['U'], defer=True)
     dR0 = c.E(M, D, dtype=f32)
     G0 = c.E(M, D)                           # operand of the next (lower) block's MLP backward, or of the patch-embed weight gradient
-    ops.layernorm_bwd(c.mode, dU, st['R0'], st['mu0'], st['rs0'], q[ix['tn']].detach(), dR1, dR0, bk.grads[lay.at(i, 'tn')], bk.grads[lay.at(i, 'tn', 1)],
+    dgamma, dbeta = bk.ln_targets(lay.at(i, 'tn'))
+    ops.layernorm_bwd(c.mode, dU, st['R0'], st['mu0'], st['rs0'], q[ix['tn']].detach(), dR1, dR0, dgamma, dbeta,
                       dx_cast=G0, cast_scale=next_scale, defer=bk.ln_jobs)
     return dR0, G0
 
@@ -742,30 +823,43 @@ def _embed_backward(c, bk, sv, gX, Gpe):
     """Embeddings (cls, pos, time) and patch embedding from gX [M,D] f32; Gpe = its operand copy * mask0 from block 0's LayerNorm backward.
     -> Gsum, the operand copy of gX summed over each clip's queries (shared rgb; None otherwise), which _input_backward takes as well."""
     Gsum = None
-    g, lay, grads, mask0 = c.g, c.lay, bk.grads, sv['mask0']
+    g, lay, grads = c.g, c.lay, bk.grads
     B, T, S, D = g['B'], g['T'], g['S'], g['D']
-    dpos_eff = grads[lay.pos][0] if sv['pos_idx'] is None else c.E(S, D, dtype=f32)
-    dtime_eff = grads[lay.time][0] if sv['time_idx'] is None else c.E(T, D, dtype=f32)
-    ops.embed_bwd(gX, B, T, S, dpos_eff, dtime_eff)
-    grads[lay.cls].copy_(dpos_eff[0].reshape(1, 1, D))
-    if sv['pos_idx'] is not None:        # nearest-resized tables (vision_tf.py:103-115): scatter back to the stored rows
-        grads[lay.pos].zero_()
-        grads[lay.pos][0].index_add_(0, sv['pos_idx'], dpos_eff)
-    if sv['time_idx'] is not None:
-        grads[lay.time].zero_()
-        grads[lay.time][0].index_add_(0, sv['time_idx'], dtime_eff)
-    dWpe = grads[lay.patch_w].reshape(D, -1)
-    if isinstance(sv['A_pe'], tuple):                                   # shared rgb: dW[:, :3 P^2] = (sum over the clip's queries of G)^T A_rgb
-        A_rgb, A_m = sv['A_pe']
-        Krgb = A_rgb.shape[1]
-        Bc = A_rgb.shape[0] // (T * S)
-        Gsum = c.E(Bc * T * S, D)
-        ops.scale_cast(c.mode, gX.reshape(Bc, B // Bc, T * S, D).sum(dim=1).reshape(Bc * T * S, D), mask0[:Bc * T * S], Gsum)
-        ops.gemm_tn(c.gmode, Gsum, A_rgb, dWpe[:, :Krgb])
-        ops.gemm_tn(c.gmode, Gpe, A_m, dWpe[:, Krgb:])
-    else:
-        ops.gemm_tn(c.gmode, Gpe, sv['A_pe'], dWpe)
-    grads[lay.patch_b].copy_(dtime_eff.sum(0))       # bias gradient = sum over all patch rows
+    if bk.wants(lay.cls, lay.pos, lay.time, lay.patch_b):
+        # (tcow_embed_bwd writes the pos | time pair in one pass, and cls and the patch bias are read off them: a frozen table's half goes to scratch)
+        dpos_eff = grads[lay.pos][0] if sv['pos_idx'] is None and grads[lay.pos] is not None else c.E(S, D, dtype=f32)
+        dtime_eff = grads[lay.time][0] if sv['time_idx'] is None and grads[lay.time] is not None else c.E(T, D, dtype=f32)
+        ops.embed_bwd(gX, B, T, S, dpos_eff, dtime_eff)
+        if grads[lay.cls] is not None:
+            grads[lay.cls].copy_(dpos_eff[0].reshape(1, 1, D))
+        if sv['pos_idx'] is not None and grads[lay.pos] is not None:        # nearest-resized tables (vision_tf.py:103-115): scatter back to the stored rows
+            grads[lay.pos].zero_()
+            grads[lay.pos][0].index_add_(0, sv['pos_idx'], dpos_eff)
+        if sv['time_idx'] is not None and grads[lay.time] is not None:
+            grads[lay.time].zero_()
+            grads[lay.time][0].index_add_(0, sv['time_idx'], dtime_eff)
+    if grads[lay.patch_w] is not None:
+        dWpe = grads[lay.patch_w].reshape(D, -1)
+        if isinstance(sv['A_pe'], tuple):                               # shared rgb: dW[:, :3 P^2] = (sum over the clip's queries of G)^T A_rgb
+            A_rgb, A_m = sv['A_pe']
+            Krgb = A_rgb.shape[1]
+            Gsum = _query_sum(c, sv, gX)
+            ops.gemm_tn(c.gmode, Gsum, A_rgb, dWpe[:, :Krgb])
+            ops.gemm_tn(c.gmode, Gpe, A_m, dWpe[:, Krgb:])
+        else:
+            ops.gemm_tn(c.gmode, Gpe, sv['A_pe'], dWpe)
+    if grads[lay.patch_b] is not None:
+        grads[lay.patch_b].copy_(dtime_eff.sum(0))       # bias gradient = sum over all patch rows
+    return Gsum
+
+
+def _query_sum(c, sv, gX):
+    """Shared rgb: the operand copy of gX [M,D] * mask0 summed over each clip's queries, [Bc*T*S, D]."""
+    g = c.g
+    B, TS, D = g['B'], g['T'] * g['S'], g['D']
+    Bc = sv['A_pe'][0].shape[0] // TS
+    Gsum = c.E(Bc * TS, D)
+    ops.scale_cast(c.mode, gX.reshape(Bc, B // Bc, TS, D).sum(dim=1).reshape(Bc * TS, D), sv['mask0'][:Bc * TS], Gsum)
     return Gsum
 
 
@@ -804,24 +898,31 @@ def _input_backward(c, bk, sv, G, want_rgb, want_qm, Gsum=None):
 
 
 def run_backward(module, sv, params, d_mask, d_flags):
-    """-> the parameter gradients, in the order of `params` (None where a parameter takes no part), every bucket published.
+    """-> the parameter gradients, in the order of `params` (None where a parameter takes no part or is frozen), every bucket published.
+    Frozen parameters (sv['frozen']) cost nothing: no launch whose only products are their gradients, and the chain runs blocks depth-1 .. sv['k']
+    only -- no block below, the embeddings only when one of their parameters is wanted, the inputs only when asked for (_GradBuckets, rule 5).
     sv['want_inputs'] = (frames, query mask), set by SeekerFunction.forward: which input gradients are wanted as well; they are left in
     sv['d_inputs'] (None where not wanted)."""
     c = _Ctx(module, sv['g'], sv['X_final'].device, True)
     have_flags = module.flag_channels > 0 and d_flags is not None and d_flags.numel() > 0
-    bk = _GradBuckets(c, params, have_flags)
+    lay, depth = c.lay, module.network_depth
+    k = sv.get('k', 0)                             # the chain stops below block k (lowest_block(), fixed by the forward with sv['frozen'])
+    bk = _GradBuckets(c, params, have_flags, sv.get('frozen', frozenset()), k)
     dR, G = _heads_backward(c, bk, sv, params, d_mask, d_flags, have_flags), None
     block_backward = _block_backward_joint if c.joint else _block_backward_divided
-    for i in reversed(range(module.network_depth)):
+    for i in reversed(range(k, depth)):
         bk.start_block(i)
         next_scale = sv['dps'][i - 1]['m'] if i > 0 else sv['mask0']
-        dR, G = block_backward(c, bk, i, params[c.lay.block(i)], sv['blocks'][i], sv['dps'][i], sv['mask0'], next_scale, dR, G)
+        dR, G = block_backward(c, bk, i, params[lay.block(i)], sv['blocks'][i], sv['dps'][i], sv['mask0'], next_scale, dR, G)
         bk.end_block(i, sv)
     bk.finish_late()
-    Gsum = _embed_backward(c, bk, sv, dR, G)
-    bk.publish('g0', bk.flat)
+    Gsum = _embed_backward(c, bk, sv, dR, G) if bk.wants(*lay.embed) else None
+    if k == 0 or k == depth:                       # (0 < k < depth: end_block(k) has published the last bucket, as 'g<k>')
+        bk.publish('g%d' % k, bk.flat)
     module.pending_inv_scale = bk.inv_gscale if bk.defer_unscale else None
     want_rgb, want_qm = sv.get('want_inputs', (False, False))
+    if want_rgb and Gsum is None and isinstance(sv['A_pe'], tuple):
+        Gsum = _query_sum(c, sv, dR)                # (shared rgb with a frozen patch weight: the frames' gradient needs the sum all the same)
     sv['d_inputs'] = _input_backward(c, bk, sv, G, want_rgb, want_qm, Gsum) if want_rgb or want_qm else (None, None)
     if bk.hook is not None and hasattr(bk.hook, 'finish'):
         # The collectives launched above were overlapped with the remaining backward compute; they must be complete (in
@@ -837,9 +938,9 @@ class SeekerFunction(torch.autograd.Function):
     def forward(ctx, module, rgb, qm, *params):
         need = any(ctx.needs_input_grad[1:])      # a parameter, the frames (1) or the query mask (2)
         ctx.set_materialize_grads(False)      # an unused output (e.g. output_flags in Kubric training) arrives as None, not zeros
-        out_mask, flags, sv = run_forward(module, rgb, qm, params, save=need)
-        if sv is not None:
-            sv['want_inputs'] = (ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+        # the frozen set is read here, once, and holds for this forward's backward: requires_grad_() between the two changes nothing
+        frozen = frozenset(j for j, wanted in enumerate(ctx.needs_input_grad[3:]) if not wanted)
+        out_mask, flags, sv = run_forward(module, rgb, qm, params, save=need, frozen=frozen, want_inputs=(ctx.needs_input_grad[1], ctx.needs_input_grad[2]))
         ctx.module = module
         ctx.sv = sv
         ctx.params = params

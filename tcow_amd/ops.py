@@ -242,6 +242,27 @@ def gemm_tn_grouped(mode, problems):
     L.check(lib.tcow_gemm_tn_grouped(_stream(), dm, n, arr, ws.data_ptr(), ws.numel()), 'tcow_gemm_tn_grouped', lib)
 
 
+COLSUM_GROUP_MAX = 16    # tcow_colsum_group_max()
+
+
+def colsum_grouped(mode, problems):
+    """Bias gradients of Linear layers whose weight gradient is not wanted: problems = [(dY [M,N], out [N] f32), ...], out = column sums of dY;
+    an optional third element `accumulate` (default 0) adds to out instead.  `mode` is the storage mode of the dY (tcow_colsum_grouped: N a
+    multiple of 8 in the 16-bit modes, of 4 in f32 storage); up to 16 problems per call of the library, more are sent in chunks."""
+    lib, dm = _sel(mode)
+    for c0 in range(0, len(problems), COLSUM_GROUP_MAX):
+        chunk = problems[c0:c0 + COLSUM_GROUP_MAX]
+        n = len(chunk)
+        arr = (L.ColsumProblem * n)()
+        for i, (dY, out, *acc) in enumerate(chunk):
+            _need_cuda(dY, out)
+            arr[i] = L.ColsumProblem(dY.shape[0], dY.shape[1], dY.data_ptr(), dY.stride(0), out.data_ptr(), int(acc[0]) if acc else 0)
+        # (the partial rows are at most 64 x N floats per problem: a tensor of the moment from torch's allocator, which keeps it for this stream until the
+        # launches have drained, not a cached workspace that would live on between steps for a path most steps never take)
+        ws = torch.empty(max(int(lib.tcow_colsum_grouped_workspace_bytes(dm, n, arr)), 16), dtype=torch.uint8, device=chunk[0][0].device)
+        L.check(lib.tcow_colsum_grouped(_stream(), dm, n, arr, ws.data_ptr(), ws.numel()), 'tcow_colsum_grouped', lib)
+
+
 def sgemm_batched(problems, accumulate=False):
     """Small f32 products C (+)= A B, several per launch (tcow_sgemm_x3_batched).  problems = [(A, B, C), ...] with 2-D f32 tensors of ANY
     strides: A [M,K], B [K,N] (pass `.t()` views for transposed operands), C [M,N] row-major with unit column stride."""

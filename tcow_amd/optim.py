@@ -175,7 +175,10 @@ class FusedAdamWClip(torch.optim.Optimizer):
                 self._key = tuple((id(p), p.grad.data_ptr(), self.state[p]['exp_avg'].data_ptr()) for p in live)
             self._live = live
             self._seen_grads = [p.grad for p in params]
-            self._step_base = int(self.state[live[0]]['step'])
+            # (one step number serves the whole table.  A parameter thawed after others have stepped starts its moments at zero and takes the others'
+            # bias correction: its first updates are smaller than torch.optim.AdamW's per-parameter count would make them, never larger; the max keeps
+            # a thawed parameter that happens to come first from resetting everybody's count.)
+            self._step_base = max(int(self.state[p]['step']) for p in live)
             self._steps_pending = 0
         if not live:
             return loss

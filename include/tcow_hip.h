@@ -311,6 +311,29 @@ int tcow_attn_temporal_ragged_paged_fwd(void* stream, const tcow_attn_shape* ste
                                         const int* t0_rows, const int* page_rows, const int* first_rows, const int* c_rows, const int* row_of_frame,
                                         const void* qkv, void* k_pages, void* v_pages, void* out);
 
+/* Compact K / V cache (new symbols, no signature changed: the ABI version stays).  The four *_cq entry points are the four above with one more
+ * argument, cache_dtype: the element type C of k_cache / v_cache (k_pages / v_pages), chosen apart from the step's storage `dtype`.
+ *   TCOW_F32, TCOW_BF16 (the build's 16-bit type) or TCOW_FP8E4M3 (one byte, OCP e4m3fn); C may not be wider than the storage (dtype TCOW_BF16
+ *   with cache_dtype TCOW_F32 is refused).  cache_dtype == dtype is the entry point without _cq, bit for bit.
+ *   rnd_C(x) = x converted to C by round-to-nearest-even and back; for fp8 saturating: x is clamped to [-448, 448] first, a NaN stays NaN --
+ *   torch's x.clamp(-448, 448).to(torch.float8_e4m3fn), subnormals kept.
+ *   out = softmax_{t' <= t}(q_t . rnd_C(k_t') / 8) rnd_C(v_t'): EVERY key and value at its rounded value, those of the step's own frames
+ *   (read from qkv, not from the cache) included; q is not rounded; the append stores the rounded bits once.  Outputs and caches therefore do
+ *   not depend on how the frames were split into steps, and the four forms agree bit for bit as the four above do.  No bitwise relation to the
+ *   cache_dtype == dtype path.  Cache shapes and addressing are those above, in elements of C.  Everything refused above is refused here; a bad
+ *   t0, slot or page writes NaN to the frame's own rows of out and touches no cache byte. */
+#define TCOW_FP8E4M3 3 /* cache_dtype of the *_cq entry points only */
+int tcow_attn_temporal_cached_cq_fwd(void* stream, const tcow_attn_shape* chunk, int T_total, const int* t0_dev, const void* qkv, void* k_cache,
+                                     void* v_cache, void* out, int cache_dtype);
+int tcow_attn_temporal_pool_cq_fwd(void* stream, const tcow_attn_shape* chunk, int T_total, int n_slots, const int* t0_rows, const int* slot_rows,
+                                   const void* qkv, void* k_cache, void* v_cache, void* out, int cache_dtype);
+int tcow_attn_temporal_ragged_cq_fwd(void* stream, const tcow_attn_shape* step, int n, int T_total, int n_slots, const int* t0_rows, const int* slot_rows,
+                                     const int* first_rows, const int* c_rows, const int* row_of_frame, const void* qkv, void* k_cache, void* v_cache,
+                                     void* out, int cache_dtype);
+int tcow_attn_temporal_ragged_paged_cq_fwd(void* stream, const tcow_attn_shape* step, int n, int T_total, int n_pages, int page_frames,
+                                           int pages_per_session, const int* t0_rows, const int* page_rows, const int* first_rows, const int* c_rows,
+                                           const int* row_of_frame, const void* qkv, void* k_pages, void* v_pages, void* out, int cache_dtype);
+
 /* ------------------------------------------------------------------------------------------- token glue
  * tcow_im2col: cat([rgb (B,3,T,H,W), query (B,1,T,H,W)]) (mask_tracker.py:107-108), optional (rgb-0.45)/0.225
  *   (vision_tf.py:81-89), flattened per patch in Conv2d weight order c*P*P + py*P + px (vit.py:233-240) into

@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get('TCOW_LIB') or os.path.join(_HERE, 'libtcow_hip.so')  
 LIB_PATH_FP16 = os.path.join(_HERE, 'libtcow_hip_fp16.so')                          # the binary16 build of the same sources (precision='fp16')
 
 TCOW_F32, TCOW_BF16, TCOW_F32X3 = 0, 1, 2
+TCOW_FP8E4M3 = 3          # cache_dtype of the tcow_attn_temporal_*_cq_fwd entry points only (one OCP e4m3fn byte per element)
 ACT_NONE, ACT_GELU, ACT_DGELU, ACT_GELU_DSAVE, ACT_MUL_AUX = 0, 1, 2, 3, 4
 
 
@@ -109,6 +110,10 @@ SIGNATURES = {
     'tcow_attn_temporal_ragged_fwd': (_i, [_vp, _ash, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'tcow_cls_ragged': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     'tcow_attn_temporal_ragged_paged_fwd': (_i, [_vp, _ash, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'tcow_attn_temporal_cached_cq_fwd': (_i, [_vp, _ash, _i, _vp, _vp, _vp, _vp, _vp, _i]),
+    'tcow_attn_temporal_pool_cq_fwd': (_i, [_vp, _ash, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    'tcow_attn_temporal_ragged_cq_fwd': (_i, [_vp, _ash, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    'tcow_attn_temporal_ragged_paged_cq_fwd': (_i, [_vp, _ash, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     'tcow_im2col': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     'tcow_gather_frames': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'tcow_resize_aa': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp]),

@@ -22,7 +22,19 @@
 // pages of P frames, [n_pages, S-1, heads, P, 64]; a session's row of the page table names the page of its frames q*P .. q*P+P-1.  Where a
 // cached key lives is all that differs: temporal_query_frame takes that as a small functor (ContiguousKeys / PagedKeys), so the four kernels
 // keep one body and agree bit for bit.
+//
+// Compact cache (the *_cq entry points): the cache element type C is a second template parameter next to the storage type T.  C == T is the
+// path above, its code unchanged.  Otherwise (16-bit -> fp8, f32 -> the build's 16-bit type, f32 -> fp8; fp8 = OCP e4m3fn, saturating) the
+// append stores rnd_C(k), rnd_C(v) once and EVERY key and value enters the arithmetic at its rounded value: a batch of keys is gathered as
+// cache words -- cached lines loaded, the chunk's own lines (read from the step's qkv rows) encoded -- and decoded where it is used, so a key
+// has one value wherever it came from and outputs and caches do not depend on how the frames were split into chunks.  q is not rounded.  A lane
+// keeps the storage type's channel slice (8 or 4 channels: 8 or 4 bytes of a cache line) and the key order is that of the uncompacted kernel;
+// CacheVec is all that knows C.  Measured ("Compact cache"): the kernels are bound by issued instructions and by waves in
+// flight, not by HBM, so what pays is gathering words (16 instead of 64 registers while the loads fly: 127 VGPRs and four waves per SIMD for
+// 16-bit -> fp8, where decoding at the load took 136 and three) and a branch-free loop over the batches that lie wholly in the cache.
 #include <math.h>
+
+#include <type_traits>
 
 #include "attention_common.h"
 
@@ -56,6 +68,74 @@ template <> struct StreamVec<float> {
 
 __device__ __forceinline__ void copy16(void* dst, const void* src) { *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src); }
 
+// ---- compact cache elements.  fp8_t: one OCP e4m3fn byte (gfx950's v_cvt_pk_fp8_f32 / v_cvt_pk_f32_fp8).
+struct fp8_t { uint8_t b; };
+
+// f32 -> e4m3fn as torch's x.clamp(-448, 448).to(torch.float8_e4m3fn): saturating, round to nearest even, subnormals kept, NaN -> 0x7f | sign.
+// The clamp is one v_med3_f32, which does not keep a NaN: a NaN's byte is set after the conversion, so what the instruction makes of a NaN
+// never shows.  Four values -> four bytes, v[0] in the lowest; a NaN among them is rare and handled on a branch of its own.
+__device__ __forceinline__ float fp8_clamp(float x) { return __builtin_amdgcn_fmed3f(x, -448.f, 448.f); }
+__device__ __forceinline__ uint32_t pack_fp8x4(const float* v) {
+    int w = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_clamp(v[0]), fp8_clamp(v[1]), 0, false);
+    w = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_clamp(v[2]), fp8_clamp(v[3]), w, true);
+    uint32_t u = (uint32_t)w;
+    if (__builtin_expect(v[0] != v[0] || v[1] != v[1] || v[2] != v[2] || v[3] != v[3], 0)) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (v[e] != v[e]) u = (u & ~(0xffu << (8 * e))) | ((0x7fu | ((__float_as_uint(v[e]) >> 24) & 0x80u)) << (8 * e));
+    }
+    return u;
+}
+__device__ __forceinline__ void unpack_fp8x4(uint32_t w, float* v) {
+    const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+    v[0] = lo[0]; v[1] = lo[1]; v[2] = hi[0]; v[3] = hi[1];
+}
+
+// A lane's StreamVec<T>::VEC channels of a cache line of C elements as a Raw word: ld from the cache, enc from f32 (what the append stores, and
+// what a chunk's own key / value becomes before it is used), dec to f32, zero (decodes to 0).  A key therefore has ONE value, dec of its Raw,
+// wherever it was read from.  Storage T, cache C; CacheVec<T, T> is never asked (C == T copies bits).
+template <typename T, typename C> struct CacheVec;
+template <> struct CacheVec<bf16_t, fp8_t> {           // 8 channels: 8 bytes
+    typedef uint2 Raw;
+    static __device__ __forceinline__ Raw ld(const fp8_t* p) { return *reinterpret_cast<const uint2*>(p); }
+    static __device__ __forceinline__ void st(fp8_t* p, Raw r) { *reinterpret_cast<uint2*>(p) = r; }
+    static __device__ __forceinline__ Raw enc(const float* v) { return make_uint2(pack_fp8x4(v), pack_fp8x4(v + 4)); }
+    static __device__ __forceinline__ void dec(Raw r, float* v) { unpack_fp8x4(r.x, v); unpack_fp8x4(r.y, v + 4); }
+    static __device__ __forceinline__ Raw zero() { return make_uint2(0u, 0u); }
+};
+template <> struct CacheVec<float, fp8_t> {            // 4 channels: 4 bytes
+    typedef uint32_t Raw;
+    static __device__ __forceinline__ Raw ld(const fp8_t* p) { return *reinterpret_cast<const uint32_t*>(p); }
+    static __device__ __forceinline__ void st(fp8_t* p, Raw r) { *reinterpret_cast<uint32_t*>(p) = r; }
+    static __device__ __forceinline__ Raw enc(const float* v) { return pack_fp8x4(v); }
+    static __device__ __forceinline__ void dec(Raw r, float* v) { unpack_fp8x4(r, v); }
+    static __device__ __forceinline__ Raw zero() { return 0u; }
+};
+template <> struct CacheVec<float, bf16_t> {           // 4 channels of the build's 16-bit type: 8 bytes
+    typedef uint2 Raw;
+    static __device__ __forceinline__ Raw ld(const bf16_t* p) { return *reinterpret_cast<const uint2*>(p); }
+    static __device__ __forceinline__ void st(bf16_t* p, Raw r) { *reinterpret_cast<uint2*>(p) = r; }
+    static __device__ __forceinline__ Raw enc(const float* v) { return make_uint2(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])); }
+    static __device__ __forceinline__ void dec(Raw r, float* v) { v[0] = bflo(r.x); v[1] = bfhi(r.x); v[2] = bflo(r.y); v[3] = bfhi(r.y); }
+    static __device__ __forceinline__ Raw zero() { return make_uint2(0u, 0u); }
+};
+
+// the lane's slice of a row of the step's qkv, rounded to C
+template <typename T, typename C> __device__ __forceinline__ typename CacheVec<T, C>::Raw encode_line(const T* src) {
+    float v[StreamVec<T>::VEC];
+    StreamVec<T>::ld(src, v);
+    return CacheVec<T, C>::enc(v);
+}
+
+// cache[position] = the lane's slice of a chunk row's K or V: bit copy when the cache has the storage type, else rounded to C once
+template <typename T, typename C> __device__ __forceinline__ void append_line(C* dst, const T* src) {
+    if constexpr (std::is_same_v<T, C>) {
+        copy16(dst, src);
+    } else {
+        CacheVec<T, C>::st(dst, encode_line<T, C>(src));
+    }
+}
+
 // Where cache position kt of the wave's (session, token slot, head) lives in a block's K / V array `base` (const or not): the address of the
 // lane's 16 bytes of that line.  The one thing in which the contiguous and the paged kernels differ.  In two steps: page(kt), which EVERY lane
 // of the wave calls together (a paged lookup may be a lane shuffle), then keys(base, page, kt) by the lanes that load or store.
@@ -80,9 +160,10 @@ struct PagedKeys {                  // [n_pages, S-1, heads, P, 64], P = 1 << lg
 // One query frame of a temporal stream step, shared by every kernel of this file so that they agree bit for bit: chunk frame j (flat frame
 // fb + j of the step's rows, fb = the chunk's first flat frame) stands at t = t0 + j and attends to keys 0 .. t, keys < t0 from the cache at
 // keys(kt) (each lane group looks up its own key: a batch of G * ST_U keys may span pages), keys t0 .. t from the step's qkv rows at flat
-// frame fb + (kt - t0).  Every lane of the wave calls it; lane group 0 stores.
-template <typename T, typename Keys>
-__device__ __forceinline__ void temporal_query_frame(const T* qkv, const T* kc, const T* vc, T* out, const Keys keys, int fb, int j, int t0, int S, int s, int D,
+// frame fb + (kt - t0).  Every lane of the wave calls it; lane group 0 stores.  A compact cache (C != T): cached lines are decoded, the
+// step's own keys / values rounded through C, so a key has one value wherever it is read from.
+template <typename T, typename C, typename Keys>
+__device__ __forceinline__ void temporal_query_frame(const T* qkv, const C* kc, const C* vc, T* out, const Keys keys, int fb, int j, int t0, int S, int s, int D,
                                                      int col, int grp) {
     constexpr int VEC = StreamVec<T>::VEC, LPR = ATT_HD / VEC, G = 64 / LPR;
     const long ld3 = 3L * D;
@@ -93,6 +174,7 @@ __device__ __forceinline__ void temporal_query_frame(const T* qkv, const T* kc, 
     float m = -INFINITY, l = 0.f, acc[VEC];
 #pragma unroll
     for (int e = 0; e < VEC; ++e) acc[e] = 0.f;
+    if constexpr (std::is_same_v<T, C>) {
     for (int k0 = 0; k0 <= t; k0 += G * ST_U) {
         float kv[ST_U][VEC], vv[ST_U][VEC];
 #pragma unroll
@@ -135,6 +217,61 @@ __device__ __forceinline__ void temporal_query_frame(const T* qkv, const T* kc, 
         }
         m = mb;
     }
+    } else {
+    // A compact cache: the same loop (key order, lane groups, arithmetic), written apart so that the loop above keeps its code.  One batch of
+    // G * ST_U keys from k0; all_cached: the whole batch lies below t0, so every key is a cached line and none is masked -- the batches of a
+    // long stream's past run without a branch; the general batch takes cached lines as they are and rounds the step's own keys / values to C.
+    auto batch = [&](const int k0, auto all_cached) {
+        constexpr bool CACHED = decltype(all_cached)::value;
+        typename CacheVec<T, C>::Raw kr[ST_U], vr[ST_U];                  // (gathered as cache words: few registers while the loads fly)
+#pragma unroll
+        for (int u = 0; u < ST_U; ++u) {
+            const int kt = k0 + u * G + grp;
+            const auto pg = keys.page(CACHED || kt <= t ? kt : t);        // (every lane, ahead of the branch)
+            if (CACHED || kt < t0) {                                      // (kt < t0 <= t)
+                kr[u] = CacheVec<T, C>::ld(keys(kc, pg, kt));
+                vr[u] = CacheVec<T, C>::ld(keys(vc, pg, kt));
+            } else if (kt <= t) {
+                const T* row = qkv + ((long)(fb + kt - t0) * S + s) * ld3 + col;
+                kr[u] = encode_line<T, C>(row + D);
+                vr[u] = encode_line<T, C>(row + 2 * D);
+            } else {
+                kr[u] = CacheVec<T, C>::zero();
+                vr[u] = CacheVec<T, C>::zero();
+            }
+        }
+        float sc[ST_U];
+        float mb = m;
+#pragma unroll
+        for (int u = 0; u < ST_U; ++u) {
+            float kv[VEC], d = 0.f;
+            CacheVec<T, C>::dec(kr[u], kv);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) d = fmaf(q[e], kv[e], d);
+#pragma unroll
+            for (int o = 1; o < LPR; o <<= 1) d += __shfl_xor(d, o, 64);
+            sc[u] = (CACHED || k0 + u * G + grp <= t) ? d * scale : -INFINITY;
+            mb = fmaxf(mb, sc[u]);
+        }
+        const float alpha = (m == -INFINITY) ? 0.f : expf(m - mb);
+        l *= alpha;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc[e] *= alpha;
+#pragma unroll
+        for (int u = 0; u < ST_U; ++u) {
+            const float p = (sc[u] == -INFINITY) ? 0.f : expf(sc[u] - mb);
+            l += p;
+            float vv[VEC];
+            CacheVec<T, C>::dec(vr[u], vv);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) acc[e] = fmaf(p, vv[e], acc[e]);
+        }
+        m = mb;
+    };
+    int k0 = 0;
+    for (; k0 + G * ST_U <= t0; k0 += G * ST_U) batch(k0, std::true_type{});
+    for (; k0 <= t; k0 += G * ST_U) batch(k0, std::false_type{});
+    }
     // merge the G groups' (m, l, acc): lanes with the same channel slice sit LPR apart
 #pragma unroll
     for (int o = LPR; o < 64; o <<= 1) {
@@ -154,10 +291,10 @@ __device__ __forceinline__ void temporal_query_frame(const T* qkv, const T* kc, 
     }
 }
 
-template <typename T>
+template <typename T, typename C>
 __global__ __launch_bounds__(64 * ST_WAVES) void temporal_cached_kernel(int B, int c, int S, int D, int heads, int T_total, int n_slots,
                                                                        const int* __restrict__ t0_rows, int t0_stride, const int* __restrict__ slot_rows,
-                                                                       const T* __restrict__ qkv, T* __restrict__ kc, T* __restrict__ vc, T* __restrict__ out) {
+                                                                       const T* __restrict__ qkv, C* __restrict__ kc, C* __restrict__ vc, T* __restrict__ out) {
     constexpr int VEC = StreamVec<T>::VEC, LPR = ATT_HD / VEC, G = 64 / LPR;
     const int lane = threadIdx.x & 63, grp = lane / LPR, sub = lane - grp * LPR;
     const long item = (long)blockIdx.x * ST_WAVES + (threadIdx.x >> 6);
@@ -181,13 +318,13 @@ __global__ __launch_bounds__(64 * ST_WAVES) void temporal_cached_kernel(int B, i
         return;
     }
     const ContiguousKeys keys{((((size_t)slot * (S - 1) + (s - 1)) * heads + h) * T_total) * ATT_HD + sub * VEC};
-    // append the chunk's keys / values: cache[t0 + j] = chunk row j (bit copies)
+    // append the chunk's keys / values: cache[t0 + j] = chunk row j (bit copies; a compact cache: rounded to C)
     for (int j = grp; j < c; j += G) {
         const T* src = qkv + ((long)(b * c + j) * S + s) * ld3 + col;
-        copy16(keys(kc, keys.page(t0 + j), t0 + j), src + D);
-        copy16(keys(vc, keys.page(t0 + j), t0 + j), src + 2 * D);
+        append_line<T, C>(keys(kc, keys.page(t0 + j), t0 + j), src + D);
+        append_line<T, C>(keys(vc, keys.page(t0 + j), t0 + j), src + 2 * D);
     }
-    for (int j = 0; j < c; ++j) temporal_query_frame<T>(qkv, kc, vc, out, keys, b * c, j, t0, S, s, D, col, grp);
+    for (int j = 0; j < c; ++j) temporal_query_frame<T, C>(qkv, kc, vc, out, keys, b * c, j, t0, S, s, D, col, grp);
 }
 
 // One wave per (flat frame f, token slot s, head h) of a ragged step: n sessions, session r with c_rows[r] frames at flat frames
@@ -197,12 +334,12 @@ __global__ __launch_bounds__(64 * ST_WAVES) void temporal_cached_kernel(int B, i
 // INVARIANT: no wave reads a cache position that this launch writes.  The launch writes positions t0 .. t0+c-1 of a session's block; a wave
 // reads cache positions < t0 only and takes keys t0 .. t from the step's qkv rows (flat frame first + (kt - t0)).  That is what makes the
 // per-frame split race-free: the waves of one session share no cache position between a writer and a reader, and sessions have distinct slots.
-template <typename T>
+template <typename T, typename C>
 __global__ __launch_bounds__(64 * ST_WAVES) void temporal_ragged_kernel(int n, int F, int S, int D, int heads, int T_total, int n_slots,
                                                                        const int* __restrict__ t0_rows, const int* __restrict__ slot_rows,
                                                                        const int* __restrict__ first_rows, const int* __restrict__ c_rows,
-                                                                       const int* __restrict__ row_of_frame, const T* __restrict__ qkv, T* __restrict__ kc,
-                                                                       T* __restrict__ vc, T* __restrict__ out) {
+                                                                       const int* __restrict__ row_of_frame, const T* __restrict__ qkv, C* __restrict__ kc,
+                                                                       C* __restrict__ vc, T* __restrict__ out) {
     constexpr int VEC = StreamVec<T>::VEC, LPR = ATT_HD / VEC;
     const int lane = threadIdx.x & 63, grp = lane / LPR, sub = lane - grp * LPR;
     const long item = (long)blockIdx.x * ST_WAVES + (threadIdx.x >> 6);
@@ -236,10 +373,10 @@ __global__ __launch_bounds__(64 * ST_WAVES) void temporal_ragged_kernel(int n, i
     if (grp == 0) {
         // append this frame's key / value: cache[t0 + j] = the frame's own row (bit copies)
         const T* src = qkv + ((long)f * S + s) * (3L * D) + col;
-        copy16(keys(kc, keys.page(t0 + j), t0 + j), src + D);
-        copy16(keys(vc, keys.page(t0 + j), t0 + j), src + 2 * D);
+        append_line<T, C>(keys(kc, keys.page(t0 + j), t0 + j), src + D);
+        append_line<T, C>(keys(vc, keys.page(t0 + j), t0 + j), src + 2 * D);
     }
-    temporal_query_frame<T>(qkv, kc, vc, out, keys, first, j, t0, S, s, D, col, grp);
+    temporal_query_frame<T, C>(qkv, kc, vc, out, keys, first, j, t0, S, s, D, col, grp);
 }
 
 // temporal_ragged_kernel on a paged cache: the K / V array of a block is [n_pages, S-1, heads, P, 64] with P = 1 << lgP frames per page, and
@@ -255,12 +392,12 @@ __global__ __launch_bounds__(64 * ST_WAVES) void temporal_ragged_kernel(int n, i
 // table row names for them); a wave reads positions < t0 of its own session's pages only and takes keys t0 .. t from the step's qkv rows.  The
 // pages of two sessions of one launch are distinct: a page in two sessions' rows is the host's error, as a slot in two rows is in the kernels
 // above (the pool's allocator never hands a page out twice).
-template <typename T>
+template <typename T, typename C>
 __global__ __launch_bounds__(64 * ST_WAVES) void temporal_ragged_paged_kernel(int n, int F, int S, int D, int heads, int T_total, int n_pages, int lgP, int pps,
                                                                              const int* __restrict__ t0_rows, const int* __restrict__ page_rows,
                                                                              const int* __restrict__ first_rows, const int* __restrict__ c_rows,
                                                                              const int* __restrict__ row_of_frame, const T* __restrict__ qkv,
-                                                                             T* __restrict__ kc, T* __restrict__ vc, T* __restrict__ out) {
+                                                                             C* __restrict__ kc, C* __restrict__ vc, T* __restrict__ out) {
     constexpr int VEC = StreamVec<T>::VEC, LPR = ATT_HD / VEC;
     const int lane = threadIdx.x & 63, grp = lane / LPR, sub = lane - grp * LPR;
     const long item = (long)blockIdx.x * ST_WAVES + (threadIdx.x >> 6);
@@ -306,10 +443,10 @@ __global__ __launch_bounds__(64 * ST_WAVES) void temporal_ragged_paged_kernel(in
     if (grp == 0) {
         // append this frame's key / value: position t0 + j of the session = the frame's own row (bit copies)
         const T* src = qkv + ((long)f * S + s) * (3L * D) + col;
-        copy16(keys(kc, own, t0 + j), src + D);
-        copy16(keys(vc, own, t0 + j), src + 2 * D);
+        append_line<T, C>(keys(kc, own, t0 + j), src + D);
+        append_line<T, C>(keys(vc, own, t0 + j), src + 2 * D);
     }
-    temporal_query_frame<T>(qkv, kc, vc, out, keys, first, j, t0, S, s, D, col, grp);
+    temporal_query_frame<T, C>(qkv, kc, vc, out, keys, first, j, t0, S, s, D, col, grp);
 }
 
 // causal_attention == 1 across chunks, for one session and 4 channels: `base` is slot 0 of the session's first frame of this step (these 4
@@ -354,33 +491,89 @@ __global__ void cls_ragged_kernel(int n, int F, int S, int D, float* __restrict_
     cls_session(slot, n_slots, t0_rows[r], x + (size_t)first * S * D + ch, c, (size_t)S * D, cls_cache, (size_t)slot * D + ch);
 }
 
-// What both temporal launchers ask of their arguments: a step of s.T >= 1 frames per row, head_dim 64, a causal mask, a stream of
-// T_min .. TCOW_STREAM_MAX_FRAMES frames, a storage type of this file and at least one cache slot.
-int check_temporal_args(const char* who, const tcow_attn_shape& s, int T_min, int T_total, int n_slots) {
+// What the temporal launchers ask of their arguments: a step of s.T >= 1 frames per row, head_dim 64, a causal mask, a stream of
+// T_min .. TCOW_STREAM_MAX_FRAMES frames, a storage type of this file, at least one cache slot, and a cache element type `cq` that is one of the
+// three and no wider than the storage (the entry points without a cache_dtype pass the storage type itself).
+int check_temporal_args(const char* who, const tcow_attn_shape& s, int T_min, int T_total, int n_slots, int cq) {
     TCOW_CHECK_ARG(s.B > 0 && s.T > 0 && s.S > 1 && s.heads > 0, "%s: bad step shape B=%d T=%d S=%d heads=%d", who, s.B, s.T, s.S, s.heads);
     TCOW_CHECK_ARG(s.D == s.heads * ATT_HD, "%s: head_dim must be 64 (D=%d heads=%d)", who, s.D, s.heads);
     TCOW_CHECK_ARG(s.causal == 1 || s.causal == 2, "%s: causal must be 1 or 2 (got %d): other masks let a frame see later frames", who, s.causal);
     TCOW_CHECK_ARG(T_total >= T_min && T_total <= TCOW_STREAM_MAX_FRAMES, "%s: T_total=%d must be in [%d, %d]", who, T_total, T_min, TCOW_STREAM_MAX_FRAMES);
     TCOW_CHECK_ARG(s.dtype == TCOW_F32 || s.dtype == TCOW_BF16, "%s: dtype must be TCOW_F32 or TCOW_BF16 (got %d)", who, s.dtype);
     TCOW_CHECK_ARG(n_slots >= 1, "%s: n_slots=%d must be >= 1", who, n_slots);
+    TCOW_CHECK_ARG(cq == TCOW_F32 || cq == TCOW_BF16 || cq == TCOW_FP8E4M3, "%s: cache_dtype must be TCOW_F32, TCOW_BF16 or TCOW_FP8E4M3 (got %d)", who, cq);
+    TCOW_CHECK_ARG(!(s.dtype == TCOW_BF16 && cq == TCOW_F32), "%s: cache_dtype TCOW_F32 is wider than the 16-bit storage (dtype TCOW_BF16)", who);
     return TCOW_OK;
 }
 
-// Argument checks and launch of temporal_cached_kernel, shared by the stream (t0 broadcast, slot = b) and the pool entry point.
+// Calls f(T{}, C{}) with the storage type T of `dtype` and the cache element type C of `cq` (both checked by check_temporal_args).
+template <typename F> void with_cache_types(int dtype, int cq, F f) {
+    if (dtype == TCOW_BF16) {
+        if (cq == TCOW_FP8E4M3) f(bf16_t{}, fp8_t{}); else f(bf16_t{}, bf16_t{});
+    } else {
+        if (cq == TCOW_FP8E4M3) f(float{}, fp8_t{}); else if (cq == TCOW_BF16) f(float{}, bf16_t{}); else f(float{}, float{});
+    }
+}
+
+// Argument checks and launch of temporal_cached_kernel, shared by the stream (t0 broadcast, slot = b) and the pool entry points.
 int launch_temporal_cached(const char* who, void* stream, const tcow_attn_shape* chunk, int T_total, int n_slots, const int* t0_rows, int t0_stride,
-                           const int* slot_rows, const void* qkv, void* k_cache, void* v_cache, void* out) {
+                           const int* slot_rows, const void* qkv, void* k_cache, void* v_cache, void* out, int cq) {
     TCOW_CHECK_ARG(chunk != nullptr, "%s: null shape", who);
     const tcow_attn_shape& s = *chunk;
-    if (const int err = check_temporal_args(who, s, s.T, T_total, n_slots)) return err;        // (the cache holds the chunk: T_total >= c)
+    if (const int err = check_temporal_args(who, s, s.T, T_total, n_slots, cq)) return err;    // (the cache holds the chunk: T_total >= c)
     TCOW_CHECK_ARG(t0_rows && qkv && k_cache && v_cache && out, "%s: null pointer", who);
     const long items = (long)s.B * s.S * s.heads;
     const dim3 grid((unsigned)cdiv(items, ST_WAVES)), block(64 * ST_WAVES);
-    if (s.dtype == TCOW_BF16)
-        hipLaunchKernelGGL(temporal_cached_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, s.B, s.T, s.S, s.D, s.heads, T_total, n_slots, t0_rows,
-                           t0_stride, slot_rows, (const bf16_t*)qkv, (bf16_t*)k_cache, (bf16_t*)v_cache, (bf16_t*)out);
-    else
-        hipLaunchKernelGGL(temporal_cached_kernel<float>, grid, block, 0, (hipStream_t)stream, s.B, s.T, s.S, s.D, s.heads, T_total, n_slots, t0_rows,
-                           t0_stride, slot_rows, (const float*)qkv, (float*)k_cache, (float*)v_cache, (float*)out);
+    with_cache_types(s.dtype, cq, [&](auto t, auto c) {
+        using T = decltype(t); using C = decltype(c);
+        hipLaunchKernelGGL((temporal_cached_kernel<T, C>), grid, block, 0, (hipStream_t)stream, s.B, s.T, s.S, s.D, s.heads, T_total, n_slots, t0_rows,
+                           t0_stride, slot_rows, (const T*)qkv, (C*)k_cache, (C*)v_cache, (T*)out);
+    });
+    TCOW_CHECK_LAUNCH();
+    return TCOW_OK;
+}
+
+int launch_temporal_ragged(const char* who, void* stream, const tcow_attn_shape* step, int n, int T_total, int n_slots, const int* t0_rows,
+                           const int* slot_rows, const int* first_rows, const int* c_rows, const int* row_of_frame, const void* qkv, void* k_cache,
+                           void* v_cache, void* out, int cq) {
+    TCOW_CHECK_ARG(step != nullptr, "%s: null shape", who);
+    const tcow_attn_shape& s = *step;
+    if (const int err = check_temporal_args(who, s, 1, T_total, n_slots, cq)) return err;      // (F counts the frames of all sessions: it may exceed T_total)
+    TCOW_CHECK_ARG(s.B == 1 && n > 0 && n <= s.T, "%s: a ragged step is one row of F frames of 1 <= n <= F sessions (B=%d F=%d n=%d)", who, s.B, s.T, n);
+    TCOW_CHECK_ARG(t0_rows && slot_rows && first_rows && c_rows && row_of_frame && qkv && k_cache && v_cache && out, "%s: null pointer", who);
+    const long items = (long)s.T * s.S * s.heads;
+    const dim3 grid((unsigned)cdiv(items, ST_WAVES)), block(64 * ST_WAVES);
+    with_cache_types(s.dtype, cq, [&](auto t, auto c) {
+        using T = decltype(t); using C = decltype(c);
+        hipLaunchKernelGGL((temporal_ragged_kernel<T, C>), grid, block, 0, (hipStream_t)stream, n, s.T, s.S, s.D, s.heads, T_total, n_slots, t0_rows,
+                           slot_rows, first_rows, c_rows, row_of_frame, (const T*)qkv, (C*)k_cache, (C*)v_cache, (T*)out);
+    });
+    TCOW_CHECK_LAUNCH();
+    return TCOW_OK;
+}
+
+int launch_temporal_ragged_paged(const char* who, void* stream, const tcow_attn_shape* step, int n, int T_total, int n_pages, int page_frames,
+                                 int pages_per_session, const int* t0_rows, const int* page_rows, const int* first_rows, const int* c_rows,
+                                 const int* row_of_frame, const void* qkv, void* k_pages, void* v_pages, void* out, int cq) {
+    TCOW_CHECK_ARG(step != nullptr, "%s: null shape", who);
+    const tcow_attn_shape& s = *step;
+    if (const int err = check_temporal_args(who, s, 1, T_total, 1, cq)) return err;            // (pages, not slots: n_pages is checked below)
+    TCOW_CHECK_ARG(s.B == 1 && n > 0 && n <= s.T, "%s: a ragged step is one row of F frames of 1 <= n <= F sessions (B=%d F=%d n=%d)", who, s.B, s.T, n);
+    TCOW_CHECK_ARG(page_frames >= 1 && page_frames <= TCOW_STREAM_MAX_FRAMES && (page_frames & (page_frames - 1)) == 0,
+                   "%s: page_frames=%d must be a power of two in [1, %d]", who, page_frames, TCOW_STREAM_MAX_FRAMES);
+    TCOW_CHECK_ARG(n_pages >= 1, "%s: n_pages=%d must be >= 1", who, n_pages);
+    TCOW_CHECK_ARG(pages_per_session >= 1 && (long)pages_per_session * page_frames >= T_total,
+                   "%s: pages_per_session=%d x page_frames=%d does not cover T_total=%d", who, pages_per_session, page_frames, T_total);
+    TCOW_CHECK_ARG(t0_rows && page_rows && first_rows && c_rows && row_of_frame && qkv && k_pages && v_pages && out, "%s: null pointer", who);
+    int lgP = 0;
+    while ((1 << lgP) < page_frames) ++lgP;
+    const long items = (long)s.T * s.S * s.heads;
+    const dim3 grid((unsigned)cdiv(items, ST_WAVES)), block(64 * ST_WAVES);
+    with_cache_types(s.dtype, cq, [&](auto t, auto c) {
+        using T = decltype(t); using C = decltype(c);
+        hipLaunchKernelGGL((temporal_ragged_paged_kernel<T, C>), grid, block, 0, (hipStream_t)stream, n, s.T, s.S, s.D, s.heads, T_total, n_pages, lgP,
+                           pages_per_session, t0_rows, page_rows, first_rows, c_rows, row_of_frame, (const T*)qkv, (C*)k_pages, (C*)v_pages, (T*)out);
+    });
     TCOW_CHECK_LAUNCH();
     return TCOW_OK;
 }
@@ -398,16 +591,31 @@ int launch_cls(const char* who, void* stream, int B, int c, int S, int D, float*
 
 extern "C" {
 
+// (the entry points without a cache_dtype keep the cache in the storage type: chunk->dtype, which the launcher checks)
 int tcow_attn_temporal_cached_fwd(void* stream, const tcow_attn_shape* chunk, int T_total, const int* t0_dev, const void* qkv, void* k_cache, void* v_cache,
                                   void* out) {
     return launch_temporal_cached("tcow_attn_temporal_cached_fwd", stream, chunk, T_total, chunk ? chunk->B : 1, t0_dev, 0, nullptr, qkv, k_cache, v_cache,
-                                  out);
+                                  out, chunk ? chunk->dtype : TCOW_F32);
+}
+
+int tcow_attn_temporal_cached_cq_fwd(void* stream, const tcow_attn_shape* chunk, int T_total, const int* t0_dev, const void* qkv, void* k_cache,
+                                     void* v_cache, void* out, int cache_dtype) {
+    return launch_temporal_cached("tcow_attn_temporal_cached_cq_fwd", stream, chunk, T_total, chunk ? chunk->B : 1, t0_dev, 0, nullptr, qkv, k_cache,
+                                  v_cache, out, cache_dtype);
 }
 
 int tcow_attn_temporal_pool_fwd(void* stream, const tcow_attn_shape* chunk, int T_total, int n_slots, const int* t0_rows, const int* slot_rows,
                                 const void* qkv, void* k_cache, void* v_cache, void* out) {
     TCOW_CHECK_ARG(slot_rows != nullptr, "tcow_attn_temporal_pool_fwd: null pointer");
-    return launch_temporal_cached("tcow_attn_temporal_pool_fwd", stream, chunk, T_total, n_slots, t0_rows, 1, slot_rows, qkv, k_cache, v_cache, out);
+    return launch_temporal_cached("tcow_attn_temporal_pool_fwd", stream, chunk, T_total, n_slots, t0_rows, 1, slot_rows, qkv, k_cache, v_cache, out,
+                                  chunk ? chunk->dtype : TCOW_F32);
+}
+
+int tcow_attn_temporal_pool_cq_fwd(void* stream, const tcow_attn_shape* chunk, int T_total, int n_slots, const int* t0_rows, const int* slot_rows,
+                                   const void* qkv, void* k_cache, void* v_cache, void* out, int cache_dtype) {
+    TCOW_CHECK_ARG(slot_rows != nullptr, "tcow_attn_temporal_pool_cq_fwd: null pointer");
+    return launch_temporal_cached("tcow_attn_temporal_pool_cq_fwd", stream, chunk, T_total, n_slots, t0_rows, 1, slot_rows, qkv, k_cache, v_cache, out,
+                                  cache_dtype);
 }
 
 int tcow_cls_stream(void* stream, int B, int c, int S, int D, float* x, float* cls_cache, const int* t0_dev) {
@@ -422,52 +630,29 @@ int tcow_cls_pool(void* stream, int n, int c, int S, int D, float* x, float* cls
 int tcow_attn_temporal_ragged_fwd(void* stream, const tcow_attn_shape* step, int n, int T_total, int n_slots, const int* t0_rows, const int* slot_rows,
                                   const int* first_rows, const int* c_rows, const int* row_of_frame, const void* qkv, void* k_cache, void* v_cache,
                                   void* out) {
-    const char* who = "tcow_attn_temporal_ragged_fwd";
-    TCOW_CHECK_ARG(step != nullptr, "%s: null shape", who);
-    const tcow_attn_shape& s = *step;
-    if (const int err = check_temporal_args(who, s, 1, T_total, n_slots)) return err;          // (F counts the frames of all sessions: it may exceed T_total)
-    TCOW_CHECK_ARG(s.B == 1 && n > 0 && n <= s.T, "%s: a ragged step is one row of F frames of 1 <= n <= F sessions (B=%d F=%d n=%d)", who, s.B, s.T, n);
-    TCOW_CHECK_ARG(t0_rows && slot_rows && first_rows && c_rows && row_of_frame && qkv && k_cache && v_cache && out, "%s: null pointer", who);
-    const long items = (long)s.T * s.S * s.heads;
-    const dim3 grid((unsigned)cdiv(items, ST_WAVES)), block(64 * ST_WAVES);
-    if (s.dtype == TCOW_BF16)
-        hipLaunchKernelGGL(temporal_ragged_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, n, s.T, s.S, s.D, s.heads, T_total, n_slots, t0_rows, slot_rows,
-                           first_rows, c_rows, row_of_frame, (const bf16_t*)qkv, (bf16_t*)k_cache, (bf16_t*)v_cache, (bf16_t*)out);
-    else
-        hipLaunchKernelGGL(temporal_ragged_kernel<float>, grid, block, 0, (hipStream_t)stream, n, s.T, s.S, s.D, s.heads, T_total, n_slots, t0_rows, slot_rows,
-                           first_rows, c_rows, row_of_frame, (const float*)qkv, (float*)k_cache, (float*)v_cache, (float*)out);
-    TCOW_CHECK_LAUNCH();
-    return TCOW_OK;
+    return launch_temporal_ragged("tcow_attn_temporal_ragged_fwd", stream, step, n, T_total, n_slots, t0_rows, slot_rows, first_rows, c_rows, row_of_frame,
+                                  qkv, k_cache, v_cache, out, step ? step->dtype : TCOW_F32);
+}
+
+int tcow_attn_temporal_ragged_cq_fwd(void* stream, const tcow_attn_shape* step, int n, int T_total, int n_slots, const int* t0_rows, const int* slot_rows,
+                                     const int* first_rows, const int* c_rows, const int* row_of_frame, const void* qkv, void* k_cache, void* v_cache,
+                                     void* out, int cache_dtype) {
+    return launch_temporal_ragged("tcow_attn_temporal_ragged_cq_fwd", stream, step, n, T_total, n_slots, t0_rows, slot_rows, first_rows, c_rows,
+                                  row_of_frame, qkv, k_cache, v_cache, out, cache_dtype);
 }
 
 int tcow_attn_temporal_ragged_paged_fwd(void* stream, const tcow_attn_shape* step, int n, int T_total, int n_pages, int page_frames, int pages_per_session,
                                         const int* t0_rows, const int* page_rows, const int* first_rows, const int* c_rows, const int* row_of_frame,
                                         const void* qkv, void* k_pages, void* v_pages, void* out) {
-    const char* who = "tcow_attn_temporal_ragged_paged_fwd";
-    TCOW_CHECK_ARG(step != nullptr, "%s: null shape", who);
-    const tcow_attn_shape& s = *step;
-    if (const int err = check_temporal_args(who, s, 1, T_total, 1)) return err;                // (pages, not slots: n_pages is checked below)
-    TCOW_CHECK_ARG(s.B == 1 && n > 0 && n <= s.T, "%s: a ragged step is one row of F frames of 1 <= n <= F sessions (B=%d F=%d n=%d)", who, s.B, s.T, n);
-    TCOW_CHECK_ARG(page_frames >= 1 && page_frames <= TCOW_STREAM_MAX_FRAMES && (page_frames & (page_frames - 1)) == 0,
-                   "%s: page_frames=%d must be a power of two in [1, %d]", who, page_frames, TCOW_STREAM_MAX_FRAMES);
-    TCOW_CHECK_ARG(n_pages >= 1, "%s: n_pages=%d must be >= 1", who, n_pages);
-    TCOW_CHECK_ARG(pages_per_session >= 1 && (long)pages_per_session * page_frames >= T_total,
-                   "%s: pages_per_session=%d x page_frames=%d does not cover T_total=%d", who, pages_per_session, page_frames, T_total);
-    TCOW_CHECK_ARG(t0_rows && page_rows && first_rows && c_rows && row_of_frame && qkv && k_pages && v_pages && out, "%s: null pointer", who);
-    int lgP = 0;
-    while ((1 << lgP) < page_frames) ++lgP;
-    const long items = (long)s.T * s.S * s.heads;
-    const dim3 grid((unsigned)cdiv(items, ST_WAVES)), block(64 * ST_WAVES);
-    if (s.dtype == TCOW_BF16)
-        hipLaunchKernelGGL(temporal_ragged_paged_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, n, s.T, s.S, s.D, s.heads, T_total, n_pages, lgP,
-                           pages_per_session, t0_rows, page_rows, first_rows, c_rows, row_of_frame, (const bf16_t*)qkv, (bf16_t*)k_pages, (bf16_t*)v_pages,
-                           (bf16_t*)out);
-    else
-        hipLaunchKernelGGL(temporal_ragged_paged_kernel<float>, grid, block, 0, (hipStream_t)stream, n, s.T, s.S, s.D, s.heads, T_total, n_pages, lgP,
-                           pages_per_session, t0_rows, page_rows, first_rows, c_rows, row_of_frame, (const float*)qkv, (float*)k_pages, (float*)v_pages,
-                           (float*)out);
-    TCOW_CHECK_LAUNCH();
-    return TCOW_OK;
+    return launch_temporal_ragged_paged("tcow_attn_temporal_ragged_paged_fwd", stream, step, n, T_total, n_pages, page_frames, pages_per_session, t0_rows,
+                                        page_rows, first_rows, c_rows, row_of_frame, qkv, k_pages, v_pages, out, step ? step->dtype : TCOW_F32);
+}
+
+int tcow_attn_temporal_ragged_paged_cq_fwd(void* stream, const tcow_attn_shape* step, int n, int T_total, int n_pages, int page_frames,
+                                           int pages_per_session, const int* t0_rows, const int* page_rows, const int* first_rows, const int* c_rows,
+                                           const int* row_of_frame, const void* qkv, void* k_pages, void* v_pages, void* out, int cache_dtype) {
+    return launch_temporal_ragged_paged("tcow_attn_temporal_ragged_paged_cq_fwd", stream, step, n, T_total, n_pages, page_frames, pages_per_session,
+                                        t0_rows, page_rows, first_rows, c_rows, row_of_frame, qkv, k_pages, v_pages, out, cache_dtype);
 }
 
 int tcow_cls_ragged(void* stream, int n, int F, int S, int D, float* x, float* cls_cache, int n_slots, const int* t0_rows, const int* slot_rows,

@@ -349,10 +349,32 @@ def _stream_attn(mode, B, c, S, D, heads, causal, *tensors):
     return lib, ctypes.byref(L.AttnShape(B, c, S, D, heads, int(causal), F32 if dm == F32X3 else dm))
 
 
-def attn_temporal_cached(mode, B, c, S, D, heads, causal, T_total, t0_dev, qkv, k_cache, v_cache, out):
+FP8 = L.TCOW_FP8E4M3      # cache_dtype of the attn_temporal_* wrappers only: a K / V cache of torch.float8_e4m3fn elements
+
+
+def _cache_dtype(who, mode, cache_dtype, k_cache, v_cache):
+    """The cache_dtype keyword of the attn_temporal_* wrappers (F32, BF16 = the 16-bit type, FP8; None is handled by the caller): the caches must
+    have the torch dtype it names -- torch.float8_e4m3fn; for BF16 the mode's 16-bit type, torch.bfloat16 under f32 storage (the main build serves
+    it); torch.float32.  A value or pair the library refuses (unknown, wider than the storage) is passed on for it to refuse.  Returns the int."""
+    cq = int(cache_dtype)
+    want = torch.float8_e4m3fn if cq == FP8 else (tdtype(mode) if is16(mode) else torch.bfloat16) if cq == BF16 else \
+        torch.float32 if cq == F32 and not is16(mode) else None
+    if want is not None and (k_cache.dtype != want or v_cache.dtype != want):
+        raise L.TcowError(f'{who}: cache_dtype={cq} needs {want} caches, got {k_cache.dtype} / {v_cache.dtype}')
+    return cq
+
+
+def attn_temporal_cached(mode, B, c, S, D, heads, causal, T_total, t0_dev, qkv, k_cache, v_cache, out, cache_dtype=None):
     """Temporal attention of a c-frame chunk (qkv [B*c*S, 3D] -> out [B*c*S, D]) against the K / V cache [B, S-1, heads, T_total, 64] of the
-    frames before t0 = t0_dev[0] (int32 device scalar); appends the chunk's K / V at t0 (see tcow_attn_temporal_cached_fwd)."""
+    frames before t0 = t0_dev[0] (int32 device scalar); appends the chunk's K / V at t0 (see tcow_attn_temporal_cached_fwd).
+    cache_dtype (here and in the three wrappers below): None = caches in the storage type; F32 / BF16 / FP8 = the compact-cache entry point
+    (tcow_attn_temporal_*_cq_fwd) on caches of that element type, every key and value taken at its value rounded to it."""
     lib, sh = _stream_attn(mode, B, c, S, D, heads, causal, qkv, k_cache, v_cache, out, t0_dev)
+    if cache_dtype is not None:
+        cq = _cache_dtype('attn_temporal_cached', mode, cache_dtype, k_cache, v_cache)
+        L.check(lib.tcow_attn_temporal_cached_cq_fwd(_stream(), sh, int(T_total), t0_dev.data_ptr(), qkv.data_ptr(), k_cache.data_ptr(),
+                                                     v_cache.data_ptr(), out.data_ptr(), cq), 'tcow_attn_temporal_cached_cq_fwd', lib)
+        return out
     L.check(lib.tcow_attn_temporal_cached_fwd(_stream(), sh, int(T_total), t0_dev.data_ptr(), qkv.data_ptr(), k_cache.data_ptr(),
                                               v_cache.data_ptr(), out.data_ptr()), 'tcow_attn_temporal_cached_fwd', lib)
     return out
@@ -364,10 +386,15 @@ def cls_stream(x, B, c, S, cls_cache, t0_dev):
     return x
 
 
-def attn_temporal_pool(mode, n, c, S, D, heads, causal, T_total, n_slots, t0_rows, slot_rows, qkv, k_cache, v_cache, out):
+def attn_temporal_pool(mode, n, c, S, D, heads, causal, T_total, n_slots, t0_rows, slot_rows, qkv, k_cache, v_cache, out, cache_dtype=None):
     """attn_temporal_cached for n rows that stand at different frames: row r attends at t0_rows[r] against block slot_rows[r] of the caches
     [n_slots, S-1, heads, T_total, 64] and appends there (int32 device tensors [n]; distinct slots -- see tcow_attn_temporal_pool_fwd)."""
     lib, sh = _stream_attn(mode, n, c, S, D, heads, causal, qkv, k_cache, v_cache, out, t0_rows, slot_rows)
+    if cache_dtype is not None:
+        cq = _cache_dtype('attn_temporal_pool', mode, cache_dtype, k_cache, v_cache)
+        L.check(lib.tcow_attn_temporal_pool_cq_fwd(_stream(), sh, int(T_total), int(n_slots), t0_rows.data_ptr(), slot_rows.data_ptr(), qkv.data_ptr(),
+                                                   k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(), cq), 'tcow_attn_temporal_pool_cq_fwd', lib)
+        return out
     L.check(lib.tcow_attn_temporal_pool_fwd(_stream(), sh, int(T_total), int(n_slots), t0_rows.data_ptr(), slot_rows.data_ptr(), qkv.data_ptr(),
                                             k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr()), 'tcow_attn_temporal_pool_fwd', lib)
     return out
@@ -394,7 +421,7 @@ def _ragged_tables(who, n, F, t0_rows, slot_rows, first_rows, c_rows, row_of_fra
 
 
 def attn_temporal_ragged(mode, n, F, S, D, heads, causal, T_total, n_slots, t0_rows, slot_rows, first_rows, c_rows, row_of_frame, qkv, k_cache, v_cache,
-                         out):
+                         out, cache_dtype=None):
     """attn_temporal_pool for n sessions that bring different numbers of frames: session r owns the flat frames first_rows[r] .. + c_rows[r] - 1 of
     the step's F frames (qkv [F*S, 3D] -> out [F*S, D]), row_of_frame[f] names the session of frame f (int32 device tensors [n] / [F]); one wave per
     frame, bit-identical per session to attn_temporal_pool (see tcow_attn_temporal_ragged_fwd)."""
@@ -402,6 +429,12 @@ def attn_temporal_ragged(mode, n, F, S, D, heads, causal, T_total, n_slots, t0_r
     _ragged_tables('attn_temporal_ragged', n, F, t0_rows, slot_rows, first_rows, c_rows, row_of_frame)
     if qkv.shape[0] != F * S or out.shape[0] != F * S:
         raise L.TcowError(f'attn_temporal_ragged: qkv / out must have F * S = {F * S} rows, got {qkv.shape[0]} / {out.shape[0]}')
+    if cache_dtype is not None:
+        cq = _cache_dtype('attn_temporal_ragged', mode, cache_dtype, k_cache, v_cache)
+        L.check(lib.tcow_attn_temporal_ragged_cq_fwd(_stream(), sh, int(n), int(T_total), int(n_slots), t0_rows.data_ptr(), slot_rows.data_ptr(),
+                                                     first_rows.data_ptr(), c_rows.data_ptr(), row_of_frame.data_ptr(), qkv.data_ptr(),
+                                                     k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(), cq), 'tcow_attn_temporal_ragged_cq_fwd', lib)
+        return out
     L.check(lib.tcow_attn_temporal_ragged_fwd(_stream(), sh, int(n), int(T_total), int(n_slots), t0_rows.data_ptr(), slot_rows.data_ptr(),
                                               first_rows.data_ptr(), c_rows.data_ptr(), row_of_frame.data_ptr(), qkv.data_ptr(), k_cache.data_ptr(),
                                               v_cache.data_ptr(), out.data_ptr()), 'tcow_attn_temporal_ragged_fwd', lib)
@@ -409,7 +442,7 @@ def attn_temporal_ragged(mode, n, F, S, D, heads, causal, T_total, n_slots, t0_r
 
 
 def attn_temporal_ragged_paged(mode, n, F, S, D, heads, causal, T_total, n_pages, page_frames, t0_rows, page_rows, first_rows, c_rows, row_of_frame, qkv,
-                               k_pages, v_pages, out):
+                               k_pages, v_pages, out, cache_dtype=None):
     """attn_temporal_ragged on a paged cache: k_pages / v_pages [n_pages, S-1, heads, page_frames, 64], and instead of a slot session r brings row r
     of page_rows (int32 device tensor [n, pages_per_session]): entry q is the page of its frames q * page_frames .. + page_frames - 1.
     Bit-identical to attn_temporal_ragged on contiguous caches of the same contents (see tcow_attn_temporal_ragged_paged_fwd)."""
@@ -420,6 +453,13 @@ def attn_temporal_ragged_paged(mode, n, F, S, D, heads, causal, T_total, n_pages
                           f'{page_rows.dtype} {tuple(page_rows.shape)}')
     if qkv.shape[0] != F * S or out.shape[0] != F * S:
         raise L.TcowError(f'attn_temporal_ragged_paged: qkv / out must have F * S = {F * S} rows, got {qkv.shape[0]} / {out.shape[0]}')
+    if cache_dtype is not None:
+        cq = _cache_dtype('attn_temporal_ragged_paged', mode, cache_dtype, k_pages, v_pages)
+        L.check(lib.tcow_attn_temporal_ragged_paged_cq_fwd(_stream(), sh, int(n), int(T_total), int(n_pages), int(page_frames), int(page_rows.shape[1]),
+                                                           t0_rows.data_ptr(), page_rows.data_ptr(), first_rows.data_ptr(), c_rows.data_ptr(),
+                                                           row_of_frame.data_ptr(), qkv.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), out.data_ptr(),
+                                                           cq), 'tcow_attn_temporal_ragged_paged_cq_fwd', lib)
+        return out
     L.check(lib.tcow_attn_temporal_ragged_paged_fwd(_stream(), sh, int(n), int(T_total), int(n_pages), int(page_frames), int(page_rows.shape[1]),
                                                     t0_rows.data_ptr(), page_rows.data_ptr(), first_rows.data_ptr(), c_rows.data_ptr(),
                                                     row_of_frame.data_ptr(), qkv.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), out.data_ptr()),

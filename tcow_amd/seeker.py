@@ -274,23 +274,27 @@ class QueryMaskTracker(nn.Module):
         T = self.num_total_frames if T is None else T
         return dict(B=B, T=T, Hp=Hp, Wp=Wp, N=N, S=N + 1, D=self.embed_dim, heads=self.num_heads, P=P, M=B * T * (N + 1))
 
-    def stream(self, batch_size=1, queries_per_clip=1, graph=False, skinny_gemm=None):
+    def stream(self, batch_size=1, queries_per_clip=1, graph=False, skinny_gemm=None, cache_dtype=None):
         """Streaming inference (causal_attention 1 or 2, eval, CUDA): a SeekerStream of at most num_total_frames frames for `batch_size` clips with
         `queries_per_clip` query masks each; stream.step(rgb, query_mask) takes the next frames and returns their outputs (tcow_amd/stream.py).
         skinny_gemm: the steps' GEMMs of a few hundred rows run on 64 x 64 tiles with a split over K -- the 16-bit modes where ops.skinny_plan
         routes them, 'bf16x3' where ops.skinny_plan_x3 does; exact 'fp32' has no such kernel.  None = the measured default of the precision,
-        stream.SKINNY_GEMM_DEFAULT (16-bit) / stream.SKINNY_GEMM_X3_DEFAULT (bf16x3)."""
+        stream.SKINNY_GEMM_DEFAULT (16-bit) / stream.SKINNY_GEMM_X3_DEFAULT (bf16x3).
+        cache_dtype: the element type of the temporal K / V cache, apart from the precision (stream.cache_plan): None = the storage type;
+        'bf16' halves the cache of 'fp32' / 'bf16x3'; 'fp8' (OCP e4m3fn) in any precision, a quarter of an f32 cache.  Keys and values are then
+        used at their rounded values: the outputs differ from the None stream's by that rounding and still do not depend on the chunking."""
         from .stream import SeekerStream
-        return SeekerStream(self, batch_size, queries_per_clip, graph, skinny_gemm)
+        return SeekerStream(self, batch_size, queries_per_clip, graph, skinny_gemm, cache_dtype)
 
-    def stream_pool(self, capacity, skinny_gemm=None, page_frames=None, pages=None):
+    def stream_pool(self, capacity, skinny_gemm=None, page_frames=None, pages=None, cache_dtype=None):
         """Streaming inference for up to `capacity` live sessions that started at different moments: a SeekerStreamPool whose step(ids, rgb,
         query_mask) advances any subset of the open sessions, each at its own frame, in one Seeker step (tcow_amd/stream.py).
         page_frames=P (a power of two): a paged pool -- the K / V caches are `pages` pages of P frames (default capacity * ceil(T / P), which cannot
         run out; lower it to the memory budget), a session holds only the pages its frames so far have filled and close() / reset() return them;
-        a step that would need more pages than are free raises TcowError and moves nothing.  Same outputs, bit for bit.  None: one full cache per slot."""
+        a step that would need more pages than are free raises TcowError and moves nothing.  Same outputs, bit for bit.  None: one full cache per slot.
+        cache_dtype: as in stream(); a pool gives the bits of a stream with the same cache_dtype."""
         from .stream import SeekerStreamPool
-        return SeekerStreamPool(self, capacity, skinny_gemm, page_frames, pages)
+        return SeekerStreamPool(self, capacity, skinny_gemm, page_frames, pages, cache_dtype)
 
     def param_list(self):
         """Fixed order of the parameters the autograd.Function sees.  Cached: walking ~250 module attributes costs 0.4 ms per call.  .to() /
@@ -363,10 +367,10 @@ class Seeker(nn.Module):
     def forward(self, *args):
         return self.seeker(*args)
 
-    def stream(self, batch_size=1, queries_per_clip=1, graph=False, skinny_gemm=None):
+    def stream(self, batch_size=1, queries_per_clip=1, graph=False, skinny_gemm=None, cache_dtype=None):
         """See QueryMaskTracker.stream."""
-        return self.seeker.stream(batch_size, queries_per_clip, graph, skinny_gemm)
+        return self.seeker.stream(batch_size, queries_per_clip, graph, skinny_gemm, cache_dtype)
 
-    def stream_pool(self, capacity, skinny_gemm=None, page_frames=None, pages=None):
+    def stream_pool(self, capacity, skinny_gemm=None, page_frames=None, pages=None, cache_dtype=None):
         """See QueryMaskTracker.stream_pool."""
-        return self.seeker.stream_pool(capacity, skinny_gemm, page_frames, pages)
+        return self.seeker.stream_pool(capacity, skinny_gemm, page_frames, pages, cache_dtype)

@@ -12,6 +12,14 @@ modes: bf16 / binary16; fp32 and bf16x3: f32), one f32 cls row per row and block
 clips x queries (the query mask changes every token's K / V), a pool rows = capacity.  At BASELINE configs[1] (T = 30, 240x320, depth 12)
 that is 332 MB per row in the 16-bit modes; at configs[3] (T = 60, 480x640) 2.65 GB; f32 twice that.
 
+cache_dtype (net.stream / net.stream_pool; cache_plan below is the one place that decides): the element type of the K / V caches, apart from
+the precision mode -- the kernel computes in f32 and only loads and stores cache lines.  None: the storage type, as above.  'bf16': halves the
+caches of 'fp32' and 'bf16x3' (the same as None in 'bf16'; refused in 'fp16').  'fp8' (OCP e4m3fn, saturating at +-448, no scales): any
+precision, a quarter of an f32 cache and half of a 16-bit one -- 166 MB per row at configs[1].  With a compact cache every key and value of
+the temporal attention, the step's own included, enters at its value rounded to that type (q does not), so the outputs still do not depend
+on how the frames were split into chunks, and the four step forms below still agree bit for bit; they differ from the None stream's by the
+rounding ("Compact cache": accuracy and time, measured).  cls rows, tables, graphs, pages and GEMMs are untouched.
+
 What belongs to one step is a _Step, and it is all run_forward sees (its `stream` argument): pos, time_rows [B*T, D] (one row of the time table
 per (row, frame) of the step), attn_temporal(i, ...) and cls_row(i, ...) for block i, and skinny: whether the step's GEMMs take the
 skinny-M entry points where ops.skinny_plan (16-bit modes) / ops.skinny_plan_x3 (bf16x3) route them (the skinny_gemm keyword of net.stream /
@@ -68,22 +76,40 @@ SKINNY_GEMM_DEFAULT = True
 SKINNY_GEMM_X3_DEFAULT = True
 
 
+def cache_plan(mode, cache_dtype):
+    """THE decision of the cache_dtype keyword (host arithmetic only): (torch dtype of the K / V caches, cache_dtype argument of the
+    ops.attn_temporal_* wrappers) for a module of ops mode `mode` (F32, BF16, FP16; bf16x3 stores F32).  None -> (the storage type, None): the
+    entry points without a cache type.  'fp8' -> torch.float8_e4m3fn in any mode.  'bf16' -> torch.bfloat16 under f32 storage; under bf16
+    storage it is what None gives; binary16 storage refuses it (bfloat16 is no narrower, and the binary16 build has no such kernel)."""
+    if cache_dtype is None:
+        return ops.tdtype(mode), None
+    if cache_dtype == 'fp8':
+        return torch.float8_e4m3fn, ops.FP8
+    if cache_dtype == 'bf16':
+        if mode == ops.FP16:
+            raise TcowError("stream: cache_dtype='bf16' with precision='fp16': the cache would be no smaller than the binary16 storage; "
+                            "use None or 'fp8'")
+        return (torch.bfloat16, None) if mode == ops.BF16 else (torch.bfloat16, ops.BF16)
+    raise TcowError(f"stream: cache_dtype={cache_dtype!r} must be None, 'bf16' or 'fp8'")
+
+
 def _skinny_default(module):
     return SKINNY_GEMM_X3_DEFAULT if module.gemm_mode == ops.F32X3 else SKINNY_GEMM_DEFAULT
 
 
 class _State:
-    """What lives as long as a stream or a pool of `rows` query rows: per block the K / V caches [rows, S-1, heads, T, 64] in the mode's storage
-    type and one f32 cls row per query row, and the effective pos table and time table [T, D]."""
+    """What lives as long as a stream or a pool of `rows` query rows: per block the K / V caches [rows, S-1, heads, T, 64] in the element type of
+    cache_plan (the mode's storage type unless cache_dtype says otherwise) and one f32 cls row per query row, and the effective pos table and
+    time table [T, D].  cq: the cache_dtype argument every step built on this state passes to its ops.attn_temporal_* wrapper."""
 
     def _kv_shape(self, depth, rows, g):
         return (depth, rows, g['S'] - 1, g['heads'], self.T_total, 64)
 
-    def __init__(self, module, rows, skinny=False):
+    def __init__(self, module, rows, skinny=False, cache_dtype=None):
         self.skinny = bool(skinny)                              # every step built on this state carries it (_Step.skinny)
         g = module.geometry(rows)
         dev = module.vit.pos_embed.device
-        cdt = ops.tdtype(module.mode)                           # (bf16x3 stores f32, like fp32)
+        cdt, self.cq = cache_plan(module.mode, cache_dtype)     # (None: the storage type -- bf16x3 stores f32, like fp32)
         self.T_total, self.n_slots, self.D = module.num_total_frames, rows, g['D']
         shape = self._kv_shape(module.network_depth, rows, g)
         self.k_cache = torch.empty(shape, dtype=cdt, device=dev)
@@ -102,10 +128,10 @@ class _PagedState(_State):
     session owns those its frames so far have filled (PageAllocator; a page id is valid in every block's arrays alike); the cls rows stay one per
     slot [rows, D], and `rows` = capacity only bounds the number of open sessions.  A session's row of the page table has pps = ceil(T / P) entries."""
 
-    def __init__(self, module, rows, skinny, page_frames, n_pages):
+    def __init__(self, module, rows, skinny, page_frames, n_pages, cache_dtype=None):
         self.P, self.n_pages = page_frames, n_pages
         self.pps = -(-module.num_total_frames // page_frames)
-        super().__init__(module, rows, skinny)
+        super().__init__(module, rows, skinny, cache_dtype)
 
     def _kv_shape(self, depth, rows, g):
         return (depth, self.n_pages, g['S'] - 1, g['heads'], self.P, 64)
@@ -126,7 +152,7 @@ class _StreamStep(_Step):
 
     def attn_temporal(self, i, amode, B, T, S, D, heads, ca, QKV, O):
         st = self.state
-        ops.attn_temporal_cached(amode, B, T, S, D, heads, ca, st.T_total, *self.tables, QKV, st.k_cache[i], st.v_cache[i], O)
+        ops.attn_temporal_cached(amode, B, T, S, D, heads, ca, st.T_total, *self.tables, QKV, st.k_cache[i], st.v_cache[i], O, st.cq)
 
     def cls_row(self, i, R2, B, T, S):
         ops.cls_stream(R2, B, T, S, self.state.cls_cache[i], *self.tables)
@@ -137,7 +163,7 @@ class _PoolStep(_Step):
 
     def attn_temporal(self, i, amode, B, T, S, D, heads, ca, QKV, O):
         st = self.state
-        ops.attn_temporal_pool(amode, B, T, S, D, heads, ca, st.T_total, st.n_slots, *self.tables, QKV, st.k_cache[i], st.v_cache[i], O)
+        ops.attn_temporal_pool(amode, B, T, S, D, heads, ca, st.T_total, st.n_slots, *self.tables, QKV, st.k_cache[i], st.v_cache[i], O, st.cq)
 
     def cls_row(self, i, R2, B, T, S):
         ops.cls_pool(R2, B, T, S, self.state.cls_cache[i], self.state.n_slots, *self.tables)
@@ -150,7 +176,7 @@ class _RaggedStep(_Step):
     def attn_temporal(self, i, amode, B, T, S, D, heads, ca, QKV, O):
         st = self.state
         ops.attn_temporal_ragged(amode, self.tables[0].numel(), T, S, D, heads, ca, st.T_total, st.n_slots, *self.tables, QKV, st.k_cache[i],
-                                 st.v_cache[i], O)
+                                 st.v_cache[i], O, st.cq)
 
     def cls_row(self, i, R2, B, T, S):
         ops.cls_ragged(R2, self.tables[0].numel(), T, S, self.state.cls_cache[i], self.state.n_slots, *self.tables[:4])
@@ -164,7 +190,7 @@ class _PagedRaggedStep(_RaggedStep):
         st = self.state
         t0_rows, _, first_rows, c_rows, row_of_frame, page_rows = self.tables
         ops.attn_temporal_ragged_paged(amode, t0_rows.numel(), T, S, D, heads, ca, st.T_total, st.n_pages, st.P, t0_rows, page_rows, first_rows, c_rows,
-                                       row_of_frame, QKV, st.k_cache[i], st.v_cache[i], O)
+                                       row_of_frame, QKV, st.k_cache[i], st.v_cache[i], O, st.cq)
 
 
 def check_streamable(module):
@@ -322,9 +348,9 @@ def _zero_mask(rows, rgb):
 
 
 class SeekerStream:
-    """net.stream(batch_size, queries_per_clip, graph, skinny_gemm) of Seeker / QueryMaskTracker; see the module docstring."""
+    """net.stream(batch_size, queries_per_clip, graph, skinny_gemm, cache_dtype) of Seeker / QueryMaskTracker; see the module docstring."""
 
-    def __init__(self, module, batch_size=1, queries_per_clip=1, graph=False, skinny_gemm=None):
+    def __init__(self, module, batch_size=1, queries_per_clip=1, graph=False, skinny_gemm=None, cache_dtype=None):
         module = getattr(module, 'seeker', module)
         check_streamable(module)
         Bc, Qs = int(batch_size), int(queries_per_clip)
@@ -335,7 +361,8 @@ class SeekerStream:
         self.T = module.num_total_frames
         self.graph = bool(graph)
         self.skinny_gemm = _skinny_default(module) if skinny_gemm is None else bool(skinny_gemm)
-        self._st = _State(module, self.B, self.skinny_gemm)
+        self.cache_dtype = cache_dtype
+        self._st = _State(module, self.B, self.skinny_gemm, cache_dtype)
         self.device = self._st.pos.device
         self._t0_dev = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._steps = {}                # c -> the step of chunk length c; its time_rows [B*c, D] f32 are static: a captured graph points into both
@@ -420,13 +447,13 @@ class SeekerStream:
 
 
 class SeekerStreamPool:
-    """net.stream_pool(capacity, skinny_gemm, page_frames, pages) of Seeker / QueryMaskTracker: up to `capacity` live sessions (one clip and one query
+    """net.stream_pool(capacity, skinny_gemm, page_frames, pages, cache_dtype) of Seeker / QueryMaskTracker: up to `capacity` live sessions (one clip and one query
     mask each) that stand at different frames, stepped together; see the module docstring.  open() -> id, step(ids, rgb, query_mask) (one chunk
     length for all) or step_ragged(ids, rgbs, query_masks) (a chunk length per session), close(id).  page_frames=P: a paged pool, whose K / V
     memory is `pages` pages of P frames shared by the sessions (pages_total, pages_free, pages_of(id)); its outputs are bit-identical to the
     contiguous pool's."""
 
-    def __init__(self, module, capacity, skinny_gemm=None, page_frames=None, pages=None):
+    def __init__(self, module, capacity, skinny_gemm=None, page_frames=None, pages=None, cache_dtype=None):
         module = getattr(module, 'seeker', module)
         capacity = int(capacity)
         if capacity < 1:
@@ -437,10 +464,12 @@ class SeekerStreamPool:
         self.capacity = capacity
         self.T = module.num_total_frames
         self.skinny_gemm = _skinny_default(module) if skinny_gemm is None else bool(skinny_gemm)
+        self.cache_dtype = cache_dtype
         if self.page_frames is None:
-            self._st, self._alloc = _State(module, capacity, self.skinny_gemm), None
+            self._st, self._alloc = _State(module, capacity, self.skinny_gemm, cache_dtype), None
         else:
-            self._st, self._alloc = _PagedState(module, capacity, self.skinny_gemm, self.page_frames, n_pages), PageAllocator(n_pages, self.page_frames)
+            self._st = _PagedState(module, capacity, self.skinny_gemm, self.page_frames, n_pages, cache_dtype)
+            self._alloc = PageAllocator(n_pages, self.page_frames)
         self.device = self._st.pos.device
         self._sig = _signature(module)
         self._slot = {}                 # open session id -> cache slot

@@ -17,6 +17,12 @@
     python tools/dev_stream_latency.py --skinny --precision bf16x3 --reps 30 --out profiles/stream_skinny_x3_latency.json
                                         # the same legs in precision='bf16x3' (ops.gemm_nt_skinny_x3 against tcow_gemm_nt with TCOW_F32X3)
     --kprof / --kstats take --precision and --skinny-gemm on|off as well: the breakdown of a bf16x3 step with and without the flag
+    python tools/dev_stream_latency.py --cache-dtype fp8 --out lat_bf16.json
+    python tools/dev_stream_latency.py --cache-dtype bf16,fp8 --precision fp32 --out lat_fp32.json
+                                        # one-frame steps with cache_dtype=None against the listed compact caches, the legs alternating in one run:
+                                        # configs[1] B = 1 and B = 8, configs[3] B = 1 at t0 = 0, T/2, T-1, and a long stream (configs[1] geometry,
+                                        # num_total_frames = 240) at t0 = 239; the two files' runs are the 'latency' list of profiles/stream_cache_dtype.json
+    --kprof / --kstats take one --cache-dtype as well (the temporal kernel's own time and bytes with a compact cache)
 
 Times are device events around each call after warm-up, profiler off.  A step at a given t0 is timed by setting the stream's host frame counter
 (the kernels then read t0 from the device scalar the step writes): the work of a step depends on t0, not on what the cache holds.  Synthetic
@@ -273,34 +279,93 @@ def skinny_leg(reps, precision='bf16'):
     return {'runs': runs, 'verdict_default_true': verdict}
 
 
+LONG_T = 240
+
+
+def cache_leg(reps, precision, keywords, only=None):
+    """One-frame eager steps with cache_dtype=None and each of `keywords`, the streams of a shape stepped in turn `reps` times (one sample, one
+    step between a pair of events, each per round) at every t0: median, min, max per leg and t0, and None's median minus the leg's next to None's
+    own max - min.  The long stream has configs[1]'s frame size and LONG_T frames; its steps are fed the clip's first frame (the work of a step
+    depends on t0 alone)."""
+    runs = []
+    shapes = [('configs1', 1, None), ('configs1', 8, None), ('configs3', 1, None), ('configs1', 1, LONG_T)]
+    for name, B, T_long in shapes:
+        tag = f'{name}_b{B}' + ('_long' if T_long else '')
+        if only and tag not in only:
+            continue
+        T, H, W = CONFIGS[name]
+        rgb, qm = inputs(B, 2 if T_long else T, H, W)
+        T = T_long or T
+        net = build(T, H, W, precision)
+        frame = (lambda x, t: x[:, :, 0:1]) if T_long else (lambda x, t: x[:, :, t:t + 1])
+        t0s = [T - 1] if T_long else [0, T // 2, T - 1]
+        r = {'shape': tag, 'config': name, 'T': T, 'H': H, 'W': W, 'B': B, 'precision': precision, 'reps': reps, 'cache_bytes': {}, 'step_ms': {}}
+        with torch.no_grad():
+            streams = {}
+            for kw in [None] + list(keywords):
+                st = streams[str(kw)] = net.stream(batch_size=B, cache_dtype=kw)
+                r['cache_bytes'][str(kw)] = st.cache_bytes
+                for t in (0, T - 1, T - 1):                     # warm-up: operand copies, the workspace
+                    st.frames_done = t
+                    st.step(frame(rgb, t), frame(qm, t))
+            for t0 in t0s:
+                samples = {k: [] for k in streams}
+
+                def one(st, t0=t0):
+                    st.frames_done = t0
+                    st.step(frame(rgb, t0), frame(qm, t0))
+                for st in streams.values():
+                    one(st)
+                for _ in range(reps):
+                    for k, st in streams.items():
+                        samples[k].append(ev_time(lambda: one(st), 1))
+                row = {}
+                for k, v in samples.items():
+                    v = sorted(v)
+                    row[k] = {'median': v[len(v) // 2], 'min': v[0], 'max': v[-1]}
+                base = row['None']
+                for k in row:
+                    if k != 'None':
+                        row[k]['none_minus_this_ms'] = base['median'] - row[k]['median']
+                        row[k]['lower_by_more_than_none_spread'] = bool(base['median'] - row[k]['median'] > base['max'] - base['min'])
+                r['step_ms'][str(t0)] = row
+        print(json.dumps(r), flush=True)
+        runs.append(r)
+        del streams, net
+        torch.cuda.empty_cache()
+    return runs
+
+
 KPROF_WARMUP, KPROF_STEPS = 3, 20
 STEP_LAST_KERNEL = 'flags_fwd_kernel'      # the last launch of every step (the flags head, engine.run_forward)
 
 
-def cached_kernel_bytes(T, H, W, e=2, heads=12, D=768):
-    """Algorithmic bytes of one tcow_attn_temporal_cached_fwd launch of a one-frame step at t0 = T - 1 (B = 1, element size e)."""
+def cached_kernel_bytes(T, H, W, e=2, heads=12, D=768, ce=None):
+    """Algorithmic bytes of one tcow_attn_temporal_cached_fwd launch of a one-frame step at t0 = T - 1 (B = 1, element size e, cache element
+    size ce: e unless the cache is compact)."""
     S, t0 = (H // 16) * (W // 16) + 1, T - 1
-    alg = {'cache_read': (S - 1) * heads * t0 * 64 * 2 * e, 'chunk_qkv_read': S * 3 * D * e, 'out_write': S * D * e,
-           'cache_append': (S - 1) * heads * 64 * 2 * e}
+    ce = e if ce is None else ce
+    alg = {'cache_read': (S - 1) * heads * t0 * 64 * 2 * ce, 'chunk_qkv_read': S * 3 * D * e, 'out_write': S * D * e,
+           'cache_append': (S - 1) * heads * 64 * 2 * ce}
     alg['total'] = sum(alg.values())
     return alg
 
 
-def kprof(precision='bf16', skinny_gemm=None):
+def kprof(precision='bf16', skinny_gemm=None, cache_dtype=None):
     """One-frame steps (bf16, or `precision`) at configs[3], t0 = 59, for a rocprofv3 kernel trace: KPROF_WARMUP steps that build the operand
     copies, then KPROF_STEPS steady ones (--kstats keeps only those)."""
     T, H, W = CONFIGS['configs3']
     net = build(T, H, W, precision)
     rgb, qm = inputs(1, T, H, W)
     with torch.no_grad():
-        st = net.stream(batch_size=1, graph=False, skinny_gemm=skinny_gemm)
+        st = net.stream(batch_size=1, graph=False, skinny_gemm=skinny_gemm, cache_dtype=cache_dtype)
         for _ in range(KPROF_WARMUP + KPROF_STEPS):
             st.frames_done = T - 1
             st.step(rgb[:, :, T - 1:T], qm[:, :, T - 1:T])
         torch.cuda.synchronize()
 
 
-def kstats(trace_csv, out, precision='bf16', skinny_gemm=None):
+def kstats(trace_csv, out, precision='bf16', skinny_gemm=None, cache_dtype=None):
     """Per-step kernel breakdown of the KPROF_STEPS profiled steps from rocprofv3's kernel-trace CSV: dispatches in start order, everything up to
     and including the KPROF_WARMUP-th STEP_LAST_KERNEL dropped, per-kernel totals divided by KPROF_STEPS."""
     import csv
@@ -315,8 +380,8 @@ def kstats(trace_csv, out, precision='bf16', skinny_gemm=None):
         n, tot, mn = per.get(r['Kernel_Name'], (0, 0, None))
         per[r['Kernel_Name']] = (n + 1, tot + d, d if mn is None else min(mn, d))
     T, H, W = CONFIGS['configs3']
-    alg = cached_kernel_bytes(T, H, W, e=2 if precision in ('bf16', 'fp16') else 4)
-    flag = '' if skinny_gemm is None else f", skinny_gemm={'on' if skinny_gemm else 'off'}"
+    alg = cached_kernel_bytes(T, H, W, e=2 if precision in ('bf16', 'fp16') else 4, ce={None: None, 'bf16': 2, 'fp8': 1}[cache_dtype])
+    flag = ('' if skinny_gemm is None else f", skinny_gemm={'on' if skinny_gemm else 'off'}") + ('' if cache_dtype is None else f', cache_dtype={cache_dtype}')
     lines = [f'# {KPROF_STEPS} one-frame {precision} stream steps at BASELINE configs[3] (T=60, 480x640, B=1), t0 = 59{flag}, after {KPROF_WARMUP} warm-up steps',
              '# (rocprofv3 --kernel-trace; tools/dev_stream_latency.py --kprof, then --kstats on the kernel-trace CSV: the warm-up dispatches are dropped)',
              '#   us/step  launches/step   avg us   min us  kernel']
@@ -348,16 +413,26 @@ def main():
     ap.add_argument('--kstats', default=None, metavar='KERNEL_TRACE_CSV')
     ap.add_argument('--precision', default='bf16', help="precision of the --skinny, --kprof and --kstats legs ('bf16' or 'bf16x3')")
     ap.add_argument('--skinny-gemm', default=None, choices=['on', 'off'], help='the skinny_gemm keyword of the --kprof steps (default: the stream default)')
-    ap.add_argument('--only', default=None, help='comma list of configs1_b1, configs1_b8, configs3_b1')
+    ap.add_argument('--cache-dtype', default=None, help="comma list of 'bf16' / 'fp8': the compact-cache leg against cache_dtype=None; one value with "
+                                                        '--kprof / --kstats')
+    ap.add_argument('--only', default=None, help='comma list of configs1_b1, configs1_b8, configs3_b1 (--cache-dtype: also configs1_b1_long)')
     a = ap.parse_args()
     flag = None if a.skinny_gemm is None else a.skinny_gemm == 'on'
     if a.kstats:
-        kstats(a.kstats, a.out, a.precision, flag)
+        kstats(a.kstats, a.out, a.precision, flag, a.cache_dtype)
         return
     if not torch.cuda.is_available():
         raise SystemExit('dev_stream_latency.py needs a GPU')
     if a.kprof:
-        kprof(a.precision, flag)
+        kprof(a.precision, flag, a.cache_dtype)
+        return
+    if a.cache_dtype:
+        out = {'device': torch.cuda.get_device_name(0),
+               'cache_dtype': cache_leg(a.reps, a.precision, a.cache_dtype.split(','), set(a.only.split(',')) if a.only else None)}
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, 'w') as f:
+                json.dump(out, f, indent=1)
         return
     if a.pool:
         out = {'device': torch.cuda.get_device_name(0), 'pool': pool_leg(a.reps)}

@@ -1,14 +1,14 @@
-// Streaming inference (tcow_amd/stream.py): temporal attention of a chunk of c new frames against a per-block K/V cache of the frames before
+// Streaming inference (tcow_amd/stream.py): temporal attention of a chunk of c new frames against a per-block K / V cache of the frames before
 // it, and the cls-row bookkeeping of causal_attention == 1 across chunks.  Replaces, for a stream, the temporal core of Attention.forward
-// (vit.py:88-109 with the tril() mask of vit.py:93-99) and the frame-0 cls broadcast of vit.py:189-198,215.
+// (vit.py:88-109 with the tril() mask of vit.py:93-99) and the frame-0 cls broadcast of vit.py:189-198,215.  This file has the per-frame body,
+// the kernels and the launchers; what a cache element is and where a key lives is attention_stream_cache.h.
 //
-// tcow_attn_temporal_cached_fwd: one wave per (clip b, slot s, head h); four waves per workgroup.  The head's 64 channels of a K / V row
-// are one 128-byte (16-bit) or 256-byte (f32) line: LPR lanes read it with one 16-byte load each, so a wave covers G = 64 / LPR key rows per
-// load (16-bit: 8 lanes x 8 elements, 8 rows; f32: 16 lanes x 4, 4 rows).  Lane group g walks keys g, g + G, ... with its own online
-// softmax (scores reduced over the group's lanes by xor shuffles), ST_U batches of G rows in flight per wave; the G partial states are merged
-// by xor shuffles at the end.  No LDS.  The cache of (b, s, h) is one contiguous [T_total, 64] block ([B, S-1, heads, T_total, 64]), so a
-// pass over it is a run of whole lines.  Keys of frames < t0 come from the cache, keys of the chunk's own frames from the chunk's qkv
-// rows; the same wave copies the chunk's K / V rows into cache positions t0 .. t0+c-1 (nothing reads them in this launch).
+// tcow_attn_temporal_cached_fwd: one wave per (clip b, slot s, head h); four waves per workgroup.  A wave covers G key rows per load (lines and
+// lane groups: the header).  Lane group g walks keys g, g + G, ... with its own online softmax (scores reduced over the group's lanes by xor
+// shuffles), ST_U batches of G rows in flight per wave; the G partial states are merged by xor shuffles at the end.  No LDS.  The cache of
+// (b, s, h) is one contiguous [T_total, 64] block ([B, S-1, heads, T_total, 64]), so a pass over it is a run of whole lines.  Keys of frames < t0
+// come from the cache, keys of the chunk's own frames from the chunk's qkv rows; the same wave copies the chunk's K / V rows into cache positions
+// t0 .. t0+c-1 (nothing reads them in this launch).
 //
 // tcow_attn_temporal_pool_fwd / tcow_cls_pool (a pool of live sessions, SeekerStreamPool): the same two kernels with a t0 and a cache slot per
 // row.  Row r reads t0_rows[r * t0_stride] and works on cache block slot_rows[r]; a stream is the case "t0 broadcast (stride 0), slot = b
@@ -23,139 +23,19 @@
 // cached key lives is all that differs: temporal_query_frame takes that as a small functor (ContiguousKeys / PagedKeys), so the four kernels
 // keep one body and agree bit for bit.
 //
-// Compact cache (the *_cq entry points): the cache element type C is a second template parameter next to the storage type T.  C == T is the
-// path above, its code unchanged.  Otherwise (16-bit -> fp8, f32 -> the build's 16-bit type, f32 -> fp8; fp8 = OCP e4m3fn, saturating) the
-// append stores rnd_C(k), rnd_C(v) once and EVERY key and value enters the arithmetic at its rounded value: a batch of keys is gathered as
-// cache words -- cached lines loaded, the chunk's own lines (read from the step's qkv rows) encoded -- and decoded where it is used, so a key
-// has one value wherever it came from and outputs and caches do not depend on how the frames were split into chunks.  q is not rounded.  A lane
-// keeps the storage type's channel slice (8 or 4 channels: 8 or 4 bytes of a cache line) and the key order is that of the uncompacted kernel;
-// CacheVec is all that knows C.  Measured ("Compact cache"): the kernels are bound by issued instructions and by waves in
+// Compact cache (the *_cq entry points, cache element type C != storage type T): a batch of keys is gathered as cache words -- cached lines
+// loaded, the chunk's own lines (read from the step's qkv rows) encoded -- and decoded where it is used; the key order is that of the C == T
+// path, whose code is unchanged.  Measured ("Compact cache"): the kernels are bound by issued instructions and by waves in
 // flight, not by HBM, so what pays is gathering words (16 instead of 64 registers while the loads fly: 127 VGPRs and four waves per SIMD for
 // 16-bit -> fp8, where decoding at the load took 136 and three) and a branch-free loop over the batches that lie wholly in the cache.
 #include <math.h>
 
-#include <type_traits>
-
-#include "attention_common.h"
+#include "attention_stream_cache.h"
 
 namespace {
 
 constexpr int ST_WAVES = 4;     // waves (items) per workgroup
 constexpr int ST_U = 4;         // batches of G key rows loaded before they are used
-
-template <typename T> struct StreamVec;
-template <> struct StreamVec<bf16_t> {
-    static constexpr int VEC = 8;
-    static __device__ __forceinline__ void ld(const bf16_t* p, float* v) {
-        const uint4 u = *reinterpret_cast<const uint4*>(p);
-        v[0] = bflo(u.x); v[1] = bfhi(u.x); v[2] = bflo(u.y); v[3] = bfhi(u.y);
-        v[4] = bflo(u.z); v[5] = bfhi(u.z); v[6] = bflo(u.w); v[7] = bfhi(u.w);
-    }
-    static __device__ __forceinline__ void st(bf16_t* p, const float* v) {
-        uint4 u;
-        u.x = pack_bf2(v[0], v[1]); u.y = pack_bf2(v[2], v[3]); u.z = pack_bf2(v[4], v[5]); u.w = pack_bf2(v[6], v[7]);
-        *reinterpret_cast<uint4*>(p) = u;
-    }
-};
-template <> struct StreamVec<float> {
-    static constexpr int VEC = 4;
-    static __device__ __forceinline__ void ld(const float* p, float* v) {
-        const float4 f = *reinterpret_cast<const float4*>(p);
-        v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
-    }
-    static __device__ __forceinline__ void st(float* p, const float* v) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
-};
-
-__device__ __forceinline__ void copy16(void* dst, const void* src) { *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src); }
-
-// ---- compact cache elements.  fp8_t: one OCP e4m3fn byte (gfx950's v_cvt_pk_fp8_f32 / v_cvt_pk_f32_fp8).
-struct fp8_t { uint8_t b; };
-
-// f32 -> e4m3fn as torch's x.clamp(-448, 448).to(torch.float8_e4m3fn): saturating, round to nearest even, subnormals kept, NaN -> 0x7f | sign.
-// The clamp is one v_med3_f32, which does not keep a NaN: a NaN's byte is set after the conversion, so what the instruction makes of a NaN
-// never shows.  Four values -> four bytes, v[0] in the lowest; a NaN among them is rare and handled on a branch of its own.
-__device__ __forceinline__ float fp8_clamp(float x) { return __builtin_amdgcn_fmed3f(x, -448.f, 448.f); }
-__device__ __forceinline__ uint32_t pack_fp8x4(const float* v) {
-    int w = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_clamp(v[0]), fp8_clamp(v[1]), 0, false);
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(fp8_clamp(v[2]), fp8_clamp(v[3]), w, true);
-    uint32_t u = (uint32_t)w;
-    if (__builtin_expect(v[0] != v[0] || v[1] != v[1] || v[2] != v[2] || v[3] != v[3], 0)) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (v[e] != v[e]) u = (u & ~(0xffu << (8 * e))) | ((0x7fu | ((__float_as_uint(v[e]) >> 24) & 0x80u)) << (8 * e));
-    }
-    return u;
-}
-__device__ __forceinline__ void unpack_fp8x4(uint32_t w, float* v) {
-    const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = hi[0]; v[3] = hi[1];
-}
-
-// A lane's StreamVec<T>::VEC channels of a cache line of C elements as a Raw word: ld from the cache, enc from f32 (what the append stores, and
-// what a chunk's own key / value becomes before it is used), dec to f32, zero (decodes to 0).  A key therefore has ONE value, dec of its Raw,
-// wherever it was read from.  Storage T, cache C; CacheVec<T, T> is never asked (C == T copies bits).
-template <typename T, typename C> struct CacheVec;
-template <> struct CacheVec<bf16_t, fp8_t> {           // 8 channels: 8 bytes
-    typedef uint2 Raw;
-    static __device__ __forceinline__ Raw ld(const fp8_t* p) { return *reinterpret_cast<const uint2*>(p); }
-    static __device__ __forceinline__ void st(fp8_t* p, Raw r) { *reinterpret_cast<uint2*>(p) = r; }
-    static __device__ __forceinline__ Raw enc(const float* v) { return make_uint2(pack_fp8x4(v), pack_fp8x4(v + 4)); }
-    static __device__ __forceinline__ void dec(Raw r, float* v) { unpack_fp8x4(r.x, v); unpack_fp8x4(r.y, v + 4); }
-    static __device__ __forceinline__ Raw zero() { return make_uint2(0u, 0u); }
-};
-template <> struct CacheVec<float, fp8_t> {            // 4 channels: 4 bytes
-    typedef uint32_t Raw;
-    static __device__ __forceinline__ Raw ld(const fp8_t* p) { return *reinterpret_cast<const uint32_t*>(p); }
-    static __device__ __forceinline__ void st(fp8_t* p, Raw r) { *reinterpret_cast<uint32_t*>(p) = r; }
-    static __device__ __forceinline__ Raw enc(const float* v) { return pack_fp8x4(v); }
-    static __device__ __forceinline__ void dec(Raw r, float* v) { unpack_fp8x4(r, v); }
-    static __device__ __forceinline__ Raw zero() { return 0u; }
-};
-template <> struct CacheVec<float, bf16_t> {           // 4 channels of the build's 16-bit type: 8 bytes
-    typedef uint2 Raw;
-    static __device__ __forceinline__ Raw ld(const bf16_t* p) { return *reinterpret_cast<const uint2*>(p); }
-    static __device__ __forceinline__ void st(bf16_t* p, Raw r) { *reinterpret_cast<uint2*>(p) = r; }
-    static __device__ __forceinline__ Raw enc(const float* v) { return make_uint2(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])); }
-    static __device__ __forceinline__ void dec(Raw r, float* v) { v[0] = bflo(r.x); v[1] = bfhi(r.x); v[2] = bflo(r.y); v[3] = bfhi(r.y); }
-    static __device__ __forceinline__ Raw zero() { return make_uint2(0u, 0u); }
-};
-
-// the lane's slice of a row of the step's qkv, rounded to C
-template <typename T, typename C> __device__ __forceinline__ typename CacheVec<T, C>::Raw encode_line(const T* src) {
-    float v[StreamVec<T>::VEC];
-    StreamVec<T>::ld(src, v);
-    return CacheVec<T, C>::enc(v);
-}
-
-// cache[position] = the lane's slice of a chunk row's K or V: bit copy when the cache has the storage type, else rounded to C once
-template <typename T, typename C> __device__ __forceinline__ void append_line(C* dst, const T* src) {
-    if constexpr (std::is_same_v<T, C>) {
-        copy16(dst, src);
-    } else {
-        CacheVec<T, C>::st(dst, encode_line<T, C>(src));
-    }
-}
-
-// Where cache position kt of the wave's (session, token slot, head) lives in a block's K / V array `base` (const or not): the address of the
-// lane's 16 bytes of that line.  The one thing in which the contiguous and the paged kernels differ.  In two steps: page(kt), which EVERY lane
-// of the wave calls together (a paged lookup may be a lane shuffle), then keys(base, page, kt) by the lanes that load or store.
-struct ContiguousKeys {             // [slots, S-1, heads, T_total, 64]: one run of whole lines from cbase (the lane's channel slice included)
-    struct NoPage {};
-    size_t cbase;
-    __device__ __forceinline__ NoPage page(int) const { return NoPage{}; }
-    template <typename P> __device__ __forceinline__ P operator()(P base, NoPage, int kt) const { return base + cbase + (size_t)kt * ATT_HD; }
-};
-struct PagedKeys {                  // [n_pages, S-1, heads, P, 64], P = 1 << lgP: page pages[kt / P], line kt % P of the (slot, head) run at `line`
-    const int* pages;               // the session's row of the page table (entries 0 .. kt / P checked by the caller)
-    size_t page_stride, line;       // (S-1) * heads * P * 64; ((s-1) * heads + h) * P * 64 + the lane's channel slice
-    int lgP;
-    int mine;                       // pages[lane], as the caller's check loaded it (lanes beyond the last checked entry: anything)
-    bool wide;                      // the wave's keys reach entries >= 64: more entries than lanes, look them up in memory
-    __device__ __forceinline__ int page(int kt) const { return wide ? pages[kt >> lgP] : __shfl(mine, kt >> lgP, 64); }
-    template <typename P> __device__ __forceinline__ P operator()(P base, int pg, int kt) const {
-        return base + ((size_t)pg * page_stride + line + (size_t)(kt & ((1 << lgP) - 1)) * ATT_HD);
-    }
-};
 
 // One query frame of a temporal stream step, shared by every kernel of this file so that they agree bit for bit: chunk frame j (flat frame
 // fb + j of the step's rows, fb = the chunk's first flat frame) stands at t = t0 + j and attends to keys 0 .. t, keys < t0 from the cache at
@@ -491,22 +371,7 @@ __global__ void cls_ragged_kernel(int n, int F, int S, int D, float* __restrict_
     cls_session(slot, n_slots, t0_rows[r], x + (size_t)first * S * D + ch, c, (size_t)S * D, cls_cache, (size_t)slot * D + ch);
 }
 
-// What the temporal launchers ask of their arguments: a step of s.T >= 1 frames per row, head_dim 64, a causal mask, a stream of
-// T_min .. TCOW_STREAM_MAX_FRAMES frames, a storage type of this file, at least one cache slot, and a cache element type `cq` that is one of the
-// three and no wider than the storage (the entry points without a cache_dtype pass the storage type itself).
-int check_temporal_args(const char* who, const tcow_attn_shape& s, int T_min, int T_total, int n_slots, int cq) {
-    TCOW_CHECK_ARG(s.B > 0 && s.T > 0 && s.S > 1 && s.heads > 0, "%s: bad step shape B=%d T=%d S=%d heads=%d", who, s.B, s.T, s.S, s.heads);
-    TCOW_CHECK_ARG(s.D == s.heads * ATT_HD, "%s: head_dim must be 64 (D=%d heads=%d)", who, s.D, s.heads);
-    TCOW_CHECK_ARG(s.causal == 1 || s.causal == 2, "%s: causal must be 1 or 2 (got %d): other masks let a frame see later frames", who, s.causal);
-    TCOW_CHECK_ARG(T_total >= T_min && T_total <= TCOW_STREAM_MAX_FRAMES, "%s: T_total=%d must be in [%d, %d]", who, T_total, T_min, TCOW_STREAM_MAX_FRAMES);
-    TCOW_CHECK_ARG(s.dtype == TCOW_F32 || s.dtype == TCOW_BF16, "%s: dtype must be TCOW_F32 or TCOW_BF16 (got %d)", who, s.dtype);
-    TCOW_CHECK_ARG(n_slots >= 1, "%s: n_slots=%d must be >= 1", who, n_slots);
-    TCOW_CHECK_ARG(cq == TCOW_F32 || cq == TCOW_BF16 || cq == TCOW_FP8E4M3, "%s: cache_dtype must be TCOW_F32, TCOW_BF16 or TCOW_FP8E4M3 (got %d)", who, cq);
-    TCOW_CHECK_ARG(!(s.dtype == TCOW_BF16 && cq == TCOW_F32), "%s: cache_dtype TCOW_F32 is wider than the 16-bit storage (dtype TCOW_BF16)", who);
-    return TCOW_OK;
-}
-
-// Calls f(T{}, C{}) with the storage type T of `dtype` and the cache element type C of `cq` (both checked by check_temporal_args).
+// Calls f(T{}, C{}) with the storage type T of `dtype` and the cache element type C of `cq` (both checked by launch_temporal).
 template <typename F> void with_cache_types(int dtype, int cq, F f) {
     if (dtype == TCOW_BF16) {
         if (cq == TCOW_FP8E4M3) f(bf16_t{}, fp8_t{}); else f(bf16_t{}, bf16_t{});
@@ -515,67 +380,80 @@ template <typename F> void with_cache_types(int dtype, int cq, F f) {
     }
 }
 
-// Argument checks and launch of temporal_cached_kernel, shared by the stream (t0 broadcast, slot = b) and the pool entry points.
+// The frame of the three temporal launchers.  What it asks of every step: a shape of s.T >= 1 frames per row, head_dim 64, a causal mask, a
+// stream of T_min .. TCOW_STREAM_MAX_FRAMES frames (a chunk of s.B rows must fit into the cache: T_min = s.T; the F frames of a ragged step
+// belong to several sessions and may exceed T_total: T_min = 1), a storage type of this file, at least one cache slot, and a cache element
+// type `cq` that is one of the three and no wider than the storage (the entry points without a cache_dtype pass the storage type itself);
+// of a ragged step of n sessions also its one row of F frames.  Then the launcher's own checks, own(), and launch(T{}, C{}, grid, block, s) on
+// one wave per item: (row, slot, head), ragged (flat frame, slot, head).
+template <typename Own, typename Launch>
+int launch_temporal(const char* who, const tcow_attn_shape* shape, bool ragged, int n, int T_total, int n_slots, int cq, Own own, Launch launch) {
+    TCOW_CHECK_ARG(shape != nullptr, "%s: null shape", who);
+    const tcow_attn_shape& s = *shape;
+    TCOW_CHECK_ARG(s.B > 0 && s.T > 0 && s.S > 1 && s.heads > 0, "%s: bad step shape B=%d T=%d S=%d heads=%d", who, s.B, s.T, s.S, s.heads);
+    TCOW_CHECK_ARG(s.D == s.heads * ATT_HD, "%s: head_dim must be 64 (D=%d heads=%d)", who, s.D, s.heads);
+    TCOW_CHECK_ARG(s.causal == 1 || s.causal == 2, "%s: causal must be 1 or 2 (got %d): other masks let a frame see later frames", who, s.causal);
+    const int T_min = ragged ? 1 : s.T;
+    TCOW_CHECK_ARG(T_total >= T_min && T_total <= TCOW_STREAM_MAX_FRAMES, "%s: T_total=%d must be in [%d, %d]", who, T_total, T_min, TCOW_STREAM_MAX_FRAMES);
+    TCOW_CHECK_ARG(s.dtype == TCOW_F32 || s.dtype == TCOW_BF16, "%s: dtype must be TCOW_F32 or TCOW_BF16 (got %d)", who, s.dtype);
+    TCOW_CHECK_ARG(n_slots >= 1, "%s: n_slots=%d must be >= 1", who, n_slots);
+    TCOW_CHECK_ARG(cq == TCOW_F32 || cq == TCOW_BF16 || cq == TCOW_FP8E4M3, "%s: cache_dtype must be TCOW_F32, TCOW_BF16 or TCOW_FP8E4M3 (got %d)", who, cq);
+    TCOW_CHECK_ARG(!(s.dtype == TCOW_BF16 && cq == TCOW_F32), "%s: cache_dtype TCOW_F32 is wider than the 16-bit storage (dtype TCOW_BF16)", who);
+    TCOW_CHECK_ARG(!ragged || (s.B == 1 && n > 0 && n <= s.T), "%s: a ragged step is one row of F frames of 1 <= n <= F sessions (B=%d F=%d n=%d)", who,
+                   s.B, s.T, n);
+    if (const int err = own()) return err;
+    const long items = (long)(ragged ? s.T : s.B) * s.S * s.heads;
+    const dim3 grid((unsigned)cdiv(items, ST_WAVES)), block(64 * ST_WAVES);
+    with_cache_types(s.dtype, cq, [&](auto t, auto c) { launch(t, c, grid, block, s); });
+    TCOW_CHECK_LAUNCH();
+    return TCOW_OK;
+}
+
+// temporal_cached_kernel, for the stream (t0 broadcast, slot = b) and the pool entry points
 int launch_temporal_cached(const char* who, void* stream, const tcow_attn_shape* chunk, int T_total, int n_slots, const int* t0_rows, int t0_stride,
                            const int* slot_rows, const void* qkv, void* k_cache, void* v_cache, void* out, int cq) {
-    TCOW_CHECK_ARG(chunk != nullptr, "%s: null shape", who);
-    const tcow_attn_shape& s = *chunk;
-    if (const int err = check_temporal_args(who, s, s.T, T_total, n_slots, cq)) return err;    // (the cache holds the chunk: T_total >= c)
-    TCOW_CHECK_ARG(t0_rows && qkv && k_cache && v_cache && out, "%s: null pointer", who);
-    const long items = (long)s.B * s.S * s.heads;
-    const dim3 grid((unsigned)cdiv(items, ST_WAVES)), block(64 * ST_WAVES);
-    with_cache_types(s.dtype, cq, [&](auto t, auto c) {
+    return launch_temporal(who, chunk, false, 0, T_total, n_slots, cq, [&]() -> int {
+        TCOW_CHECK_ARG(t0_rows && qkv && k_cache && v_cache && out, "%s: null pointer", who);
+        return TCOW_OK;
+    }, [&](auto t, auto c, dim3 grid, dim3 block, const tcow_attn_shape& s) {
         using T = decltype(t); using C = decltype(c);
         hipLaunchKernelGGL((temporal_cached_kernel<T, C>), grid, block, 0, (hipStream_t)stream, s.B, s.T, s.S, s.D, s.heads, T_total, n_slots, t0_rows,
                            t0_stride, slot_rows, (const T*)qkv, (C*)k_cache, (C*)v_cache, (T*)out);
     });
-    TCOW_CHECK_LAUNCH();
-    return TCOW_OK;
 }
 
 int launch_temporal_ragged(const char* who, void* stream, const tcow_attn_shape* step, int n, int T_total, int n_slots, const int* t0_rows,
                            const int* slot_rows, const int* first_rows, const int* c_rows, const int* row_of_frame, const void* qkv, void* k_cache,
                            void* v_cache, void* out, int cq) {
-    TCOW_CHECK_ARG(step != nullptr, "%s: null shape", who);
-    const tcow_attn_shape& s = *step;
-    if (const int err = check_temporal_args(who, s, 1, T_total, n_slots, cq)) return err;      // (F counts the frames of all sessions: it may exceed T_total)
-    TCOW_CHECK_ARG(s.B == 1 && n > 0 && n <= s.T, "%s: a ragged step is one row of F frames of 1 <= n <= F sessions (B=%d F=%d n=%d)", who, s.B, s.T, n);
-    TCOW_CHECK_ARG(t0_rows && slot_rows && first_rows && c_rows && row_of_frame && qkv && k_cache && v_cache && out, "%s: null pointer", who);
-    const long items = (long)s.T * s.S * s.heads;
-    const dim3 grid((unsigned)cdiv(items, ST_WAVES)), block(64 * ST_WAVES);
-    with_cache_types(s.dtype, cq, [&](auto t, auto c) {
+    return launch_temporal(who, step, true, n, T_total, n_slots, cq, [&]() -> int {
+        TCOW_CHECK_ARG(t0_rows && slot_rows && first_rows && c_rows && row_of_frame && qkv && k_cache && v_cache && out, "%s: null pointer", who);
+        return TCOW_OK;
+    }, [&](auto t, auto c, dim3 grid, dim3 block, const tcow_attn_shape& s) {
         using T = decltype(t); using C = decltype(c);
         hipLaunchKernelGGL((temporal_ragged_kernel<T, C>), grid, block, 0, (hipStream_t)stream, n, s.T, s.S, s.D, s.heads, T_total, n_slots, t0_rows,
                            slot_rows, first_rows, c_rows, row_of_frame, (const T*)qkv, (C*)k_cache, (C*)v_cache, (T*)out);
     });
-    TCOW_CHECK_LAUNCH();
-    return TCOW_OK;
 }
 
+// (pages, not slots: the frame's n_slots check is given 1, and n_pages is checked here)
 int launch_temporal_ragged_paged(const char* who, void* stream, const tcow_attn_shape* step, int n, int T_total, int n_pages, int page_frames,
                                  int pages_per_session, const int* t0_rows, const int* page_rows, const int* first_rows, const int* c_rows,
                                  const int* row_of_frame, const void* qkv, void* k_pages, void* v_pages, void* out, int cq) {
-    TCOW_CHECK_ARG(step != nullptr, "%s: null shape", who);
-    const tcow_attn_shape& s = *step;
-    if (const int err = check_temporal_args(who, s, 1, T_total, 1, cq)) return err;            // (pages, not slots: n_pages is checked below)
-    TCOW_CHECK_ARG(s.B == 1 && n > 0 && n <= s.T, "%s: a ragged step is one row of F frames of 1 <= n <= F sessions (B=%d F=%d n=%d)", who, s.B, s.T, n);
-    TCOW_CHECK_ARG(page_frames >= 1 && page_frames <= TCOW_STREAM_MAX_FRAMES && (page_frames & (page_frames - 1)) == 0,
-                   "%s: page_frames=%d must be a power of two in [1, %d]", who, page_frames, TCOW_STREAM_MAX_FRAMES);
-    TCOW_CHECK_ARG(n_pages >= 1, "%s: n_pages=%d must be >= 1", who, n_pages);
-    TCOW_CHECK_ARG(pages_per_session >= 1 && (long)pages_per_session * page_frames >= T_total,
-                   "%s: pages_per_session=%d x page_frames=%d does not cover T_total=%d", who, pages_per_session, page_frames, T_total);
-    TCOW_CHECK_ARG(t0_rows && page_rows && first_rows && c_rows && row_of_frame && qkv && k_pages && v_pages && out, "%s: null pointer", who);
-    int lgP = 0;
-    while ((1 << lgP) < page_frames) ++lgP;
-    const long items = (long)s.T * s.S * s.heads;
-    const dim3 grid((unsigned)cdiv(items, ST_WAVES)), block(64 * ST_WAVES);
-    with_cache_types(s.dtype, cq, [&](auto t, auto c) {
+    return launch_temporal(who, step, true, n, T_total, 1, cq, [&]() -> int {
+        TCOW_CHECK_ARG(page_frames >= 1 && page_frames <= TCOW_STREAM_MAX_FRAMES && (page_frames & (page_frames - 1)) == 0,
+                       "%s: page_frames=%d must be a power of two in [1, %d]", who, page_frames, TCOW_STREAM_MAX_FRAMES);
+        TCOW_CHECK_ARG(n_pages >= 1, "%s: n_pages=%d must be >= 1", who, n_pages);
+        TCOW_CHECK_ARG(pages_per_session >= 1 && (long)pages_per_session * page_frames >= T_total,
+                       "%s: pages_per_session=%d x page_frames=%d does not cover T_total=%d", who, pages_per_session, page_frames, T_total);
+        TCOW_CHECK_ARG(t0_rows && page_rows && first_rows && c_rows && row_of_frame && qkv && k_pages && v_pages && out, "%s: null pointer", who);
+        return TCOW_OK;
+    }, [&](auto t, auto c, dim3 grid, dim3 block, const tcow_attn_shape& s) {
         using T = decltype(t); using C = decltype(c);
+        int lgP = 0;
+        while ((1 << lgP) < page_frames) ++lgP;
         hipLaunchKernelGGL((temporal_ragged_paged_kernel<T, C>), grid, block, 0, (hipStream_t)stream, n, s.T, s.S, s.D, s.heads, T_total, n_pages, lgP,
                            pages_per_session, t0_rows, page_rows, first_rows, c_rows, row_of_frame, (const T*)qkv, (C*)k_pages, (C*)v_pages, (T*)out);
     });
-    TCOW_CHECK_LAUNCH();
-    return TCOW_OK;
 }
 
 int launch_cls(const char* who, void* stream, int B, int c, int S, int D, float* x, float* cls_cache, int n_slots, const int* t0_rows, int t0_stride,

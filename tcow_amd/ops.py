@@ -364,19 +364,24 @@ def _cache_dtype(who, mode, cache_dtype, k_cache, v_cache):
     return cq
 
 
+def _stream_attn_call(lib, name, mode, cache_dtype, k_cache, v_cache, args):
+    """The call of the four attn_temporal_* wrappers: entry point `name` (tcow_attn_temporal_*_fwd) on `args` when cache_dtype is None, else its
+    compact-cache twin (..._cq_fwd) on `args` and the checked cache_dtype.  Errors of the library carry the name of the symbol that was called,
+    those of the cache_dtype check the wrapper's (the symbol without 'tcow_' and '_fwd')."""
+    if cache_dtype is not None:
+        args += (_cache_dtype(name[5:-4], mode, cache_dtype, k_cache, v_cache),)
+        name = name[:-4] + '_cq_fwd'
+    L.check(getattr(lib, name)(_stream(), *args), name, lib)
+
+
 def attn_temporal_cached(mode, B, c, S, D, heads, causal, T_total, t0_dev, qkv, k_cache, v_cache, out, cache_dtype=None):
     """Temporal attention of a c-frame chunk (qkv [B*c*S, 3D] -> out [B*c*S, D]) against the K / V cache [B, S-1, heads, T_total, 64] of the
     frames before t0 = t0_dev[0] (int32 device scalar); appends the chunk's K / V at t0 (see tcow_attn_temporal_cached_fwd).
     cache_dtype (here and in the three wrappers below): None = caches in the storage type; F32 / BF16 / FP8 = the compact-cache entry point
     (tcow_attn_temporal_*_cq_fwd) on caches of that element type, every key and value taken at its value rounded to it."""
     lib, sh = _stream_attn(mode, B, c, S, D, heads, causal, qkv, k_cache, v_cache, out, t0_dev)
-    if cache_dtype is not None:
-        cq = _cache_dtype('attn_temporal_cached', mode, cache_dtype, k_cache, v_cache)
-        L.check(lib.tcow_attn_temporal_cached_cq_fwd(_stream(), sh, int(T_total), t0_dev.data_ptr(), qkv.data_ptr(), k_cache.data_ptr(),
-                                                     v_cache.data_ptr(), out.data_ptr(), cq), 'tcow_attn_temporal_cached_cq_fwd', lib)
-        return out
-    L.check(lib.tcow_attn_temporal_cached_fwd(_stream(), sh, int(T_total), t0_dev.data_ptr(), qkv.data_ptr(), k_cache.data_ptr(),
-                                              v_cache.data_ptr(), out.data_ptr()), 'tcow_attn_temporal_cached_fwd', lib)
+    _stream_attn_call(lib, 'tcow_attn_temporal_cached_fwd', mode, cache_dtype, k_cache, v_cache,
+                      (sh, int(T_total), t0_dev.data_ptr(), qkv.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr()))
     return out
 
 
@@ -390,13 +395,9 @@ def attn_temporal_pool(mode, n, c, S, D, heads, causal, T_total, n_slots, t0_row
     """attn_temporal_cached for n rows that stand at different frames: row r attends at t0_rows[r] against block slot_rows[r] of the caches
     [n_slots, S-1, heads, T_total, 64] and appends there (int32 device tensors [n]; distinct slots -- see tcow_attn_temporal_pool_fwd)."""
     lib, sh = _stream_attn(mode, n, c, S, D, heads, causal, qkv, k_cache, v_cache, out, t0_rows, slot_rows)
-    if cache_dtype is not None:
-        cq = _cache_dtype('attn_temporal_pool', mode, cache_dtype, k_cache, v_cache)
-        L.check(lib.tcow_attn_temporal_pool_cq_fwd(_stream(), sh, int(T_total), int(n_slots), t0_rows.data_ptr(), slot_rows.data_ptr(), qkv.data_ptr(),
-                                                   k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(), cq), 'tcow_attn_temporal_pool_cq_fwd', lib)
-        return out
-    L.check(lib.tcow_attn_temporal_pool_fwd(_stream(), sh, int(T_total), int(n_slots), t0_rows.data_ptr(), slot_rows.data_ptr(), qkv.data_ptr(),
-                                            k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr()), 'tcow_attn_temporal_pool_fwd', lib)
+    _stream_attn_call(lib, 'tcow_attn_temporal_pool_fwd', mode, cache_dtype, k_cache, v_cache,
+                      (sh, int(T_total), int(n_slots), t0_rows.data_ptr(), slot_rows.data_ptr(), qkv.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                       out.data_ptr()))
     return out
 
 
@@ -420,6 +421,12 @@ def _ragged_tables(who, n, F, t0_rows, slot_rows, first_rows, c_rows, row_of_fra
                               f'{t.dtype} {tuple(t.shape)}')
 
 
+def _ragged_rows(who, F, S, qkv, out):
+    """The rows of a ragged attention step: all F frames of all sessions, flat."""
+    if qkv.shape[0] != F * S or out.shape[0] != F * S:
+        raise L.TcowError(f'{who}: qkv / out must have F * S = {F * S} rows, got {qkv.shape[0]} / {out.shape[0]}')
+
+
 def attn_temporal_ragged(mode, n, F, S, D, heads, causal, T_total, n_slots, t0_rows, slot_rows, first_rows, c_rows, row_of_frame, qkv, k_cache, v_cache,
                          out, cache_dtype=None):
     """attn_temporal_pool for n sessions that bring different numbers of frames: session r owns the flat frames first_rows[r] .. + c_rows[r] - 1 of
@@ -427,17 +434,10 @@ def attn_temporal_ragged(mode, n, F, S, D, heads, causal, T_total, n_slots, t0_r
     frame, bit-identical per session to attn_temporal_pool (see tcow_attn_temporal_ragged_fwd)."""
     lib, sh = _stream_attn(mode, 1, F, S, D, heads, causal, qkv, k_cache, v_cache, out)
     _ragged_tables('attn_temporal_ragged', n, F, t0_rows, slot_rows, first_rows, c_rows, row_of_frame)
-    if qkv.shape[0] != F * S or out.shape[0] != F * S:
-        raise L.TcowError(f'attn_temporal_ragged: qkv / out must have F * S = {F * S} rows, got {qkv.shape[0]} / {out.shape[0]}')
-    if cache_dtype is not None:
-        cq = _cache_dtype('attn_temporal_ragged', mode, cache_dtype, k_cache, v_cache)
-        L.check(lib.tcow_attn_temporal_ragged_cq_fwd(_stream(), sh, int(n), int(T_total), int(n_slots), t0_rows.data_ptr(), slot_rows.data_ptr(),
-                                                     first_rows.data_ptr(), c_rows.data_ptr(), row_of_frame.data_ptr(), qkv.data_ptr(),
-                                                     k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(), cq), 'tcow_attn_temporal_ragged_cq_fwd', lib)
-        return out
-    L.check(lib.tcow_attn_temporal_ragged_fwd(_stream(), sh, int(n), int(T_total), int(n_slots), t0_rows.data_ptr(), slot_rows.data_ptr(),
-                                              first_rows.data_ptr(), c_rows.data_ptr(), row_of_frame.data_ptr(), qkv.data_ptr(), k_cache.data_ptr(),
-                                              v_cache.data_ptr(), out.data_ptr()), 'tcow_attn_temporal_ragged_fwd', lib)
+    _ragged_rows('attn_temporal_ragged', F, S, qkv, out)
+    _stream_attn_call(lib, 'tcow_attn_temporal_ragged_fwd', mode, cache_dtype, k_cache, v_cache,
+                      (sh, int(n), int(T_total), int(n_slots), t0_rows.data_ptr(), slot_rows.data_ptr(), first_rows.data_ptr(), c_rows.data_ptr(),
+                       row_of_frame.data_ptr(), qkv.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr()))
     return out
 
 
@@ -451,19 +451,11 @@ def attn_temporal_ragged_paged(mode, n, F, S, D, heads, causal, T_total, n_pages
     if page_rows.dtype != torch.int32 or page_rows.dim() != 2 or page_rows.shape[0] != n or page_rows.shape[1] < 1 or not page_rows.is_contiguous():
         raise L.TcowError(f'attn_temporal_ragged_paged: page_rows must be a contiguous int32 tensor of n = {n} rows of pages_per_session entries, got '
                           f'{page_rows.dtype} {tuple(page_rows.shape)}')
-    if qkv.shape[0] != F * S or out.shape[0] != F * S:
-        raise L.TcowError(f'attn_temporal_ragged_paged: qkv / out must have F * S = {F * S} rows, got {qkv.shape[0]} / {out.shape[0]}')
-    if cache_dtype is not None:
-        cq = _cache_dtype('attn_temporal_ragged_paged', mode, cache_dtype, k_pages, v_pages)
-        L.check(lib.tcow_attn_temporal_ragged_paged_cq_fwd(_stream(), sh, int(n), int(T_total), int(n_pages), int(page_frames), int(page_rows.shape[1]),
-                                                           t0_rows.data_ptr(), page_rows.data_ptr(), first_rows.data_ptr(), c_rows.data_ptr(),
-                                                           row_of_frame.data_ptr(), qkv.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), out.data_ptr(),
-                                                           cq), 'tcow_attn_temporal_ragged_paged_cq_fwd', lib)
-        return out
-    L.check(lib.tcow_attn_temporal_ragged_paged_fwd(_stream(), sh, int(n), int(T_total), int(n_pages), int(page_frames), int(page_rows.shape[1]),
-                                                    t0_rows.data_ptr(), page_rows.data_ptr(), first_rows.data_ptr(), c_rows.data_ptr(),
-                                                    row_of_frame.data_ptr(), qkv.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(), out.data_ptr()),
-            'tcow_attn_temporal_ragged_paged_fwd', lib)
+    _ragged_rows('attn_temporal_ragged_paged', F, S, qkv, out)
+    _stream_attn_call(lib, 'tcow_attn_temporal_ragged_paged_fwd', mode, cache_dtype, k_pages, v_pages,
+                      (sh, int(n), int(T_total), int(n_pages), int(page_frames), int(page_rows.shape[1]), t0_rows.data_ptr(), page_rows.data_ptr(),
+                       first_rows.data_ptr(), c_rows.data_ptr(), row_of_frame.data_ptr(), qkv.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(),
+                       out.data_ptr()))
     return out
 
 

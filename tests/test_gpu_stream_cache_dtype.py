@@ -315,6 +315,56 @@ def test_compact_paged_ragged_form_equals_the_stream_form(cuda, pair, P, T_total
         assert torch.equal(_b(vp), _b(_to_pages(v_after, page_of, n_pages, P, 12))), (pair, P, causal)
 
 
+@pytest.mark.parametrize('mode', [ops.F32, ops.BF16, ops.FP16], ids=['f32', 'bf16', 'fp16'])
+def test_storage_typed_cache_dtype_is_the_none_path(cuda, mode):
+    """A cache_dtype that names the storage type goes through the *_cq entry points to the instantiation that None reaches: each of the four
+    wrappers, called with None and with the storage type on clones of the same inputs, leaves the same bytes in the output and in both caches.
+    Two sessions at t0 = 0 and 4 G + 1 (one whole cached trip of the key loop, one that crosses into the step's own keys, masked tail keys)."""
+    cq, dt, G = (ops.F32 if mode == ops.F32 else ops.BF16), ops.tdtype(mode), _G(mode)
+    S, heads, D, n_slots, P = 3, 1, 64, 3, 4
+    T_total, t0s, slots = 8 * G + 8, [0, 4 * G + 1], [2, 0]
+    g = torch.Generator(device='cuda').manual_seed(17)
+    shape = (n_slots, S - 1, heads, T_total, 64)
+    kc0, vc0 = _pattern(shape, dt, 18), _pattern(shape, dt, 19)              # random bytes; a session's positions < t0: encoded randn
+    for cache in (kc0, vc0):
+        _b(cache)[slots[1], ..., :t0s[1], :] = _b(_enc(torch.randn(S - 1, heads, t0s[1], 64, device='cuda', generator=g), dt))
+    qkv_all = torch.randn(2 * 3 * S, 3 * D, device='cuda', generator=g).to(dt)
+
+    def both(tag, rows, k0, v0, call):
+        got = []
+        for cache_dtype in (None, cq):
+            k, v, out = k0.clone(), v0.clone(), torch.full((rows, D), float('nan'), device='cuda').to(dt)
+            call(k, v, out, cache_dtype)
+            assert not torch.isnan(out.float()).any(), (tag, cache_dtype)
+            got.append((out, k, v))
+        for a, b in zip(*got):
+            assert torch.equal(_b(a), _b(b)), tag
+        assert not torch.equal(_b(got[0][1]), _b(k0)) and not torch.equal(_b(got[0][2]), _b(v0)), tag         # (the step appended)
+
+    for r, (t0, sl) in enumerate(zip(t0s, slots)):                              # stream form: one session a call, chunk length 3
+        qkv = qkv_all[r * 3 * S:(r + 1) * 3 * S].clone()
+        both(('stream', r), 3 * S, kc0[sl:sl + 1], vc0[sl:sl + 1], lambda k, v, out, cd: ops.attn_temporal_cached(
+            mode, 1, 3, S, D, heads, 1, T_total, _i32([t0]), qkv, k, v, out, cache_dtype=cd))
+    both('pool', 2 * 3 * S, kc0, vc0, lambda k, v, out, cd: ops.attn_temporal_pool(
+        mode, 2, 3, S, D, heads, 1, T_total, n_slots, _i32(t0s), _i32(slots), qkv_all.clone(), k, v, out, cache_dtype=cd))
+    cs = [3, 2]                                                                 # the ragged forms: chunk lengths (3, 2)
+    F = sum(cs)
+    qkv_r = qkv_all[:F * S]
+    tab = {k: _i32(v) for k, v in stream.ragged_tables(t0s, slots, cs).items()}
+    both('ragged', F * S, kc0, vc0, lambda k, v, out, cd: ops.attn_temporal_ragged(
+        mode, 2, F, S, D, heads, 1, T_total, n_slots, tab['t0'], tab['slot'], tab['first'], tab['c'], tab['row_of_frame'], qkv_r.clone(), k, v, out,
+        cache_dtype=cd))
+    pps = -(-T_total // P)
+    n_pages = 2 * pps + 3                                                       # spare pages, a shuffled table
+    ids = [int(i) for i in np.random.default_rng(5).permutation(n_pages)[:2 * pps]]
+    page_of = [ids[:pps], ids[pps:]]
+    assert any(a > b for a, b in zip(page_of[1], page_of[1][1:]))
+    kp0, vp0 = _to_pages(kc0[slots], page_of, n_pages, P, 20), _to_pages(vc0[slots], page_of, n_pages, P, 21)
+    both('paged', F * S, kp0, vp0, lambda k, v, out, cd: ops.attn_temporal_ragged_paged(
+        mode, 2, F, S, D, heads, 1, T_total, n_pages, P, tab['t0'], _i32(sum(page_of, [])).view(2, pps), tab['first'], tab['c'], tab['row_of_frame'],
+        qkv_r.clone(), k, v, out, cache_dtype=cd))
+
+
 # ---------------------------------------------------------------------------------------------- (e) refusals
 
 def test_compact_entry_points_refuse_bad_arguments(cuda):

@@ -157,8 +157,12 @@ def gemm_nt_skinny_x3(A, W, out, bias=None, row_scale=None, resid=None, act=ACT_
     return _skinny_call('tcow_gemm_nt_skinny_x3', F32X3, A, W, out, bias, row_scale, resid, act, aux, bias2, row_scale2, split)
 
 
-_ws_cache = {}
-_ws_pinned = threading.local()
+class _Scratch(threading.local):          # the calling thread's scratch, gone with the thread
+    def __init__(self):
+        self.bufs, self.pinned = {}, {}                 # {(str(device), raw stream, tag): uint8 tensor}, {tag: tensor}
+
+
+_scratch = _Scratch()
 
 
 class pinned_workspace:
@@ -170,43 +174,46 @@ class pinned_workspace:
         self.tag, self.buf = tag, buf
 
     def __enter__(self):
-        d = _ws_pinned.__dict__.setdefault('tags', {})
-        self.prev = d.get(self.tag)
-        d[self.tag] = self.buf
+        self.prev = _scratch.pinned.get(self.tag)
+        _scratch.pinned[self.tag] = self.buf
         return self.buf
 
     def __exit__(self, *exc):
-        d = _ws_pinned.tags
         if self.prev is None:
-            del d[self.tag]
+            del _scratch.pinned[self.tag]
         else:
-            d[self.tag] = self.prev
-        return False
+            _scratch.pinned[self.tag] = self.prev
 
 
 def workspace(nbytes, device, tag='default'):
-    """Grow-only scratch buffer per (device, STREAM, host thread, tag).  Kernels on one stream run in order, so reuse within a stream is safe; two streams of one
-    device (two host threads driving replicas -- the torch.nn.DataParallel thread model of train.py:222-223 -- or a side stream) never share scratch:
-    the key carries torch's current stream, the one the kernels that use the buffer are launched on (tests/test_gpu_seeker.py::test_two_threads_two_streams).
-    A buffer that has to grow is replaced, not freed under a running kernel: the old tensor's storage returns to torch's caching allocator, which holds
-    it for this stream until the work queued on it has drained."""
-    # (_stream(): the current stream of the current device -- the same call the launch that follows makes; the thread id: two host threads that share
-    # a stream -- torch.nn.DataParallel replicas placed on one device -- interleave their launches, and some scratch lives across two launches)
-    pinned = getattr(_ws_pinned, 'tags', None)
-    if pinned and tag in pinned:
-        if pinned[tag].numel() < nbytes:
-            raise L.TcowError(f'workspace({tag!r}): the pinned buffer holds {pinned[tag].numel()} bytes, {nbytes} are needed')
-        return pinned[tag]
-    key = (str(device), _stream(), tag, threading.get_ident())
-    buf = _ws_cache.get(key)
+    """Grow-only scratch buffer of the calling host thread per (device, STREAM, tag); workspace(0, device, tag) returns the one the thread has.
+    Kernels on one stream run in order, so reuse within a stream is safe; two streams of one device never share scratch: the key carries torch's
+    current stream, the one the launch that follows is made on.  Two host threads never share scratch either, not even on one stream (replicas of
+    torch.nn.DataParallel placed on one device interleave their launches, and some scratch lives across two launches): each has its own table,
+    which nothing counts or prunes.  A buffer that has to grow is replaced, and a thread's buffers go when the thread ends; neither frees memory
+    under a running kernel: a thread's buffers were allocated under the stream they are used on, so their storage returns to torch's caching
+    allocator, which keeps the blocks for that stream until the work queued on it has drained."""
+    s = _scratch
+    pin = s.pinned.get(tag)
+    if pin is not None:
+        if pin.numel() < nbytes:
+            raise L.TcowError(f'workspace({tag!r}): the pinned buffer holds {pin.numel()} bytes, {nbytes} are needed')
+        return pin
+    key = (str(device), _stream(), tag)
+    buf = s.bufs.get(key)
     if buf is None or buf.numel() < nbytes:
-        if buf is None and len(_ws_cache) >= 48:         # short-lived host threads (DataParallel starts new ones per forward): forget the scratch of threads that are gone
-            alive = {t.ident for t in threading.enumerate()}
-            for k in [k for k in _ws_cache if k[3] not in alive]:
-                del _ws_cache[k]
-        buf = torch.empty(int(nbytes * 1.25) + 1024, dtype=torch.uint8, device=device)
-        _ws_cache[key] = buf
+        buf = s.bufs[key] = torch.empty(int(nbytes * 1.25) + 1024, dtype=torch.uint8, device=device)
     return buf
+
+
+def workspace_view(tag):
+    """{raw stream handle: tensor} of the calling thread's buffers under `tag`."""
+    return {stream: buf for (_, stream, t), buf in _scratch.bufs.items() if t == tag}
+
+
+def workspace_drop(tag):
+    """Forget the calling thread's buffers under `tag`, on all streams."""
+    _scratch.bufs = {key: buf for key, buf in _scratch.bufs.items() if key[2] != tag}
 
 
 def gemm_tn(mode, dY, X, dW, bias_grad=None, accumulate=False):
@@ -257,9 +264,7 @@ def colsum_grouped(mode, problems):
         for i, (dY, out, *acc) in enumerate(chunk):
             _need_cuda(dY, out)
             arr[i] = L.ColsumProblem(dY.shape[0], dY.shape[1], dY.data_ptr(), dY.stride(0), out.data_ptr(), int(acc[0]) if acc else 0)
-        # (the partial rows are at most 64 x N floats per problem: a tensor of the moment from torch's allocator, which keeps it for this stream until the
-        # launches have drained, not a cached workspace that would live on between steps for a path most steps never take)
-        ws = torch.empty(max(int(lib.tcow_colsum_grouped_workspace_bytes(dm, n, arr)), 16), dtype=torch.uint8, device=chunk[0][0].device)
+        ws = workspace(lib.tcow_colsum_grouped_workspace_bytes(dm, n, arr), chunk[0][0].device, 'colsum')
         L.check(lib.tcow_colsum_grouped(_stream(), dm, n, arr, ws.data_ptr(), ws.numel()), 'tcow_colsum_grouped', lib)
 
 

@@ -756,8 +756,13 @@ def test_two_threads_two_streams_match_sequential_calls(cuda):
     """The torch.nn.DataParallel thread model (train.py:222-223) on ONE device: two host threads, each with its own stream and its own replica (same
     weights, different clips), run forward + backward at the same time.  Outputs and every gradient must equal the sequential calls bit for bit --
     which needs the library's scratch (attention / weight-gradient / LayerNorm / mask-head workspaces, ops.workspace) to be private to a stream:
-    with the per-device cache of rounds 1-5 both threads wrote the same attention and weight-gradient workspaces."""
+    with the per-device cache of rounds 1-5 both threads wrote the same attention and weight-gradient workspaces.
+    Whose scratch: ops.workspace keeps one table per host thread, and the backward of every caller runs on autograd's thread of the device, so
+    the attention backward's buffers ('attn') of all three runs are in THAT thread's table, apart only by their stream, and the callers' own
+    tables hold none.  Each run therefore takes ops.workspace_view('attn') in a hook right behind its backward, on the thread that ran it; of
+    that view only the run's own stream is looked at, so nothing else that the process has run can change the outcome."""
     import threading
+    from tcow_amd import ops
     cfg = synth.seeker_config(num_total_frames=8, frame_height=96, frame_width=128, embed_dim=256, depth=3, num_heads=4, causal_attention=1)
     sd = synth.make_state_dict(cfg, 11)
     clips = [synth.make_clip(2, 8, 96, 128, seed=40 + i) for i in range(2)]
@@ -765,8 +770,16 @@ def test_two_threads_two_streams_match_sequential_calls(cuda):
 
     def one(net, rgb, qm):
         om, fl = net(rgb, qm)
+        views = []
+        om.grad_fn.register_hook(lambda *grads: views.append(ops.workspace_view('attn')))
         (om.square().mean() + fl.square().mean()).backward()
-        return om.detach().clone(), fl.detach().clone(), [None if p.grad is None else p.grad.detach().clone() for p in net.parameters()]
+        (view,) = views
+        return om.detach().clone(), fl.detach().clone(), [None if p.grad is None else p.grad.detach().clone() for p in net.parameters()], view
+
+    def scratch(run, stream):
+        """The 'attn' buffer that a run's backward used: the entry of its stream in the view taken behind that backward."""
+        assert stream.cuda_stream in run[3], (stream, sorted(run[3]))
+        return run[3][stream.cuda_stream]
 
     for precision in ('bf16', 'fp32'):
         nets = [build_hip_seeker(cfg, sd, precision).cuda().train() for _ in range(2)]
@@ -797,8 +810,9 @@ def test_two_threads_two_streams_match_sequential_calls(cuda):
                 assert torch.equal(res[i][0], seq[i][0]) and torch.equal(res[i][1], seq[i][1]), (precision, rep, i)
                 for a, b in zip(res[i][2], seq[i][2]):
                     assert (a is None) == (b is None) and (a is None or torch.equal(a, b)), (precision, rep, i)
-    from tcow_amd import ops
-    assert len({k[1] for k in ops._ws_cache if k[2] == 'attn'}) >= 3        # the default stream's and the two side streams' attention scratch are distinct buffers
+            # the default stream's and the two side streams' attention scratch: each keyed by its own stream, three distinct buffers (all three held here)
+            held = [scratch(seq[1], torch.cuda.default_stream())] + [scratch(res[i], streams[i]) for i in range(2)]
+            assert len({b.data_ptr() for b in held}) == 3 and all(b.numel() > 0 for b in held), (precision, rep)
 
 
 def test_torch_dataparallel_wrapper_matches_the_plain_module(cuda):

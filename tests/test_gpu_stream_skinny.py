@@ -19,11 +19,11 @@ ROUTED = [p for p in ENTRY if ENTRY[p]]
 
 @pytest.fixture(scope='module', autouse=True)
 def _leave_no_scratch():
-    """ops.workspace is a process-wide, grow-only cache that other tests look at: this module leaves none of its split-K scratch in it."""
+    """ops.workspace keeps a thread's grow-only buffers for as long as the thread lives, and other tests look at them: this module leaves none of
+    its split-K scratch behind."""
     yield
     from tcow_amd import ops as o
-    for k in [k for k in o._ws_cache if k[2] == 'nt_skinny']:
-        del o._ws_cache[k]
+    o.workspace_drop('nt_skinny')
 
 
 def _net(which, precision, ca=1, seed=11):

@@ -334,6 +334,20 @@ int tcow_attn_temporal_ragged_paged_cq_fwd(void* stream, const tcow_attn_shape* 
                                            int pages_per_session, const int* t0_rows, const int* page_rows, const int* first_rows, const int* c_rows,
                                            const int* row_of_frame, const void* qkv, void* k_pages, void* v_pages, void* out, int cache_dtype);
 
+/* Hand-off of a rollover pool (SeekerStreamPool with rollover = k; a new symbol, no signature changed: the ABI version stays).  A session that
+ * runs past frame T_total - 1 is a chain of overlapping windows; the query mask of the next window is the model's own output at the frame
+ * where that window starts, binarised as eval/metrics.py:18 does (output_mask > threshold).
+ * tcow_requery_mask: for hand-off i < n, with x = logits + src_off[i] (src_off: device int64 element offsets into the logits_len f32 elements
+ *   of `logits`) and r = dst_rows[i] (device int32):  mask[r][e] = x[e] > threshold ? 1.0f : 0.0f for e < plane (a NaN and a value equal to
+ *   the threshold give 0), and pixels[r] = the number of ones (overwritten, not accumulated; an integer sum over a fixed tree, so the same for
+ *   every run).  mask is [n_dst, plane] f32, pixels [n_dst] int32.  A hand-off with r outside [0, n_dst), or whose plane does not lie inside
+ *   [0, logits_len), writes nothing; every row of mask / pixels that no hand-off names stays untouched.  Two hand-offs of one launch that
+ *   name the same row are UNDEFINED.  Planes are f32 in every precision mode (the mask logits are), so both builds export the same code.
+ *   16-byte loads and stores where a plane and its row start on a 16-byte boundary, element by element otherwise and for the last plane % 4.
+ *   Refused: a null pointer, n < 1, n_dst < 1, plane outside 1 .. 2^31 - 1, logits_len < plane, a threshold that is not finite. */
+int tcow_requery_mask(void* stream, int n, long plane, const float* logits, long logits_len, const long* src_off, float threshold, float* mask,
+                      const int* dst_rows, int n_dst, int* pixels);
+
 /* ------------------------------------------------------------------------------------------- token glue
  * tcow_im2col: cat([rgb (B,3,T,H,W), query (B,1,T,H,W)]) (mask_tracker.py:107-108), optional (rgb-0.45)/0.225
  *   (vision_tf.py:81-89), flattened per patch in Conv2d weight order c*P*P + py*P + px (vit.py:233-240) into

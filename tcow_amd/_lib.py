@@ -114,6 +114,7 @@ SIGNATURES = {
     'tcow_attn_temporal_pool_cq_fwd': (_i, [_vp, _ash, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     'tcow_attn_temporal_ragged_cq_fwd': (_i, [_vp, _ash, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     'tcow_attn_temporal_ragged_paged_cq_fwd': (_i, [_vp, _ash, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    'tcow_requery_mask': (_i, [_vp, _i, _l, _vp, _l, _vp, _f, _vp, _vp, _i, _vp]),
     'tcow_im2col': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     'tcow_gather_frames': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'tcow_resize_aa': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp]),

@@ -148,6 +148,18 @@ int tcow_gemm_nt_skinny_x3(void* stream, const tcow_gemm_args* a, int split, voi
     return tcow_gemm_nt_skinny_launch_x3((hipStream_t)stream, a, split, (float*)workspace);
 }
 
+// ---- hand-off of a rollover stream pool (stream_requery.hip): logit planes -> 0 / 1 query masks and their pixel counts, all on the device
+int tcow_requery_mask(void* stream, int n, long plane, const float* logits, long logits_len, const long* src_off, float threshold, float* mask,
+                      const int* dst_rows, int n_dst, int* pixels) {
+    TCOW_CHECK_ARG(logits && src_off && mask && dst_rows && pixels, "tcow_requery_mask: null pointer");
+    TCOW_CHECK_ARG(n >= 1, "tcow_requery_mask: n=%d must be >= 1", n);
+    TCOW_CHECK_ARG(plane >= 1 && plane < (1L << 31), "tcow_requery_mask: plane=%ld must be 1 .. 2^31 - 1", plane);
+    TCOW_CHECK_ARG(logits_len >= plane, "tcow_requery_mask: logits_len=%ld holds no plane of %ld elements", logits_len, plane);
+    TCOW_CHECK_ARG(n_dst >= 1, "tcow_requery_mask: n_dst=%d must be >= 1", n_dst);
+    TCOW_CHECK_ARG(threshold - threshold == 0.0f, "tcow_requery_mask: the threshold must be finite");
+    return tcow_launch_requery_mask((hipStream_t)stream, n, plane, logits, logits_len, src_off, threshold, mask, dst_rows, n_dst, pixels);
+}
+
 // ---- weight gradients.  Every number below -- kernel, slices, how the bias gradient is produced, workspace offsets -- is the plan's (gemm_tn_plan.h).
 long tcow_gemm_tn_workspace_bytes(int M, int N, int K) { return tcow_tn_workspace_total(M, N, K); }
 

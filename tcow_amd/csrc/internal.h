@@ -24,6 +24,10 @@ int tcow_gemm_tn_bf16_group(hipStream_t stream, const TnGroupPlan& pl, int n, co
 int tcow_gemm_tn_f32(hipStream_t stream, const TnPlan& pl, int M, int N, int K, const float* dY, long ldy, const float* X, long ldx, float* slab);      // gemm_f32.hip
 int tcow_gemm_tn_x3(hipStream_t stream, const TnPlan& pl, int M, int N, int K, const float* dY, long ldy, const float* X, long ldx, float* slab);       // gemm_x3.hip
 
+// ---- hand-off of a rollover stream pool (stream_requery.hip); tcow_requery_mask checks the arguments
+int tcow_launch_requery_mask(hipStream_t stream, int n, long plane, const float* logits, long logits_len, const long* src_off, float threshold, float* mask,
+                             const int* dst_rows, int n_dst, int* pixels);
+
 // ---- reduction launchers (reduce.hip)
 int tcow_launch_slab_reduce(hipStream_t stream, const float* slab, int nz, long slab_stride, long rows, long cols, float* out, long ldo, int accumulate,
                             const float* bias_part, int bias_nparts, int bias_n, float* bias_out);

@@ -475,6 +475,26 @@ def cls_ragged(x, n, F, S, cls_cache, n_slots, t0_rows, slot_rows, first_rows, c
     return x
 
 
+def requery_mask(logits, src_off, threshold, mask, dst_rows, pixels):
+    """The hand-offs of a rollover pool step (see tcow_requery_mask): for hand-off i, the plane of mask.shape[1] f32 elements at element
+    src_off[i] (device int64 [n]) of `logits` (any shape, f32, contiguous) -> mask[dst_rows[i]] (f32 [n_dst, plane]) as 0.0 / 1.0 of
+    `> threshold`, and its number of ones -> pixels[dst_rows[i]] (int32 [n_dst]); dst_rows device int32 [n].  Nothing comes back to the host."""
+    _need_cuda(logits, src_off, mask, dst_rows, pixels)
+    if logits.dtype != torch.float32 or mask.dtype != torch.float32 or not logits.is_contiguous() or not mask.is_contiguous() or mask.dim() != 2:
+        raise L.TcowError('requery_mask: logits and mask must be contiguous f32 tensors, mask [n_dst, plane]')
+    n, n_dst = src_off.numel(), mask.shape[0]
+    if n < 1 or mask.numel() < 1:
+        raise L.TcowError(f'requery_mask: n={n} hand-offs, mask {tuple(mask.shape)}: at least one hand-off, one row and a plane of one element')
+    if src_off.dtype != torch.int64 or dst_rows.dtype != torch.int32 or dst_rows.numel() != n or not src_off.is_contiguous() or not dst_rows.is_contiguous():
+        raise L.TcowError(f'requery_mask: src_off must be int64 [n], dst_rows int32 [n], both contiguous, got {src_off.dtype} {tuple(src_off.shape)} / '
+                          f'{dst_rows.dtype} {tuple(dst_rows.shape)}')
+    if pixels.dtype != torch.int32 or pixels.numel() != n_dst or not pixels.is_contiguous():
+        raise L.TcowError(f'requery_mask: pixels must be a contiguous int32 tensor of n_dst = {n_dst} entries, got {pixels.dtype} {tuple(pixels.shape)}')
+    L.check(L.lib().tcow_requery_mask(_stream(), n, mask.shape[1], logits.data_ptr(), logits.numel(), src_off.data_ptr(), float(threshold), mask.data_ptr(),
+                                      dst_rows.data_ptr(), n_dst, pixels.data_ptr()), 'tcow_requery_mask')
+    return mask, pixels
+
+
 def im2col(mode, rgb, query, P, pretrained_norm, out):
     B, _, T, H, W = rgb.shape
     lib, dm = _sel(mode)

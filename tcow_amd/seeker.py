@@ -286,14 +286,21 @@ class QueryMaskTracker(nn.Module):
         from .stream import SeekerStream
         return SeekerStream(self, batch_size, queries_per_clip, graph, skinny_gemm, cache_dtype)
 
-    def stream_pool(self, capacity, skinny_gemm=None, page_frames=None, pages=None, cache_dtype=None):
+    def stream_pool(self, capacity, skinny_gemm=None, page_frames=None, pages=None, cache_dtype=None, rollover=None, requery_threshold=0.0):
         """Streaming inference for up to `capacity` live sessions that started at different moments: a SeekerStreamPool whose step(ids, rgb,
         query_mask) advances any subset of the open sessions, each at its own frame, in one Seeker step (tcow_amd/stream.py).
         page_frames=P (a power of two): a paged pool -- the K / V caches are `pages` pages of P frames (default capacity * ceil(T / P), which cannot
         run out; lower it to the memory budget), a session holds only the pages its frames so far have filled and close() / reset() return them;
         a step that would need more pages than are free raises TcowError and moves nothing.  Same outputs, bit for bit.  None: one full cache per slot.
-        cache_dtype: as in stream(); a pool gives the bits of a stream with the same cache_dtype."""
-        from .stream import SeekerStreamPool
+        cache_dtype: as in stream(); a pool gives the bits of a stream with the same cache_dtype.
+        rollover=k (1 .. num_total_frames // 2): a SeekerRolloverPool, whose sessions have no last frame.  A session is a chain of windows of
+        num_total_frames frames that overlap by k; each later window is queried with the model's own output at its first frame, thresholded on
+        the device (mask logits > requery_threshold), and its first k frames only warm it up.  The outputs are forward() of every such window.
+        A session takes two cache slots and at most num_total_frames - k frames per call; frames_done() counts on, window(), requery_mask() and
+        requery_pixels() show the chain.  None: sessions end at frame num_total_frames - 1, as above."""
+        from .stream import SeekerRolloverPool, SeekerStreamPool
+        if rollover is not None:
+            return SeekerRolloverPool(self, capacity, skinny_gemm, page_frames, pages, cache_dtype, rollover, requery_threshold)
         return SeekerStreamPool(self, capacity, skinny_gemm, page_frames, pages, cache_dtype)
 
     def param_list(self):
@@ -371,6 +378,6 @@ class Seeker(nn.Module):
         """See QueryMaskTracker.stream."""
         return self.seeker.stream(batch_size, queries_per_clip, graph, skinny_gemm, cache_dtype)
 
-    def stream_pool(self, capacity, skinny_gemm=None, page_frames=None, pages=None, cache_dtype=None):
+    def stream_pool(self, capacity, skinny_gemm=None, page_frames=None, pages=None, cache_dtype=None, rollover=None, requery_threshold=0.0):
         """See QueryMaskTracker.stream_pool."""
-        return self.seeker.stream_pool(capacity, skinny_gemm, page_frames, pages, cache_dtype)
+        return self.seeker.stream_pool(capacity, skinny_gemm, page_frames, pages, cache_dtype, rollover, requery_threshold)

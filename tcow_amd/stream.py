@@ -51,6 +51,14 @@ Where a key lives does not enter the arithmetic, so a paged pool gives the bits 
 and 0.13 ms more than on the contiguous pool (profiles/stream_paged_latency.json; P = 8 is the recommendation, P = 1 the
 dearest): the keywords are off by default.  SeekerStream stays contiguous.
 
+A rollover pool (net.stream_pool(capacity, rollover=k, requery_threshold=0.0) -> SeekerRolloverPool): a stream or a pool session ends at frame
+T - 1, because the time table has T rows and the query belongs to frame 0.  With rollover a session is a chain of windows of T frames that
+start every T - k frames (RolloverPlan: all of the host arithmetic); each later window is queried with the thresholded mask logits the window
+before it returned for the frame where it starts (ops.requery_mask, tcow_requery_mask: on the device, nothing is read back), its first k frames
+only fill its cache, and the reported outputs are forward() of every window built that way.  A session owns two cache slots, a call is one
+Seeker step unless a chunk goes on after a hand-off frame (then two), and the steps are the ragged forms above, unchanged.  Without the keyword
+a pool is what it was.
+
 graph=True (SeekerStream): the first step of each chunk length c runs eagerly and captures the step as a torch.cuda.CUDAGraph; later steps copy
 their inputs into the graph's static buffers, write t0 and the time rows (the stream keeps one _StreamStep with static time rows per chunk
 length, and one t0 scalar: the graph points into both) and replay.  No step synchronises the host except the one capture per chunk length.  A
@@ -302,6 +310,100 @@ def page_plan(capacity, T, page_frames, pages):
     return P, n_pages
 
 
+class RolloverPlan:
+    """THE host arithmetic of a rollover pool (stream_pool(rollover=k)): plain Python, no device.  A session of a model of T frames is a chain of
+    windows of T frames that start every s = T - k frames: window w covers the global frames w*s .. w*s + T - 1, frame g is its local frame
+    g - w*s.  Window w + 1 starts at the hand-off frame (w + 1)*s, which window w reports and whose thresholded mask logits are the query mask
+    of window w + 1.  1 <= k <= T // 2, so at most two windows are live at a frame and a hand-off frame is never a warm-up frame of the older."""
+
+    def __init__(self, T, k):
+        T = int(T)
+        if isinstance(k, bool) or int(k) != k or k < 1 or k > T // 2:
+            raise TcowError(f'stream_pool: rollover ({k!r}) must be an integer in 1 .. num_total_frames // 2 = {T // 2}: the frames two consecutive '
+                            'windows share')
+        self.T, self.k, self.s = T, int(k), T - int(k)
+
+    def window(self, g):
+        """The window that reports global frame g: window 0 its whole span, a later window its local frames k .. T - 1 (the first k warm it up)."""
+        return 0 if g < self.T else (g - self.k) // self.s
+
+    def live(self, g):
+        """The windows that frame g belongs to, oldest first: the reporting one, and the next once its first frame has come."""
+        w = self.window(g)
+        return (w, w + 1) if g >= (w + 1) * self.s else (w,)
+
+    def is_handoff(self, g):
+        """Frame g is the first frame of a window w >= 1 (g = w*s)."""
+        return g >= self.s and g % self.s == 0
+
+    def split(self, g0, c):
+        """A session at global frame g0 brings c <= s frames -> the Seeker steps they take part in and where their outputs come from.
+        'parts': one or two lists of rows (window, t0, c, g): the window takes its local frames t0 .. t0 + c - 1 = the global frames g .. g + c - 1
+        in that step.  Part 1 holds the frames up to and including the chunk's hand-off frame h, if it has one, else all; part 2, only if frames
+        follow h, holds those, and the new window from h on (t0 = 0), after the hand-off has made its query mask.  When h is the chunk's last
+        frame ('keep') the caller retains that frame, and the next call's part 1 gives it to the new window: a row that starts at g0 - 1.
+        'handoff': h or None.  'report': runs (part, window, g, count) in frame order, together the chunk's c frames: where each is reported."""
+        g0, c, s = int(g0), int(c), self.s
+        if c < 1 or c > s:
+            raise TcowError(f'stream_pool: a chunk of {c} frames: a rollover pool takes 1 .. num_total_frames - rollover = {s} frames of a session '
+                            'per call (at most one hand-off frame)')
+        end = g0 + c
+        h = next((g for g in range(g0, end) if self.is_handoff(g)), None)
+        cut = end if h is None else h + 1
+        born = None if h is None else h // s
+        parts = []
+        for p, (lo, hi) in enumerate(((g0, cut), (cut, end))):
+            if lo >= hi:
+                continue
+            rows = {}                                           # window -> [first global frame, frames]
+            for g in range(lo, hi):
+                for w in self.live(g):
+                    if not (p == 0 and w == born):              # the new window waits for its query mask
+                        rows.setdefault(w, [g, 0])[1] += 1
+            if p == 0 and g0 >= 1 and self.is_handoff(g0 - 1):  # the frame the call before retained
+                r = rows[(g0 - 1) // s]
+                r[0], r[1] = g0 - 1, r[1] + 1
+            if p == 1:
+                r = rows[born]
+                r[0], r[1] = h, r[1] + 1
+            parts.append([(w, g - w * s, n, g) for w, (g, n) in sorted(rows.items())])
+        report = []
+        for g in range(g0, end):
+            p, w = int(g >= cut), self.window(g)
+            if report and report[-1][:2] == (p, w):
+                report[-1] = (p, w, report[-1][2], report[-1][3] + 1)
+            else:
+                report.append((p, w, g, 1))
+        return {'parts': parts, 'handoff': h, 'keep': h == end - 1, 'report': report}
+
+
+def rollover_threshold(threshold):
+    """The requery_threshold keyword as a float; a threshold that is not finite is refused."""
+    try:
+        t = float(threshold)
+    except (TypeError, ValueError):
+        t = float('nan')
+    if t != t or t in (float('inf'), float('-inf')):
+        raise TcowError(f'stream_pool: requery_threshold ({threshold!r}) must be a finite number')
+    return t
+
+
+def rollover_capacity(capacity):
+    """A session of a rollover pool owns two cache slots, one per live window."""
+    if int(capacity) < 2:
+        raise TcowError(f'stream_pool: capacity ({capacity}) must be >= 2 with rollover: a session owns two cache slots, one per live window')
+    return int(capacity)
+
+
+def rollover_pages(capacity, T, k, page_frames, pages):
+    """page_plan for a rollover pool: a session holds at most ceil(T / P) + ceil(k / P) pages after a call (the window that ends and the k
+    warm-up frames of the next), and capacity // 2 sessions fit, so that is what pages defaults to, rounded up."""
+    P, n_pages = page_plan(capacity, T, page_frames, pages)
+    if P is not None and pages is None:
+        n_pages = -(-capacity * (-(-T // P) + -(-k // P)) // 2)
+    return P, n_pages
+
+
 class PageAllocator:
     """Which pages of a paged pool each session owns: plain Python, no device.  Pages 0 .. n_pages-1 hold P frames each; a session that has
     `frames` frames owns ceil(frames / P) pages, in frame order (entry q holds its frames q*P .. q*P+P-1).  Deterministic: grow() hands out the
@@ -348,7 +450,8 @@ def _zero_mask(rows, rgb):
 
 
 class SeekerStream:
-    """net.stream(batch_size, queries_per_clip, graph, skinny_gemm, cache_dtype) of Seeker / QueryMaskTracker; see the module docstring."""
+    """net.stream(batch_size, queries_per_clip, graph, skinny_gemm, cache_dtype) of Seeker / QueryMaskTracker; see the module docstring.  A stream
+    ends at frame num_total_frames - 1; a session without a last frame is net.stream_pool(capacity, rollover=k) (SeekerRolloverPool)."""
 
     def __init__(self, module, batch_size=1, queries_per_clip=1, graph=False, skinny_gemm=None, cache_dtype=None):
         module = getattr(module, 'seeker', module)
@@ -387,7 +490,7 @@ class SeekerStream:
         t0 = self.frames_done
         if t0 + c > self.T:
             raise TcowError(f'stream.step: frames {t0}..{t0 + c - 1} run past the last frame {self.T - 1} of the stream (num_total_frames = {self.T}); '
-                            'reset() to start again')
+                            'reset() to start again, or run the camera on net.stream_pool(capacity, rollover=k), whose sessions have no last frame')
         with torch.no_grad(), torch.cuda.device(self.device):
             step = self._steps.get(c)
             if step is None:
@@ -549,13 +652,18 @@ class SeekerStreamPool:
             self._alloc.grow(ids, [t0 + c for t0, c in zip(t0s, cs)])
         return ids, t0s, cs
 
-    def _run(self, step, ids, cs, rgb, qm):
-        """One Seeker step (qm None: all zeros), after which every session has moved on by its chunk length."""
+    def _forward(self, step, rgb, qm):
+        """One Seeker step (qm None: all zeros)."""
         m = self.module
         out_mask, flags, _ = engine.run_forward(m, rgb, _zero_mask(rgb.shape[0], rgb) if qm is None else qm, m.param_list(), save=False, stream=step)
+        return out_mask, (flags if m.flag_channels > 0 else None)
+
+    def _run(self, step, ids, cs, rgb, qm):
+        """One Seeker step, after which every session has moved on by its chunk length."""
+        out = self._forward(step, rgb, qm)
         for sid, c in zip(ids, cs):
             self._done[sid] += c
-        return out_mask, (flags if m.flag_channels > 0 else None)
+        return out
 
     def step(self, ids, rgb, query_mask=None):
         """ids: n distinct open sessions, at any phases; rgb (n, 3, c, H, W), query_mask (n, 1, c, H, W) or None (all zeros): the next c >= 1
@@ -572,11 +680,12 @@ class SeekerStreamPool:
             step = _PoolStep(st, st.time.index_select(0, frames), t0_rows, slot_rows)         # [n*c, D]: row r*c + j = time row t0_rows[r] + j
             return self._run(step, ids, cs, rgb.to(torch.float32).contiguous(), None if query_mask is None else query_mask.to(torch.float32).contiguous())
 
-    def _ragged_form(self, ids, t0s, cs):
+    def _ragged_form(self, ids, t0s, cs, slots=None):
         """The step object of a ragged step (inside no_grad on the pool's device) and every session's first flat frame.  A paged pool sends the
-        sessions' page rows in the same host-to-device copy as the other tables."""
+        sessions' page rows in the same host-to-device copy as the other tables.  ids: what the page allocator knows the rows by; slots: their
+        cache slots (None: those of the sessions `ids`)."""
         n, st = len(ids), self._st
-        tab = ragged_tables(t0s, [self._slot[sid] for sid in ids], cs)
+        tab = ragged_tables(t0s, [self._slot[sid] for sid in ids] if slots is None else slots, cs)
         F = len(tab['frames'])
         # all tables in one host-to-device copy: [t0 | slot | first | c] per session, [row_of_frame | frames] per flat frame, [pages] per session
         flat = tab['t0'] + tab['slot'] + tab['first'] + tab['c'] + tab['row_of_frame'] + tab['frames']
@@ -625,3 +734,199 @@ class SeekerStreamPool:
             out_mask, flags = self._run(step, ids, cs, rgb32, qm32)
         masks = [out_mask[:, :, f0:f0 + c] for f0, c in zip(first, cs)]
         return masks, (None if flags is None else [flags[:, f0:f0 + c] for f0, c in zip(first, cs)])
+
+
+class SeekerRolloverPool(SeekerStreamPool):
+    """net.stream_pool(capacity, ..., rollover=k, requery_threshold=0.0): a pool whose sessions run past the last frame of the model.  A session
+    is a chain of windows of T frames that overlap by k (RolloverPlan); window w + 1 is queried with the thresholded mask logits that window w
+    returned for the frame where it starts (ops.requery_mask: on the device, nothing is read back), its first k frames only fill its cache, and
+    the caller sees one unbroken run of frames.  The reported outputs are forward() of each window, built that way, sliced by the reporting
+    rule.  A session owns two cache slots (the current and the next window, alternating; cls rows per slot), so capacity // 2 sessions fit.
+
+    Every call becomes ragged steps over (session, window) rows.  Part 1: every session's frames up to and including its hand-off frame, if
+    its chunk holds one, for each window live at them; then the one re-query launch; part 2, only if some chunk has frames after its hand-off
+    frame: those frames, and the new window from the hand-off frame on.  When the hand-off frame ends the chunk, the pool keeps that RGB frame
+    and the next call gives it to the new window with its own frames.  So a call in which no chunk continues past a hand-off frame is exactly
+    one Seeker step -- every call of a camera that sends one frame per call -- and any other call exactly two.
+
+    Paged: pages are owned per (session, window); everything both parts need is checked before anything is launched (a refused call moves no
+    counter, page or retained frame), and a window's pages return after the step that brings its last frame.  Fed one frame per call a session
+    holds at most ceil(T / P) + ceil(k / P) pages (the window that ends and the k warm-up frames of the next), which is what `pages` defaults
+    to for capacity // 2 sessions.  A chunk that runs past a window's last frame keeps that window's pages through the step in which the next
+    one grows past k frames: up to ceil((k + c - 1) / P) for it; with pages at the default and every session in that phase at once such a
+    call can be refused, and feeding it in two calls is always enough."""
+
+    def __init__(self, module, capacity, skinny_gemm=None, page_frames=None, pages=None, cache_dtype=None, rollover=1, requery_threshold=0.0):
+        m = getattr(module, 'seeker', module)
+        self.plan = RolloverPlan(m.num_total_frames, rollover)
+        self.rollover = self.plan.k
+        self.requery_threshold = rollover_threshold(requery_threshold)
+        capacity = rollover_capacity(capacity)
+        _, n_pages = rollover_pages(capacity, m.num_total_frames, self.plan.k, page_frames, pages)
+        super().__init__(m, capacity, skinny_gemm, page_frames, n_pages, cache_dtype)       # _slot: session -> its two slots, window w on w & 1
+        self._hw = (m.frame_height, m.frame_width)
+        self._masks = torch.zeros(capacity, self._hw[0] * self._hw[1], dtype=torch.float32, device=self.device)      # row = the slot of the window it queries
+        self._pixels = torch.zeros(capacity, dtype=torch.int32, device=self.device)
+        self._keep = {}                 # session -> the hand-off frame (1, 3, 1, H, W) f32 that ended its last chunk
+        self._last = {}                 # session -> the row of _masks / _pixels of its last hand-off
+
+    def open(self):
+        """A new session at frame 0 on the two smallest free slots; returns its id (ids are never reused)."""
+        taken = {s for pair in self._slot.values() for s in pair}
+        free = [s for s in range(self.capacity) if s not in taken]
+        if len(free) < 2:
+            raise TcowError(f'stream_pool.open: {len(free)} of {self.capacity} slots are free and a rollover session takes two; close() a session first')
+        sid = self._next_id
+        self._next_id += 1
+        self._slot[sid], self._done[sid] = (free[0], free[1]), 0
+        return sid
+
+    def _forget(self, sid):
+        self._keep.pop(sid, None)
+        self._last.pop(sid, None)
+        if self._alloc is not None:
+            self._alloc.release((sid, 0))
+            self._alloc.release((sid, 1))
+
+    def close(self, sid):
+        """End the session: both slots, the pages of both windows, the retained frame and the pending mask are released."""
+        self._known(sid)
+        self._forget(sid)
+        del self._slot[sid], self._done[sid]
+
+    def reset(self, sid):
+        """Put the session back at frame 0 (it keeps its slots; the pages of both windows, the retained frame and the pending mask go)."""
+        self._done[self._known(sid)] = 0
+        self._forget(sid)
+
+    def window(self, sid):
+        """The window that reports the session's next frame."""
+        return self.plan.window(self._done[self._known(sid)])
+
+    def pages_of(self, sid):
+        """The pages the session owns: those of its older live window in frame order, then those of the newer."""
+        a, w = self._paged(), self.plan.window(max(self._done[self._known(sid)] - 1, 0))
+        return a.pages_of((sid, w & 1)) + a.pages_of((sid, (w + 1) & 1))
+
+    def _handed(self, sid):
+        if self._known(sid) not in self._last:
+            raise TcowError(f'stream_pool: session {sid} has had no hand-off yet (the first is frame {self.plan.s})')
+        return self._last[sid]
+
+    def requery_mask(self, sid):
+        """(1, 1, 1, H, W) f32 on the device: the query mask the session's last hand-off made, returned logits > requery_threshold as 0.0 / 1.0."""
+        return self._masks[self._handed(sid)].view(1, 1, 1, *self._hw).clone()
+
+    def requery_pixels(self, sid):
+        """A device int32 scalar: the number of ones of requery_mask(sid).  An empty mask is used as it is; this is where the caller sees it."""
+        return self._pixels[self._handed(sid)].clone()
+
+    def _check_pages(self, ids, splits):
+        """The all-or-nothing page check of a call: part by part, what the rows lack against what is free, a window that ends in a part giving
+        its pages back to the next.  Nothing moves."""
+        a = self._alloc
+        free, held = a.free, {}
+        for p in range(2):
+            need, ended = 0, []
+            for sid, sp in zip(ids, splits):
+                for w, t0, c, _ in (sp['parts'][p] if p < len(sp['parts']) else ()):
+                    key = (sid, w & 1)
+                    have = held.setdefault(key, len(a.pages_of(key)))
+                    want = max(have, -(-(t0 + c) // a.P))
+                    need += want - have
+                    held[key] = want
+                    if t0 + c == self.T:
+                        ended.append(key)
+            if need > free:
+                raise TcowError(f'stream_pool: out of pages: this step needs {need} more page(s) of {a.P} frame(s), {free} of {a.n_pages} are free; '
+                                'close() or reset() a session, or open the pool with more pages')
+            free += sum(held[key] for key in ended) - need
+            held.update((key, 0) for key in ended)
+
+    def _roll(self, who, ids, rgbs, qms, per):
+        """step() and step_ragged(): every check, then part 1, the re-query launch, part 2 if any chunk goes on after its hand-off frame.  Returns
+        per session (mask logits (1, Co, c, H, W), flags (1, c, F) or None) of its c frames."""
+        m, plan = self.module, self.plan
+        ids = check_sessions(who, ids, len(rgbs) if per else None, len(qms) if per and qms is not None else None, self.capacity, self._slot)
+        _check_module(m, self._sig)
+        if per:
+            cs = [_check_inputs(f'{who}: session {sid}', m, self.device, 1, 1, rgbs[k], None if qms is None else qms[k]) for k, sid in enumerate(ids)]
+        else:
+            cs = [_check_inputs(who, m, self.device, len(ids), len(ids), rgbs, qms)] * len(ids)
+            rgbs, qms = [rgbs[k:k + 1] for k in range(len(ids))], (None if qms is None else [qms[k:k + 1] for k in range(len(ids))])
+        g0s = [self._done[sid] for sid in ids]
+        splits = [plan.split(g0, c) for g0, c in zip(g0s, cs)]
+        if self._alloc is not None:
+            self._check_pages(ids, splits)
+        HW = self._hw[0] * self._hw[1]
+        outs = []                                               # per part: (mask logits, flags, {(session index, window): (first flat frame, its global frame)})
+        with torch.no_grad(), torch.cuda.device(self.device):
+            rgbs = [r.to(torch.float32) for r in rgbs]
+            qms = [None] * len(ids) if qms is None else [None if q is None else q.to(torch.float32) for q in qms]
+            for p in range(max(len(sp['parts']) for sp in splits)):
+                rows = [(k, *row) for k, sp in enumerate(splits) if p < len(sp['parts']) for row in sp['parts'][p]]
+                keys = [(ids[k], w & 1) for k, w, _, _, _ in rows]
+                slots = [self._slot[ids[k]][w & 1] for k, w, _, _, _ in rows]
+                if self._alloc is not None:
+                    self._alloc.grow(keys, [t0 + c for _, _, t0, c, _ in rows])
+                step, first = self._ragged_form(keys, [r[2] for r in rows], [r[3] for r in rows], slots)
+                rgb_p, qm_p = [], []
+                for (k, w, t0, c, g), slot in zip(rows, slots):
+                    j = g - g0s[k]                              # -1: the row starts at the frame the call before retained
+                    if j < 0:
+                        rgb_p.append(self._keep[ids[k]])
+                    rgb_p.append(rgbs[k][:, :, max(j, 0):j + c])
+                    if w >= 1 and t0 == 0:                      # the window's query: the mask of its hand-off in place of the caller's frame
+                        qm_p.append(self._masks[slot].view(1, 1, 1, *self._hw))
+                        j, c = j + 1, c - 1
+                    if c:
+                        qm_p.append(_zero_mask(1, rgbs[k][:, :, j:j + c]) if qms[k] is None else qms[k][:, :, j:j + c])
+                rgb_p, qm_p = [t for t in rgb_p if t.shape[2]], [t for t in qm_p if t.shape[2]]
+                rgb32 = rgb_p[0].contiguous() if len(rgb_p) == 1 else torch.cat(rgb_p, 2)
+                qm32 = qm_p[0].contiguous() if len(qm_p) == 1 else torch.cat(qm_p, 2)
+                out_mask, flags = self._forward(step, rgb32, qm32)
+                where = {(k, w): (f, g) for (k, w, _, _, g), f in zip(rows, first)}
+                outs.append((out_mask, flags, where))
+                if p == 0:
+                    hand = [(k, sp['handoff']) for k, sp in enumerate(splits) if sp['handoff'] is not None]
+                    if hand:
+                        src, dst = [], []
+                        for k, h in hand:
+                            born = h // plan.s
+                            f, g = where[(k, born - 1)]          # the older window reports the hand-off frame: channel 0 of flat frame f + h - g
+                            src.append((f + h - g) * HW)
+                            dst.append(self._slot[ids[k]][born & 1])
+                            self._last[ids[k]] = dst[-1]
+                        tab = torch.cat([torch.tensor(src, dtype=torch.int64).view(torch.int32), torch.tensor(dst, dtype=torch.int32)]).to(self.device)
+                        ops.requery_mask(out_mask, tab[:2 * len(src)].view(torch.int64), self.requery_threshold, self._masks, tab[2 * len(src):], self._pixels)
+                if self._alloc is not None:
+                    for key, (_, _, t0, c, _) in zip(keys, rows):
+                        if t0 + c == self.T:                    # the window has produced its last frame
+                            self._alloc.release(key)
+            for k, (sid, sp) in enumerate(zip(ids, splits)):
+                if sp['keep']:
+                    self._keep[sid] = rgbs[k][:, :, -1:].clone()
+                else:
+                    self._keep.pop(sid, None)
+                self._done[sid] += cs[k]
+            res = []
+            for k, sp in enumerate(splits):
+                ms, fs = [], []
+                for p, w, g, n in sp['report']:
+                    out_mask, flags, where = outs[p]
+                    f = where[(k, w)][0] + g - where[(k, w)][1]
+                    ms.append(out_mask[:, :, f:f + n])
+                    fs.append(None if flags is None else flags[:, f:f + n])
+                res.append((ms[0] if len(ms) == 1 else torch.cat(ms, 2), None if fs[0] is None else fs[0] if len(fs) == 1 else torch.cat(fs, 1)))
+        return res
+
+    def step(self, ids, rgb, query_mask=None):
+        """SeekerStreamPool.step with c <= T - rollover frames per session, at any global frame."""
+        res = self._roll('stream_pool.step', ids, rgb, query_mask, False)
+        masks = torch.cat([r[0] for r in res], 0) if len(res) > 1 else res[0][0].contiguous()
+        return masks, (None if res[0][1] is None else torch.cat([r[1] for r in res], 0))
+
+    def step_ragged(self, ids, rgbs, query_masks=None):
+        """SeekerStreamPool.step_ragged with c_i <= T - rollover frames of session i, at any global frame."""
+        res = self._roll('stream_pool.step_ragged', ids, list(rgbs), None if query_masks is None else list(query_masks), True)
+        return [r[0] for r in res], (None if res[0][1] is None else [r[1] for r in res])

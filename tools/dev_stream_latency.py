@@ -23,6 +23,10 @@
                                         # configs[1] B = 1 and B = 8, configs[3] B = 1 at t0 = 0, T/2, T-1, and a long stream (configs[1] geometry,
                                         # num_total_frames = 240) at t0 = 239; the two files' runs are the 'latency' list of profiles/stream_cache_dtype.json
     --kprof / --kstats take one --cache-dtype as well (the temporal kernel's own time and bytes with a compact cache)
+    python tools/dev_stream_latency.py --rollover 10 --out profiles/stream_rollover_latency.json
+                                        # one session of a rollover pool (stream_pool(2, rollover=K)) at configs[1], B = 1, bf16, one frame per call over
+                                        # three windows: plain, overlap and hand-off ticks, each followed by the one-frame step of a pool without the
+                                        # keyword at the same local frame; and the re-query launch alone at the configs[1] / configs[3] plane sizes
 
 Times are device events around each call after warm-up, profiler off.  A step at a given t0 is timed by setting the stream's host frame counter
 (the kernels then read t0 from the device scalar the step writes): the work of a step depends on t0, not on what the cache holds.  Synthetic
@@ -340,6 +344,75 @@ KPROF_WARMUP, KPROF_STEPS = 3, 20
 STEP_LAST_KERNEL = 'flags_fwd_kernel'      # the last launch of every step (the flags head, engine.run_forward)
 
 
+def _mmm(v):
+    v = sorted(v)
+    return {'median': v[len(v) // 2], 'min': v[0], 'max': v[-1], 'samples': len(v)}
+
+
+def rollover_leg(reps, k):
+    """One session of net.stream_pool(2, rollover=k) at configs[1], bf16, fed one frame per call over three windows (2 * (T - k) + T frames), `reps`
+    times.  Every tick is followed by the tick the code took before the keyword existed: the one-frame step of a pool opened without it, one
+    session, at the local frame of the window that reports the tick -- so the two legs alternate tick by tick and drift hits both alike.  Ticks by
+    kind: 'plain' (one window live: one frame-row), 'overlap' (two windows live; the tick after a hand-off frame also carries the retained frame),
+    'handoff' (the tick of a hand-off frame: the re-query launch and the copy of the retained frame ride on it).  Also the re-query launch alone,
+    one plane per launch, at the plane sizes of configs[1] and configs[3]."""
+    from tcow_amd import ops
+    name = 'configs1'
+    T, H, W = CONFIGS[name]
+    s, frames = T - k, 2 * (T - k) + T
+    net = build(T, H, W, 'bf16')
+    rgb, qm = inputs(1, T, H, W)
+    f = lambda x, g: x[:, :, g % T:g % T + 1]
+    with torch.no_grad():
+        roll = net.stream_pool(2, rollover=k)
+        sid = roll.open()
+        old = net.stream_pool(1)
+        oid = old.open()
+        plan = roll.plan
+        kinds, rows = [], []
+        for g in range(frames):
+            sp = plan.split(g, 1)
+            kinds.append('handoff' if sp['handoff'] is not None else 'overlap' if len(sp['parts'][0]) == 2 else 'plain')
+            rows.append(sum(r[2] for r in sp['parts'][0]))
+
+        def tick(g):
+            roll.step([sid], f(rgb, g), f(qm, g))
+
+        def old_tick(g):
+            old._done[oid] = g - plan.window(g) * s         # (the step's work depends on t0, not on what the cache holds)
+            old.step([oid], f(rgb, g), f(qm, g))
+
+        for g in range(frames):                             # warm-up: the three windows once through each
+            tick(g); old_tick(g)
+        samples = {leg: {kd: [] for kd in ('plain', 'overlap', 'handoff')} for leg in ('rollover_ms', 'without_keyword_ms')}
+        for _ in range(reps):
+            roll.reset(sid)
+            for g in range(frames):
+                samples['rollover_ms'][kinds[g]].append(ev_time(lambda: tick(g), 1))
+                samples['without_keyword_ms'][kinds[g]].append(ev_time(lambda: old_tick(g), 1))
+        res = {'config': name, 'T': T, 'H': H, 'W': W, 'B': 1, 'precision': 'bf16', 'rollover': k, 'frames_per_round': frames, 'rounds': reps,
+               'ticks_per_round': {kd: kinds.count(kd) for kd in ('plain', 'overlap', 'handoff')},
+               'frame_rows_per_tick': {kd: sorted({r for r, q in zip(rows, kinds) if q == kd}) for kd in ('plain', 'overlap', 'handoff')},
+               'mean_frame_rows_per_frame': sum(rows[T:]) / len(rows[T:]), 'cache_bytes': roll.cache_bytes}
+        for leg, by in samples.items():
+            res[leg] = {kd: _mmm(v) for kd, v in by.items() if v}
+        sp = res['without_keyword_ms']['plain']
+        res['plain_inside_parent_spread'] = bool(sp['min'] <= res['rollover_ms']['plain']['median'] <= sp['max'])
+        res['requery_launch_us'] = {}
+        for cfg, (_, h, w) in CONFIGS.items():
+            plane, n = h * w, 50
+            logits = torch.randn(3 * plane, device='cuda')
+            mask = torch.zeros(2, plane, device='cuda'); pixels = torch.zeros(2, dtype=torch.int32, device='cuda')
+            src = torch.tensor([plane], dtype=torch.int64, device='cuda'); dst = torch.tensor([1], dtype=torch.int32, device='cuda')
+
+            def many():
+                for _ in range(n):
+                    ops.requery_mask(logits, src, 0.0, mask, dst, pixels)
+            many()
+            res['requery_launch_us'][cfg] = {'plane': plane, **{q: v * 1e3 / n for q, v in _mmm([ev_time(many, 1) for _ in range(reps)]).items() if q != 'samples'}}
+    return res
+
+
 def cached_kernel_bytes(T, H, W, e=2, heads=12, D=768, ce=None):
     """Algorithmic bytes of one tcow_attn_temporal_cached_fwd launch of a one-frame step at t0 = T - 1 (B = 1, element size e, cache element
     size ce: e unless the cache is compact)."""
@@ -415,6 +488,7 @@ def main():
     ap.add_argument('--skinny-gemm', default=None, choices=['on', 'off'], help='the skinny_gemm keyword of the --kprof steps (default: the stream default)')
     ap.add_argument('--cache-dtype', default=None, help="comma list of 'bf16' / 'fp8': the compact-cache leg against cache_dtype=None; one value with "
                                                         '--kprof / --kstats')
+    ap.add_argument('--rollover', type=int, default=None, metavar='K', help='the rollover-pool leg: one session at configs1 over three windows that overlap by K')
     ap.add_argument('--only', default=None, help='comma list of configs1_b1, configs1_b8, configs3_b1 (--cache-dtype: also configs1_b1_long)')
     a = ap.parse_args()
     flag = None if a.skinny_gemm is None else a.skinny_gemm == 'on'
@@ -429,6 +503,14 @@ def main():
     if a.cache_dtype:
         out = {'device': torch.cuda.get_device_name(0),
                'cache_dtype': cache_leg(a.reps, a.precision, a.cache_dtype.split(','), set(a.only.split(',')) if a.only else None)}
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, 'w') as f:
+                json.dump(out, f, indent=1)
+        return
+    if a.rollover is not None:
+        out = {'device': torch.cuda.get_device_name(0), 'rollover': rollover_leg(a.reps, a.rollover)}
+        print(json.dumps(out['rollover']), flush=True)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, 'w') as f:

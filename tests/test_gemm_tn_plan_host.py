@@ -2,7 +2,7 @@
 
   1. tools/tn_plan_check.cpp, built with the host compiler, sweeps shapes, dtypes and groups and asserts the plan's invariants (slices, stage
      multiples, bias-table rows written <= reserved, workspace regions disjoint, aligned and inside the total).
-  2. The plan of every shape that tests/test_gpu_gemm_tn.py and tests/test_gpu_gemm_tn_k32.py were chosen for: (kernel, slices requested, token
+  2. The plan of every shape that tests/test_gpu_gemm_tn.py, tests/test_gpu_gemm_tn_k32.py and tests/test_gpu_gemm_x3_planes.py were chosen for: (kernel, slices requested, token
      rows per slice, slices, rows of the last slice).  A change of a slice rule that moves one of those shapes off the kernel form it was
      chosen for fails here, on the CPU, instead of silently un-testing that form.
   3. tcow_gemm_tn_workspace_bytes and tcow_gemm_tn_grouped_workspace_bytes of both library builds against tests/golden/tn_workspace_bytes.json,
@@ -101,6 +101,12 @@ PLANS = [
     (BF16, 4129, 768, 776, (K256_1, 16, 320, 13, 289)),
     (BF16, 4129, 768, 768, (K256_2, 16, 320, 13, 289)),
 ]
+# tests/test_gpu_gemm_x3_planes.py: the token sweep of the exact hi / lo checks of the bf16 x 3 kernel (tcow_tn_splits_x3: 768 / tiles slices, at least 256
+# rows each), whose contraction stays within 1800 rows.  513: two slices of 288 rows = 9 k-slices of 32, an odd count; 1793: 7 slices, 65 rows in the last.
+# (kept apart from PLANS: SINGLES below, and with it the recorded workspace fixture, stays as it is)
+X3_PLANE_SWEEP = {1: (1, 32, 1, 1), 31: (1, 32, 1, 31), 32: (1, 32, 1, 32), 33: (1, 64, 1, 33), 64: (1, 64, 1, 64), 65: (1, 96, 1, 65), 255: (1, 256, 1, 255),
+                  513: (2, 288, 2, 225), 1793: (7, 288, 7, 65)}
+X3_PLANE_PLANS = [(F32X3, M, N, K, (KX3,) + want) for N, K in ((264, 136), (70, 50)) for M, want in X3_PLANE_SWEEP.items()]
 # (dtype, M, N, K) -> (how the bias gradient is produced, bias-table rows written, rows_per_pk)
 BIAS = [
     (BF16, 4096, 8, 4224, ('fused', 16 * 33 * 2, 1)),
@@ -113,7 +119,7 @@ BIAS = [
 ]
 
 
-@pytest.mark.parametrize('dtype,M,N,K,want', PLANS)
+@pytest.mark.parametrize('dtype,M,N,K,want', PLANS + X3_PLANE_PLANS)
 def test_plan_of_gpu_test_shape(plan_check, dtype, M, N, K, want):
     p = _plan(plan_check, 'one', dtype, M, N, K, 1)
     assert (p['kernel'].replace('_', ' '), p['splits'], p['mps'], p['nz'], p['last']) == want

@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from kernel_forms import hi_lo_operand, want_hi_lo
 from test_gpu_kernels import GEMM_MODES
 
 pytestmark = pytest.mark.gpu
@@ -42,19 +43,9 @@ def rel(a, b):
     return float((a.double() - b.double()).abs().max() / (b.double().abs().max() + 1e-12))
 
 
-def _integers(ri, r24):
+def _integers(gen, shape, device):
     """Elements in {-3 .. 3}: every sum stays below 2^24, so the f32 output is the integer product exactly, whatever the order."""
-    return ri
-
-
-def _hi_lo(ri, r24):
-    """x = h + l with h in {+-2, +-3} and l in {-3 .. 3} 2^-10: bf16(x) = h and bf16(x - h) = l exactly."""
-    return lambda *s: r24(*s) + ri(*s) / 1024.0
-
-
-def _planes(x):
-    h = x.bfloat16().float()
-    return h.double(), (x - h).bfloat16().double()
+    return torch.randint(-3, 4, shape, device=device, generator=gen).float()
 
 
 def _want_integers(c):
@@ -62,13 +53,8 @@ def _want_integers(c):
 
 
 def _want_hi_lo(c):
-    """Every kept term (hi hi, hi lo, lo hi) is a multiple of 2^-10 and every partial sum stays below 2^24 of those units up to K = 1 024, so the
-    f32 output is hi_A hi_W^T + hi_A lo_W^T + lo_A hi_W^T exactly, in any order."""
-    (ah, al), (wh, wl) = _planes(c.A), _planes(c.W)
-    assert torch.equal(ah + al, c.A.double()) and torch.equal(wh + wl, c.W.double()) and bool((al != 0).any()) and bool((wl != 0).any())
-    want = ah @ wh.t() + ah @ wl.t() + al @ wh.t()
-    assert not torch.equal(want, c.ref0)                              # (the dropped lo lo term is visible)
-    return want
+    """Operands of kernel_forms.hi_lo_operand: the f32 output is hi_A hi_W^T + hi_A lo_W^T + lo_A hi_W^T exactly, in any order (want_hi_lo)."""
+    return want_hi_lo(c.A, c.W)
 
 
 def _arith(ops, fmt):
@@ -82,7 +68,7 @@ def _arith(ops, fmt):
         a.skinny = lambda A, W, out, **kw: ops.gemm_nt_skinny_x3(A, W, out, **kw)
         a.tile128 = lambda A, W, out, **kw: ops.gemm_nt(ops.F32X3, A, W, out, **kw)
         a.tol = a.tol32 = TOLX3
-        a.exact, a.exact_want = _hi_lo, _want_hi_lo
+        a.exact, a.exact_want = hi_lo_operand, _want_hi_lo
         a.refused = [(dict(ws_off=4), 'workspace'), (dict(dtype=L.TCOW_BF16), 'dtype'), (dict(dtype=L.TCOW_F32), 'dtype'), (dict(ldc_extra=-2), 'ldc')]
     else:
         a.mode, a.dt, a.entry = {'bf16': (ops.BF16, torch.bfloat16), 'fp16': (ops.FP16, torch.float16)}[fmt] + ('tcow_gemm_nt_skinny',)
@@ -101,8 +87,7 @@ def _case(cuda, a, M, N, K, seed, exact=False):
     c = types.SimpleNamespace(M=M, N=N, K=K, dt=a.dt)
     if exact:
         ri = lambda *s: torch.randint(-3, 4, s, device=cuda, generator=g).float()
-        r24 = lambda *s: torch.randint(2, 4, s, device=cuda, generator=g).float() * (torch.randint(0, 2, s, device=cuda, generator=g).float() * 2 - 1)
-        x = a.exact(ri, r24)
+        x = lambda *s: a.exact(g, s, cuda)
         c.A = x(M, K + 8).to(a.dt)[:, 8:]; c.W = x(N, K).to(a.dt)
         c.bias = ri(N); c.resid = ri(M, N)
     else:

@@ -1,4 +1,6 @@
-"""Streaming inference: the Seeker one chunk of frames at a time, for callers that receive frames live (a camera, a decoder).
+"""Streaming inference: the Seeker one chunk of frames at a time, for callers that receive frames live (a camera, a decoder).  This module owns
+the tensors, graphs and launches; what is arithmetic on plain ints (tables, refusals, pages, rollover windows) lives in stream_plan.py, runs on
+the CPU, and is imported here by name.
 
 With causal_attention 1 or 2 the model is causal along time: frame t's mask logits and flags depend on frames 0..t only (the tril() mask of
 vit.py:93-99, the cls row taken from frame 0, vit.py:192-198; everything else works per token or per frame).  A stream step therefore runs
@@ -12,7 +14,7 @@ modes: bf16 / binary16; fp32 and bf16x3: f32), one f32 cls row per row and block
 clips x queries (the query mask changes every token's K / V), a pool rows = capacity.  At BASELINE configs[1] (T = 30, 240x320, depth 12)
 that is 332 MB per row in the 16-bit modes; at configs[3] (T = 60, 480x640) 2.65 GB; f32 twice that.
 
-cache_dtype (net.stream / net.stream_pool; cache_plan below is the one place that decides): the element type of the K / V caches, apart from
+cache_dtype (net.stream / net.stream_pool; stream_plan.cache_plan is the one place that decides): the element type of the K / V caches, apart from
 the precision mode -- the kernel computes in f32 and only loads and stores cache lines.  None: the storage type, as above.  'bf16': halves the
 caches of 'fp32' and 'bf16x3' (the same as None in 'bf16'; refused in 'fp16').  'fp8' (OCP e4m3fn, saturating at +-448, no scales): any
 precision, a quarter of an f32 cache and half of a 16-bit one -- 166 MB per row at configs[1].  With a compact cache every key and value of
@@ -53,7 +55,7 @@ dearest): the keywords are off by default.  SeekerStream stays contiguous.
 
 A rollover pool (net.stream_pool(capacity, rollover=k, requery_threshold=0.0) -> SeekerRolloverPool): a stream or a pool session ends at frame
 T - 1, because the time table has T rows and the query belongs to frame 0.  With rollover a session is a chain of windows of T frames that
-start every T - k frames (RolloverPlan: all of the host arithmetic); each later window is queried with the thresholded mask logits the window
+start every T - k frames (stream_plan.RolloverPlan and RolloverCall: all of the host arithmetic); each later window is queried with the thresholded mask logits the window
 before it returned for the frame where it starts (ops.requery_mask, tcow_requery_mask: on the device, nothing is read back), its first k frames
 only fill its cache, and the reported outputs are forward() of every window built that way.  A session owns two cache slots, a call is one
 Seeker step unless a chunk goes on after a hand-off frame (then two), and the steps are the ragged forms above, unchanged.  Without the keyword
@@ -71,8 +73,8 @@ import torch
 
 from . import engine, ops
 from ._lib import TcowError
-
-MAX_FRAMES = 1024       # TCOW_STREAM_MAX_FRAMES of include/tcow_hip.h
+from .stream_plan import (MAX_FRAMES, PageAllocator, RolloverCall, RolloverPlan, cache_plan, check_range, check_sessions, page_plan,  # noqa: F401
+                          ragged_tables, rollover_capacity, rollover_page_moves, rollover_pages, rollover_threshold)
 
 # Default of the skinny_gemm keyword.  True: measured (profiles/stream_skinny_latency.json) -- a one-frame bf16 step takes
 # 1.42 ms instead of 2.41 at configs[1] B = 1, 2.41 instead of 3.35 at configs[3] B = 1 and 2.60 instead of 3.24 at configs[1] B = 8, on / off
@@ -82,23 +84,6 @@ SKINNY_GEMM_DEFAULT = True
 # (profiles/stream_skinny_x3_latency.json) -- a one-frame bf16x3 step takes 1.94 ms instead of 4.28 at configs[1] B = 1,
 # 4.45 instead of 5.88 at configs[3] B = 1 and 5.17 instead of 6.06 at configs[1] B = 8, each difference above the off leg's own max - min.
 SKINNY_GEMM_X3_DEFAULT = True
-
-
-def cache_plan(mode, cache_dtype):
-    """THE decision of the cache_dtype keyword (host arithmetic only): (torch dtype of the K / V caches, cache_dtype argument of the
-    ops.attn_temporal_* wrappers) for a module of ops mode `mode` (F32, BF16, FP16; bf16x3 stores F32).  None -> (the storage type, None): the
-    entry points without a cache type.  'fp8' -> torch.float8_e4m3fn in any mode.  'bf16' -> torch.bfloat16 under f32 storage; under bf16
-    storage it is what None gives; binary16 storage refuses it (bfloat16 is no narrower, and the binary16 build has no such kernel)."""
-    if cache_dtype is None:
-        return ops.tdtype(mode), None
-    if cache_dtype == 'fp8':
-        return torch.float8_e4m3fn, ops.FP8
-    if cache_dtype == 'bf16':
-        if mode == ops.FP16:
-            raise TcowError("stream: cache_dtype='bf16' with precision='fp16': the cache would be no smaller than the binary16 storage; "
-                            "use None or 'fp8'")
-        return (torch.bfloat16, None) if mode == ops.BF16 else (torch.bfloat16, ops.BF16)
-    raise TcowError(f"stream: cache_dtype={cache_dtype!r} must be None, 'bf16' or 'fp8'")
 
 
 def _skinny_default(module):
@@ -246,207 +231,25 @@ def _check_inputs(who, m, device, clips, rows, rgb, query_mask):
     return c
 
 
-def ragged_tables(t0s, slots, cs):
-    """The tables of a ragged step, as lists of ints: n sessions, session r at frame t0s[r] on cache slot slots[r] with cs[r] >= 1 new frames.
-    The F = sum(cs) frames lie flat in session order.  Returns a dictionary with, per session, 't0', 'slot', 'first' (its first flat frame: the
-    exclusive prefix sum of cs) and 'c', and per flat frame 'row_of_frame' (its session) and 'frames' (its index in the stream, t0 + j: the row
-    of the time table it takes)."""
-    t0s, slots, cs = [int(v) for v in t0s], [int(v) for v in slots], [int(v) for v in cs]
-    if not (len(t0s) == len(slots) == len(cs)) or not cs:
-        raise TcowError(f'ragged_tables: {len(t0s)} t0 / {len(slots)} slots / {len(cs)} chunk lengths: one of each per session, at least one session')
-    if min(cs) < 1:
-        raise TcowError(f'ragged_tables: chunk lengths must be >= 1, got {cs}')
-    first, row_of_frame, frames, f = [], [], [], 0
-    for r, (t0, c) in enumerate(zip(t0s, cs)):
-        first.append(f)
-        row_of_frame += [r] * c
-        frames += range(t0, t0 + c)
-        f += c
-    return {'t0': t0s, 'slot': slots, 'first': first, 'c': cs, 'row_of_frame': row_of_frame, 'frames': frames}
-
-
-def check_sessions(who, ids, n_rgbs, n_masks, capacity, open_ids):
-    """The checks of a pool step (`who`) that look at the lists alone: 1 .. capacity sessions, every id open, none twice, and for a list of rgb
-    entries (n_rgbs not None) one entry per session, the same for a list of query masks (n_masks not None).  Returns the ids as a list."""
-    ids = list(ids)
-    n = len(ids)
-    if n < 1 or n > capacity:
-        raise TcowError(f'{who}: {n} sessions given; a step takes 1 .. capacity = {capacity}')
-    if n_rgbs is not None and (n_rgbs != n or (n_masks is not None and n_masks != n)):
-        raise TcowError(f'{who}: {n} ids, {n_rgbs} rgb entries' + ('' if n_masks is None else f', {n_masks} query_masks entries')
-                        + ': the lengths must agree (one entry per session)')
-    seen = set()
-    for sid in ids:
-        if sid not in open_ids:
-            raise TcowError(f'stream_pool: session {sid!r} is not open (unknown or closed id)')
-        if sid in seen:
-            raise TcowError(f'{who}: duplicate session {sid!r}: a session is one run of frames of a step')
-        seen.add(sid)
-    return ids
-
-
-def check_range(who, ids, t0s, cs, T):
-    """No session runs past the last frame: frames_done + c_i <= T for every session, the offender named."""
-    for sid, t0, c in zip(ids, t0s, cs):
-        if t0 + c > T:
-            raise TcowError(f'{who}: session {sid}: frames {t0}..{t0 + c - 1} run past the last frame {T - 1} of the stream '
-                            f'(num_total_frames = {T}); reset() or close() it')
-
-
-def page_plan(capacity, T, page_frames, pages):
-    """The page_frames / pages keywords of stream_pool for a pool of `capacity` sessions of T frames -> (P, n_pages), or (None, None) for the
-    contiguous pool (page_frames None).  P must be a power of two in 1 .. TCOW_STREAM_MAX_FRAMES; pages defaults to capacity * ceil(T / P), with
-    which no step can run out of pages."""
-    if page_frames is None:
-        if pages is not None:
-            raise TcowError(f'stream_pool: pages ({pages}) given without page_frames: only a paged pool is sized in pages')
-        return None, None
-    P = int(page_frames)
-    if P != page_frames or P < 1 or P > MAX_FRAMES or P & (P - 1):
-        raise TcowError(f'stream_pool: page_frames ({page_frames}) must be a power of two in 1 .. {MAX_FRAMES}')
-    n_pages = capacity * -(-T // P) if pages is None else int(pages)
-    if n_pages < 1 or (pages is not None and n_pages != pages):
-        raise TcowError(f'stream_pool: pages ({pages}) must be an integer >= 1')
-    return P, n_pages
-
-
-class RolloverPlan:
-    """THE host arithmetic of a rollover pool (stream_pool(rollover=k)): plain Python, no device.  A session of a model of T frames is a chain of
-    windows of T frames that start every s = T - k frames: window w covers the global frames w*s .. w*s + T - 1, frame g is its local frame
-    g - w*s.  Window w + 1 starts at the hand-off frame (w + 1)*s, which window w reports and whose thresholded mask logits are the query mask
-    of window w + 1.  1 <= k <= T // 2, so at most two windows are live at a frame and a hand-off frame is never a warm-up frame of the older."""
-
-    def __init__(self, T, k):
-        T = int(T)
-        if isinstance(k, bool) or int(k) != k or k < 1 or k > T // 2:
-            raise TcowError(f'stream_pool: rollover ({k!r}) must be an integer in 1 .. num_total_frames // 2 = {T // 2}: the frames two consecutive '
-                            'windows share')
-        self.T, self.k, self.s = T, int(k), T - int(k)
-
-    def window(self, g):
-        """The window that reports global frame g: window 0 its whole span, a later window its local frames k .. T - 1 (the first k warm it up)."""
-        return 0 if g < self.T else (g - self.k) // self.s
-
-    def live(self, g):
-        """The windows that frame g belongs to, oldest first: the reporting one, and the next once its first frame has come."""
-        w = self.window(g)
-        return (w, w + 1) if g >= (w + 1) * self.s else (w,)
-
-    def is_handoff(self, g):
-        """Frame g is the first frame of a window w >= 1 (g = w*s)."""
-        return g >= self.s and g % self.s == 0
-
-    def split(self, g0, c):
-        """A session at global frame g0 brings c <= s frames -> the Seeker steps they take part in and where their outputs come from.
-        'parts': one or two lists of rows (window, t0, c, g): the window takes its local frames t0 .. t0 + c - 1 = the global frames g .. g + c - 1
-        in that step.  Part 1 holds the frames up to and including the chunk's hand-off frame h, if it has one, else all; part 2, only if frames
-        follow h, holds those, and the new window from h on (t0 = 0), after the hand-off has made its query mask.  When h is the chunk's last
-        frame ('keep') the caller retains that frame, and the next call's part 1 gives it to the new window: a row that starts at g0 - 1.
-        'handoff': h or None.  'report': runs (part, window, g, count) in frame order, together the chunk's c frames: where each is reported."""
-        g0, c, s = int(g0), int(c), self.s
-        if c < 1 or c > s:
-            raise TcowError(f'stream_pool: a chunk of {c} frames: a rollover pool takes 1 .. num_total_frames - rollover = {s} frames of a session '
-                            'per call (at most one hand-off frame)')
-        end = g0 + c
-        h = next((g for g in range(g0, end) if self.is_handoff(g)), None)
-        cut = end if h is None else h + 1
-        born = None if h is None else h // s
-        parts = []
-        for p, (lo, hi) in enumerate(((g0, cut), (cut, end))):
-            if lo >= hi:
-                continue
-            rows = {}                                           # window -> [first global frame, frames]
-            for g in range(lo, hi):
-                for w in self.live(g):
-                    if not (p == 0 and w == born):              # the new window waits for its query mask
-                        rows.setdefault(w, [g, 0])[1] += 1
-            if p == 0 and g0 >= 1 and self.is_handoff(g0 - 1):  # the frame the call before retained
-                r = rows[(g0 - 1) // s]
-                r[0], r[1] = g0 - 1, r[1] + 1
-            if p == 1:
-                r = rows[born]
-                r[0], r[1] = h, r[1] + 1
-            parts.append([(w, g - w * s, n, g) for w, (g, n) in sorted(rows.items())])
-        report = []
-        for g in range(g0, end):
-            p, w = int(g >= cut), self.window(g)
-            if report and report[-1][:2] == (p, w):
-                report[-1] = (p, w, report[-1][2], report[-1][3] + 1)
-            else:
-                report.append((p, w, g, 1))
-        return {'parts': parts, 'handoff': h, 'keep': h == end - 1, 'report': report}
-
-
-def rollover_threshold(threshold):
-    """The requery_threshold keyword as a float; a threshold that is not finite is refused."""
-    try:
-        t = float(threshold)
-    except (TypeError, ValueError):
-        t = float('nan')
-    if t != t or t in (float('inf'), float('-inf')):
-        raise TcowError(f'stream_pool: requery_threshold ({threshold!r}) must be a finite number')
-    return t
-
-
-def rollover_capacity(capacity):
-    """A session of a rollover pool owns two cache slots, one per live window."""
-    if int(capacity) < 2:
-        raise TcowError(f'stream_pool: capacity ({capacity}) must be >= 2 with rollover: a session owns two cache slots, one per live window')
-    return int(capacity)
-
-
-def rollover_pages(capacity, T, k, page_frames, pages):
-    """page_plan for a rollover pool: a session holds at most ceil(T / P) + ceil(k / P) pages after a call (the window that ends and the k
-    warm-up frames of the next), and capacity // 2 sessions fit, so that is what pages defaults to, rounded up."""
-    P, n_pages = page_plan(capacity, T, page_frames, pages)
-    if P is not None and pages is None:
-        n_pages = -(-capacity * (-(-T // P) + -(-k // P)) // 2)
-    return P, n_pages
-
-
-class PageAllocator:
-    """Which pages of a paged pool each session owns: plain Python, no device.  Pages 0 .. n_pages-1 hold P frames each; a session that has
-    `frames` frames owns ceil(frames / P) pages, in frame order (entry q holds its frames q*P .. q*P+P-1).  Deterministic: grow() hands out the
-    lowest free page first, session by session in the order given, as open() takes the lowest free slot."""
-
-    def __init__(self, n_pages, page_frames):
-        self.n_pages, self.P = int(n_pages), int(page_frames)
-        self._free = list(range(self.n_pages))                  # ascending
-        self._pages = {}                                        # session -> its pages in frame order
-
-    @property
-    def free(self):
-        return len(self._free)
-
-    def pages_of(self, sid):
-        return tuple(self._pages.get(sid, ()))
-
-    def missing(self, sid, frames):
-        """Pages the session lacks to hold `frames` frames: more than 0 only when the frames cross a page boundary."""
-        return max(0, -(-int(frames) // self.P) - len(self._pages.get(sid, ())))
-
-    def grow(self, sids, frames):
-        """Every session sids[k] gets the pages it lacks to hold frames[k] frames.  All or nothing: if the free pages do not cover the sum, raises
-        TcowError (pages needed and free named) and nothing has moved.  Returns each session's pages."""
-        need = sum(self.missing(sid, f) for sid, f in zip(sids, frames))
-        if need > len(self._free):
-            raise TcowError(f'stream_pool: out of pages: this step needs {need} more page(s) of {self.P} frame(s), {len(self._free)} of '
-                            f'{self.n_pages} are free; close() or reset() a session, or open the pool with more pages')
-        for sid, f in zip(sids, frames):
-            k = self.missing(sid, f)
-            if k:
-                self._pages.setdefault(sid, []).extend(self._free[:k])
-                del self._free[:k]
-        return [self.pages_of(sid) for sid in sids]
-
-    def release(self, sid):
-        """The session's pages are free again (a session without pages: nothing happens)."""
-        self._free = sorted(self._free + self._pages.pop(sid, []))
-
-
 def _zero_mask(rows, rgb):
     """The query mask of a step that was given none: all zeros, (rows, 1, c, H, W) for rgb (clips, 3, c, H, W)."""
     return torch.zeros(rows, 1, *rgb.shape[2:], dtype=torch.float32, device=rgb.device)
+
+
+def _f32(x):
+    """An input of a step as the kernels take it: f32 and contiguous (None stays None)."""
+    return None if x is None else x.to(torch.float32).contiguous()
+
+
+def _cat_f32(chunks):
+    """Chunks (rows, C, c_i, H, W) as one run of frames, f32 and contiguous."""
+    return _f32(chunks[0]) if len(chunks) == 1 else torch.cat([x.to(torch.float32) for x in chunks], 2)
+
+
+def _seeker_step(module, step, rgb, qm, rows):
+    """One Seeker step of `rows` query rows (qm None: all zeros) -> (mask logits, flags or None)."""
+    out_mask, flags, _ = engine.run_forward(module, rgb, _zero_mask(rows, rgb) if qm is None else qm, module.param_list(), save=False, stream=step)
+    return out_mask, (flags if module.flag_channels > 0 else None)
 
 
 class SeekerStream:
@@ -497,16 +300,10 @@ class SeekerStream:
                 step = self._steps[c] = _StreamStep(self._st, torch.empty(self.B * c, self._st.D, dtype=torch.float32, device=self.device), self._t0_dev)
             step.time_rows.view(self.B, c, -1).copy_(self._st.time[t0:t0 + c])      # row b*c + j = time row t0 + j, for every b
             self._t0_dev.fill_(t0)
-            rgb32 = rgb.to(torch.float32).contiguous()
-            qm32 = None if query_mask is None else query_mask.to(torch.float32).contiguous()
-            out = self._graph_step(step, rgb32, qm32) if self.graph else self._run(step, rgb32, qm32)
+            rgb32, qm32 = _f32(rgb), _f32(query_mask)
+            out = self._graph_step(step, rgb32, qm32) if self.graph else _seeker_step(self.module, step, rgb32, qm32, self.B)
         self.frames_done = t0 + c
         return out
-
-    def _run(self, step, rgb, qm):
-        m = self.module
-        out_mask, flags, _ = engine.run_forward(m, rgb, _zero_mask(self.B, rgb) if qm is None else qm, m.param_list(), save=False, stream=step)
-        return out_mask, (flags if m.flag_channels > 0 else None)
 
     def _operand_generation(self):
         """Identifies the module's operand caches (16-bit weight copies, folded projection, row vectors in module._operands).  .cuda() / .to()
@@ -516,12 +313,13 @@ class SeekerStream:
 
     def _graph_step(self, step, rgb, qm):
         c = rgb.shape[2]
+        run = lambda r, q: _seeker_step(self.module, step, r, q, self.B)
         gen = self._operand_generation()
         if any(e['gen'] != gen for e in self._graphs.values()):
             self._graphs.clear()                # captured against replaced operand copies: capture again (the pool of a dropped graph is stream-ordered)
         ent = self._graphs.get(c)
         if ent is None:
-            out = self._run(step, rgb, qm)      # this step's result; it also creates every lazily built operand the capture needs
+            out = run(rgb, qm)                  # this step's result; it also creates every lazily built operand the capture needs
             s_rgb = rgb.clone()
             s_qm = qm.clone() if qm is not None else _zero_mask(self.B, rgb)
             graph = torch.cuda.CUDAGraph()
@@ -530,10 +328,10 @@ class SeekerStream:
             ws = ops.workspace(0, self.device, 'nt_skinny') if step.skinny else None
             with torch.cuda.graph(graph):
                 if ws is None:
-                    g_mask, g_flags = self._run(step, s_rgb, s_qm)
+                    g_mask, g_flags = run(s_rgb, s_qm)
                 else:
                     with ops.pinned_workspace('nt_skinny', ws):
-                        g_mask, g_flags = self._run(step, s_rgb, s_qm)
+                        g_mask, g_flags = run(s_rgb, s_qm)
             # The graph holds raw pointers into tensors that only module._operands owns (operand copies, folded W' / b', mask0): a shallow copy
             # of the dictionary keeps them alive as long as the graph, whatever later replaces the dictionary or its entries.
             keep = self.module._operands.keep_alive()
@@ -637,30 +435,26 @@ class SeekerStreamPool:
 
     def _checked(self, who, ids, rgbs, qms, per):
         """Every check of a step (`who`), before anything is launched or any counter moves.  rgbs / qms: one tensor of all sessions, or (per) a list
-        with an entry per session.  Returns (ids, the frame every session stands at, the chunk length of every session)."""
+        with an entry per session.  Returns (ids, the frame every session stands at, the chunk length of every session, and in a paged pool the pages
+        of every session, grown to hold the step's frames; else None)."""
+        ids, cs = self._prologue(who, ids, rgbs, qms, per)
+        t0s = [self._done[sid] for sid in ids]
+        check_range(who, ids, t0s, cs, self.T)
+        # the last check, and the only thing of a refused step that could have moved: the pages of frames up to t0 + c_i - 1 (all or nothing)
+        return ids, t0s, cs, (None if self._alloc is None else self._alloc.grow(ids, [t0 + c for t0, c in zip(t0s, cs)]))
+
+    def _prologue(self, who, ids, rgbs, qms, per):
+        """What every pool call (`who`) checks first, in this order: the sessions, the module, the inputs.  Returns (ids, every session's chunk length)."""
         m = self.module
         ids = check_sessions(who, ids, len(rgbs) if per else None, len(qms) if per and qms is not None else None, self.capacity, self._slot)
         _check_module(m, self._sig)
         if per:
-            cs = [_check_inputs(f'{who}: session {sid}', m, self.device, 1, 1, rgbs[k], None if qms is None else qms[k]) for k, sid in enumerate(ids)]
-        else:
-            cs = [_check_inputs(who, m, self.device, len(ids), len(ids), rgbs, qms)] * len(ids)
-        t0s = [self._done[sid] for sid in ids]
-        check_range(who, ids, t0s, cs, self.T)
-        if self._alloc is not None:
-            # the last check, and the only thing of a refused step that could have moved: the pages of frames up to t0 + c_i - 1 (all or nothing)
-            self._alloc.grow(ids, [t0 + c for t0, c in zip(t0s, cs)])
-        return ids, t0s, cs
-
-    def _forward(self, step, rgb, qm):
-        """One Seeker step (qm None: all zeros)."""
-        m = self.module
-        out_mask, flags, _ = engine.run_forward(m, rgb, _zero_mask(rgb.shape[0], rgb) if qm is None else qm, m.param_list(), save=False, stream=step)
-        return out_mask, (flags if m.flag_channels > 0 else None)
+            return ids, [_check_inputs(f'{who}: session {sid}', m, self.device, 1, 1, rgbs[k], None if qms is None else qms[k]) for k, sid in enumerate(ids)]
+        return ids, [_check_inputs(who, m, self.device, len(ids), len(ids), rgbs, qms)] * len(ids)
 
     def _run(self, step, ids, cs, rgb, qm):
         """One Seeker step, after which every session has moved on by its chunk length."""
-        out = self._forward(step, rgb, qm)
+        out = _seeker_step(self.module, step, rgb, qm, rgb.shape[0])
         for sid, c in zip(ids, cs):
             self._done[sid] += c
         return out
@@ -669,44 +463,41 @@ class SeekerStreamPool:
         """ids: n distinct open sessions, at any phases; rgb (n, 3, c, H, W), query_mask (n, 1, c, H, W) or None (all zeros): the next c >= 1
         frames of each -> (mask logits (n, Co, c, H, W) f32, flags (n, c, F) or None) in the order of `ids`, owned by the caller.  Every check
         runs before anything is launched: a refused step leaves every session where it was."""
-        ids, t0s, cs = self._checked('stream_pool.step', ids, rgb, query_mask, False)
-        if self._alloc is not None:
-            return self._step_paged(ids, t0s, cs, rgb, query_mask)
+        ids, t0s, cs, pages = self._checked('stream_pool.step', ids, rgb, query_mask, False)
+        if pages is not None:
+            return self._step_paged(ids, t0s, cs, pages, rgb, query_mask)
         st, c = self._st, cs[0]
         with torch.no_grad(), torch.cuda.device(self.device):
             t0_rows = torch.tensor(t0s, dtype=torch.int32, device=self.device)
             slot_rows = torch.tensor([self._slot[sid] for sid in ids], dtype=torch.int32, device=self.device)
             frames = (t0_rows[:, None] + torch.arange(c, dtype=torch.int32, device=self.device)[None, :]).reshape(-1)
             step = _PoolStep(st, st.time.index_select(0, frames), t0_rows, slot_rows)         # [n*c, D]: row r*c + j = time row t0_rows[r] + j
-            return self._run(step, ids, cs, rgb.to(torch.float32).contiguous(), None if query_mask is None else query_mask.to(torch.float32).contiguous())
+            return self._run(step, ids, cs, _f32(rgb), _f32(query_mask))
 
-    def _ragged_form(self, ids, t0s, cs, slots=None):
-        """The step object of a ragged step (inside no_grad on the pool's device) and every session's first flat frame.  A paged pool sends the
-        sessions' page rows in the same host-to-device copy as the other tables.  ids: what the page allocator knows the rows by; slots: their
-        cache slots (None: those of the sessions `ids`)."""
-        n, st = len(ids), self._st
-        tab = ragged_tables(t0s, [self._slot[sid] for sid in ids] if slots is None else slots, cs)
+    def _ragged_form(self, t0s, slots, cs, pages):
+        """The step object of a ragged step (inside no_grad on the pool's device) and every row's first flat frame.  pages: None, or in a paged
+        pool every row's pages (PageAllocator.grow's), sent in the same host-to-device copy as the other tables."""
+        n, st = len(t0s), self._st
+        tab = ragged_tables(t0s, slots, cs)
         F = len(tab['frames'])
         # all tables in one host-to-device copy: [t0 | slot | first | c] per session, [row_of_frame | frames] per flat frame, [pages] per session
         flat = tab['t0'] + tab['slot'] + tab['first'] + tab['c'] + tab['row_of_frame'] + tab['frames']
-        if self._alloc is not None:
-            for sid in ids:
-                own = self._alloc.pages_of(sid)
-                flat += list(own) + [-1] * (st.pps - len(own))
+        for own in pages or ():
+            flat += list(own) + [-1] * (st.pps - len(own))
         dev = torch.tensor(flat, dtype=torch.int32).to(self.device)
         time_rows = st.time.index_select(0, dev[4 * n + F:4 * n + 2 * F])               # [F, D]: flat frame f = time row t0 + j of its session
         tables = (dev[0:n], dev[n:2 * n], dev[2 * n:3 * n], dev[3 * n:4 * n], dev[4 * n:4 * n + F])
-        if self._alloc is None:
+        if pages is None:
             return _RaggedStep(st, time_rows, *tables), tab['first']
         return _PagedRaggedStep(st, time_rows, *tables, dev[4 * n + 2 * F:].view(n, st.pps)), tab['first']
 
-    def _step_paged(self, ids, t0s, cs, rgb, query_mask):
+    def _step_paged(self, ids, t0s, cs, pages, rgb, query_mask):
         """step() of a paged pool: the ragged form with equal chunk lengths (bit-equal to the pool form), in and out in step()'s shapes."""
         n, c = len(ids), cs[0]
         # (n, C, c, H, W) -> (1, C, n*c, H, W): the frames flat in session order
         flat = lambda x: x.to(torch.float32).transpose(0, 1).reshape(1, x.shape[1], n * c, *x.shape[3:]).contiguous()
         with torch.no_grad(), torch.cuda.device(self.device):
-            step, _ = self._ragged_form(ids, t0s, cs)
+            step, _ = self._ragged_form(t0s, [self._slot[sid] for sid in ids], cs, pages)
             out_mask, flags = self._run(step, ids, cs, flat(rgb), None if query_mask is None else flat(query_mask))
             out_mask = out_mask.view(out_mask.shape[1], n, c, *out_mask.shape[3:]).transpose(0, 1).contiguous()
         return out_mask, (None if flags is None else flags.reshape(n, c, -1))
@@ -719,13 +510,12 @@ class SeekerStreamPool:
         is launched: a refused step leaves every session where it was."""
         rgbs = list(rgbs)
         qms = None if query_masks is None else list(query_masks)
-        ids, t0s, cs = self._checked('stream_pool.step_ragged', ids, rgbs, qms, True)
-        n = len(ids)
+        ids, t0s, cs, pages = self._checked('stream_pool.step_ragged', ids, rgbs, qms, True)
         with torch.no_grad(), torch.cuda.device(self.device):
-            step, first = self._ragged_form(ids, t0s, cs)
-            rgb32 = rgbs[0].to(torch.float32).contiguous() if n == 1 else torch.cat([r.to(torch.float32) for r in rgbs], 2)
+            step, first = self._ragged_form(t0s, [self._slot[sid] for sid in ids], cs, pages)
+            rgb32 = _cat_f32(rgbs)
             if qms is not None and all(q is not None for q in qms):
-                qm32 = qms[0].to(torch.float32).contiguous() if n == 1 else torch.cat([q.to(torch.float32) for q in qms], 2)
+                qm32 = _cat_f32(qms)
             else:
                 qm32 = _zero_mask(1, rgb32)
                 for q, f0, c in zip(qms or (), first, cs):
@@ -821,102 +611,53 @@ class SeekerRolloverPool(SeekerStreamPool):
         """A device int32 scalar: the number of ones of requery_mask(sid).  An empty mask is used as it is; this is where the caller sees it."""
         return self._pixels[self._handed(sid)].clone()
 
-    def _check_pages(self, ids, splits):
-        """The all-or-nothing page check of a call: part by part, what the rows lack against what is free, a window that ends in a part giving
-        its pages back to the next.  Nothing moves."""
-        a = self._alloc
-        free, held = a.free, {}
-        for p in range(2):
-            need, ended = 0, []
-            for sid, sp in zip(ids, splits):
-                for w, t0, c, _ in (sp['parts'][p] if p < len(sp['parts']) else ()):
-                    key = (sid, w & 1)
-                    have = held.setdefault(key, len(a.pages_of(key)))
-                    want = max(have, -(-(t0 + c) // a.P))
-                    need += want - have
-                    held[key] = want
-                    if t0 + c == self.T:
-                        ended.append(key)
-            if need > free:
-                raise TcowError(f'stream_pool: out of pages: this step needs {need} more page(s) of {a.P} frame(s), {free} of {a.n_pages} are free; '
-                                'close() or reset() a session, or open the pool with more pages')
-            free += sum(held[key] for key in ended) - need
-            held.update((key, 0) for key in ended)
-
     def _roll(self, who, ids, rgbs, qms, per):
         """step() and step_ragged(): every check, then part 1, the re-query launch, part 2 if any chunk goes on after its hand-off frame.  Returns
         per session (mask logits (1, Co, c, H, W), flags (1, c, F) or None) of its c frames."""
-        m, plan = self.module, self.plan
-        ids = check_sessions(who, ids, len(rgbs) if per else None, len(qms) if per and qms is not None else None, self.capacity, self._slot)
-        _check_module(m, self._sig)
-        if per:
-            cs = [_check_inputs(f'{who}: session {sid}', m, self.device, 1, 1, rgbs[k], None if qms is None else qms[k]) for k, sid in enumerate(ids)]
-        else:
-            cs = [_check_inputs(who, m, self.device, len(ids), len(ids), rgbs, qms)] * len(ids)
-            rgbs, qms = [rgbs[k:k + 1] for k in range(len(ids))], (None if qms is None else [qms[k:k + 1] for k in range(len(ids))])
-        g0s = [self._done[sid] for sid in ids]
-        splits = [plan.split(g0, c) for g0, c in zip(g0s, cs)]
-        if self._alloc is not None:
-            self._check_pages(ids, splits)
+        ids, cs = self._prologue(who, ids, rgbs, qms, per)
+        n = len(ids)
+        if not per:
+            rgbs, qms = [rgbs[k:k + 1] for k in range(n)], (None if qms is None else [qms[k:k + 1] for k in range(n)])
+        call = RolloverCall(self.plan, [self._done[sid] for sid in ids], cs)
+        if self._alloc is not None:                             # all or nothing: both parts' page moves on a copy, before anything is launched
+            trial = self._alloc.copy()
+            for rows in call.parts:
+                rollover_page_moves(trial, self.T, ids, rows)
         HW = self._hw[0] * self._hw[1]
-        outs = []                                               # per part: (mask logits, flags, {(session index, window): (first flat frame, its global frame)})
+        outs = []                                               # per part: (mask logits, flags)
         with torch.no_grad(), torch.cuda.device(self.device):
             rgbs = [r.to(torch.float32) for r in rgbs]
-            qms = [None] * len(ids) if qms is None else [None if q is None else q.to(torch.float32) for q in qms]
-            for p in range(max(len(sp['parts']) for sp in splits)):
-                rows = [(k, *row) for k, sp in enumerate(splits) if p < len(sp['parts']) for row in sp['parts'][p]]
-                keys = [(ids[k], w & 1) for k, w, _, _, _ in rows]
-                slots = [self._slot[ids[k]][w & 1] for k, w, _, _, _ in rows]
-                if self._alloc is not None:
-                    self._alloc.grow(keys, [t0 + c for _, _, t0, c, _ in rows])
-                step, first = self._ragged_form(keys, [r[2] for r in rows], [r[3] for r in rows], slots)
+            qms = [None] * n if qms is None else [None if q is None else q.to(torch.float32) for q in qms]
+            for p, rows in enumerate(call.parts):
+                slots = [self._slot[ids[r.k]][r.w & 1] for r in rows]
+                pages = None if self._alloc is None else rollover_page_moves(self._alloc, self.T, ids, rows)
+                step, _ = self._ragged_form([r.t0 for r in rows], slots, [r.c for r in rows], pages)
                 rgb_p, qm_p = [], []
-                for (k, w, t0, c, g), slot in zip(rows, slots):
-                    j = g - g0s[k]                              # -1: the row starts at the frame the call before retained
-                    if j < 0:
-                        rgb_p.append(self._keep[ids[k]])
-                    rgb_p.append(rgbs[k][:, :, max(j, 0):j + c])
-                    if w >= 1 and t0 == 0:                      # the window's query: the mask of its hand-off in place of the caller's frame
+                for r, slot in zip(rows, slots):
+                    if r.kept:
+                        rgb_p.append(self._keep[ids[r.k]])
+                    rgb_p.append(rgbs[r.k][:, :, r.lo:r.hi])
+                    if r.handed:                                # the window's query: the mask of its hand-off in place of the caller's frame
                         qm_p.append(self._masks[slot].view(1, 1, 1, *self._hw))
-                        j, c = j + 1, c - 1
-                    if c:
-                        qm_p.append(_zero_mask(1, rgbs[k][:, :, j:j + c]) if qms[k] is None else qms[k][:, :, j:j + c])
-                rgb_p, qm_p = [t for t in rgb_p if t.shape[2]], [t for t in qm_p if t.shape[2]]
-                rgb32 = rgb_p[0].contiguous() if len(rgb_p) == 1 else torch.cat(rgb_p, 2)
-                qm32 = qm_p[0].contiguous() if len(qm_p) == 1 else torch.cat(qm_p, 2)
-                out_mask, flags = self._forward(step, rgb32, qm32)
-                where = {(k, w): (f, g) for (k, w, _, _, g), f in zip(rows, first)}
-                outs.append((out_mask, flags, where))
-                if p == 0:
-                    hand = [(k, sp['handoff']) for k, sp in enumerate(splits) if sp['handoff'] is not None]
-                    if hand:
-                        src, dst = [], []
-                        for k, h in hand:
-                            born = h // plan.s
-                            f, g = where[(k, born - 1)]          # the older window reports the hand-off frame: channel 0 of flat frame f + h - g
-                            src.append((f + h - g) * HW)
-                            dst.append(self._slot[ids[k]][born & 1])
-                            self._last[ids[k]] = dst[-1]
-                        tab = torch.cat([torch.tensor(src, dtype=torch.int64).view(torch.int32), torch.tensor(dst, dtype=torch.int32)]).to(self.device)
-                        ops.requery_mask(out_mask, tab[:2 * len(src)].view(torch.int64), self.requery_threshold, self._masks, tab[2 * len(src):], self._pixels)
-                if self._alloc is not None:
-                    for key, (_, _, t0, c, _) in zip(keys, rows):
-                        if t0 + c == self.T:                    # the window has produced its last frame
-                            self._alloc.release(key)
-            for k, (sid, sp) in enumerate(zip(ids, splits)):
-                if sp['keep']:
+                    if r.qlo < r.hi:
+                        qm_p.append(_zero_mask(1, rgbs[r.k][:, :, r.qlo:r.hi]) if qms[r.k] is None else qms[r.k][:, :, r.qlo:r.hi])
+                outs.append(_seeker_step(self.module, step, _cat_f32(rgb_p), _cat_f32(qm_p), 1))
+                if p == 0 and call.handoffs:                    # channel 0 of the flat frame at which the older window reports the hand-off frame
+                    src = [f * HW for _, _, f in call.handoffs]
+                    dst = [self._slot[ids[k]][born & 1] for k, born, _ in call.handoffs]
+                    self._last.update((ids[k], d) for (k, _, _), d in zip(call.handoffs, dst))
+                    tab = torch.cat([torch.tensor(src, dtype=torch.int64).view(torch.int32), torch.tensor(dst, dtype=torch.int32)]).to(self.device)
+                    ops.requery_mask(outs[0][0], tab[:2 * len(src)].view(torch.int64), self.requery_threshold, self._masks, tab[2 * len(src):], self._pixels)
+            for k, sid in enumerate(ids):
+                if call.keep[k]:
                     self._keep[sid] = rgbs[k][:, :, -1:].clone()
                 else:
                     self._keep.pop(sid, None)
                 self._done[sid] += cs[k]
             res = []
-            for k, sp in enumerate(splits):
-                ms, fs = [], []
-                for p, w, g, n in sp['report']:
-                    out_mask, flags, where = outs[p]
-                    f = where[(k, w)][0] + g - where[(k, w)][1]
-                    ms.append(out_mask[:, :, f:f + n])
-                    fs.append(None if flags is None else flags[:, f:f + n])
+            for runs in call.report:
+                ms = [outs[p][0][:, :, f:f + c] for p, f, c in runs]
+                fs = [None if outs[p][1] is None else outs[p][1][:, f:f + c] for p, f, c in runs]
                 res.append((ms[0] if len(ms) == 1 else torch.cat(ms, 2), None if fs[0] is None else fs[0] if len(fs) == 1 else torch.cat(fs, 1)))
         return res
 

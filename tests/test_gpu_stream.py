@@ -5,35 +5,13 @@ import pytest
 import torch
 
 from conftest import build_hip_seeker, golden_inputs, load_golden
-from test_gpu_seeker import EXACT, TRAINED_REL, bf16_flags_tol, bf16_tol, h16, h16f
+from stream_kit import PRECISIONS, _check_vs, _splits, _stream, f64_cached_attention
+from test_gpu_seeker import EXACT, TRAINED_REL, bf16_flags_tol, h16, h16f
 from test_oracle_golden import summarise
 from tcow_amd import ops, synth
 from tcow_amd._lib import TcowError
 
 pytestmark = pytest.mark.gpu
-
-PRECISIONS = ['fp32', 'bf16', 'bf16x3', 'fp16']
-
-
-def _splits(T, chunks):
-    """Chunk lengths: `chunks` first, then single frames up to T."""
-    out, n = [], 0
-    for c in chunks:
-        if n + c <= T:
-            out.append(c); n += c
-    return out + [1] * (T - n)
-
-
-def _stream(net, rgb, qm, split, graph=False, Qs=1):
-    """Stream the clip through a fresh stream in chunks `split`; the concatenated outputs."""
-    st = net.stream(batch_size=rgb.shape[0], queries_per_clip=Qs, graph=graph)
-    ms, fs, t = [], [], 0
-    for c in split:
-        m, f = st.step(rgb[:, :, t:t + c], qm[:, :, t:t + c])
-        assert tuple(m.shape[2:3]) == (c,) and st.frames_done == t + c
-        ms.append(m); fs.append(f); t += c
-    return torch.cat(ms, 2), (torch.cat(fs, 1) if fs[0] is not None else None)
-
 
 # ---------------------------------------------------------------------------------------------- kernels
 
@@ -49,13 +27,7 @@ def _attn_case(mode, B, c, S, heads, T_total, t0, causal, seed):
     out = torch.full((B * c * S, D), float('nan'), device=dev).to(dt)
     t0_dev = torch.tensor([t0], dtype=torch.int32, device=dev)
     ops.attn_temporal_cached(ops.F32X3 if mode == 'x3' else mode, B, c, S, D, heads, causal, T_total, t0_dev, qkv, kc, vc, out)
-    # f64 restatement on the same (rounded) inputs
-    per = lambda x: x.double().view(B, c, S, heads, 64)[:, :, 1:].permute(0, 2, 3, 1, 4)           # (B, S-1, heads, c, 64)
-    Q, Kc, Vc = per(qkv[:, :D]), per(qkv[:, D:2 * D]), per(qkv[:, 2 * D:])
-    K = torch.cat([kc0[..., :t0, :].double(), Kc], 3); V = torch.cat([vc0[..., :t0, :].double(), Vc], 3)
-    sc = Q @ K.transpose(-1, -2) / 8.0
-    allowed = torch.arange(t0 + c, device=dev)[None, :] <= (t0 + torch.arange(c, device=dev))[:, None]
-    ref = torch.softmax(sc.masked_fill(~allowed, float('-inf')), -1) @ V
+    ref, V = f64_cached_attention(qkv, kc0, vc0, B, c, S, heads, t0)              # on the same (rounded) inputs
     got = out.view(B, c, S, heads, 64)[:, :, 1:].permute(0, 2, 3, 1, 4).double()
     err = float((got - ref).abs().max())
     if dt == torch.float32:
@@ -126,15 +98,6 @@ def test_cls_stream_vs_torch(cuda):
 
 
 # ---------------------------------------------------------------------------------------------- streams vs goldens / clip forward
-
-def _check_vs(om, fl, ref_mask, ref_flags, precision, gold_mask, gold_flags):
-    d = float((om - ref_mask).abs().max())
-    df = float((fl - ref_flags).abs().max())
-    if precision in EXACT:
-        assert d < EXACT[precision] and df < EXACT[precision], (d, df)
-    else:
-        assert d < h16(precision) * bf16_tol(gold_mask) and df < h16f(precision) * bf16_flags_tol(gold_flags), (d, df)
-
 
 @pytest.mark.parametrize('name', ['g1_cfg1_d256', 'g2_ca2', 'g2_normemb_nearest', 'g2_stride1_prenorm', 'g2_stride2', 'g11_depth18', 'g11_depth24',
                                   'g17_resize_a'])

@@ -12,7 +12,8 @@ import pytest
 import torch
 
 from conftest import build_hip_seeker, golden_inputs, load_golden
-from tcow_amd import _lib, ops, stream, synth
+from stream_kit import _i32, _to_pages as _pages_filled, f64_cached_attention, synth_clips, synth_net
+from tcow_amd import _lib, ops, stream
 from tcow_amd._lib import TcowError
 
 pytestmark = pytest.mark.gpu
@@ -51,10 +52,6 @@ def _pattern(shape, cdt, seed):
     return torch.randint(0, 256, (*shape[:-1], shape[-1] * es), dtype=torch.uint8, device='cuda', generator=g).view(cdt)
 
 
-def _i32(v):
-    return torch.tensor(list(v), dtype=torch.int32, device='cuda')
-
-
 def _per(x, B, c, S, heads):
     """Rows (b*c + j)*S + s of a [B*c*S, heads*64] block -> (B, S-1, heads, c, 64), slot 0 dropped: the layout of a cache."""
     return x.view(B, c, S, heads, 64)[:, :, 1:].permute(0, 2, 3, 1, 4)
@@ -75,12 +72,7 @@ def _inputs(mode, cdt, B, c, S, heads, T_total, t0, seed):
 
 def _f64_reference(qkv, kc0, vc0, cdt, B, c, S, heads, t0):
     """(B, S-1, heads, c, 64) f64: q unrounded, keys / values < t0 decoded from the cache, the chunk's own through _enc; and max |V|."""
-    D = heads * 64
-    Q = _per(qkv[:, :D], B, c, S, heads).double()
-    Kn, Vn = (_dec(_enc(_per(qkv[:, o:o + D], B, c, S, heads).contiguous(), cdt)) for o in (D, 2 * D))
-    K = torch.cat([_dec(kc0[..., :t0, :]), Kn], 3); V = torch.cat([_dec(vc0[..., :t0, :]), Vn], 3)
-    allowed = torch.arange(t0 + c, device='cuda')[None, :] <= (t0 + torch.arange(c, device='cuda'))[:, None]
-    ref = torch.softmax((Q @ K.transpose(-1, -2) / 8.0).masked_fill(~allowed, float('-inf')), -1) @ V
+    ref, V = f64_cached_attention(qkv, kc0, vc0, B, c, S, heads, t0, own=lambda x: _dec(_enc(x.contiguous(), cdt)), cached=_dec)
     return ref, float(V.abs().max())
 
 
@@ -274,13 +266,7 @@ def test_compact_pool_and_ragged_forms_equal_the_stream_form(cuda, pair):
 
 def _to_pages(cache, page_of, n_pages, P, seed):
     """Contiguous caches [n, S-1, heads, T_total, 64] -> page arrays [n_pages, S-1, heads, P, 64] under page_of[r][q]; everything else random bytes."""
-    n, Sm, heads, T_total, _ = cache.shape
-    pages = _pattern((n_pages, Sm, heads, P, 64), cache.dtype, seed)
-    for r in range(n):
-        for q, pg in enumerate(page_of[r]):
-            lo, hi = q * P, min(T_total, q * P + P)
-            _b(pages)[pg, :, :, :hi - lo] = _b(cache)[r, :, :, lo:hi]
-    return pages
+    return _pages_filled(cache, page_of, n_pages, P, _pattern((n_pages, *cache.shape[1:3], P, 64), cache.dtype, seed))
 
 
 @pytest.mark.parametrize('P,T_total', [(1, 70), (4, 30)])
@@ -463,14 +449,12 @@ TINY_T = 8
 
 @functools.lru_cache(maxsize=None)
 def _tiny_net(precision, ca):
-    cfg = synth.seeker_config(num_total_frames=TINY_T, frame_height=32, frame_width=48, embed_dim=128, depth=2, num_heads=2, causal_attention=ca)
-    return build_hip_seeker(cfg, synth.make_state_dict(cfg, 9), precision).cuda().eval()
+    return synth_net(precision, TINY_T, 32, 48, embed_dim=128, depth=2, num_heads=2, ca=ca, seed=9)
 
 
 @functools.lru_cache(maxsize=None)
 def _tiny_clips():
-    clip = synth.make_clip(2, TINY_T, 32, 48, seed=4)
-    return torch.from_numpy(clip['rgb']).cuda(), torch.from_numpy(synth.make_query_mask(clip, 0, 0)).cuda()
+    return synth_clips(2, TINY_T, 32, 48, seed=4)
 
 
 def _stream_split(net, rgb, qm, split, **kw):

@@ -8,29 +8,18 @@ import pytest
 import torch
 
 from conftest import build_hip_seeker, golden_inputs, load_golden
-from test_gpu_stream import PRECISIONS, _check_vs
-from test_gpu_stream_pool import MODES, _cat, _pool_step, _small_clips, _small_net
-from test_gpu_stream_ragged import CHUNK_LISTS, _i32, _ragged_launch, _ragged_step, _run_ragged, _t0_sets, _tables
+from stream_kit import (CHUNK_LISTS, MODES, PRECISIONS, _check_vs, _i32, _pool_step, _ragged_launch, _ragged_step, _run_ragged, _small_clips,
+                        _small_net, _t0_sets, _tables, _to_pages as _pages_filled)
 from tcow_amd import _lib, ops, stream, synth
 from tcow_amd._lib import TcowError
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = 7.0                                                  # what unowned pages (and the tail of a session's last page) hold: finite, exact in every type
+_to_pages = functools.partial(_pages_filled, fill=SENTINEL)     # (caches, page_of, n_pages, P) -> page arrays; everything else SENTINEL
 
 
 # ---------------------------------------------------------------------------------------------- kernel
-
-def _to_pages(kc, page_of, n_pages, P):
-    """Contiguous caches [n, S-1, heads, T_total, 64] -> page arrays [n_pages, S-1, heads, P, 64] under page_of[r][q]; everything else SENTINEL."""
-    n, Sm, heads, T_total, _ = kc.shape
-    pages = torch.full((n_pages, Sm, heads, P, 64), SENTINEL, device=kc.device).to(kc.dtype)
-    for r in range(n):
-        for q, pg in enumerate(page_of[r]):
-            lo, hi = q * P, min(T_total, q * P + P)
-            pages[pg, :, :, :hi - lo] = kc[r, :, :, lo:hi]
-    return pages
-
 
 def _page_table(n, T_total, P, extra, rng):
     """A non-identity injection of the (session, page index) pairs into n * pps + extra page ids."""

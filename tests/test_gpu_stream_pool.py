@@ -6,14 +6,11 @@ import pytest
 import torch
 
 from conftest import build_hip_seeker, golden_inputs, load_golden
-from test_gpu_stream import PRECISIONS, _check_vs, _stream
+from stream_kit import MODES, PRECISIONS, _cat, _check_vs, _pool_step, _small_clips, _small_net, _stream, f64_cached_attention
 from tcow_amd import ops, synth
 from tcow_amd._lib import TcowError
 
 pytestmark = pytest.mark.gpu
-
-MODES = {'f32': ops.F32, 'bf16': ops.BF16, 'fp16': ops.FP16, 'x3': ops.F32X3}
-
 
 # ---------------------------------------------------------------------------------------------- kernels
 
@@ -31,17 +28,6 @@ def _slots_and_t0(n, c, T_total, n_slots, rng):
         t0.append(int(rest.pop()) if rest else T_total - c)
     order = rng.permutation(n)
     return slots, [t0[i] for i in order]
-
-
-def _f64_row(qkv, kc0, vc0, c, S, heads, t0):
-    """_attn_case's f64 restatement for one row: qkv [c*S, 3D], kc0 / vc0 [S-1, heads, T_total, 64] before the launch -> (ref [S-1, heads, c, 64], V)."""
-    D = heads * 64
-    per = lambda x: x.double().view(c, S, heads, 64)[:, 1:].permute(1, 2, 0, 3)
-    Q, Kc, Vc = per(qkv[:, :D]), per(qkv[:, D:2 * D]), per(qkv[:, 2 * D:])
-    K = torch.cat([kc0[..., :t0, :].double(), Kc], 2); V = torch.cat([vc0[..., :t0, :].double(), Vc], 2)
-    sc = Q @ K.transpose(-1, -2) / 8.0
-    allowed = torch.arange(t0 + c, device=qkv.device)[None, :] <= (t0 + torch.arange(c, device=qkv.device))[:, None]
-    return torch.softmax(sc.masked_fill(~allowed, float('-inf')), -1) @ V, V
 
 
 def _pool_case(mode_name, n, c, S, heads, T_total, n_slots, causal, seed, t0_rows=None):
@@ -73,7 +59,7 @@ def _pool_case(mode_name, n, c, S, heads, T_total, n_slots, causal, seed, t0_row
     assert torch.equal(out, out_r), tag
     assert torch.equal(kc, kc_r) and torch.equal(vc, vc_r), tag                       # the whole tensors: unnamed slots bit-unchanged
     for r in range(n):
-        ref, V = _f64_row(qkv[r * R:(r + 1) * R], kc0[slots[r]], vc0[slots[r]], c, S, heads, t0s[r])
+        ref, V = (x[0] for x in f64_cached_attention(qkv[r * R:(r + 1) * R], kc0[slots[r]][None], vc0[slots[r]][None], 1, c, S, heads, t0s[r]))
         got = out[r * R:(r + 1) * R].view(c, S, heads, 64)[:, 1:].permute(1, 2, 0, 3).double()
         err = float((got - ref).abs().max())
         print('pool kernel', tag, 'row', r, 'err', err)
@@ -152,24 +138,6 @@ def test_pool_kernels_refuse_bad_arguments(cuda):
 
 # ---------------------------------------------------------------------------------------------- pooled sessions
 
-def _cat(parts):
-    ms = torch.cat([m for m, _ in parts], 2)
-    return ms, (torch.cat([f for _, f in parts], 1) if parts[0][1] is not None else None)
-
-
-def _pool_step(pool, feeds, c=1):
-    """feeds: [(session id, rgb (1,3,T,H,W), qm (1,1,T,H,W))] -> {id: (mask, flags)} of the next c frames of each, taken at its own counter."""
-    ids = [f[0] for f in feeds]
-    t = [pool.frames_done(i) for i in ids]
-    rgb = torch.cat([f[1][:, :, t0:t0 + c] for f, t0 in zip(feeds, t)], 0)
-    qm = torch.cat([f[2][:, :, t0:t0 + c] for f, t0 in zip(feeds, t)], 0)
-    m, fl = pool.step(ids, rgb, qm)
-    assert tuple(m.shape[:1]) == (len(ids),) and m.shape[2] == c and m.dtype == torch.float32
-    for i, t0 in zip(ids, t):
-        assert pool.frames_done(i) == t0 + c
-    return {i: (m[k:k + 1], None if fl is None else fl[k:k + 1]) for k, i in enumerate(ids)}
-
-
 @pytest.mark.parametrize('name', ['g1_cfg1_d256', 'g2_ca2'])
 @pytest.mark.parametrize('precision', PRECISIONS)
 def test_pool_vs_reference_golden_and_clip_forward(cuda, name, precision):
@@ -204,19 +172,6 @@ def test_pool_vs_reference_golden_and_clip_forward(cuda, name, precision):
     _check_vs(om, fl, clip_m, clip_f, precision, g['output_mask'], g['output_flags'])
     lm, lf = _cat(got[lead])
     _check_vs(lm, lf, lead_m, lead_f, precision, g['output_mask'], g['output_flags'])
-
-
-def _small_net(precision, ca=1, seed=11):
-    """The config of test_stream_shared_rgb_and_batched_clips (its tolerances carry over): fp32 2e-5, bf16 1.5e-2."""
-    cfg = synth.seeker_config(num_total_frames=4, frame_height=64, frame_width=96, embed_dim=256, depth=2, num_heads=4, causal_attention=ca)
-    return build_hip_seeker(cfg, synth.make_state_dict(cfg, seed), precision).cuda().eval()
-
-
-def _small_clips(n, seed=5):
-    clip = synth.make_clip(n, 4, 64, 96, seed=seed)
-    rgb = torch.from_numpy(clip['rgb']).cuda()
-    qm = torch.from_numpy(synth.make_query_mask(clip, 0, 0)).cuda()
-    return [(rgb[b:b + 1], qm[b:b + 1]) for b in range(n)]
 
 
 @pytest.mark.parametrize('precision,tol', [('fp32', 2e-5), ('bf16', 1.5e-2)])

@@ -6,34 +6,15 @@ import pytest
 import torch
 
 from conftest import build_hip_seeker, golden_inputs, load_golden
-from test_gpu_stream import PRECISIONS, _check_vs, _stream
-from test_gpu_stream_pool import MODES, _cat, _f64_row, _pool_step, _small_clips, _small_net
+from stream_kit import (CHUNK_LISTS, MODES, PRECISIONS, _cat, _check_vs, _i32, _pool_step, _ragged_launch, _ragged_step, _run_ragged, _small_clips,
+                        _small_net, _stream, _t0_sets, _tables, f64_cached_attention)
 from tcow_amd import ops, stream, synth
 from tcow_amd._lib import TcowError
 
 pytestmark = pytest.mark.gpu
 
 
-def _i32(v, dev='cuda'):
-    return torch.tensor(list(v), dtype=torch.int32, device=dev)
-
-
-def _tables(t0s, slots, cs):
-    tab = stream.ragged_tables(t0s, slots, cs)
-    return {k: _i32(tab[k]) for k in ('t0', 'slot', 'first', 'c', 'row_of_frame')}, tab['first']
-
-
 # ---------------------------------------------------------------------------------------------- kernels
-
-def _ragged_launch(mode, cs, S, heads, causal, T_total, n_slots, t0s, slots, qkv, kc, vc, fill=float('nan')):
-    """One ragged launch into a NaN-poisoned (or `fill`ed) output; returns it."""
-    F, D = sum(cs), heads * 64
-    tb, _ = _tables(t0s, slots, cs)
-    out = torch.full((F * S, D), fill, device=qkv.device).to(qkv.dtype)
-    ops.attn_temporal_ragged(mode, len(cs), F, S, D, heads, causal, T_total, n_slots, tb['t0'], tb['slot'], tb['first'], tb['c'], tb['row_of_frame'],
-                             qkv, kc, vc, out)
-    return out
-
 
 def _ragged_case(mode_name, cs, S, heads, T_total, n_slots, causal, seed, t0s):
     dev = torch.device('cuda')
@@ -63,7 +44,7 @@ def _ragged_case(mode_name, cs, S, heads, T_total, n_slots, causal, seed, t0s):
     assert torch.equal(kc, kc_r) and torch.equal(vc, vc_r), tag               # the whole tensors: unnamed slots and positions outside [t0, t0 + c) bit-unchanged
     for r in range(n):
         lo, hi = first[r] * S, (first[r] + cs[r]) * S
-        ref, V = _f64_row(qkv[lo:hi], kc0[slots[r]], vc0[slots[r]], cs[r], S, heads, t0s[r])
+        ref, V = (x[0] for x in f64_cached_attention(qkv[lo:hi], kc0[slots[r]][None], vc0[slots[r]][None], 1, cs[r], S, heads, t0s[r]))
         got = out[lo:hi].view(cs[r], S, heads, 64)[:, 1:].permute(1, 2, 0, 3).double()
         err = float((got - ref).abs().max())
         print('ragged kernel', tag, 'session', r, 'err', err)
@@ -72,20 +53,6 @@ def _ragged_case(mode_name, cs, S, heads, T_total, n_slots, causal, seed, t0s):
         else:
             assert err <= ((2.0 ** -8 if dt == torch.bfloat16 else 2.0 ** -11) + 1e-5) * float(V.abs().max()), (tag, r, err)
         assert float(out[lo:hi].view(cs[r], S, D)[:, 0].float().abs().max()) == 0.0, tag       # slot-0 rows: zero
-
-
-def _t0_sets(cs, T_total, rng):
-    """The t0 lists of a chunk-length list: one session at 0 and one at T_total - c_r in each (a single session: one list per end)."""
-    n = len(cs)
-    if n == 1:
-        return [[0], [T_total - cs[0]]]
-    t0s = [int(rng.integers(0, T_total - c + 1)) for c in cs]
-    a, b = (int(v) for v in rng.permutation(n)[:2])
-    t0s[a], t0s[b] = 0, T_total - cs[b]
-    return [t0s]
-
-
-CHUNK_LISTS = [([1], 4), ([1], 30), ([3], 4), ([3], 30), ([1, 3, 2], 30), ([4, 1, 1], 30), ([9, 1], 30)]
 
 
 @pytest.mark.parametrize('mode', ['f32', 'bf16', 'fp16'])
@@ -242,39 +209,6 @@ def test_ragged_kernels_refuse_bad_arguments(cuda):
 
 
 # ---------------------------------------------------------------------------------------------- ragged sessions
-
-def _ragged_step(pool, feeds, cs):
-    """feeds: [(session id, rgb (1,3,T,H,W), qm (1,1,T,H,W))], cs: a chunk length per feed -> {id: (mask, flags)} of the next cs[k] frames of each,
-    taken at its own counter."""
-    ids = [f[0] for f in feeds]
-    t = [pool.frames_done(i) for i in ids]
-    rgbs = [f[1][:, :, t0:t0 + c] for f, t0, c in zip(feeds, t, cs)]
-    qms = [f[2][:, :, t0:t0 + c] for f, t0, c in zip(feeds, t, cs)]
-    ms, fls = pool.step_ragged(ids, rgbs, qms)
-    assert len(ms) == len(ids) and (fls is None or len(fls) == len(ids))
-    for k, (i, t0, c) in enumerate(zip(ids, t, cs)):
-        assert ms[k].shape[0] == 1 and ms[k].shape[2] == c and ms[k].dtype == torch.float32 and tuple(ms[k].shape[3:]) == tuple(feeds[k][1].shape[3:])
-        assert fls is None or tuple(fls[k].shape[:2]) == (1, c)
-        assert pool.frames_done(i) == t0 + c
-    return {i: (ms[k], None if fls is None else fls[k]) for k, i in enumerate(ids)}
-
-
-def _run_ragged(pool, clips, T, opens, cycle=(1, 2, 3)):
-    """Session b opens at step opens[b] and advances by chunk lengths cycling through `cycle`, offset per session and truncated at T."""
-    ids, got, step = {}, {b: [] for b in range(len(clips))}, 0
-    while len(ids) < len(clips) or any(pool.frames_done(i) < T for i in ids.values()):
-        for b in range(len(clips)):
-            if opens[b] == step:
-                ids[b] = pool.open()
-        rows = [b for b in ids if pool.frames_done(ids[b]) < T]
-        if rows:
-            cs = [min(cycle[(step + b) % len(cycle)], T - pool.frames_done(ids[b])) for b in rows]
-            out = _ragged_step(pool, [(ids[b], *clips[b]) for b in rows], cs)
-            for b in rows:
-                got[b].append(out[ids[b]])
-        step += 1
-    return [_cat(got[b]) for b in range(len(clips))]
-
 
 @pytest.mark.parametrize('name', ['g1_cfg1_d256', 'g2_ca2'])
 @pytest.mark.parametrize('precision', PRECISIONS)

@@ -12,7 +12,7 @@ import functools
 import pytest
 import torch
 
-from test_gpu_stream_pool import _small_net
+from stream_kit import _small_net
 from tcow_amd import engine, ops, synth
 from tcow_amd._lib import TcowError
 

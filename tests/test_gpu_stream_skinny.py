@@ -5,9 +5,9 @@ and embed_dim 768 (K = 768, and K = 3072 with a split above 1), at 32 x 48 pixel
 import pytest
 import torch
 
-from conftest import build_hip_seeker
+from stream_kit import synth_clips, synth_net
 from test_gpu_seeker import X3_TOL
-from tcow_amd import ops, synth
+from tcow_amd import ops
 
 pytestmark = pytest.mark.gpu
 
@@ -27,17 +27,11 @@ def _leave_no_scratch():
 
 
 def _net(which, precision, ca=1, seed=11):
-    cfg = synth.seeker_config(num_total_frames=T, frame_height=H, frame_width=W, causal_attention=ca, **NETS[which])
-    return build_hip_seeker(cfg, synth.make_state_dict(cfg, seed), precision).cuda().eval()
+    return synth_net(precision, T, H, W, ca=ca, seed=seed, **NETS[which])
 
 
 def _clips(n, seed=5):
-    clip = synth.make_clip(n, T, H, W, seed=seed)
-    rgb = torch.from_numpy(clip['rgb']).cuda()
-    qm = torch.from_numpy(synth.make_query_mask(clip, 0, 0)).cuda()
-    if qm.shape[0] != n:
-        qm = qm.expand(n, -1, -1, -1, -1).contiguous()
-    return rgb, qm
+    return synth_clips(n, T, H, W, seed)
 
 
 def _stream(net, rgb, qm, split, **kw):

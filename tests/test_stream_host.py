@@ -3,14 +3,9 @@ import pytest
 import torch
 
 from conftest import build_hip_seeker
+from stream_kit import _net
 from tcow_amd import engine, synth
 from tcow_amd._lib import TcowError
-
-
-def _net(ca=1, attention_type='divided_space_time'):
-    from tcow_amd.seeker import Seeker
-    return Seeker(None, num_total_frames=4, frame_height=32, frame_width=48, network_depth=1, embed_dim=64, num_heads=1, causal_attention=ca,
-                  attention_type=attention_type, drop_path_rate=0.0, precision='fp32')
 
 
 @pytest.mark.parametrize('ca', [0, -1, 3])

@@ -1,12 +1,12 @@
 """CPU: the host side of a paged stream pool (stream_pool(page_frames=P, pages=N), tcow_amd/stream.py) -- the page allocator against a set-based
-model, the keyword checks, and the ABI entry of the paged attention kernel."""
+model, the page moves of a rollover call against the accounting they replaced, the keyword checks, and the ABI entry of the paged attention kernel."""
 import os
 import re
 
 import numpy as np
 import pytest
 
-from test_stream_host import _net
+from stream_kit import _net
 from tcow_amd import _lib, stream
 from tcow_amd._lib import TcowError
 
@@ -119,6 +119,93 @@ def test_allocator_lowest_free_first_after_random_releases():
     a.release('d'); a.release('b')                                              # pages 6, 7 and 2, 3 come back
     assert a.grow(['f'], [3]) == [(2, 3, 6)]
     assert a.grow(['g'], [1]) == [(7,)] and a.free == 0
+
+
+def test_allocator_copy_is_independent():
+    a = stream.PageAllocator(6, 2)
+    a.grow(['x', 'y'], [3, 1])
+    b = a.copy()
+    assert (b.n_pages, b.P, b.free, b.pages_of('x'), b.pages_of('y')) == (6, 2, 3, (0, 1), (2,))
+    b.grow(['y', 'z'], [4, 2]); b.release('x')
+    assert (a.free, a.pages_of('x'), a.pages_of('y'), a.pages_of('z')) == (3, (0, 1), (2,), ())
+    assert (b.free, b.pages_of('x'), b.pages_of('y'), b.pages_of('z')) == (3, (), (2, 3), (4,))
+    a.release('y')
+    assert b.pages_of('y') == (2, 3)
+
+
+def _old_page_check(a, T, ids, splits):
+    """The page accounting a rollover call used to do with counters of its own before anything was launched, restated as the oracle: part by
+    part, what the rows lack against what is free, a window that ends in a part giving its pages back to the next.  -> None, or (needed, free)
+    of the part that is refused."""
+    free, held = a.free, {}
+    for p in range(2):
+        need, ended = 0, []
+        for sid, sp in zip(ids, splits):
+            for w, t0, c, _ in (sp['parts'][p] if p < len(sp['parts']) else ()):
+                key = (sid, w & 1)
+                have = held.setdefault(key, len(a.pages_of(key)))
+                want = max(have, -(-(t0 + c) // a.P))
+                need += want - have
+                held[key] = want
+                if t0 + c == T:
+                    ended.append(key)
+        if need > free:
+            return need, free
+        free += sum(held[key] for key in ended) - need
+        held.update((key, 0) for key in ended)
+    return None
+
+
+@pytest.mark.parametrize('T', [4, 5, 8, 30])
+def test_rollover_page_moves_decide_as_the_old_accounting_did(T):
+    """Random calls of 1 .. 4 sessions on pools from a third of the peak to above it, every k, P in 1, 2, 4, 8: a run of rollover_page_moves on a
+    copy of the allocator refuses exactly the calls the old accounting refused, with the same message, and moves nothing; the real run then
+    leaves every window's pages as growing per part and releasing the ended windows afterwards did."""
+    rng = np.random.default_rng(7 + T)
+    calls = refused = 0
+    for k in range(1, T // 2 + 1):
+        plan = stream.RolloverPlan(T, k)
+        for P in (1, 2, 4, 8):
+            for _ in range(3):
+                n_sessions = int(rng.integers(1, 5))
+                peak = n_sessions * (-(-T // P) + -(-k // P))
+                a = stream.PageAllocator(int(rng.integers(max(1, peak // 3), peak + 3)), P)
+                done = [0] * n_sessions
+                for _ in range(40):
+                    ids = [int(i) for i in rng.permutation(n_sessions)[:int(rng.integers(1, n_sessions + 1))]]
+                    cs = [int(rng.integers(1, plan.s + 1)) for _ in ids]
+                    g0s = [done[i] for i in ids]
+                    old = _old_page_check(a, T, ids, [plan.split(g0, c) for g0, c in zip(g0s, cs)])
+                    call = stream.RolloverCall(plan, g0s, cs)
+                    before = (a.free, {key: a.pages_of(key) for i in range(n_sessions) for key in ((i, 0), (i, 1))})
+                    calls += 1
+                    try:
+                        trial = a.copy()
+                        for rows in call.parts:
+                            stream.rollover_page_moves(trial, T, ids, rows)
+                    except TcowError as e:
+                        refused += 1
+                        assert old is not None and str(e) == (f'stream_pool: out of pages: this step needs {old[0]} more page(s) of {P} frame(s), {old[1]} of '
+                                                              f'{a.n_pages} are free; close() or reset() a session, or open the pool with more pages')
+                        assert before == (a.free, {key: a.pages_of(key) for key in before[1]})
+                        i = ids[int(rng.integers(len(ids)))]                    # the caller makes room: reset() of one of the sessions
+                        a.release((i, 0)); a.release((i, 1))
+                        done[i] = 0
+                        continue
+                    assert old is None and before == (a.free, {key: a.pages_of(key) for key in before[1]})
+                    ref = a.copy()
+                    for rows in call.parts:                                    # as the pool used to: grow, launch, then release
+                        keys = [(ids[r.k], r.w & 1) for r in rows]
+                        want = ref.grow(keys, [r.t0 + r.c for r in rows])
+                        assert stream.rollover_page_moves(a, T, ids, rows) == want
+                        for key, r in zip(keys, rows):
+                            if r.t0 + r.c == T:
+                                ref.release(key)
+                        assert a.free == ref.free
+                    assert (trial.free, trial._pages) == (a.free, a._pages) == (ref.free, ref._pages)
+                    for i, c in zip(ids, cs):
+                        done[i] += c
+    assert calls >= 400 and refused >= calls // 20, (calls, refused)
 
 
 # ---------------------------------------------------------------------------------------------- keywords

@@ -3,7 +3,7 @@ and a pool without a slot."""
 import pytest
 
 from conftest import build_hip_seeker
-from test_stream_host import _net
+from stream_kit import _net
 from tcow_amd import synth
 from tcow_amd._lib import TcowError
 

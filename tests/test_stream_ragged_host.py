@@ -3,7 +3,7 @@ argument refusals that look at the lists alone, and the ABI entries."""
 import pytest
 import torch
 
-from test_stream_host import _net
+from stream_kit import _net
 from tcow_amd import _lib, stream
 from tcow_amd._lib import TcowError
 

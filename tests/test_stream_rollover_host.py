@@ -5,7 +5,7 @@ import re
 
 import pytest
 
-from test_stream_host import _net
+from stream_kit import _net
 from tcow_amd import _lib, stream
 from tcow_amd._lib import TcowError
 
@@ -75,6 +75,75 @@ def test_chunk_splits(T, k):
             assert frames == list(range(w * s, w * s + len(frames))) and len(frames) <= T
             if (w + 1) * s + k <= g0 - c:                       # windows that must have ended by now are complete
                 assert len(frames) == T
+
+
+def _call(plan, g0s, cs, keep, fed, handed):
+    """One call of a rollover pool as SeekerRolloverPool._roll runs a RolloverCall, with lists of frame ids in place of tensors and a stand-in
+    forward that returns (session, window, local frame) per flat frame.  Session i stands at g0s[i] and brings cs[i] frames; keep[i]: the frame
+    it retained or None, fed[i]: {window: frames given so far}, handed[i]: the windows whose hand-off mask has been made -- all updated."""
+    s, n = plan.s, len(g0s)
+    call = stream.RolloverCall(plan, g0s, cs)
+    chunks = [list(range(g0, g0 + c)) for g0, c in zip(g0s, cs)]
+    outs = []
+    for p, rows in enumerate(call.parts):
+        first = stream.ragged_tables([r.t0 for r in rows], [0] * len(rows), [r.c for r in rows])['first']
+        out = []
+        for r, f0 in zip(rows, first):
+            assert r.first == f0 == len(out) and r.t0 == r.g - r.w * s
+            frames = ([keep[r.k]] if r.kept else []) + chunks[r.k][r.lo:r.hi]
+            assert frames == list(range(r.g, r.g + r.c))        # exactly its frames, in order, the retained frame included
+            assert fed[r.k].get(r.w, 0) == r.t0                 # nothing twice, nothing skipped
+            fed[r.k][r.w] = r.t0 + r.c
+            queries = (['hand-off'] if r.handed else []) + [('caller', g) for g in chunks[r.k][r.qlo:r.hi]]
+            want = [('caller', g) for g in frames]
+            if r.w >= 1 and r.t0 == 0:                          # a window >= 1: the hand-off mask at its local frame 0, made before this part
+                want[0] = 'hand-off'
+                assert r.w in handed[r.k]
+            assert queries == want
+            out += [(r.k, r.w, r.t0 + j) for j in range(r.c)]
+        outs.append(out)
+        if p == 0:
+            for i, born, f in call.handoffs:                    # the source: where window born - 1 processed the hand-off frame
+                assert born * s in chunks[i] and out[f] == (i, born - 1, born * s - (born - 1) * s)
+                handed[i].add(born)
+    assert [i for i, _, _ in call.handoffs] == [i for i in range(n) if any(plan.is_handoff(g) for g in chunks[i])]
+    follows = any(plan.is_handoff(g) for ch in chunks for g in ch[:-1])
+    assert len(call.parts) == (2 if follows else 1)
+    for i in range(n):
+        assert call.keep[i] == plan.is_handoff(chunks[i][-1])
+        keep[i] = chunks[i][-1] if call.keep[i] else None
+        reported = [outs[p][f + j] for p, f, c in call.report[i] for j in range(c)]
+        assert reported == [(i, plan.window(g), g - plan.window(g) * s) for g in chunks[i]]
+    return call
+
+
+@pytest.mark.parametrize('T,k', CASES)
+def test_a_call_feeds_every_window_and_reports_every_frame(T, k):
+    """RolloverCall by brute force (_call above holds the assertions): every start g0 < 4T with every allowed c, beside a second session out of
+    phase, from the state that one frame per call leaves; then two sessions fed in chunks of 1, 2 and s, the second a call behind."""
+    plan, s, G = stream.RolloverPlan(T, k), T - k, 4 * T
+    keep, fed, handed, snap = [None], [{}], [set()], []
+    for g in range(G):
+        snap.append((keep[0], dict(fed[0]), set(handed[0])))
+        _call(plan, [g], [1], keep, fed, handed)
+    for g0 in range(G):
+        for c in range(1, s + 1):
+            g1, c1 = (g0 + 2) % G, 1 + (g0 + c) % s
+            _call(plan, [g0, g1], [c, c1], [snap[g0][0], snap[g1][0]], [dict(snap[g0][1]), dict(snap[g1][1])], [set(snap[g0][2]), set(snap[g1][2])])
+    for c in sorted({1, 2, s}):
+        keep, fed, handed, done = [None, None], [{}, {}], [set(), set()], [0, 0]
+        for call_no in range(G // c):
+            live = [0] if call_no == 0 else [1, 0]
+            kp = [keep[i] for i in live]
+            _call(plan, [done[i] for i in live], [c] * len(live), kp, [fed[i] for i in live], [handed[i] for i in live])
+            for j, i in enumerate(live):
+                keep[i], done[i] = kp[j], done[i] + c
+        for i in (0, 1):
+            assert sorted(fed[i]) == list(range(len(fed[i]))) and len(fed[i]) >= 3
+            for w, count in fed[i].items():
+                assert count <= T
+                if (w + 1) * s + k <= done[i] - c:              # windows that must have ended by now are complete
+                    assert count == T
 
 
 def test_refusals():

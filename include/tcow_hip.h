@@ -57,7 +57,7 @@ extern "C" {
 
 /* ABI version (bumped on any signature change) and last error text of the calling thread.  A host compares tcow_version() with the TCOW_ABI_VERSION it
  * was built against before the first call (tcow_amd/_lib.py does, for both builds of the library). */
-#define TCOW_ABI_VERSION 14
+#define TCOW_ABI_VERSION 15
 int tcow_version(void);
 const char* tcow_last_error(void);
 
@@ -459,26 +459,27 @@ long tcow_cast_desc_bytes(void);
 int tcow_cast_transpose_batched(void* stream, int dtype, const void* table, int n, int total_tiles);
 
 /* ------------------------------------------------------------------------------------------- optimizer step
- * clip_grad_norm_(params, max_norm) followed by AdamW.step() (train.py:99-102; torch defaults) in three
- * launches over a device-resident chunk table: records {float* p; const float* g; float* m; float* v; long n} of
- * tcow_adamw_chunk_bytes() bytes each, n <= 65536.  scratch: f32 [n_chunks + 2]; afterwards scratch[n_chunks] is the clip
- * coefficient and scratch[n_chunks + 1] the total gradient norm.  max_norm <= 0 disables clipping.  step counts from 1. */
+ * clip_grad_norm_(params, max_norm) followed by AdamW.step() (train.py:99-102; torch defaults) in three launches over
+ * device-resident tables: squared-norm partials per chunk -> clip coefficient -> update.  One entry point since ABI 15.  Chunk records are
+ * {float* p; const float* g; float* m; float* v; long n} (tcow_adamw_chunk_bytes() bytes; all f32, 16-byte aligned starts).  Tile records are
+ * {float* p; const float* g; float* m; float* v; void* wc; void* wt; int K, N;} (tcow_adamw_tile_bytes() bytes): one 64 x 64 tile of a GEMM weight [N, K]
+ * (multiples of 64), the pointers at the tile's origin in p / g / m / v / wc ([N, K], row stride K) and wt ([K, N], row stride N); wc / wt receive the updated
+ * values in this library's 16-bit format (instead of tcow_cast_transpose_batched).  A table whose count is 0 may be NULL; its kernel is not launched. */
+typedef struct {
+    const void* chunks;       int n_chunks;   /* every parameter: the gradient norm is taken over them, partial sums in this order */
+    const void* flat_chunks;  int n_flat;     /* what the flat kernel updates: the chunk table itself when nothing is tiled */
+    const void* tiles;        int n_tiles;    /* the weights updated tile by tile, their 16-bit operand copies written along */
+    float lr, beta1, beta2, eps, weight_decay;
+    int step;                                 /* number of calls so far (>= 1); the bias correction uses step - scratch[n_chunks + 2]: the updates actually applied */
+    float max_norm;                           /* <= 0 disables clipping */
+    float* scratch;                           /* f32 [n_chunks + 3]: partial sums | clip coefficient (-1 = the norm was not finite and the step was SKIPPED: nothing
+                                               * written), total gradient norm, steps skipped so far (+= 1 per skip; the caller zeroes it once; device side, no sync) */
+    const float* grad_inv_scale;              /* the gradients are still multiplied by a loss scale (binary16 training): device scalar, a power of two, its inverse; NULL = 1.
+                                               * Norm and coefficient are the true gradients'; the update multiplies the stored ones by coefficient x inverse scale: exact */
+} tcow_adamw_args;
 long tcow_adamw_chunk_bytes(void);
-int tcow_adamw_clip_step(void* stream, const void* chunks, int n_chunks, float lr, float beta1, float beta2, float eps,
-                         float weight_decay, int step, float max_norm, float* scratch);
-/* The same on gradients that are still multiplied by a loss scale (binary16 training): *grad_inv_scale (device scalar, a power of two; NULL = 1) is
- * the inverse scale.  The norm and the clip coefficient are those of the true gradients, the update multiplies the stored gradients by
- * coefficient x inverse scale -- exact, and the separate unscaling pass over all gradients is gone.  (ABI 9) */
-int tcow_adamw_clip_step_scaled(void* stream, const void* chunks, int n_chunks, float lr, float beta1, float beta2, float eps,
-                                float weight_decay, int step, float max_norm, float* scratch, const float* grad_inv_scale);
-/* The same step with the 16-bit operand copies of the GEMM weights written by the update itself (ABI 10): chunks[0 .. n_chunks) cover every parameter (gradient
- * norm); flat_chunks[0 .. n_flat) the ones updated flat, the others as 64 x 64 tiles -- tiles[0 .. n_tiles) = records of tcow_adamw_tile_bytes() bytes
- * {float* p; const float* g; float* m; float* v; void* wc; void* wt; int K, N;} with the pointers at the tile's origin in p / g / m / v / wc ([N, K], row
- * stride K) and wt ([K, N], row stride N); wc / wt receive the updated values in this library's 16-bit format.  Replaces tcow_cast_transpose_batched for
- * those weights (one read of 4 bytes per parameter less per step). */
 long tcow_adamw_tile_bytes(void);
-int tcow_adamw_clip_step_cast(void* stream, const void* chunks, int n_chunks, const void* flat_chunks, int n_flat, const void* tiles, int n_tiles, float lr, float beta1,
-                              float beta2, float eps, float weight_decay, int step, float max_norm, float* scratch, const float* grad_inv_scale);
+int tcow_adamw_clip_step(void* stream, const tcow_adamw_args* args);
 
 /* ------------------------------------------------------------------------------------------- mask objective (caller row L)
  * One channel of the TCOW mask loss, forward value and d(loss)/d(logits) together (loss.py:164-225, with

@@ -67,6 +67,12 @@ class MaskLossArgs(ctypes.Structure):
                 ('ws', ctypes.c_void_p), ('ws_bytes', ctypes.c_size_t), ('focal', ctypes.c_int)]
 
 
+class AdamwArgs(ctypes.Structure):
+    _fields_ = [('chunks', ctypes.c_void_p), ('n_chunks', ctypes.c_int), ('flat_chunks', ctypes.c_void_p), ('n_flat', ctypes.c_int), ('tiles', ctypes.c_void_p), ('n_tiles', ctypes.c_int),
+                ('lr', ctypes.c_float), ('beta1', ctypes.c_float), ('beta2', ctypes.c_float), ('eps', ctypes.c_float), ('weight_decay', ctypes.c_float),
+                ('step', ctypes.c_int), ('max_norm', ctypes.c_float), ('scratch', ctypes.c_void_p), ('grad_inv_scale', ctypes.c_void_p)]
+
+
 _libs = {}
 
 _vp, _i, _l, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
@@ -141,10 +147,8 @@ SIGNATURES = {
     'tcow_cast_desc_bytes': (_l, []),
     'tcow_cast_transpose_batched': (_i, [_vp, _i, _vp, _i, _i]),
     'tcow_adamw_chunk_bytes': (_l, []),
-    'tcow_adamw_clip_step': (_i, [_vp, _vp, _i, _f, _f, _f, _f, _f, _i, _f, _vp]),
-    'tcow_adamw_clip_step_scaled': (_i, [_vp, _vp, _i, _f, _f, _f, _f, _f, _i, _f, _vp, _vp]),
     'tcow_adamw_tile_bytes': (_l, []),
-    'tcow_adamw_clip_step_cast': (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _f, _f, _f, _f, _f, _i, _f, _vp, _vp]),
+    'tcow_adamw_clip_step': (_i, [_vp, ctypes.POINTER(AdamwArgs)]),
     'tcow_mask_loss_workspace_bytes': (ctypes.c_size_t, [_l, _l]),
     'tcow_mask_loss_workspace_bytes_for': (ctypes.c_size_t, [_l, _l, ctypes.c_double, _f]),
     'tcow_mask_loss': (_i, [_vp, ctypes.POINTER(MaskLossArgs)]),
@@ -158,7 +162,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 14       # TCOW_ABI_VERSION of include/tcow_hip.h
+ABI_VERSION = 15      # TCOW_ABI_VERSION of include/tcow_hip.h
 
 
 def _declare(L, tolerant=False):

@@ -3,8 +3,7 @@
 // every parameter).  The reference's foreach implementation walks ~250 tensors from Python / ATen per step;
 // here a device-resident chunk table (<= 65536 elements per chunk) lets one grid cover every tensor.
 //   1. sumsq_kernel   : per-chunk sum of squares of the gradient
-//   2. clipcoef_kernel: total norm -> clip coefficient min(1, max_norm / (norm + 1e-6))   (torch.nn.utils.clip_grad_norm_);
-//                       a NaN / infinite norm -> -1 = "skip this step" (the update kernel returns at once)
+//   2. clipcoef_kernel: total norm -> clip coefficient min(1, max_norm / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_); NaN / infinite -> -1 = "skip this step"
 //   3. adamw_kernel   : p, m, v update with the clipped gradient (decoupled weight decay, bias correction as torch.optim.AdamW)
 #include "common.h"
 
@@ -49,24 +48,33 @@ __global__ __launch_bounds__(256) void clipcoef_kernel(const float* __restrict__
     }
 }
 
-__global__ __launch_bounds__(256) void adamw_kernel(const Chunk* __restrict__ chunks, const float* __restrict__ coef_ptr, float lr, float beta1, float beta2, float eps,
-                                                    float weight_decay, int step) {
-    const Chunk c = chunks[blockIdx.x];
-    const float coef = coef_ptr[0];
-    if (coef < 0.f) return;                        // non-finite gradients: parameters and moments stay as they are (like a GradScaler skip)
-    // bias correction with the number of updates actually APPLIED: the caller counts calls, skipped ones are subtracted here, so the moments
-    // and their correction stay in step after an overflow (torch's GradScaler does not advance the optimizer on a skipped step either)
-    const float eff = fmaxf((float)step - coef_ptr[2], 1.0f);
-    const float bc1 = 1.0f - powf(beta1, eff), bc2_sqrt = sqrtf(1.0f - powf(beta2, eff));
-    const float decay = 1.0f - lr * weight_decay, step_size = lr / bc1;
-    const long n4 = c.n >> 2;
-    auto upd = [&](float& p, float g, float& m, float& v) {
+// One element's update, and what of it is the same for every element of a step; both update kernels build it after their early return.  The bias correction
+// runs with the number of updates actually APPLIED: the caller counts calls, skipped ones (coef_ptr[2]) are subtracted here, so the moments and their
+// correction stay in step after an overflow (torch's GradScaler does not advance the optimizer on a skipped step either).
+struct AdamwUpdate {
+    float coef, beta1, beta2, eps, bc2_sqrt, decay, step_size;
+    __device__ __forceinline__ AdamwUpdate(float coef, const float* coef_ptr, float lr, float beta1, float beta2, float eps, float weight_decay, int step)
+        : coef(coef), beta1(beta1), beta2(beta2), eps(eps) {
+        const float eff = fmaxf((float)step - coef_ptr[2], 1.0f);
+        const float bc1 = 1.0f - powf(beta1, eff);
+        bc2_sqrt = sqrtf(1.0f - powf(beta2, eff)), decay = 1.0f - lr * weight_decay, step_size = lr / bc1;
+    }
+    __device__ __forceinline__ void operator()(float& p, float g, float& m, float& v) const {
         g *= coef;
         p *= decay;
         m = beta1 * m + (1.0f - beta1) * g;
         v = beta2 * v + (1.0f - beta2) * g * g;
         p -= step_size * m / (sqrtf(v) / bc2_sqrt + eps);
-    };
+    }
+};
+
+__global__ __launch_bounds__(256) void adamw_kernel(const Chunk* __restrict__ chunks, const float* __restrict__ coef_ptr, float lr, float beta1, float beta2, float eps,
+                                                    float weight_decay, int step) {
+    const Chunk c = chunks[blockIdx.x];
+    const float coef = coef_ptr[0];
+    if (coef < 0.f) return;                        // non-finite gradients: parameters and moments stay as they are (like a GradScaler skip)
+    const AdamwUpdate upd(coef, coef_ptr, lr, beta1, beta2, eps, weight_decay, step);
+    const long n4 = c.n >> 2;
     for (long i = threadIdx.x; i < n4; i += 256) {
         float4 p = ld4(c.p + i * 4), m = ld4(c.m + i * 4), v = ld4(c.v + i * 4);
         const float4 g = ld4(c.g + i * 4);
@@ -88,16 +96,7 @@ __global__ __launch_bounds__(256) void adamw_cast_kernel(const CastTile* __restr
     const float coef = coef_ptr[0];
     if (coef < 0.f) return;                        // skipped step: parameters unchanged, the copies stay valid
     const CastTile d = tiles[blockIdx.x];
-    const float eff = fmaxf((float)step - coef_ptr[2], 1.0f);
-    const float bc1 = 1.0f - powf(beta1, eff), bc2_sqrt = sqrtf(1.0f - powf(beta2, eff));
-    const float decay = 1.0f - lr * weight_decay, step_size = lr / bc1;
-    auto upd = [&](float& p, float g, float& m, float& v) {
-        g *= coef;
-        p *= decay;
-        m = beta1 * m + (1.0f - beta1) * g;
-        v = beta2 * v + (1.0f - beta2) * g * g;
-        p -= step_size * m / (sqrtf(v) / bc2_sqrt + eps);
-    };
+    const AdamwUpdate upd(coef, coef_ptr, lr, beta1, beta2, eps, weight_decay, step);
     const int c4 = (threadIdx.x & 15) * 4, r0 = threadIdx.x >> 4;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -125,51 +124,33 @@ extern "C" {
 long tcow_adamw_chunk_bytes(void) { return (long)sizeof(Chunk); }
 long tcow_adamw_tile_bytes(void) { return (long)sizeof(CastTile); }
 
-// tcow_adamw_clip_step_scaled with the operand copies of the GEMM weights written by the update itself (ABI 10).  chunks[0 .. n_chunks): every parameter
-// (the gradient norm is taken over all of them, partial sums in this order); flat_chunks[0 .. n_flat): the parameters the flat kernel updates; the others tile by tile:
-// tiles[0 .. n_tiles) = {p, g, m, v, wc, wt, K, N} records of 64 x 64 tiles (pointers at the tile's origin; N, K multiples of 64; wc / wt in this
-// library's 16-bit format).  scratch as in tcow_adamw_clip_step: f32 [n_chunks + 3].
-int tcow_adamw_clip_step_cast(void* stream, const void* chunks, int n_chunks, const void* flat_chunks, int n_flat, const void* tiles, int n_tiles, float lr, float beta1,
-                              float beta2, float eps, float weight_decay, int step, float max_norm, float* scratch, const float* grad_inv_scale) {
-    TCOW_CHECK_ARG(chunks && scratch && n_chunks > 0 && step >= 1 && n_flat >= 0 && (flat_chunks || n_flat == 0) && n_tiles >= 0 && (tiles || n_tiles == 0),
-                   "tcow_adamw_clip_step_cast: bad arguments");
-    const Chunk* c = (const Chunk*)chunks;
-    hipLaunchKernelGGL(sumsq_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, c, scratch);
+// Arguments: include/tcow_hip.h.  One launch sequence: the flat table is the chunk table when nothing is tiled; a kernel whose table is empty is not launched.
+int tcow_adamw_clip_step(void* stream, const tcow_adamw_args* args) {
+    TCOW_CHECK_ARG(args, "tcow_adamw_clip_step: args is NULL");
+    const tcow_adamw_args& a = *args;
+    TCOW_CHECK_ARG(a.chunks, "tcow_adamw_clip_step: chunks is NULL");
+    TCOW_CHECK_ARG(a.scratch, "tcow_adamw_clip_step: scratch is NULL");
+    TCOW_CHECK_ARG(a.n_chunks >= 1, "tcow_adamw_clip_step: n_chunks = %d, must be >= 1", a.n_chunks);
+    TCOW_CHECK_ARG(a.step >= 1, "tcow_adamw_clip_step: step = %d, must be >= 1", a.step);
+    TCOW_CHECK_ARG(a.n_flat >= 0, "tcow_adamw_clip_step: n_flat = %d, must be >= 0", a.n_flat);
+    TCOW_CHECK_ARG(a.n_tiles >= 0, "tcow_adamw_clip_step: n_tiles = %d, must be >= 0", a.n_tiles);
+    TCOW_CHECK_ARG(a.flat_chunks || a.n_flat == 0, "tcow_adamw_clip_step: flat_chunks is NULL with n_flat = %d", a.n_flat);
+    TCOW_CHECK_ARG(a.tiles || a.n_tiles == 0, "tcow_adamw_clip_step: tiles is NULL with n_tiles = %d", a.n_tiles);
+    hipStream_t s = (hipStream_t)stream;
+    float* tail = a.scratch + a.n_chunks;          // coefficient, norm, skipped count
+    hipLaunchKernelGGL(sumsq_kernel, dim3(a.n_chunks), dim3(256), 0, s, (const Chunk*)a.chunks, a.scratch);
     TCOW_CHECK_LAUNCH();
-    hipLaunchKernelGGL(clipcoef_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, scratch, n_chunks, max_norm, scratch + n_chunks, grad_inv_scale);
+    hipLaunchKernelGGL(clipcoef_kernel, dim3(1), dim3(256), 0, s, a.scratch, a.n_chunks, a.max_norm, tail, a.grad_inv_scale);
     TCOW_CHECK_LAUNCH();
-    if (n_flat > 0) {
-        hipLaunchKernelGGL(adamw_kernel, dim3(n_flat), dim3(256), 0, (hipStream_t)stream, (const Chunk*)flat_chunks, scratch + n_chunks, lr, beta1, beta2, eps, weight_decay, step);
+    if (a.n_flat > 0) {
+        hipLaunchKernelGGL(adamw_kernel, dim3(a.n_flat), dim3(256), 0, s, (const Chunk*)a.flat_chunks, tail, a.lr, a.beta1, a.beta2, a.eps, a.weight_decay, a.step);
         TCOW_CHECK_LAUNCH();
     }
-    if (n_tiles > 0) {
-        hipLaunchKernelGGL(adamw_cast_kernel, dim3(n_tiles), dim3(256), 0, (hipStream_t)stream, (const CastTile*)tiles, scratch + n_chunks, lr, beta1, beta2, eps, weight_decay, step);
+    if (a.n_tiles > 0) {
+        hipLaunchKernelGGL(adamw_cast_kernel, dim3(a.n_tiles), dim3(256), 0, s, (const CastTile*)a.tiles, tail, a.lr, a.beta1, a.beta2, a.eps, a.weight_decay, a.step);
         TCOW_CHECK_LAUNCH();
     }
     return TCOW_OK;
-}
-
-// chunks: device array of n_chunks {p, g, m, v, n} records (all f32, 16-byte aligned starts); scratch: f32 [n_chunks + 3];
-// on return scratch[n_chunks] = clip coefficient (-1 = step skipped), scratch[n_chunks + 1] = total gradient norm,
-// scratch[n_chunks + 2] += 1 if the step was skipped (the caller zeroes it once; device side, no sync).  `step` = number of calls so far
-// (>= 1); the bias correction uses step - scratch[n_chunks + 2].
-// tcow_adamw_clip_step_scaled: the gradients are still multiplied by a loss scale; grad_inv_scale (device scalar, a power of two; NULL = 1) is its inverse.
-int tcow_adamw_clip_step_scaled(void* stream, const void* chunks, int n_chunks, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-                                float max_norm, float* scratch, const float* grad_inv_scale) {
-    TCOW_CHECK_ARG(chunks && scratch && n_chunks > 0 && step >= 1, "tcow_adamw_clip_step: bad arguments");
-    const Chunk* c = (const Chunk*)chunks;
-    hipLaunchKernelGGL(sumsq_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, c, scratch);
-    TCOW_CHECK_LAUNCH();
-    hipLaunchKernelGGL(clipcoef_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, scratch, n_chunks, max_norm, scratch + n_chunks, grad_inv_scale);
-    TCOW_CHECK_LAUNCH();
-    hipLaunchKernelGGL(adamw_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, c, scratch + n_chunks, lr, beta1, beta2, eps, weight_decay, step);
-    TCOW_CHECK_LAUNCH();
-    return TCOW_OK;
-}
-
-int tcow_adamw_clip_step(void* stream, const void* chunks, int n_chunks, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-                         float max_norm, float* scratch) {
-    return tcow_adamw_clip_step_scaled(stream, chunks, n_chunks, lr, beta1, beta2, eps, weight_decay, step, max_norm, scratch, nullptr);
 }
 
 }  // extern "C"

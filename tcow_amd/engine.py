@@ -522,7 +522,7 @@ class _GradBuckets:
         # Who undoes the loss scale.  With a data-parallel hook every finished bucket is multiplied back before the hook sees it (ranks choose their
         # own scales).  Without one (or with one that says it is not `active`: a GradSync of one rank), and with a live FusedAdamWClip(module=net)
         # attached, the buckets stay scaled and the optimizer's clip-coefficient kernel folds the inverse scale into the update
-        # (tcow_adamw_clip_step_scaled): 488 MB less read and written per step.  param.grad then holds SCALED gradients (as under
+        # (grad_inv_scale of tcow_adamw_clip_step): 488 MB less read and written per step.  param.grad then holds SCALED gradients (as under
         # torch.cuda.amp.GradScaler before unscale_); module.pending_inv_scale (device scalar, valid until the next backward) is the factor the
         # optimizer applies on the fly.  The deferral needs ONE backward per optimizer step -- several backwards into the same param.grad (the
         # reference's per-query model loop, gradient accumulation, DataParallel replicas) would make autograd add buckets that carry different

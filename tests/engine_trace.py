@@ -1,7 +1,7 @@
 """Host trace kit: the launch schedule of tcow_amd.engine on CPU tensors, without the library.
 
 install(monkeypatch) puts three replacements in place (pytest's monkeypatch takes them out again): tcow_amd._lib.lib returns a fake
-library whose every entry point records its arguments and returns 0 (tcow_gemm_tn_group_max: 32, tcow_cast_desc_bytes: the record size),
+library whose every entry point records its arguments and returns 0 (tcow_gemm_tn_group_max: 32, tcow_cast_desc_bytes and the optimizer's two: the record sizes),
 ops._stream returns 0 and ops._need_cuda does nothing.  The schedule does not depend on the data and nothing syncs the host, so
 SeekerFunction.apply(...) + .backward() and engine.run_forward(..., stream=step) run to the end; what they compute is garbage and is never
 looked at.  Call the module through those two, not through Seeker.forward, which refuses CPU tensors.
@@ -29,6 +29,7 @@ from tcow_amd.seeker import Seeker
 
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'engine_trace.json.gz')
 CAST_DESC_BYTES = 40                    # struct '<QQQiiii' of operands.OperandCache.refresh
+ADAMW_CHUNK_BYTES, ADAMW_TILE_BYTES = 40, 56     # the optimizer's chunk and tile records (tcow_amd/optim_plan.py; tests/optim_calls.py runs it on this library)
 
 
 def _struct(s, ptrs):
@@ -75,7 +76,8 @@ class Trace:
             ptrs = []
             self.calls.append([name] + [_argument(a, d, ptrs) for a, d in zip(args, declared)])
             self.events.append(('call', name, ptrs))
-            return {'tcow_gemm_tn_group_max': 32, 'tcow_cast_desc_bytes': CAST_DESC_BYTES}.get(name, 0)
+            return {'tcow_gemm_tn_group_max': 32, 'tcow_cast_desc_bytes': CAST_DESC_BYTES, 'tcow_adamw_chunk_bytes': ADAMW_CHUNK_BYTES,
+                    'tcow_adamw_tile_bytes': ADAMW_TILE_BYTES}.get(name, 0)
         return entry
 
 

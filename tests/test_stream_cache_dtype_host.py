@@ -50,7 +50,7 @@ def test_cache_bytes_formula_at_configs1():
 
 def test_the_cq_entry_points_are_new_symbols_of_abi_14():
     hdr = open(os.path.join(ROOT, 'include', 'tcow_hip.h')).read()
-    assert int(re.search(r'#define\s+TCOW_ABI_VERSION\s+(\d+)', hdr).group(1)) == 14 and _lib.ABI_VERSION == 14      # new symbols, no signature changed
+    assert int(re.search(r'#define\s+TCOW_ABI_VERSION\s+(\d+)', hdr).group(1)) == 15 and _lib.ABI_VERSION == 15      # new symbols, no signature changed
     assert int(re.search(r'#define\s+TCOW_FP8E4M3\s+(\d+)', hdr).group(1)) == _lib.TCOW_FP8E4M3 == ops.FP8 == 3
     assert len({_lib.TCOW_F32, _lib.TCOW_BF16, _lib.TCOW_F32X3, _lib.TCOW_FP8E4M3}) == 4
     code = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
@@ -67,7 +67,7 @@ def test_the_cq_entry_points_are_new_symbols_of_abi_14():
 def test_both_builds_export_the_cq_entry_points():
     for fmt in ('bf16', 'fp16'):
         lib = _lib.lib(fmt)
-        assert lib.tcow_version() == 14
+        assert lib.tcow_version() == 15
         for name in CQ:
             assert hasattr(lib, name), f'{name} is not exported by the {fmt} build'
             assert getattr(lib, name).argtypes == _lib.SIGNATURES[name][1]

@@ -244,7 +244,7 @@ def test_stream_pool_refuses_bad_page_keywords_before_anything_else():
 
 def test_paged_abi_entry():
     hdr = open(os.path.join(ROOT, 'include', 'tcow_hip.h')).read()
-    assert int(re.search(r'#define\s+TCOW_ABI_VERSION\s+(\d+)', hdr).group(1)) == 14 and _lib.ABI_VERSION == 14
+    assert int(re.search(r'#define\s+TCOW_ABI_VERSION\s+(\d+)', hdr).group(1)) == 15 and _lib.ABI_VERSION == 15
     name = 'tcow_attn_temporal_ragged_paged_fwd'
     decl = re.search(r'\bint\s+' + name + r'\s*\(([^;]*)\)\s*;', hdr)
     assert decl, f'{name} is not declared in tcow_hip.h'

@@ -57,7 +57,7 @@ extern "C" {
 
 /* ABI version (bumped on any signature change) and last error text of the calling thread.  A host compares tcow_version() with the TCOW_ABI_VERSION it
  * was built against before the first call (tcow_amd/_lib.py does, for both builds of the library). */
-#define TCOW_ABI_VERSION 15
+#define TCOW_ABI_VERSION 16
 int tcow_version(void);
 const char* tcow_last_error(void);
 
@@ -243,98 +243,94 @@ int tcow_attn_spatial_bwd(void* stream, const tcow_attn_shape* shape, const void
 
 /* ------------------------------------------------------------------------------------------- streaming inference (attention_stream.hip)
  * A stream feeds the model c >= 1 new frames at a time (tcow_amd/stream.py).  With causal_attention 1 or 2 frame t depends on frames 0..t only
- * (tril() of vit.py:93-99, frame-0 cls of vit.py:192-198), so each chunk runs the block schedule on its own rows and takes the temporal keys /
- * values of earlier frames from a per-block cache.
- * tcow_attn_temporal_cached_fwd: `chunk` = {B, T = c, S, D, heads, causal, dtype}; qkv [B*c*S, 3D], out [B*c*S, D] in the chunk's row order
- *   (b*c + j)*S + s; k_cache / v_cache [B, S-1, heads, T_total, 64] (`dtype`: TCOW_BF16 = the build's 16-bit type, TCOW_F32; arithmetic f32).
- *   For every b, slot s >= 1, head h, chunk frame j, t = t0 + j:  out = softmax_{t' <= t}(q_t . k_t' / 8) v_t', keys / values of t' < t0 from
- *   the cache and of t' >= t0 from the chunk (replaces vit.py:88-109 of the temporal attention, vit.py:169-172); then the chunk's K / V are
- *   the cache's rows t0 .. t0+c-1.  Slot-0 rows of out are zero.  t0 is read from device memory (*t0_dev), so one captured graph serves every
- *   step; a t0 with t0 + c > T_total writes NaN to out and leaves the cache alone.  causal must be 1 or 2, T_total <= TCOW_STREAM_MAX_FRAMES.
- * tcow_cls_stream: x [B*c*S, D] f32 after the spatial projection (causal_attention == 1; replaces tcow_cls_merge mode 1, vit.py:189-198,215):
- *   t0 == 0: every frame's slot 0 <- frame 0's slot 0, and that row -> cls_cache [B, D]; t0 > 0: every frame's slot 0 <- cls_cache.
+ * (tril() of vit.py:93-99, frame-0 cls of vit.py:192-198), so each step runs the block schedule on its own rows and takes the temporal keys /
+ * values of earlier frames from a per-block cache.  One entry point serves every form of the step (since ABI 16; one record, as tcow_gemm_nt).
  *
- * A pool of live sessions (SeekerStreamPool) steps rows that stand at different frames in one launch: every row r of the step has its own
- * t0 = t0_rows[r] and its own cache block slot_rows[r] of n_slots (both device int32 [n]).  The two pool entry points run the kernels of the two
- * above (which are the case "one t0 for all rows, slot = row") and replace the same reference lines per row: vit.py:88-109 with the tril() of
- * vit.py:93-99, and the frame-0 cls of vit.py:189-198,215.
- * tcow_attn_temporal_pool_fwd: `chunk` = {B = n rows, T = c, S, D, heads, causal, dtype}; qkv / out in the row order (r*c + j)*S + s;
- *   k_cache / v_cache [n_slots, S-1, heads, T_total, 64].  Row r is tcow_attn_temporal_cached_fwd of one clip at t0_rows[r] on block slot_rows[r]:
- *   keys / values < t0 from the slot, >= t0 from the chunk, the chunk's K / V then rows t0 .. t0+c-1 of the slot, slot-0 rows of out zero.  A row
- *   with t0 < 0, t0 + c > T_total or a slot outside [0, n_slots) writes NaN to its own rows of out and touches no cache row; the other rows are
- *   unaffected.  Two rows of one launch that name the same slot are UNDEFINED (both append to it while the other reads): the caller must pass
- *   distinct slots (SeekerStreamPool.step refuses a duplicate session).  causal 1 or 2, T_total <= TCOW_STREAM_MAX_FRAMES, n_slots >= 1.
- * tcow_cls_pool: x [n*c*S, D] f32, cls_cache [n_slots, D]; per row r: t0_rows[r] == 0: every chunk frame's slot 0 <- chunk frame 0's slot 0,
- *   and that row -> cls_cache[slot_rows[r]]; t0_rows[r] > 0: every chunk frame's slot 0 <- cls_cache[slot_rows[r]].  Rows of both kinds mix in
- *   one launch; distinct slots as above.
+ * tcow_attn_temporal_step.  A step is a set of SESSIONS, session r bringing c_r >= 1 new frames that stand at t0_r .. t0_r + c_r - 1 of its
+ *   stream of T_total <= TCOW_STREAM_MAX_FRAMES frames.  qkv [rows, 3D] -> out [rows, D], rows = (flat frame)*S + s in session order.  For
+ *   every session, slot s >= 1, head h and frame j of the session, t = t0 + j:
+ *       out = softmax_{t' <= t}(q_t . k_t' / 8) v_t',
+ *   keys / values of t' < t0 from the session's cache, of t' >= t0 from the step's own qkv rows (replaces vit.py:88-109 of the temporal
+ *   attention, vit.py:169-172, per session); then the step's K / V lines are positions t0 .. t0+c-1 of the session's cache.  Slot-0 rows of out
+ *   are zero.  Arithmetic is f32.  t0 and every table are read from DEVICE memory (int32), so one captured graph serves every step.  causal must
+ *   be 1 or 2, head_dim 64.  Position kt of (session, slot s >= 1, head h) is a line of 64 cache elements; where it lives is the layout.
  *
- * A ragged step (SeekerStreamPool.step_ragged): n sessions, session r with c_rows[r] >= 1 frames, F = sum of c_rows frames flat in session
- * order: session r owns the flat frames first_rows[r] .. first_rows[r] + c_rows[r] - 1 (first_rows = exclusive prefix sum of c_rows), rows of
- * qkv / out / x are f*S + s.  Per session device int32 [n]: t0_rows, slot_rows, first_rows, c_rows; per frame device int32 [F]: row_of_frame.
- * tcow_attn_temporal_ragged_fwd: `step` = {B = 1, T = F, S, D, heads, causal, dtype}; k_cache / v_cache [n_slots, S-1, heads, T_total, 64].
- *   One wave per (flat frame f, slot s, head h): r = row_of_frame[f], j = f - first_rows[r], t = t0_rows[r] + j; frame f's K / V line becomes
- *   position t of block slot_rows[r]; its query attends to keys 0 .. t, keys < t0 from the cache, keys t0 .. t from the step's rows at flat
- *   frame first + (t' - t0).  No wave reads a cache position that the launch writes.  Per session the results (out and caches) are bit-identical
- *   to tcow_attn_temporal_pool_fwd of that session alone.  Slot-0 rows of out are zero.  A frame whose session has t0 < 0, t0 + c > T_total, a
- *   slot outside [0, n_slots) or j outside [0, c) writes NaN to its own rows of out and touches no cache row.  Distinct slots as above.
- *   causal 1 or 2, T_total <= TCOW_STREAM_MAX_FRAMES, n_slots >= 1, 1 <= n <= F.
- * tcow_cls_ragged: x [F*S, D] f32, cls_cache [n_slots, D]; per session r: t0_rows[r] == 0: slot 0 of every frame of the session <- slot 0 of
- *   its frame first_rows[r], and that row -> cls_cache[slot_rows[r]]; t0_rows[r] > 0: slot 0 of every frame of the session <- cls_cache[slot].
- *   A slot outside [0, n_slots) writes NaN and touches no cache row.
- *
- * A paged pool (SeekerStreamPool with page_frames = P): the K / V cache of a block is a heap of n_pages pages of P frames,
- * k_pages / v_pages [n_pages, S-1, heads, P, 64], and a page id is valid in every block's arrays alike.  Session r of a step brings row r of
- * page_rows [n, pages_per_session] (device int32): entry q is the page that holds its frames q*P .. q*P+P-1, so cache position kt of
- * (session r, slot s >= 1, head h) is the 64 elements at (((page_rows[r][kt / P]*(S-1) + (s-1))*heads + h)*P + kt % P)*64.
- * tcow_attn_temporal_ragged_paged_fwd: tcow_attn_temporal_ragged_fwd with that addressing and nothing else changed (one wave per (flat frame,
- *   slot, head), the same per-frame body): out, and the pages gathered back into [T_total, 64] runs, are bit-identical to the ragged entry
- *   point on contiguous caches with the same contents.  Before a wave touches a page it checks every entry it would dereference: a frame at
- *   t = t0 + j needs page_rows[r][0 .. t / P] inside [0, n_pages); entries beyond t / P are never read.  A frame with such an entry outside
- *   the heap, or one that the ragged entry point would refuse (t0 < 0, t0 + c > T_total, j outside [0, c)), writes NaN to its own rows of out
- *   and touches no page.  No wave reads a cache position that the launch writes.  Two sessions of one launch that name the same page are
- *   UNDEFINED, as two rows that name one slot are above.  P a power of two, 1 <= P <= TCOW_STREAM_MAX_FRAMES; n_pages >= 1;
- *   pages_per_session * P >= T_total; causal 1 or 2, T_total <= TCOW_STREAM_MAX_FRAMES, 1 <= n <= F.  The cls rows stay per slot
- *   (tcow_cls_ragged). */
-#define TCOW_STREAM_MAX_FRAMES 1024
-int tcow_attn_temporal_cached_fwd(void* stream, const tcow_attn_shape* chunk, int T_total, const int* t0_dev, const void* qkv, void* k_cache,
-                                  void* v_cache, void* out);
-int tcow_cls_stream(void* stream, int B, int c, int S, int D, float* x, float* cls_cache, const int* t0_dev);
-int tcow_attn_temporal_pool_fwd(void* stream, const tcow_attn_shape* chunk, int T_total, int n_slots, const int* t0_rows, const int* slot_rows,
-                                const void* qkv, void* k_cache, void* v_cache, void* out);
-int tcow_cls_pool(void* stream, int n, int c, int S, int D, float* x, float* cls_cache, int n_slots, const int* t0_rows, const int* slot_rows);
-int tcow_attn_temporal_ragged_fwd(void* stream, const tcow_attn_shape* step, int n, int T_total, int n_slots, const int* t0_rows, const int* slot_rows,
-                                  const int* first_rows, const int* c_rows, const int* row_of_frame, const void* qkv, void* k_cache, void* v_cache,
-                                  void* out);
-int tcow_cls_ragged(void* stream, int n, int F, int S, int D, float* x, float* cls_cache, int n_slots, const int* t0_rows, const int* slot_rows,
-                    const int* first_rows, const int* c_rows);
-int tcow_attn_temporal_ragged_paged_fwd(void* stream, const tcow_attn_shape* step, int n, int T_total, int n_pages, int page_frames, int pages_per_session,
-                                        const int* t0_rows, const int* page_rows, const int* first_rows, const int* c_rows, const int* row_of_frame,
-                                        const void* qkv, void* k_pages, void* v_pages, void* out);
-
-/* Compact K / V cache (new symbols, no signature changed: the ABI version stays).  The four *_cq entry points are the four above with one more
- * argument, cache_dtype: the element type C of k_cache / v_cache (k_pages / v_pages), chosen apart from the step's storage `dtype`.
- *   TCOW_F32, TCOW_BF16 (the build's 16-bit type) or TCOW_FP8E4M3 (one byte, OCP e4m3fn); C may not be wider than the storage (dtype TCOW_BF16
- *   with cache_dtype TCOW_F32 is refused).  cache_dtype == dtype is the entry point without _cq, bit for bit.
- *   rnd_C(x) = x converted to C by round-to-nearest-even and back; for fp8 saturating: x is clamped to [-448, 448] first, a NaN stays NaN --
- *   torch's x.clamp(-448, 448).to(torch.float8_e4m3fn), subnormals kept.
+ *   choice                         | what it means, and what it adds to the record
+ *   rows form   (n_sessions == 0)  | shape = {B = rows, T = c, ...}: row r is a session of c frames, flat frames r*c .. r*c+c-1; T_total >= c.  t0_rows, slot_rows [B];
+ *                                  | slot_rows NULL = the STREAM: ONE t0 entry read by every row, row b on slot b, n_slots taken as B
+ *   ragged form (n_sessions = n)   | shape = {B = 1, T = F, ...}, 1 <= n <= F: session r owns the flat frames first_rows[r] .. + c_rows[r] - 1 (first_rows = exclusive
+ *                                  | prefix sum of c_rows).  t0_rows, slot_rows (required), first_rows, c_rows [n]; row_of_frame [F] = the session of each flat frame
+ *   contiguous  (page_frames == 0) | k_cache / v_cache [n_slots, S-1, heads, T_total, 64], n_slots >= 1: position kt is line kt of block slot_rows[r]
+ *   paged       (page_frames = P)  | a heap [n_pages, S-1, heads, P, 64], a page id valid in every block's arrays alike; page_rows [n, pages_per_session]: entry q is the
+ *                                  | page of frames q*P .. q*P+P-1, position kt the line at (((page_rows[r][kt / P]*(S-1) + (s-1))*heads + h)*P + kt % P)*64.  P a power
+ *                                  | of two <= TCOW_STREAM_MAX_FRAMES, n_pages >= 1, pages_per_session * P >= T_total; n_slots and slot_rows are not read.  Ragged steps
+ *                                  | only: rows + paged has no kernel and is refused
+ *   cache_dtype == shape.dtype     | caches in the storage type (TCOW_BF16 = the build's 16-bit type, TCOW_F32): the appended lines are bit copies
+ *   cache_dtype narrower           | TCOW_BF16 under TCOW_F32, TCOW_FP8E4M3 (one byte, OCP e4m3fn) under either: the compact cache below.  Wider (TCOW_F32 under
+ *                                  | TCOW_BF16) is refused
+ *   Bad rows.  A session with t0 < 0, t0 + c > T_total or a slot outside [0, n_slots) -- ragged: also a frame whose row_of_frame entry lies
+ *   outside [0, n) or whose j = f - first_rows[r] lies outside [0, c) -- writes NaN to its own rows of out and touches no cache byte; the other
+ *   sessions are unaffected.  Paged: before a wave touches a page it checks every entry it would dereference: a frame at t = t0 + j needs
+ *   page_rows[r][0 .. t / P] inside [0, n_pages); entries beyond t / P are never read.  A frame with such an entry outside the heap writes NaN
+ *   to its own rows of out and touches no page.
+ *   No wave reads a cache position that the launch writes.  Two sessions of one launch that name the same slot, or the same page, are UNDEFINED
+ *   (both append to it while the other reads): distinct slots and pages are the caller's duty (SeekerStreamPool.step refuses a duplicate
+ *   session; the pool's allocator never hands a page out twice).
+ *   Bit for bit.  The forms share one per-frame body: per session, out and the caches of a ragged step are bit-identical to the rows form of
+ *   that session alone, the stream is the rows form with one t0 and slot = row, and the paged layout gives the out of the contiguous one on
+ *   caches of the same contents, its pages gathered back into [T_total, 64] runs equal to those caches.
+ *   Compact cache (C != storage).  rnd_C(x) = x converted to C by round-to-nearest-even and back; for fp8 saturating: x is clamped to
+ *   [-448, 448] first, a NaN stays NaN -- torch's x.clamp(-448, 448).to(torch.float8_e4m3fn), subnormals kept.
  *   out = softmax_{t' <= t}(q_t . rnd_C(k_t') / 8) rnd_C(v_t'): EVERY key and value at its rounded value, those of the step's own frames
  *   (read from qkv, not from the cache) included; q is not rounded; the append stores the rounded bits once.  Outputs and caches therefore do
- *   not depend on how the frames were split into steps, and the four forms agree bit for bit as the four above do.  No bitwise relation to the
- *   cache_dtype == dtype path.  Cache shapes and addressing are those above, in elements of C.  Everything refused above is refused here; a bad
- *   t0, slot or page writes NaN to the frame's own rows of out and touches no cache byte. */
-#define TCOW_FP8E4M3 3 /* cache_dtype of the *_cq entry points only */
-int tcow_attn_temporal_cached_cq_fwd(void* stream, const tcow_attn_shape* chunk, int T_total, const int* t0_dev, const void* qkv, void* k_cache,
-                                     void* v_cache, void* out, int cache_dtype);
-int tcow_attn_temporal_pool_cq_fwd(void* stream, const tcow_attn_shape* chunk, int T_total, int n_slots, const int* t0_rows, const int* slot_rows,
-                                   const void* qkv, void* k_cache, void* v_cache, void* out, int cache_dtype);
-int tcow_attn_temporal_ragged_cq_fwd(void* stream, const tcow_attn_shape* step, int n, int T_total, int n_slots, const int* t0_rows, const int* slot_rows,
-                                     const int* first_rows, const int* c_rows, const int* row_of_frame, const void* qkv, void* k_cache, void* v_cache,
-                                     void* out, int cache_dtype);
-int tcow_attn_temporal_ragged_paged_cq_fwd(void* stream, const tcow_attn_shape* step, int n, int T_total, int n_pages, int page_frames,
-                                           int pages_per_session, const int* t0_rows, const int* page_rows, const int* first_rows, const int* c_rows,
-                                           const int* row_of_frame, const void* qkv, void* k_pages, void* v_pages, void* out, int cache_dtype);
+ *   not depend on how the frames were split into steps, and the forms agree bit for bit as above.  No bitwise relation to the
+ *   cache_dtype == shape.dtype path.  Cache shapes and addressing are those above, in elements of C.
+ *   Every refusal (TCOW_ERR_INVALID_ARG, the message names the argument) happens before the launch.
+ *
+ * tcow_cls_step: the cls row of causal_attention == 1 across steps, on x [rows, D] f32 after the spatial projection (replaces tcow_cls_merge mode
+ *   1, vit.py:189-198,215, per session); cls_cache [n_slots, D] f32.  Session r with t0_rows[r] == 0: slot 0 of every frame of the session <-
+ *   slot 0 of its first frame, and that row -> cls_cache[slot]; t0_rows[r] > 0: slot 0 of every frame of the session <- cls_cache[slot].
+ *   Sessions of both kinds mix in one launch; distinct slots as above.  A slot outside [0, n_slots) writes NaN and touches no cache row.
+ *   Rows form (first_rows and c_rows NULL): n rows of c frames each; slot_rows NULL = the stream (one t0 entry for every row, row b on slot b,
+ *   n_slots = n).  Ragged form (first_rows and c_rows given): n sessions over F >= n flat frames, c is not read, slot_rows is required; a
+ *   session whose frames do not lie inside the step owns no row of x.  The cls rows stay per slot under a paged K / V cache. */
+#define TCOW_STREAM_MAX_FRAMES 1024
+#define TCOW_FP8E4M3 3 /* cache_dtype of tcow_attn_temporal_step only */
+typedef struct {
+    tcow_attn_shape shape;      /* rows: {B = rows, T = c}; ragged: {B = 1, T = F}; dtype = the storage type of qkv / out */
+    int cache_dtype;            /* element type of k_cache / v_cache; == shape.dtype: the storage type */
+    int T_total;
+    int n_sessions;             /* 0 = rows form; >= 1 = a ragged step of that many sessions */
+    int n_slots;                /* contiguous cache (the stream: taken as shape.B) */
+    int page_frames, n_pages, pages_per_session;    /* paged cache; page_frames == 0 = contiguous */
+    const int* t0_rows;
+    const int* slot_rows;       /* rows form: NULL = the stream */
+    const int* first_rows;      /* first_rows, c_rows, row_of_frame: ragged form */
+    const int* c_rows;
+    const int* row_of_frame;
+    const int* page_rows;       /* paged cache */
+    const void* qkv;
+    void* k_cache;
+    void* v_cache;
+    void* out;
+} tcow_stream_attn_args;
+int tcow_attn_temporal_step(void* stream, const tcow_stream_attn_args* args);
+typedef struct {
+    int n;                      /* rows (rows form) or sessions (ragged form) */
+    int c;                      /* rows form: frames per row */
+    int F;                      /* ragged form: flat frames of the step */
+    int S, D;
+    int n_slots;                /* (the stream: taken as n) */
+    float* x;
+    float* cls_cache;
+    const int* t0_rows;
+    const int* slot_rows;       /* rows form: NULL = the stream */
+    const int* first_rows;      /* first_rows, c_rows: non-NULL = the ragged form */
+    const int* c_rows;
+} tcow_stream_cls_args;
+int tcow_cls_step(void* stream, const tcow_stream_cls_args* args);
 
-/* Hand-off of a rollover pool (SeekerStreamPool with rollover = k; a new symbol, no signature changed: the ABI version stays).  A session that
+/* Hand-off of a rollover pool (SeekerStreamPool with rollover = k).  A session that
  * runs past frame T_total - 1 is a chain of overlapping windows; the query mask of the next window is the model's own output at the frame
  * where that window starts, binarised as eval/metrics.py:18 does (output_mask > threshold).
  * tcow_requery_mask: for hand-off i < n, with x = logits + src_off[i] (src_off: device int64 element offsets into the logits_len f32 elements

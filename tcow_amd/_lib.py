@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get('TCOW_LIB') or os.path.join(_HERE, 'libtcow_hip.so')  
 LIB_PATH_FP16 = os.path.join(_HERE, 'libtcow_hip_fp16.so')                          # the binary16 build of the same sources (precision='fp16')
 
 TCOW_F32, TCOW_BF16, TCOW_F32X3 = 0, 1, 2
-TCOW_FP8E4M3 = 3          # cache_dtype of the tcow_attn_temporal_*_cq_fwd entry points only (one OCP e4m3fn byte per element)
+TCOW_FP8E4M3 = 3          # cache_dtype of tcow_attn_temporal_step only (one OCP e4m3fn byte per element)
 ACT_NONE, ACT_GELU, ACT_DGELU, ACT_GELU_DSAVE, ACT_MUL_AUX = 0, 1, 2, 3, 4
 
 
@@ -22,6 +22,20 @@ class TcowError(RuntimeError):
 class AttnShape(ctypes.Structure):
     _fields_ = [('B', ctypes.c_int), ('T', ctypes.c_int), ('S', ctypes.c_int), ('D', ctypes.c_int),
                 ('heads', ctypes.c_int), ('causal', ctypes.c_int), ('dtype', ctypes.c_int)]
+
+
+class StreamAttnArgs(ctypes.Structure):
+    _fields_ = [('shape', AttnShape), ('cache_dtype', ctypes.c_int), ('T_total', ctypes.c_int), ('n_sessions', ctypes.c_int), ('n_slots', ctypes.c_int),
+                ('page_frames', ctypes.c_int), ('n_pages', ctypes.c_int), ('pages_per_session', ctypes.c_int),
+                ('t0_rows', ctypes.c_void_p), ('slot_rows', ctypes.c_void_p), ('first_rows', ctypes.c_void_p), ('c_rows', ctypes.c_void_p),
+                ('row_of_frame', ctypes.c_void_p), ('page_rows', ctypes.c_void_p),
+                ('qkv', ctypes.c_void_p), ('k_cache', ctypes.c_void_p), ('v_cache', ctypes.c_void_p), ('out', ctypes.c_void_p)]
+
+
+class StreamClsArgs(ctypes.Structure):
+    _fields_ = [('n', ctypes.c_int), ('c', ctypes.c_int), ('F', ctypes.c_int), ('S', ctypes.c_int), ('D', ctypes.c_int), ('n_slots', ctypes.c_int),
+                ('x', ctypes.c_void_p), ('cls_cache', ctypes.c_void_p), ('t0_rows', ctypes.c_void_p), ('slot_rows', ctypes.c_void_p),
+                ('first_rows', ctypes.c_void_p), ('c_rows', ctypes.c_void_p)]
 
 
 class GemmArgs(ctypes.Structure):
@@ -109,17 +123,8 @@ SIGNATURES = {
     'tcow_attn_bwd_workspace_bytes': (_l, [_ash]),
     'tcow_attn_temporal_bwd': (_i, [_vp, _ash, _vp, _vp, _vp, _vp, _vp, _vp, _l]),
     'tcow_attn_spatial_bwd': (_i, [_vp, _ash, _vp, _vp, _vp, _vp, _vp, _vp, _l]),
-    'tcow_attn_temporal_cached_fwd': (_i, [_vp, _ash, _i, _vp, _vp, _vp, _vp, _vp]),
-    'tcow_cls_stream': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
-    'tcow_attn_temporal_pool_fwd': (_i, [_vp, _ash, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'tcow_cls_pool': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
-    'tcow_attn_temporal_ragged_fwd': (_i, [_vp, _ash, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'tcow_cls_ragged': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
-    'tcow_attn_temporal_ragged_paged_fwd': (_i, [_vp, _ash, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'tcow_attn_temporal_cached_cq_fwd': (_i, [_vp, _ash, _i, _vp, _vp, _vp, _vp, _vp, _i]),
-    'tcow_attn_temporal_pool_cq_fwd': (_i, [_vp, _ash, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
-    'tcow_attn_temporal_ragged_cq_fwd': (_i, [_vp, _ash, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
-    'tcow_attn_temporal_ragged_paged_cq_fwd': (_i, [_vp, _ash, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    'tcow_attn_temporal_step': (_i, [_vp, ctypes.POINTER(StreamAttnArgs)]),
+    'tcow_cls_step': (_i, [_vp, ctypes.POINTER(StreamClsArgs)]),
     'tcow_requery_mask': (_i, [_vp, _i, _l, _vp, _l, _vp, _f, _vp, _vp, _i, _vp]),
     'tcow_im2col': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     'tcow_gather_frames': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
@@ -162,7 +167,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 15      # TCOW_ABI_VERSION of include/tcow_hip.h
+ABI_VERSION = 16      # TCOW_ABI_VERSION of include/tcow_hip.h
 
 
 def _declare(L, tolerant=False):

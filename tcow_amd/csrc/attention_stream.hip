@@ -1,29 +1,26 @@
 // Streaming inference (tcow_amd/stream.py): temporal attention of a chunk of c new frames against a per-block K / V cache of the frames before
 // it, and the cls-row bookkeeping of causal_attention == 1 across chunks.  Replaces, for a stream, the temporal core of Attention.forward
 // (vit.py:88-109 with the tril() mask of vit.py:93-99) and the frame-0 cls broadcast of vit.py:189-198,215.  This file has the per-frame body,
-// the kernels and the launchers; what a cache element is and where a key lives is attention_stream_cache.h.
+// the kernels and the two entry points; what a cache element is and where a key lives is attention_stream_cache.h.
 //
-// tcow_attn_temporal_cached_fwd: one wave per (clip b, slot s, head h); four waves per workgroup.  A wave covers G key rows per load (lines and
-// lane groups: the header).  Lane group g walks keys g, g + G, ... with its own online softmax (scores reduced over the group's lanes by xor
+// tcow_attn_temporal_step switches over three kernels (the record and its forms: the header).
+// temporal_cached_kernel, the rows form: one wave per (row b, slot s, head h); four waves per workgroup.  A wave covers G key rows per load (lines
+// and lane groups: the header).  Lane group g walks keys g, g + G, ... with its own online softmax (scores reduced over the group's lanes by xor
 // shuffles), ST_U batches of G rows in flight per wave; the G partial states are merged by xor shuffles at the end.  No LDS.  The cache of
-// (b, s, h) is one contiguous [T_total, 64] block ([B, S-1, heads, T_total, 64]), so a pass over it is a run of whole lines.  Keys of frames < t0
-// come from the cache, keys of the chunk's own frames from the chunk's qkv rows; the same wave copies the chunk's K / V rows into cache positions
-// t0 .. t0+c-1 (nothing reads them in this launch).
+// (slot, s, h) is one contiguous [T_total, 64] block ([n_slots, S-1, heads, T_total, 64]), so a pass over it is a run of whole lines.  Keys of
+// frames < t0 come from the cache, keys of the chunk's own frames from the chunk's qkv rows; the same wave copies the chunk's K / V rows into cache
+// positions t0 .. t0+c-1 (nothing reads them in this launch).  Row r reads t0_rows[r * t0_stride] and works on cache block slot_rows[r]; a stream
+// is the case "t0 broadcast (stride 0), slot = b (no table)".  Rows of different t0 run key loops of different length; nothing else differs.
+// temporal_ragged_kernel (SeekerStreamPool.step_ragged): sessions that bring different numbers of frames to one step.  The frames lie flat in
+// session order; one wave per (flat frame, slot, head) on the per-frame body it shares with temporal_cached_kernel (temporal_query_frame), so a
+// long chunk spreads over as many waves as it has frames.
+// temporal_ragged_paged_kernel (a paged SeekerStreamPool, stream_pool(page_frames=P)): the ragged kernel on a cache that is a heap of pages of P
+// frames, [n_pages, S-1, heads, P, 64]; a session's row of the page table names the page of its frames q*P .. q*P+P-1.  Where a cached key lives
+// is all that differs: temporal_query_frame takes that as a small functor (ContiguousKeys / PagedKeys), so the kernels keep one body and agree
+// bit for bit.
+// tcow_cls_step: cls_stream_kernel for the rows form (t0 and slot per row, or the stream's broadcast), cls_ragged_kernel for a ragged step.
 //
-// tcow_attn_temporal_pool_fwd / tcow_cls_pool (a pool of live sessions, SeekerStreamPool): the same two kernels with a t0 and a cache slot per
-// row.  Row r reads t0_rows[r * t0_stride] and works on cache block slot_rows[r]; a stream is the case "t0 broadcast (stride 0), slot = b
-// (no table)".  Rows of different t0 run key loops of different length; nothing else differs.
-//
-// tcow_attn_temporal_ragged_fwd / tcow_cls_ragged (SeekerStreamPool.step_ragged): sessions that bring different numbers of frames to one step.
-// The frames lie flat in session order; the attention kernel runs one wave per (flat frame, slot, head) on the per-frame body it shares with
-// temporal_cached_kernel (temporal_query_frame), so a long chunk spreads over as many waves as it has frames.
-//
-// tcow_attn_temporal_ragged_paged_fwd (a paged SeekerStreamPool, stream_pool(page_frames=P)): the ragged kernel on a cache that is a heap of
-// pages of P frames, [n_pages, S-1, heads, P, 64]; a session's row of the page table names the page of its frames q*P .. q*P+P-1.  Where a
-// cached key lives is all that differs: temporal_query_frame takes that as a small functor (ContiguousKeys / PagedKeys), so the four kernels
-// keep one body and agree bit for bit.
-//
-// Compact cache (the *_cq entry points, cache element type C != storage type T): a batch of keys is gathered as cache words -- cached lines
+// Compact cache (cache element type C != storage type T): a batch of keys is gathered as cache words -- cached lines
 // loaded, the chunk's own lines (read from the step's qkv rows) encoded -- and decoded where it is used; the key order is that of the C == T
 // path, whose code is unchanged.  Measured ("Compact cache"): the kernels are bound by issued instructions and by waves in
 // flight, not by HBM, so what pays is gathering words (16 instead of 64 registers while the loads fly: 127 VGPRs and four waves per SIMD for
@@ -371,7 +368,7 @@ __global__ void cls_ragged_kernel(int n, int F, int S, int D, float* __restrict_
     cls_session(slot, n_slots, t0_rows[r], x + (size_t)first * S * D + ch, c, (size_t)S * D, cls_cache, (size_t)slot * D + ch);
 }
 
-// Calls f(T{}, C{}) with the storage type T of `dtype` and the cache element type C of `cq` (both checked by launch_temporal).
+// Calls f(T{}, C{}) with the storage type T of `dtype` and the cache element type C of `cq` (both checked by tcow_attn_temporal_step).
 template <typename F> void with_cache_types(int dtype, int cq, F f) {
     if (dtype == TCOW_BF16) {
         if (cq == TCOW_FP8E4M3) f(bf16_t{}, fp8_t{}); else f(bf16_t{}, bf16_t{});
@@ -380,165 +377,96 @@ template <typename F> void with_cache_types(int dtype, int cq, F f) {
     }
 }
 
-// The frame of the three temporal launchers.  What it asks of every step: a shape of s.T >= 1 frames per row, head_dim 64, a causal mask, a
-// stream of T_min .. TCOW_STREAM_MAX_FRAMES frames (a chunk of s.B rows must fit into the cache: T_min = s.T; the F frames of a ragged step
-// belong to several sessions and may exceed T_total: T_min = 1), a storage type of this file, at least one cache slot, and a cache element
-// type `cq` that is one of the three and no wider than the storage (the entry points without a cache_dtype pass the storage type itself);
-// of a ragged step of n sessions also its one row of F frames.  Then the launcher's own checks, own(), and launch(T{}, C{}, grid, block, s) on
-// one wave per item: (row, slot, head), ragged (flat frame, slot, head).
-template <typename Own, typename Launch>
-int launch_temporal(const char* who, const tcow_attn_shape* shape, bool ragged, int n, int T_total, int n_slots, int cq, Own own, Launch launch) {
-    TCOW_CHECK_ARG(shape != nullptr, "%s: null shape", who);
-    const tcow_attn_shape& s = *shape;
-    TCOW_CHECK_ARG(s.B > 0 && s.T > 0 && s.S > 1 && s.heads > 0, "%s: bad step shape B=%d T=%d S=%d heads=%d", who, s.B, s.T, s.S, s.heads);
-    TCOW_CHECK_ARG(s.D == s.heads * ATT_HD, "%s: head_dim must be 64 (D=%d heads=%d)", who, s.D, s.heads);
-    TCOW_CHECK_ARG(s.causal == 1 || s.causal == 2, "%s: causal must be 1 or 2 (got %d): other masks let a frame see later frames", who, s.causal);
-    const int T_min = ragged ? 1 : s.T;
-    TCOW_CHECK_ARG(T_total >= T_min && T_total <= TCOW_STREAM_MAX_FRAMES, "%s: T_total=%d must be in [%d, %d]", who, T_total, T_min, TCOW_STREAM_MAX_FRAMES);
-    TCOW_CHECK_ARG(s.dtype == TCOW_F32 || s.dtype == TCOW_BF16, "%s: dtype must be TCOW_F32 or TCOW_BF16 (got %d)", who, s.dtype);
-    TCOW_CHECK_ARG(n_slots >= 1, "%s: n_slots=%d must be >= 1", who, n_slots);
-    TCOW_CHECK_ARG(cq == TCOW_F32 || cq == TCOW_BF16 || cq == TCOW_FP8E4M3, "%s: cache_dtype must be TCOW_F32, TCOW_BF16 or TCOW_FP8E4M3 (got %d)", who, cq);
-    TCOW_CHECK_ARG(!(s.dtype == TCOW_BF16 && cq == TCOW_F32), "%s: cache_dtype TCOW_F32 is wider than the 16-bit storage (dtype TCOW_BF16)", who);
-    TCOW_CHECK_ARG(!ragged || (s.B == 1 && n > 0 && n <= s.T), "%s: a ragged step is one row of F frames of 1 <= n <= F sessions (B=%d F=%d n=%d)", who,
-                   s.B, s.T, n);
-    if (const int err = own()) return err;
-    const long items = (long)(ragged ? s.T : s.B) * s.S * s.heads;
-    const dim3 grid((unsigned)cdiv(items, ST_WAVES)), block(64 * ST_WAVES);
-    with_cache_types(s.dtype, cq, [&](auto t, auto c) { launch(t, c, grid, block, s); });
-    TCOW_CHECK_LAUNCH();
-    return TCOW_OK;
-}
-
-// temporal_cached_kernel, for the stream (t0 broadcast, slot = b) and the pool entry points
-int launch_temporal_cached(const char* who, void* stream, const tcow_attn_shape* chunk, int T_total, int n_slots, const int* t0_rows, int t0_stride,
-                           const int* slot_rows, const void* qkv, void* k_cache, void* v_cache, void* out, int cq) {
-    return launch_temporal(who, chunk, false, 0, T_total, n_slots, cq, [&]() -> int {
-        TCOW_CHECK_ARG(t0_rows && qkv && k_cache && v_cache && out, "%s: null pointer", who);
-        return TCOW_OK;
-    }, [&](auto t, auto c, dim3 grid, dim3 block, const tcow_attn_shape& s) {
-        using T = decltype(t); using C = decltype(c);
-        hipLaunchKernelGGL((temporal_cached_kernel<T, C>), grid, block, 0, (hipStream_t)stream, s.B, s.T, s.S, s.D, s.heads, T_total, n_slots, t0_rows,
-                           t0_stride, slot_rows, (const T*)qkv, (C*)k_cache, (C*)v_cache, (T*)out);
-    });
-}
-
-int launch_temporal_ragged(const char* who, void* stream, const tcow_attn_shape* step, int n, int T_total, int n_slots, const int* t0_rows,
-                           const int* slot_rows, const int* first_rows, const int* c_rows, const int* row_of_frame, const void* qkv, void* k_cache,
-                           void* v_cache, void* out, int cq) {
-    return launch_temporal(who, step, true, n, T_total, n_slots, cq, [&]() -> int {
-        TCOW_CHECK_ARG(t0_rows && slot_rows && first_rows && c_rows && row_of_frame && qkv && k_cache && v_cache && out, "%s: null pointer", who);
-        return TCOW_OK;
-    }, [&](auto t, auto c, dim3 grid, dim3 block, const tcow_attn_shape& s) {
-        using T = decltype(t); using C = decltype(c);
-        hipLaunchKernelGGL((temporal_ragged_kernel<T, C>), grid, block, 0, (hipStream_t)stream, n, s.T, s.S, s.D, s.heads, T_total, n_slots, t0_rows,
-                           slot_rows, first_rows, c_rows, row_of_frame, (const T*)qkv, (C*)k_cache, (C*)v_cache, (T*)out);
-    });
-}
-
-// (pages, not slots: the frame's n_slots check is given 1, and n_pages is checked here)
-int launch_temporal_ragged_paged(const char* who, void* stream, const tcow_attn_shape* step, int n, int T_total, int n_pages, int page_frames,
-                                 int pages_per_session, const int* t0_rows, const int* page_rows, const int* first_rows, const int* c_rows,
-                                 const int* row_of_frame, const void* qkv, void* k_pages, void* v_pages, void* out, int cq) {
-    return launch_temporal(who, step, true, n, T_total, 1, cq, [&]() -> int {
-        TCOW_CHECK_ARG(page_frames >= 1 && page_frames <= TCOW_STREAM_MAX_FRAMES && (page_frames & (page_frames - 1)) == 0,
-                       "%s: page_frames=%d must be a power of two in [1, %d]", who, page_frames, TCOW_STREAM_MAX_FRAMES);
-        TCOW_CHECK_ARG(n_pages >= 1, "%s: n_pages=%d must be >= 1", who, n_pages);
-        TCOW_CHECK_ARG(pages_per_session >= 1 && (long)pages_per_session * page_frames >= T_total,
-                       "%s: pages_per_session=%d x page_frames=%d does not cover T_total=%d", who, pages_per_session, page_frames, T_total);
-        TCOW_CHECK_ARG(t0_rows && page_rows && first_rows && c_rows && row_of_frame && qkv && k_pages && v_pages && out, "%s: null pointer", who);
-        return TCOW_OK;
-    }, [&](auto t, auto c, dim3 grid, dim3 block, const tcow_attn_shape& s) {
-        using T = decltype(t); using C = decltype(c);
-        int lgP = 0;
-        while ((1 << lgP) < page_frames) ++lgP;
-        hipLaunchKernelGGL((temporal_ragged_paged_kernel<T, C>), grid, block, 0, (hipStream_t)stream, n, s.T, s.S, s.D, s.heads, T_total, n_pages, lgP,
-                           pages_per_session, t0_rows, page_rows, first_rows, c_rows, row_of_frame, (const T*)qkv, (C*)k_pages, (C*)v_pages, (T*)out);
-    });
-}
-
-int launch_cls(const char* who, void* stream, int B, int c, int S, int D, float* x, float* cls_cache, int n_slots, const int* t0_rows, int t0_stride,
-               const int* slot_rows) {
-    TCOW_CHECK_ARG(B > 0 && c > 0 && S > 1 && D > 0 && D % 4 == 0 && n_slots >= 1 && x && cls_cache && t0_rows, "%s: bad arguments", who);
-    hipLaunchKernelGGL(cls_stream_kernel, dim3(cdiv((long)B * D / 4, 64)), dim3(64), 0, (hipStream_t)stream, B, c, S, D, x, cls_cache, n_slots, t0_rows,
-                       t0_stride, slot_rows);
-    TCOW_CHECK_LAUNCH();
-    return TCOW_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
-// (the entry points without a cache_dtype keep the cache in the storage type: chunk->dtype, which the launcher checks)
-int tcow_attn_temporal_cached_fwd(void* stream, const tcow_attn_shape* chunk, int T_total, const int* t0_dev, const void* qkv, void* k_cache, void* v_cache,
-                                  void* out) {
-    return launch_temporal_cached("tcow_attn_temporal_cached_fwd", stream, chunk, T_total, chunk ? chunk->B : 1, t0_dev, 0, nullptr, qkv, k_cache, v_cache,
-                                  out, chunk ? chunk->dtype : TCOW_F32);
+// What it asks of every step: a shape of s.T >= 1 frames per row, head_dim 64, a causal mask, a stream of T_min .. TCOW_STREAM_MAX_FRAMES frames
+// (a chunk of s.B rows must fit into the cache: T_min = s.T; the F frames of a ragged step belong to several sessions and may exceed T_total:
+// T_min = 1), a storage type of this file, at least one cache slot (the stream: a slot per row; a paged cache has pages, checked below), and a
+// cache element type that is one of the three and no wider than the storage; of a ragged step of n sessions also its one row of F frames, of
+// a paged cache its geometry; then the pointers of the form.  One wave per item: (row, slot, head), ragged (flat frame, slot, head).
+int tcow_attn_temporal_step(void* stream, const tcow_stream_attn_args* args) {
+    TCOW_CHECK_ARG(args != nullptr, "tcow_attn_temporal_step: null args");
+    const tcow_stream_attn_args& a = *args;
+    const tcow_attn_shape& s = a.shape;
+    const bool ragged = a.n_sessions != 0, paged = a.page_frames != 0;
+    const int n = a.n_sessions, cq = a.cache_dtype, T_total = a.T_total;
+    TCOW_CHECK_ARG(ragged || !paged, "tcow_attn_temporal_step: a paged cache (page_frames=%d) serves ragged steps only (n_sessions=0 is the rows form)",
+                   a.page_frames);
+    TCOW_CHECK_ARG(s.B > 0 && s.T > 0 && s.S > 1 && s.heads > 0, "tcow_attn_temporal_step: bad step shape B=%d T=%d S=%d heads=%d", s.B, s.T, s.S, s.heads);
+    TCOW_CHECK_ARG(s.D == s.heads * ATT_HD, "tcow_attn_temporal_step: head_dim must be 64 (D=%d heads=%d)", s.D, s.heads);
+    TCOW_CHECK_ARG(s.causal == 1 || s.causal == 2, "tcow_attn_temporal_step: causal must be 1 or 2 (got %d): other masks let a frame see later frames", s.causal);
+    const int T_min = ragged ? 1 : s.T;
+    TCOW_CHECK_ARG(T_total >= T_min && T_total <= TCOW_STREAM_MAX_FRAMES, "tcow_attn_temporal_step: T_total=%d must be in [%d, %d]", T_total, T_min,
+                   TCOW_STREAM_MAX_FRAMES);
+    TCOW_CHECK_ARG(s.dtype == TCOW_F32 || s.dtype == TCOW_BF16, "tcow_attn_temporal_step: dtype must be TCOW_F32 or TCOW_BF16 (got %d)", s.dtype);
+    const int n_slots = !ragged && !a.slot_rows ? s.B : a.n_slots;
+    TCOW_CHECK_ARG(paged || n_slots >= 1, "tcow_attn_temporal_step: n_slots=%d must be >= 1", n_slots);
+    TCOW_CHECK_ARG(cq == TCOW_F32 || cq == TCOW_BF16 || cq == TCOW_FP8E4M3,
+                   "tcow_attn_temporal_step: cache_dtype must be TCOW_F32, TCOW_BF16 or TCOW_FP8E4M3 (got %d)", cq);
+    TCOW_CHECK_ARG(!(s.dtype == TCOW_BF16 && cq == TCOW_F32), "tcow_attn_temporal_step: cache_dtype TCOW_F32 is wider than the 16-bit storage (dtype TCOW_BF16)");
+    TCOW_CHECK_ARG(!ragged || (s.B == 1 && n > 0 && n <= s.T),
+                   "tcow_attn_temporal_step: a ragged step is one row of F frames of 1 <= n <= F sessions (B=%d F=%d n=%d)", s.B, s.T, n);
+    if (paged) {
+        TCOW_CHECK_ARG(a.page_frames >= 1 && a.page_frames <= TCOW_STREAM_MAX_FRAMES && (a.page_frames & (a.page_frames - 1)) == 0,
+                       "tcow_attn_temporal_step: page_frames=%d must be a power of two in [1, %d]", a.page_frames, TCOW_STREAM_MAX_FRAMES);
+        TCOW_CHECK_ARG(a.n_pages >= 1, "tcow_attn_temporal_step: n_pages=%d must be >= 1", a.n_pages);
+        TCOW_CHECK_ARG(a.pages_per_session >= 1 && (long)a.pages_per_session * a.page_frames >= T_total,
+                       "tcow_attn_temporal_step: pages_per_session=%d x page_frames=%d does not cover T_total=%d", a.pages_per_session, a.page_frames, T_total);
+    }
+    TCOW_CHECK_ARG(a.t0_rows && a.qkv && a.k_cache && a.v_cache && a.out &&
+                   (!ragged || (a.first_rows && a.c_rows && a.row_of_frame && (paged ? a.page_rows : a.slot_rows))), "tcow_attn_temporal_step: null pointer");
+    const long items = (long)(ragged ? s.T : s.B) * s.S * s.heads;
+    const dim3 grid((unsigned)cdiv(items, ST_WAVES)), block(64 * ST_WAVES);
+    const hipStream_t st = (hipStream_t)stream;
+    with_cache_types(s.dtype, cq, [&](auto t, auto c) {
+        using T = decltype(t); using C = decltype(c);
+        const T* qkv = (const T*)a.qkv;
+        C *kc = (C*)a.k_cache, *vc = (C*)a.v_cache;
+        T* out = (T*)a.out;
+        if (!ragged) {      // (the stream: one t0 entry for every row -- stride 0 --, slot = row)
+            hipLaunchKernelGGL((temporal_cached_kernel<T, C>), grid, block, 0, st, s.B, s.T, s.S, s.D, s.heads, T_total, n_slots, a.t0_rows,
+                               a.slot_rows ? 1 : 0, a.slot_rows, qkv, kc, vc, out);
+        } else if (!paged) {
+            hipLaunchKernelGGL((temporal_ragged_kernel<T, C>), grid, block, 0, st, n, s.T, s.S, s.D, s.heads, T_total, n_slots, a.t0_rows, a.slot_rows,
+                               a.first_rows, a.c_rows, a.row_of_frame, qkv, kc, vc, out);
+        } else {
+            int lgP = 0;
+            while ((1 << lgP) < a.page_frames) ++lgP;
+            hipLaunchKernelGGL((temporal_ragged_paged_kernel<T, C>), grid, block, 0, st, n, s.T, s.S, s.D, s.heads, T_total, a.n_pages, lgP,
+                               a.pages_per_session, a.t0_rows, a.page_rows, a.first_rows, a.c_rows, a.row_of_frame, qkv, kc, vc, out);
+        }
+    });
+    TCOW_CHECK_LAUNCH();
+    return TCOW_OK;
 }
 
-int tcow_attn_temporal_cached_cq_fwd(void* stream, const tcow_attn_shape* chunk, int T_total, const int* t0_dev, const void* qkv, void* k_cache,
-                                     void* v_cache, void* out, int cache_dtype) {
-    return launch_temporal_cached("tcow_attn_temporal_cached_cq_fwd", stream, chunk, T_total, chunk ? chunk->B : 1, t0_dev, 0, nullptr, qkv, k_cache,
-                                  v_cache, out, cache_dtype);
-}
-
-int tcow_attn_temporal_pool_fwd(void* stream, const tcow_attn_shape* chunk, int T_total, int n_slots, const int* t0_rows, const int* slot_rows,
-                                const void* qkv, void* k_cache, void* v_cache, void* out) {
-    TCOW_CHECK_ARG(slot_rows != nullptr, "tcow_attn_temporal_pool_fwd: null pointer");
-    return launch_temporal_cached("tcow_attn_temporal_pool_fwd", stream, chunk, T_total, n_slots, t0_rows, 1, slot_rows, qkv, k_cache, v_cache, out,
-                                  chunk ? chunk->dtype : TCOW_F32);
-}
-
-int tcow_attn_temporal_pool_cq_fwd(void* stream, const tcow_attn_shape* chunk, int T_total, int n_slots, const int* t0_rows, const int* slot_rows,
-                                   const void* qkv, void* k_cache, void* v_cache, void* out, int cache_dtype) {
-    TCOW_CHECK_ARG(slot_rows != nullptr, "tcow_attn_temporal_pool_cq_fwd: null pointer");
-    return launch_temporal_cached("tcow_attn_temporal_pool_cq_fwd", stream, chunk, T_total, n_slots, t0_rows, 1, slot_rows, qkv, k_cache, v_cache, out,
-                                  cache_dtype);
-}
-
-int tcow_cls_stream(void* stream, int B, int c, int S, int D, float* x, float* cls_cache, const int* t0_dev) {
-    return launch_cls("tcow_cls_stream", stream, B, c, S, D, x, cls_cache, B > 0 ? B : 1, t0_dev, 0, nullptr);
-}
-
-int tcow_cls_pool(void* stream, int n, int c, int S, int D, float* x, float* cls_cache, int n_slots, const int* t0_rows, const int* slot_rows) {
-    TCOW_CHECK_ARG(slot_rows != nullptr, "tcow_cls_pool: bad arguments");
-    return launch_cls("tcow_cls_pool", stream, n, c, S, D, x, cls_cache, n_slots, t0_rows, 1, slot_rows);
-}
-
-int tcow_attn_temporal_ragged_fwd(void* stream, const tcow_attn_shape* step, int n, int T_total, int n_slots, const int* t0_rows, const int* slot_rows,
-                                  const int* first_rows, const int* c_rows, const int* row_of_frame, const void* qkv, void* k_cache, void* v_cache,
-                                  void* out) {
-    return launch_temporal_ragged("tcow_attn_temporal_ragged_fwd", stream, step, n, T_total, n_slots, t0_rows, slot_rows, first_rows, c_rows, row_of_frame,
-                                  qkv, k_cache, v_cache, out, step ? step->dtype : TCOW_F32);
-}
-
-int tcow_attn_temporal_ragged_cq_fwd(void* stream, const tcow_attn_shape* step, int n, int T_total, int n_slots, const int* t0_rows, const int* slot_rows,
-                                     const int* first_rows, const int* c_rows, const int* row_of_frame, const void* qkv, void* k_cache, void* v_cache,
-                                     void* out, int cache_dtype) {
-    return launch_temporal_ragged("tcow_attn_temporal_ragged_cq_fwd", stream, step, n, T_total, n_slots, t0_rows, slot_rows, first_rows, c_rows,
-                                  row_of_frame, qkv, k_cache, v_cache, out, cache_dtype);
-}
-
-int tcow_attn_temporal_ragged_paged_fwd(void* stream, const tcow_attn_shape* step, int n, int T_total, int n_pages, int page_frames, int pages_per_session,
-                                        const int* t0_rows, const int* page_rows, const int* first_rows, const int* c_rows, const int* row_of_frame,
-                                        const void* qkv, void* k_pages, void* v_pages, void* out) {
-    return launch_temporal_ragged_paged("tcow_attn_temporal_ragged_paged_fwd", stream, step, n, T_total, n_pages, page_frames, pages_per_session, t0_rows,
-                                        page_rows, first_rows, c_rows, row_of_frame, qkv, k_pages, v_pages, out, step ? step->dtype : TCOW_F32);
-}
-
-int tcow_attn_temporal_ragged_paged_cq_fwd(void* stream, const tcow_attn_shape* step, int n, int T_total, int n_pages, int page_frames,
-                                           int pages_per_session, const int* t0_rows, const int* page_rows, const int* first_rows, const int* c_rows,
-                                           const int* row_of_frame, const void* qkv, void* k_pages, void* v_pages, void* out, int cache_dtype) {
-    return launch_temporal_ragged_paged("tcow_attn_temporal_ragged_paged_cq_fwd", stream, step, n, T_total, n_pages, page_frames, pages_per_session,
-                                        t0_rows, page_rows, first_rows, c_rows, row_of_frame, qkv, k_pages, v_pages, out, cache_dtype);
-}
-
-int tcow_cls_ragged(void* stream, int n, int F, int S, int D, float* x, float* cls_cache, int n_slots, const int* t0_rows, const int* slot_rows,
-                    const int* first_rows, const int* c_rows) {
-    TCOW_CHECK_ARG(n > 0 && F >= n && S > 1 && D > 0 && D % 4 == 0 && n_slots >= 1 && x && cls_cache && t0_rows && slot_rows && first_rows && c_rows,
-                   "tcow_cls_ragged: bad arguments");
-    hipLaunchKernelGGL(cls_ragged_kernel, dim3(cdiv((long)n * D / 4, 64)), dim3(64), 0, (hipStream_t)stream, n, F, S, D, x, cls_cache, n_slots, t0_rows,
-                       slot_rows, first_rows, c_rows);
+int tcow_cls_step(void* stream, const tcow_stream_cls_args* args) {
+    TCOW_CHECK_ARG(args != nullptr, "tcow_cls_step: args is NULL");
+    const tcow_stream_cls_args& a = *args;
+    const bool ragged = a.first_rows || a.c_rows;
+    const int n_slots = !ragged && !a.slot_rows ? a.n : a.n_slots;          // (the stream: a cache row per row)
+    TCOW_CHECK_ARG(a.n >= 1, "tcow_cls_step: n = %d, must be >= 1", a.n);
+    TCOW_CHECK_ARG(ragged || a.c >= 1, "tcow_cls_step: c = %d, must be >= 1", a.c);
+    TCOW_CHECK_ARG(!ragged || a.F >= a.n, "tcow_cls_step: F = %d, must be >= n = %d (a ragged step)", a.F, a.n);
+    TCOW_CHECK_ARG(a.S > 1, "tcow_cls_step: S = %d, must be > 1", a.S);
+    TCOW_CHECK_ARG(a.D > 0 && a.D % 4 == 0, "tcow_cls_step: D = %d, must be a positive multiple of 4", a.D);
+    TCOW_CHECK_ARG(n_slots >= 1, "tcow_cls_step: n_slots = %d, must be >= 1", n_slots);
+    TCOW_CHECK_ARG(a.x, "tcow_cls_step: x is NULL");
+    TCOW_CHECK_ARG(a.cls_cache, "tcow_cls_step: cls_cache is NULL");
+    TCOW_CHECK_ARG(a.t0_rows, "tcow_cls_step: t0_rows is NULL");
+    const dim3 grid(cdiv((long)a.n * a.D / 4, 64)), block(64);
+    if (ragged) {
+        TCOW_CHECK_ARG(a.slot_rows, "tcow_cls_step: slot_rows is NULL in a ragged step");
+        TCOW_CHECK_ARG(a.first_rows, "tcow_cls_step: first_rows is NULL with c_rows given");
+        TCOW_CHECK_ARG(a.c_rows, "tcow_cls_step: c_rows is NULL with first_rows given");
+        hipLaunchKernelGGL(cls_ragged_kernel, grid, block, 0, (hipStream_t)stream, a.n, a.F, a.S, a.D, a.x, a.cls_cache, n_slots, a.t0_rows, a.slot_rows,
+                           a.first_rows, a.c_rows);
+    } else {
+        hipLaunchKernelGGL(cls_stream_kernel, grid, block, 0, (hipStream_t)stream, a.n, a.c, a.S, a.D, a.x, a.cls_cache, n_slots, a.t0_rows,
+                           a.slot_rows ? 1 : 0, a.slot_rows);
+    }
     TCOW_CHECK_LAUNCH();
     return TCOW_OK;
 }

@@ -346,76 +346,71 @@ def attn_bwd(shape, spatial, qkv, out, dout, lse, dqkv):
     return dqkv
 
 
-def _stream_attn(mode, B, c, S, D, heads, causal, *tensors):
-    """What the stream attention wrappers start with: (library, reference to the step's shape).  `mode` is the attention mode: F32X3
-    (precision='bf16x3') stores f32 and runs as F32."""
-    _need_cuda(*tensors)
-    lib, dm = _sel(mode)
-    return lib, ctypes.byref(L.AttnShape(B, c, S, D, heads, int(causal), F32 if dm == F32X3 else dm))
-
-
 FP8 = L.TCOW_FP8E4M3      # cache_dtype of the attn_temporal_* wrappers only: a K / V cache of torch.float8_e4m3fn elements
 
 
-def _cache_dtype(who, mode, cache_dtype, k_cache, v_cache):
-    """The cache_dtype keyword of the attn_temporal_* wrappers (F32, BF16 = the 16-bit type, FP8; None is handled by the caller): the caches must
-    have the torch dtype it names -- torch.float8_e4m3fn; for BF16 the mode's 16-bit type, torch.bfloat16 under f32 storage (the main build serves
-    it); torch.float32.  A value or pair the library refuses (unknown, wider than the storage) is passed on for it to refuse.  Returns the int."""
-    cq = int(cache_dtype)
-    want = torch.float8_e4m3fn if cq == FP8 else (tdtype(mode) if is16(mode) else torch.bfloat16) if cq == BF16 else \
-        torch.float32 if cq == F32 and not is16(mode) else None
-    if want is not None and (k_cache.dtype != want or v_cache.dtype != want):
-        raise L.TcowError(f'{who}: cache_dtype={cq} needs {want} caches, got {k_cache.dtype} / {v_cache.dtype}')
-    return cq
-
-
-def _stream_attn_call(lib, name, mode, cache_dtype, k_cache, v_cache, args):
-    """The call of the four attn_temporal_* wrappers: entry point `name` (tcow_attn_temporal_*_fwd) on `args` when cache_dtype is None, else its
-    compact-cache twin (..._cq_fwd) on `args` and the checked cache_dtype.  Errors of the library carry the name of the symbol that was called,
-    those of the cache_dtype check the wrapper's (the symbol without 'tcow_' and '_fwd')."""
+def _stream_attn(who, mode, B, T, S, D, heads, causal, cache_dtype, T_total, t0_rows, qkv, k_cache, v_cache, out, n_sessions=0, n_slots=0, slot_rows=None,
+                 first_rows=None, c_rows=None, row_of_frame=None, page_frames=0, n_pages=0, pages_per_session=0, page_rows=None):
+    """The call of the four attn_temporal_* wrappers (`who`): fills tcow_stream_attn_args (include/tcow_hip.h: which fields a form leaves 0 / None;
+    the keywords are those) and calls tcow_attn_temporal_step of the mode's build.  `mode` is the attention mode: F32X3 (precision='bf16x3') stores f32 and runs as F32.
+    cache_dtype None = the storage type.  F32, BF16 (= the 16-bit type) or FP8: the caches must have the torch dtype it names -- torch.float8_e4m3fn;
+    for BF16 the mode's 16-bit type, torch.bfloat16 under f32 storage (the main build serves it); torch.float32 -- and that refusal carries the
+    wrapper's name.  A value or pair the library refuses (unknown, wider than the storage) is passed on for it to refuse, under its symbol."""
+    lib, dm = _sel(mode)
+    dm = F32 if dm == F32X3 else dm
+    cq = dm if cache_dtype is None else int(cache_dtype)
     if cache_dtype is not None:
-        args += (_cache_dtype(name[5:-4], mode, cache_dtype, k_cache, v_cache),)
-        name = name[:-4] + '_cq_fwd'
-    L.check(getattr(lib, name)(_stream(), *args), name, lib)
+        want = torch.float8_e4m3fn if cq == FP8 else (tdtype(mode) if is16(mode) else torch.bfloat16) if cq == BF16 else \
+            torch.float32 if cq == F32 and not is16(mode) else None
+        if want is not None and (k_cache.dtype != want or v_cache.dtype != want):
+            raise L.TcowError(f'{who}: cache_dtype={cq} needs {want} caches, got {k_cache.dtype} / {v_cache.dtype}')
+    args = L.StreamAttnArgs(L.AttnShape(B, T, S, D, heads, int(causal), dm), cq, int(T_total), int(n_sessions), int(n_slots), int(page_frames), int(n_pages),
+                            int(pages_per_session), t0_rows.data_ptr(), _p(slot_rows), _p(first_rows), _p(c_rows), _p(row_of_frame), _p(page_rows),
+                            qkv.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr())
+    L.check(lib.tcow_attn_temporal_step(_stream(), ctypes.byref(args)), 'tcow_attn_temporal_step', lib)
+    return out
+
+
+def _stream_cls(x, n, c, F, S, cls_cache, n_slots, t0_rows, slot_rows=None, first_rows=None, c_rows=None):
+    """The call of the three cls_* wrappers: fills tcow_stream_cls_args and calls tcow_cls_step (f32 rows: the main build)."""
+    args = L.StreamClsArgs(int(n), int(c), int(F), S, x.shape[1], int(n_slots), x.data_ptr(), cls_cache.data_ptr(), t0_rows.data_ptr(), _p(slot_rows),
+                           _p(first_rows), _p(c_rows))
+    L.check(L.lib().tcow_cls_step(_stream(), ctypes.byref(args)), 'tcow_cls_step')
+    return x
 
 
 def attn_temporal_cached(mode, B, c, S, D, heads, causal, T_total, t0_dev, qkv, k_cache, v_cache, out, cache_dtype=None):
     """Temporal attention of a c-frame chunk (qkv [B*c*S, 3D] -> out [B*c*S, D]) against the K / V cache [B, S-1, heads, T_total, 64] of the
-    frames before t0 = t0_dev[0] (int32 device scalar); appends the chunk's K / V at t0 (see tcow_attn_temporal_cached_fwd).
-    cache_dtype (here and in the three wrappers below): None = caches in the storage type; F32 / BF16 / FP8 = the compact-cache entry point
-    (tcow_attn_temporal_*_cq_fwd) on caches of that element type, every key and value taken at its value rounded to it."""
-    lib, sh = _stream_attn(mode, B, c, S, D, heads, causal, qkv, k_cache, v_cache, out, t0_dev)
-    _stream_attn_call(lib, 'tcow_attn_temporal_cached_fwd', mode, cache_dtype, k_cache, v_cache,
-                      (sh, int(T_total), t0_dev.data_ptr(), qkv.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr()))
-    return out
+    frames before t0 = t0_dev[0] (int32 device scalar); appends the chunk's K / V at t0 (tcow_attn_temporal_step, the stream of the rows form).
+    cache_dtype (here and in the three wrappers below): None = caches in the storage type; F32 / BF16 / FP8 = caches of that element type, every
+    key and value taken at its value rounded to it (the compact cache of tcow_attn_temporal_step)."""
+    _need_cuda(qkv, k_cache, v_cache, out, t0_dev)
+    return _stream_attn('attn_temporal_cached', mode, B, c, S, D, heads, causal, cache_dtype, T_total, t0_dev, qkv, k_cache, v_cache, out)
 
 
 def cls_stream(x, B, c, S, cls_cache, t0_dev):
     """causal_attention == 1 in a stream: t0 == 0 -> tcow_cls_merge mode 1 + keep the row in cls_cache [B, D]; t0 > 0 -> cls_cache to slot 0."""
-    L.check(L.lib().tcow_cls_stream(_stream(), B, c, S, x.shape[1], x.data_ptr(), cls_cache.data_ptr(), t0_dev.data_ptr()), 'tcow_cls_stream')
-    return x
+    return _stream_cls(x, B, c, 0, S, cls_cache, 0, t0_dev)
 
 
 def attn_temporal_pool(mode, n, c, S, D, heads, causal, T_total, n_slots, t0_rows, slot_rows, qkv, k_cache, v_cache, out, cache_dtype=None):
     """attn_temporal_cached for n rows that stand at different frames: row r attends at t0_rows[r] against block slot_rows[r] of the caches
-    [n_slots, S-1, heads, T_total, 64] and appends there (int32 device tensors [n]; distinct slots -- see tcow_attn_temporal_pool_fwd)."""
-    lib, sh = _stream_attn(mode, n, c, S, D, heads, causal, qkv, k_cache, v_cache, out, t0_rows, slot_rows)
-    _stream_attn_call(lib, 'tcow_attn_temporal_pool_fwd', mode, cache_dtype, k_cache, v_cache,
-                      (sh, int(T_total), int(n_slots), t0_rows.data_ptr(), slot_rows.data_ptr(), qkv.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                       out.data_ptr()))
-    return out
+    [n_slots, S-1, heads, T_total, 64] and appends there (int32 device tensors [n]; distinct slots -- the rows form of tcow_attn_temporal_step)."""
+    _need_cuda(qkv, k_cache, v_cache, out, t0_rows, slot_rows)
+    return _stream_attn('attn_temporal_pool', mode, n, c, S, D, heads, causal, cache_dtype, T_total, t0_rows, qkv, k_cache, v_cache, out, n_slots=n_slots,
+                        slot_rows=slot_rows)
 
 
 def cls_pool(x, n, c, S, cls_cache, n_slots, t0_rows, slot_rows):
     """cls_stream per row: t0_rows[r] == 0 -> merge (mode 1) and keep the row in cls_cache[slot_rows[r]] ([n_slots, D]); > 0 -> that row to slot 0."""
     _need_cuda(x, cls_cache, t0_rows, slot_rows)
-    L.check(L.lib().tcow_cls_pool(_stream(), n, c, S, x.shape[1], x.data_ptr(), cls_cache.data_ptr(), int(n_slots), t0_rows.data_ptr(), slot_rows.data_ptr()),
-            'tcow_cls_pool')
-    return x
+    return _stream_cls(x, n, c, 0, S, cls_cache, n_slots, t0_rows, slot_rows)
 
 
 def _ragged_tables(who, n, F, t0_rows, slot_rows, first_rows, c_rows, row_of_frame=None):
     """What a host can check of a ragged step's tables: on the device, int32, one entry per session (per frame: row_of_frame)."""
+    if n < 1:                   # (0 sessions in the record says "rows form")
+        raise L.TcowError(f'{who}: a ragged step is one row of F frames of 1 <= n <= F sessions (F={F} n={n})')
     for name, t, want in (('t0_rows', t0_rows, n), ('slot_rows', slot_rows, n), ('first_rows', first_rows, n), ('c_rows', c_rows, n),
                           ('row_of_frame', row_of_frame, F)):
         if t is None and name in ('row_of_frame', 'slot_rows'):         # (cls_ragged has no frame table, the paged attention no slot table)
@@ -436,43 +431,40 @@ def attn_temporal_ragged(mode, n, F, S, D, heads, causal, T_total, n_slots, t0_r
                          out, cache_dtype=None):
     """attn_temporal_pool for n sessions that bring different numbers of frames: session r owns the flat frames first_rows[r] .. + c_rows[r] - 1 of
     the step's F frames (qkv [F*S, 3D] -> out [F*S, D]), row_of_frame[f] names the session of frame f (int32 device tensors [n] / [F]); one wave per
-    frame, bit-identical per session to attn_temporal_pool (see tcow_attn_temporal_ragged_fwd)."""
-    lib, sh = _stream_attn(mode, 1, F, S, D, heads, causal, qkv, k_cache, v_cache, out)
+    frame, bit-identical per session to attn_temporal_pool (the ragged form of tcow_attn_temporal_step)."""
+    _need_cuda(qkv, k_cache, v_cache, out)
     _ragged_tables('attn_temporal_ragged', n, F, t0_rows, slot_rows, first_rows, c_rows, row_of_frame)
     _ragged_rows('attn_temporal_ragged', F, S, qkv, out)
-    _stream_attn_call(lib, 'tcow_attn_temporal_ragged_fwd', mode, cache_dtype, k_cache, v_cache,
-                      (sh, int(n), int(T_total), int(n_slots), t0_rows.data_ptr(), slot_rows.data_ptr(), first_rows.data_ptr(), c_rows.data_ptr(),
-                       row_of_frame.data_ptr(), qkv.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr()))
-    return out
+    return _stream_attn('attn_temporal_ragged', mode, 1, F, S, D, heads, causal, cache_dtype, T_total, t0_rows, qkv, k_cache, v_cache, out, n_sessions=n,
+                        n_slots=n_slots, slot_rows=slot_rows, first_rows=first_rows, c_rows=c_rows, row_of_frame=row_of_frame)
 
 
 def attn_temporal_ragged_paged(mode, n, F, S, D, heads, causal, T_total, n_pages, page_frames, t0_rows, page_rows, first_rows, c_rows, row_of_frame, qkv,
                                k_pages, v_pages, out, cache_dtype=None):
     """attn_temporal_ragged on a paged cache: k_pages / v_pages [n_pages, S-1, heads, page_frames, 64], and instead of a slot session r brings row r
     of page_rows (int32 device tensor [n, pages_per_session]): entry q is the page of its frames q * page_frames .. + page_frames - 1.
-    Bit-identical to attn_temporal_ragged on contiguous caches of the same contents (see tcow_attn_temporal_ragged_paged_fwd)."""
-    lib, sh = _stream_attn(mode, 1, F, S, D, heads, causal, qkv, k_pages, v_pages, out, page_rows)
+    Bit-identical to attn_temporal_ragged on contiguous caches of the same contents (the paged layout of tcow_attn_temporal_step)."""
+    _need_cuda(qkv, k_pages, v_pages, out, page_rows)
     _ragged_tables('attn_temporal_ragged_paged', n, F, t0_rows, None, first_rows, c_rows, row_of_frame)
     if page_rows.dtype != torch.int32 or page_rows.dim() != 2 or page_rows.shape[0] != n or page_rows.shape[1] < 1 or not page_rows.is_contiguous():
         raise L.TcowError(f'attn_temporal_ragged_paged: page_rows must be a contiguous int32 tensor of n = {n} rows of pages_per_session entries, got '
                           f'{page_rows.dtype} {tuple(page_rows.shape)}')
     _ragged_rows('attn_temporal_ragged_paged', F, S, qkv, out)
-    _stream_attn_call(lib, 'tcow_attn_temporal_ragged_paged_fwd', mode, cache_dtype, k_pages, v_pages,
-                      (sh, int(n), int(T_total), int(n_pages), int(page_frames), int(page_rows.shape[1]), t0_rows.data_ptr(), page_rows.data_ptr(),
-                       first_rows.data_ptr(), c_rows.data_ptr(), row_of_frame.data_ptr(), qkv.data_ptr(), k_pages.data_ptr(), v_pages.data_ptr(),
-                       out.data_ptr()))
-    return out
+    if not page_frames:         # (0 in the record says "contiguous": refused here, in the words the library has for every other bad page size)
+        raise L.TcowError('attn_temporal_ragged_paged: page_frames=0 must be a power of two in [1, 1024]')
+    return _stream_attn('attn_temporal_ragged_paged', mode, 1, F, S, D, heads, causal, cache_dtype, T_total, t0_rows, qkv, k_pages, v_pages, out, n_sessions=n,
+                        first_rows=first_rows, c_rows=c_rows, row_of_frame=row_of_frame, page_frames=page_frames, n_pages=n_pages,
+                        pages_per_session=page_rows.shape[1], page_rows=page_rows)
 
 
 def cls_ragged(x, n, F, S, cls_cache, n_slots, t0_rows, slot_rows, first_rows, c_rows):
-    """cls_pool for sessions of different chunk lengths: x [F*S, D]; session r's frames are first_rows[r] .. + c_rows[r] - 1 (see tcow_cls_ragged)."""
+    """cls_pool for sessions of different chunk lengths: x [F*S, D]; session r's frames are first_rows[r] .. + c_rows[r] - 1 (the ragged form of
+    tcow_cls_step)."""
     _need_cuda(x, cls_cache)
     _ragged_tables('cls_ragged', n, F, t0_rows, slot_rows, first_rows, c_rows)
     if x.shape[0] != F * S:
         raise L.TcowError(f'cls_ragged: x must have F * S = {F * S} rows, got {x.shape[0]}')
-    L.check(L.lib().tcow_cls_ragged(_stream(), int(n), int(F), S, x.shape[1], x.data_ptr(), cls_cache.data_ptr(), int(n_slots), t0_rows.data_ptr(),
-                                    slot_rows.data_ptr(), first_rows.data_ptr(), c_rows.data_ptr()), 'tcow_cls_ragged')
-    return x
+    return _stream_cls(x, n, 0, F, S, cls_cache, n_slots, t0_rows, slot_rows, first_rows, c_rows)
 
 
 def requery_mask(logits, src_off, threshold, mask, dst_rows, pixels):

@@ -30,13 +30,13 @@ its device tables and calls its own pair of ops entry points; step(), pool.step(
 their form, and nothing else asks which form a step has:
 
   _StreamStep (SeekerStream.step): every row stands at the same frame t0, a device scalar, and row b uses cache slot b
-  (tcow_attn_temporal_cached_fwd, tcow_cls_stream).
+  (the rows form of tcow_attn_temporal_step / tcow_cls_step without a slot table).
   _PoolStep (SeekerStreamPool.step): live sessions that started at different moments, stepped together with one chunk length: a t0 and a
-  cache slot per row (tcow_attn_temporal_pool_fwd, tcow_cls_pool -- the stream's kernels, of which the stream is the case "one t0, slot = row").
+  cache slot per row (the rows form with t0_rows and slot_rows -- the stream's kernels, of which the stream is the case "one t0, slot = row").
   _RaggedStep (SeekerStreamPool.step_ragged): the sessions bring different numbers of frames (cameras at different rates, a decoder's GOP, a
   session that catches up while its neighbours advance by one).  The F = sum of the c_i frames lie flat in session order and run as ONE row
   of F frames; ragged_tables() gives every session its t0, slot, first flat frame and chunk length and every frame its session
-  (tcow_attn_temporal_ragged_fwd, one wave per frame, not per session, and tcow_cls_ragged).
+  (the ragged form of both entry points: one wave per frame, not per session).
 
 A paged pool (net.stream_pool(capacity, page_frames=P, pages=N)): a contiguous pool reserves a whole stream's cache per slot, whether its session
 is at frame 2, at frame 59 or closed.  With page_frames the K / V caches of a block are a heap of N pages of P frames (_PagedState:
@@ -47,7 +47,7 @@ cannot run out; with fewer, a step that needs more pages than are free raises Tc
 moves.  Both step() and step_ragged() of a paged pool run a fourth form:
 
   _PagedRaggedStep: the _RaggedStep tables plus page_rows [n, ceil(T / P)], the sessions' pages in frame order, sent in the same host-to-device
-  copy (tcow_attn_temporal_ragged_paged_fwd: the ragged kernel with "page page_rows[r][kt / P], line kt % P" for "slot, line kt"; tcow_cls_ragged).
+  copy (the paged layout of tcow_attn_temporal_step: the ragged kernel with "page page_rows[r][kt / P], line kt % P" for "slot, line kt"; cls as ragged).
 
 Where a key lives does not enter the arithmetic, so a paged pool gives the bits of the contiguous pool.  A one-frame step costs between nothing measurable
 and 0.13 ms more than on the contiguous pool (profiles/stream_paged_latency.json; P = 8 is the recommendation, P = 1 the

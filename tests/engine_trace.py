@@ -56,6 +56,38 @@ def _argument(a, declared, ptrs):
     return a
 
 
+# The stream step's two entry points take one record each (tcow_stream_attn_args, tcow_stream_cls_args).  The fixture was recorded when every form
+# of the step had a positional entry point of its own, and it is not regenerated: a recorded record is written out as that form's call -- the
+# form's label (the former symbol), then these fields in this order -- and every field the form leaves out must be at rest (0 / NULL), so the
+# pinned call and the record say the same thing.  (The record itself, field by field: tests/test_stream_attn_record_host.py.)
+_ATTN_TAIL = ['qkv', 'k_cache', 'v_cache', 'out']
+_RAGGED = ['first_rows', 'c_rows', 'row_of_frame']
+STREAM_FORMS = {
+    'cached': ['shape', 'T_total', 't0_rows'] + _ATTN_TAIL,
+    'pool': ['shape', 'T_total', 'n_slots', 't0_rows', 'slot_rows'] + _ATTN_TAIL,
+    'ragged': ['shape', 'n_sessions', 'T_total', 'n_slots', 't0_rows', 'slot_rows'] + _RAGGED + _ATTN_TAIL,
+    'ragged_paged': ['shape', 'n_sessions', 'T_total', 'n_pages', 'page_frames', 'pages_per_session', 't0_rows', 'page_rows'] + _RAGGED + _ATTN_TAIL,
+    'cls_stream': ['n', 'c', 'S', 'D', 'x', 'cls_cache', 't0_rows'],
+    'cls_pool': ['n', 'c', 'S', 'D', 'x', 'cls_cache', 'n_slots', 't0_rows', 'slot_rows'],
+    'cls_ragged': ['n', 'F', 'S', 'D', 'x', 'cls_cache', 'n_slots', 't0_rows', 'slot_rows', 'first_rows', 'c_rows'],
+}
+
+
+def _stream_form_call(name, rec, ptrs):
+    """[form label, None (the stream), the form's fields ...] of a stream step record."""
+    if name == 'tcow_cls_step':
+        form = 'cls_ragged' if rec.first_rows or rec.c_rows else 'cls_pool' if rec.slot_rows else 'cls_stream'
+        label, tail = 'tcow_' + form, []
+    else:
+        form = ('ragged_paged' if rec.page_frames else 'ragged') if rec.n_sessions else 'pool' if rec.slot_rows else 'cached'
+        compact = rec.cache_dtype != rec.shape.dtype                # the storage type: the former entry points without a cache_dtype
+        label, tail = f"tcow_attn_temporal_{form}{'_cq' if compact else ''}_fwd", [rec.cache_dtype] if compact else []
+    fields, types = STREAM_FORMS[form], dict(rec._fields_)
+    rest = {f: getattr(rec, f) for f in types if f not in fields and f != 'cache_dtype'}
+    assert not any(rest.values()), (label, 'fields outside the form are set', rest)
+    return [label, None] + [_struct(rec.shape, ptrs) if f == 'shape' else _argument(getattr(rec, f), types[f], ptrs) for f in fields] + tail
+
+
 class Trace:
     """calls: the normalised calls in order.  events: ('call', entry name, [raw pointers]) in the same order, among which a RecordingHook
     puts its ('publish', tag, (lo, hi)) and ('finish',)."""
@@ -66,9 +98,20 @@ class Trace:
     def clear(self):
         del self.calls[:], self.events[:]
 
+    def _stream_step(self, name):
+        def entry(stream, args):
+            assert not stream, stream
+            ptrs = []
+            self.calls.append(_stream_form_call(name, args._obj, ptrs))
+            self.events.append(('call', self.calls[-1][0], ptrs))
+            return 0
+        return entry
+
     def __getattr__(self, name):                                    # the fake library: any entry point
         if not name.startswith('tcow_'):
             raise AttributeError(name)
+        if name in ('tcow_attn_temporal_step', 'tcow_cls_step'):
+            return self._stream_step(name)
         declared = _lib.SIGNATURES[name][1]
 
         def entry(*args):

@@ -322,7 +322,7 @@ def test_abi_has_the_grouped_column_sum():
     assert re.search(r'\blong\s+tcow_colsum_grouped_workspace_bytes\s*\(', code)
     assert {'tcow_colsum_grouped', 'tcow_colsum_grouped_workspace_bytes'} <= set(_lib.SIGNATURES)
     assert [f for f, _ in _lib.ColsumProblem._fields_] == ['M', 'N', 'dY', 'lddy', 'out', 'accumulate']
-    assert _lib.ABI_VERSION == 15 and int(re.search(r'#define\s+TCOW_ABI_VERSION\s+(\d+)', hdr).group(1)) == 15      # (14 when this symbol arrived, no signature changed; 15: the optimizer step became one entry point)
+    assert _lib.ABI_VERSION == 16 and int(re.search(r'#define\s+TCOW_ABI_VERSION\s+(\d+)', hdr).group(1)) == 16      # (14 when this symbol arrived, no signature changed; 15: the optimizer step became one entry point; 16: the stream step did)
     for fmt in ('bf16', 'fp16'):
         lib = _lib.lib(fmt)
-        assert lib.tcow_version() == 15 and lib.tcow_colsum_group_max() == 16
+        assert lib.tcow_version() == 16 and lib.tcow_colsum_group_max() == 16

@@ -81,7 +81,7 @@ def test_plan_reproduces_the_measured_table():
 def test_abi_14_declares_the_two_entry_points():
     from tcow_amd import _lib
     hdr = open(os.path.join(ROOT, 'include', 'tcow_hip.h')).read()
-    assert int(re.search(r'#define\s+TCOW_ABI_VERSION\s+(\d+)', hdr).group(1)) == 15 and _lib.ABI_VERSION == 15
+    assert int(re.search(r'#define\s+TCOW_ABI_VERSION\s+(\d+)', hdr).group(1)) == 16 and _lib.ABI_VERSION == 16
     assert re.search(r'long\s+tcow_gemm_nt_skinny_workspace_bytes\(int M, int N, int split\);', hdr)
     assert re.search(r'int\s+tcow_gemm_nt_skinny\(void\* stream, const tcow_gemm_args\* args, int split, void\* workspace, long workspace_bytes\);', hdr)
     i, l, vp = ctypes.c_int, ctypes.c_long, ctypes.c_void_p
@@ -89,7 +89,7 @@ def test_abi_14_declares_the_two_entry_points():
     assert _lib.SIGNATURES['tcow_gemm_nt_skinny'] == (i, [vp, ctypes.POINTER(_lib.GemmArgs), i, vp, l])
     for fmt in ('bf16', 'fp16'):
         lib = _lib.lib(fmt)
-        assert lib.tcow_version() == 15
+        assert lib.tcow_version() == 16
         assert lib.tcow_gemm_nt_skinny_workspace_bytes(301, 768, 1) == 0 and lib.tcow_gemm_nt_skinny_workspace_bytes(301, 768, 4) == 4 * 301 * 768 * 4
 
 
@@ -106,14 +106,14 @@ def test_public_keyword_and_default():
 def test_abi_14_declares_the_x3_entry_point():
     from tcow_amd import _lib
     hdr = open(os.path.join(ROOT, 'include', 'tcow_hip.h')).read()
-    assert int(re.search(r'#define\s+TCOW_ABI_VERSION\s+(\d+)', hdr).group(1)) == 15 and _lib.ABI_VERSION == 15
+    assert int(re.search(r'#define\s+TCOW_ABI_VERSION\s+(\d+)', hdr).group(1)) == 16 and _lib.ABI_VERSION == 16
     assert re.search(r'int\s+tcow_gemm_nt_skinny_x3\(void\* stream, const tcow_gemm_args\* args, int split, void\* workspace, long workspace_bytes\);', hdr)
     i, l, vp = ctypes.c_int, ctypes.c_long, ctypes.c_void_p
     assert _lib.SIGNATURES['tcow_gemm_nt_skinny_x3'] == (i, [vp, ctypes.POINTER(_lib.GemmArgs), i, vp, l])
     assert _lib.SIGNATURES['tcow_gemm_nt_skinny'] == (i, [vp, ctypes.POINTER(_lib.GemmArgs), i, vp, l])       # (unchanged)
     for fmt in ('bf16', 'fp16'):
         lib = _lib.lib(fmt)
-        assert lib.tcow_version() == 15
+        assert lib.tcow_version() == 16
         assert hasattr(lib, 'tcow_gemm_nt_skinny_x3')
 
 

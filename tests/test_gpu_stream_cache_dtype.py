@@ -1,10 +1,11 @@
-"""GPU: the compact K / V cache of a stream (net.stream(cache_dtype='bf16' | 'fp8'), the tcow_attn_temporal_*_cq_fwd entry points).
+"""GPU: the compact K / V cache of a stream (net.stream(cache_dtype='bf16' | 'fp8'), the cache_dtype field of tcow_attn_temporal_step).
 
 The contract (include/tcow_hip.h): with a cache of element type C a step computes softmax_{t' <= t}(q_t . rnd_C(k_t') / 8) rnd_C(v_t') with EVERY
 key and value at its rounded value, the step's own frames included, and appends the rounded bits once.  rnd_C is defined by torch on the CPU:
 x.clamp(-448, 448).to(torch.float8_e4m3fn) for fp8, x.to(torch.bfloat16) for the 16-bit cache of the f32-storage modes (_enc below).  So the
 kernel tests compare against an f64 restatement on inputs rounded that way with the tolerances of test_gpu_stream._attn_case (they cover the
 output rounding only), the cache bytes against _enc bit for bit, and the four step forms and every chunking against each other bit for bit."""
+import ctypes
 import functools
 
 import numpy as np
@@ -377,20 +378,20 @@ def test_compact_entry_points_refuse_bad_arguments(cuda):
             assert bool((out == 5.0).all()) and torch.equal(_b(kc), _b(kc0)) and torch.equal(_b(vc), _b(vc0)), (mode, match, kw)
         run()
         assert not bool((out == 5.0).any())
-    # the other three entry points refuse the same cache types, by their own names
+    # the other three wrappers reach the same refusal of the one entry point
     qkv = torch.zeros(S, 192, device='cuda'); out = torch.full((S, 64), 5.0, device='cuda')
     kc = _pattern((1, S - 1, 1, T, 64), FP8T, 3)
     one = _i32([0])
-    with pytest.raises(TcowError, match='tcow_attn_temporal_pool_cq_fwd: cache_dtype must be'):
+    with pytest.raises(TcowError, match='tcow_attn_temporal_step: cache_dtype must be'):
         ops.attn_temporal_pool(ops.F32, 1, 1, S, 64, 1, 1, T, 1, one, one, qkv, kc, kc.clone(), out, cache_dtype=9)
-    with pytest.raises(TcowError, match='tcow_attn_temporal_ragged_cq_fwd: cache_dtype must be'):
+    with pytest.raises(TcowError, match='tcow_attn_temporal_step: cache_dtype must be'):
         ops.attn_temporal_ragged(ops.F32, 1, 1, S, 64, 1, 1, T, 1, one, one, one, _i32([1]), one, qkv, kc, kc.clone(), out, cache_dtype=9)
-    with pytest.raises(TcowError, match='tcow_attn_temporal_ragged_paged_cq_fwd: cache_dtype must be'):
+    with pytest.raises(TcowError, match='tcow_attn_temporal_step: cache_dtype must be'):
         ops.attn_temporal_ragged_paged(ops.F32, 1, 1, S, 64, 1, 1, T, 1, 8, one, one.view(1, 1), one, _i32([1]), one, qkv, kc, kc.clone(), out, cache_dtype=9)
     lib = _lib.lib()
-    sh = _lib.AttnShape(1, 1, S, 64, 1, 1, _lib.TCOW_BF16)
-    assert lib.tcow_attn_temporal_pool_cq_fwd(None, sh, T, 1, one.data_ptr(), one.data_ptr(), qkv.data_ptr(), kc.data_ptr(), kc.data_ptr(), out.data_ptr(),
-                                              _lib.TCOW_F32) != 0 and b'wider than the 16-bit storage' in lib.tcow_last_error()
+    rec = _lib.StreamAttnArgs(shape=_lib.AttnShape(1, 1, S, 64, 1, 1, _lib.TCOW_BF16), cache_dtype=_lib.TCOW_F32, T_total=T, n_slots=1, t0_rows=one.data_ptr(),
+                              slot_rows=one.data_ptr(), qkv=qkv.data_ptr(), k_cache=kc.data_ptr(), v_cache=kc.data_ptr(), out=out.data_ptr())      # the pool form
+    assert lib.tcow_attn_temporal_step(None, ctypes.byref(rec)) != 0 and b'wider than the 16-bit storage' in lib.tcow_last_error()
     assert bool((out == 5.0).all())
 
 

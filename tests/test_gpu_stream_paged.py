@@ -1,6 +1,7 @@
 """GPU: a stream pool whose K / V caches are a heap of pages (stream_pool(page_frames=P, pages=N), tcow_amd/stream.py).  Where a key lives does
 not enter the arithmetic of temporal attention, so everything here is exact: the paged kernel against the contiguous ragged kernel bit for bit
 (outputs, and the pages gathered back), a paged pool against a contiguous pool on the same feed schedule bit for bit, and the page accounting."""
+import ctypes
 import functools
 
 import numpy as np
@@ -215,14 +216,15 @@ def test_paged_kernel_refuses_bad_arguments(cuda):
             run(**kw)
         assert bool((out == 5.0).all()), (match, kw)
     # null pointers cannot come through ops: the entry point itself
-    sh = _lib.AttnShape(1, F, S, 64, heads, 1, _lib.TCOW_F32)
-    ptrs = [tb['t0'], pages, tb['first'], tb['c'], tb['row_of_frame'], qkv, kp, kp.clone(), out]
-    fn = _lib.lib().tcow_attn_temporal_ragged_paged_fwd
-    for k in range(len(ptrs)):
-        p = [None if i == k else t.data_ptr() for i, t in enumerate(ptrs)]
-        assert fn(None, sh, n, T, n_pages, P, 2, *p) != 0 and b'null pointer' in _lib.lib().tcow_last_error()
+    ptrs = dict(t0_rows=tb['t0'], page_rows=pages, first_rows=tb['first'], c_rows=tb['c'], row_of_frame=tb['row_of_frame'], qkv=qkv, k_cache=kp, v_cache=kp.clone(),
+                out=out)
+    fn = _lib.lib().tcow_attn_temporal_step
+    for k in ptrs:                                                              # each pointer field of a paged ragged record in turn
+        rec = _lib.StreamAttnArgs(shape=_lib.AttnShape(1, F, S, 64, heads, 1, _lib.TCOW_F32), cache_dtype=_lib.TCOW_F32, T_total=T, n_sessions=n, page_frames=P,
+                                  n_pages=n_pages, pages_per_session=2, **{name: None if name == k else t.data_ptr() for name, t in ptrs.items()})
+        assert fn(None, ctypes.byref(rec)) != 0 and b'null pointer' in _lib.lib().tcow_last_error()
         assert bool((out == 5.0).all()), k
-    assert fn(None, None, n, T, n_pages, P, 2, *[t.data_ptr() for t in ptrs]) != 0 and b'null shape' in _lib.lib().tcow_last_error()
+    assert fn(None, None) != 0 and b'null args' in _lib.lib().tcow_last_error()
     run()
     assert not bool((out == 5.0).any())
 

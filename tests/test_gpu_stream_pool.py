@@ -130,7 +130,7 @@ def test_pool_kernels_refuse_bad_arguments(cuda):
     for bad in (0, -1):
         with pytest.raises(TcowError, match='n_slots'):
             ops.attn_temporal_pool(ops.F32, n, c, S, 64, heads, 1, T, bad, t0, sl, qkv, kc, kc.clone(), out)
-        with pytest.raises(TcowError, match='tcow_cls_pool'):
+        with pytest.raises(TcowError, match='tcow_cls_step: n_slots'):
             ops.cls_pool(torch.zeros(n * c * S, 64, device=dev), n, c, S, torch.zeros(n_slots, 64, device=dev), bad, t0, sl)
     with pytest.raises(TcowError, match='CUDA'):
         ops.attn_temporal_pool(ops.F32, n, c, S, 64, heads, 1, T, n_slots, t0.cpu(), sl, qkv, kc, kc.clone(), out)

@@ -183,7 +183,7 @@ def test_ragged_kernels_refuse_bad_arguments(cuda):
     for bad in (0, -1):
         with pytest.raises(TcowError, match='n_slots'):
             run(slots=bad)
-        with pytest.raises(TcowError, match='tcow_cls_ragged'):
+        with pytest.raises(TcowError, match='tcow_cls_step: n_slots'):
             ops.cls_ragged(x, n, F, S, cc, bad, tb['t0'], tb['slot'], tb['first'], tb['c'])
     for name in ('t0', 'slot', 'first', 'c', 'row_of_frame'):
         with pytest.raises(TcowError, match='CUDA'):

@@ -1,21 +1,17 @@
 """CPU: the host side of the compact K / V cache of a stream (net.stream(cache_dtype=...), tcow_amd/stream.py) -- the one function that decides
-the cache's element type, for every (precision, keyword) pair with its refusals, and the ABI of the four tcow_attn_temporal_*_cq_fwd symbols."""
+the cache's element type, for every (precision, keyword) pair with its refusals, and the ABI of the step record that carries it (tests/stream_abi.py)."""
 import ctypes
-import os
 import re
 
 import pytest
 import torch
 
+import stream_abi as abi
 from tcow_amd import _lib, ops, stream
 from tcow_amd._lib import TcowError
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 # precision -> the ops mode a module of that precision stores in (seeker.py: bf16x3 stores f32)
 MODES = {'fp32': ops.F32, 'bf16x3': ops.F32, 'bf16': ops.BF16, 'fp16': ops.FP16}
-CQ = ['tcow_attn_temporal_cached_cq_fwd', 'tcow_attn_temporal_pool_cq_fwd', 'tcow_attn_temporal_ragged_cq_fwd',
-      'tcow_attn_temporal_ragged_paged_cq_fwd']
 
 
 @pytest.mark.parametrize('precision,keyword,want', [
@@ -49,25 +45,17 @@ def test_cache_bytes_formula_at_configs1():
 
 
 def test_the_cq_entry_points_are_new_symbols_of_abi_14():
-    hdr = open(os.path.join(ROOT, 'include', 'tcow_hip.h')).read()
-    assert int(re.search(r'#define\s+TCOW_ABI_VERSION\s+(\d+)', hdr).group(1)) == 15 and _lib.ABI_VERSION == 15      # new symbols, no signature changed
+    """Since ABI 16 the cache element type is a field of the one step record, always present: no entry point of its own."""
+    hdr, code = abi.header()
+    abi.check_version()
     assert int(re.search(r'#define\s+TCOW_FP8E4M3\s+(\d+)', hdr).group(1)) == _lib.TCOW_FP8E4M3 == ops.FP8 == 3
     assert len({_lib.TCOW_F32, _lib.TCOW_BF16, _lib.TCOW_F32X3, _lib.TCOW_FP8E4M3}) == 4
-    code = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
-    for name in CQ:
-        base = name.replace('_cq_fwd', '_fwd')
-        decl = re.search(r'\bint\s+' + name + r'\s*\(([^)]*)\)\s*;', code)
-        old = re.search(r'\bint\s+' + base + r'\s*\(([^)]*)\)\s*;', code)
-        assert decl and old, f'{name} / {base} not declared in tcow_hip.h'
-        args, old_args = [a.strip() for a in decl.group(1).split(',')], [a.strip() for a in old.group(1).split(',')]
-        assert args[:-1] == old_args and args[-1] == 'int cache_dtype'                  # the old entry point's arguments and one more
-        assert _lib.SIGNATURES[name] == (ctypes.c_int, _lib.SIGNATURES[base][1] + [ctypes.c_int])
+    abi.check_header_and_records()
+    assert ('cache_dtype', ctypes.c_int) in abi.header_fields(code, 'tcow_stream_attn_args')
+    assert not any('_cq' in name for name in _lib.SIGNATURES) and '_cq_fwd' not in code
 
 
 def test_both_builds_export_the_cq_entry_points():
-    for fmt in ('bf16', 'fp16'):
-        lib = _lib.lib(fmt)
-        assert lib.tcow_version() == 15
-        for name in CQ:
-            assert hasattr(lib, name), f'{name} is not exported by the {fmt} build'
-            assert getattr(lib, name).argtypes == _lib.SIGNATURES[name][1]
+    """Both builds export the step's two entry points with the declared argument types, and none of the eight attention symbols they replaced."""
+    abi.check_builds_export()
+    abi.check_old_symbols_are_gone([n for n in abi.OLD if 'attn' in n])

@@ -1,11 +1,13 @@
 """CPU: the host side of a paged stream pool (stream_pool(page_frames=P, pages=N), tcow_amd/stream.py) -- the page allocator against a set-based
 model, the page moves of a rollover call against the accounting they replaced, the keyword checks, and the ABI entry of the paged attention kernel."""
+import ctypes
 import os
 import re
 
 import numpy as np
 import pytest
 
+import stream_abi as abi
 from stream_kit import _net
 from tcow_amd import _lib, stream
 from tcow_amd._lib import TcowError
@@ -243,11 +245,12 @@ def test_stream_pool_refuses_bad_page_keywords_before_anything_else():
 # ---------------------------------------------------------------------------------------------- ABI
 
 def test_paged_abi_entry():
-    hdr = open(os.path.join(ROOT, 'include', 'tcow_hip.h')).read()
-    assert int(re.search(r'#define\s+TCOW_ABI_VERSION\s+(\d+)', hdr).group(1)) == 15 and _lib.ABI_VERSION == 15
-    name = 'tcow_attn_temporal_ragged_paged_fwd'
-    decl = re.search(r'\bint\s+' + name + r'\s*\(([^;]*)\)\s*;', hdr)
-    assert decl, f'{name} is not declared in tcow_hip.h'
-    n_args = len(decl.group(1).split(','))
-    assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name][1]) == n_args == 16
-    assert hasattr(_lib.lib(), name) and hasattr(_lib.lib('fp16'), name)
+    """The paged layout is three ints and a table of the step record (page_frames == 0: contiguous), not an entry point."""
+    abi.check_version()
+    abi.check_header_and_records()
+    fields = abi.header_fields(abi.header()[1], 'tcow_stream_attn_args')
+    assert [f for f in fields if 'page' in f[0]] == [('page_frames', ctypes.c_int), ('n_pages', ctypes.c_int), ('pages_per_session', ctypes.c_int),
+                                                     ('page_rows', ctypes.c_void_p)]
+    assert len(_lib.SIGNATURES['tcow_attn_temporal_step'][1]) == 2
+    abi.check_builds_export()
+    abi.check_old_symbols_are_gone(['tcow_attn_temporal_ragged_paged_fwd', 'tcow_attn_temporal_ragged_paged_cq_fwd'])

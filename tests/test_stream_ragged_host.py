@@ -3,6 +3,7 @@ argument refusals that look at the lists alone, and the ABI entries."""
 import pytest
 import torch
 
+import stream_abi as abi
 from stream_kit import _net
 from tcow_amd import _lib, stream
 from tcow_amd._lib import TcowError
@@ -89,7 +90,10 @@ def test_step_ragged_input_refusals():
 
 
 def test_ragged_abi_entries():
+    """A ragged step is a form of the two step records (n_sessions >= 1; first_rows / c_rows given), not an entry point."""
     assert _lib.ABI_VERSION >= 13
-    for name in ('tcow_attn_temporal_ragged_fwd', 'tcow_cls_ragged'):
+    abi.check_header_and_records()
+    for name in abi.RECORDS:
         assert name in _lib.SIGNATURES
         assert hasattr(_lib.lib(), name) and hasattr(_lib.lib('fp16'), name)
+    abi.check_old_symbols_are_gone(['tcow_attn_temporal_ragged_fwd', 'tcow_attn_temporal_ragged_cq_fwd', 'tcow_cls_stream', 'tcow_cls_pool', 'tcow_cls_ragged'])

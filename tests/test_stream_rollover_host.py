@@ -201,13 +201,13 @@ def test_page_default_and_peak():
 
 def test_requery_abi_entry():
     hdr = open(os.path.join(ROOT, 'include', 'tcow_hip.h')).read()
-    assert int(re.search(r'#define\s+TCOW_ABI_VERSION\s+(\d+)', hdr).group(1)) == 15 and _lib.ABI_VERSION == 15      # a new symbol, no signature changed
+    assert int(re.search(r'#define\s+TCOW_ABI_VERSION\s+(\d+)', hdr).group(1)) == 16 and _lib.ABI_VERSION == 16
     code = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
     decl = re.search(r'\bint\s+tcow_requery_mask\s*\(([^;]*)\)\s*;', code)
     assert decl, 'tcow_requery_mask is not declared in tcow_hip.h'
     assert len(decl.group(1).split(',')) == len(_lib.SIGNATURES['tcow_requery_mask'][1]) == 11
     for fmt in ('bf16', 'fp16'):
         lib = _lib.lib(fmt)
-        assert lib.tcow_version() == 15
+        assert lib.tcow_version() == 16
         assert hasattr(lib, 'tcow_requery_mask'), f'tcow_requery_mask is not exported by the {fmt} build'
         assert lib.tcow_requery_mask.argtypes == _lib.SIGNATURES['tcow_requery_mask'][1]

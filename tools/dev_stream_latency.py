@@ -414,7 +414,7 @@ def rollover_leg(reps, k):
 
 
 def cached_kernel_bytes(T, H, W, e=2, heads=12, D=768, ce=None):
-    """Algorithmic bytes of one tcow_attn_temporal_cached_fwd launch of a one-frame step at t0 = T - 1 (B = 1, element size e, cache element
+    """Algorithmic bytes of one tcow_attn_temporal_step launch (the stream form) of a one-frame step at t0 = T - 1 (B = 1, element size e, cache element
     size ce: e unless the cache is compact)."""
     S, t0 = (H // 16) * (W // 16) + 1, T - 1
     ce = e if ce is None else ce

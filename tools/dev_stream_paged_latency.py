@@ -88,7 +88,7 @@ def paged_leg(name, n, precision, reps):
 
 def kernel_leg(name, n, storage, reps, heads=12, D=768):
     """One block's temporal-attention launch of the one-frame step at t0 = T - 1 (n sessions, random contents and a random page table), in us per
-    launch: tcow_attn_temporal_pool_fwd, tcow_attn_temporal_ragged_fwd and tcow_attn_temporal_ragged_paged_fwd at P = 1, 8, 32."""
+    launch: tcow_attn_temporal_step in its pool (rows), ragged and paged ragged forms at P = 1, 8, 32."""
     T, H, W = CONFIGS[name]
     S = (H // 16) * (W // 16) + 1
     mode, dt = (ops.BF16, torch.bfloat16) if storage == 'bf16' else (ops.F32, torch.float32)

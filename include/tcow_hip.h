@@ -241,6 +241,38 @@ int tcow_attn_temporal_bwd(void* stream, const tcow_attn_shape* shape, const voi
 int tcow_attn_spatial_bwd(void* stream, const tcow_attn_shape* shape, const void* qkv, const void* out,
                           const void* dout, const float* lse, void* dqkv, void* workspace, long workspace_bytes);
 
+/* Attention maps (attention_probs.hip; a new entry point, no signature changed: the ABI version stays): the softmax rows themselves, which the kernels above never store, from a block's qkv
+ * GEMM output [rows, 3D] -- row = (b*T + t)*S + s, column = which*D + head*64 + j, the sequences and masks exactly those stated above.
+ *   temporal form (TCOW_PROBS_TEMPORAL): for every (clip b, slot s >= 1, head h), query frame tq and key frame tk
+ *       out[b, s-1, h, tq, tk] = softmax_tk(q . k / 8) over the keys the mask allows: causal in {1,2}: tk <= tq; causal >= 3: tk <= tq + causal - 2;
+ *       causal <= 0: all.  A masked entry is written as exactly +0.0 (the reference's -1e10 fill, vit.py:99, underflows to that in f32).
+ *       out f32 [B, S-1, heads, T, T]: the batch order of the reference's '(b h w) t m' (vit.py:169-171).  1 <= T <= TCOW_STREAM_MAX_FRAMES.
+ *       lse (NULL = not wanted) f32 [B*T*S, heads], entry (row, head) as tcow_attn_temporal_fwd writes it; slot-0 rows are not touched.
+ *   rows form (TCOW_PROBS_ROWS): a table pos [nq] (DEVICE int32) of query positions of the sequences of tcow_attn_spatial_fwd for this shape --
+ *       G = B*T sequences over slots s0 .. S-1, s0 = 0 when causal is in {0,1} (the cls takes part) and 1 otherwise; position p is slot s0 + p.  A
+ *       joint_space_time block is the same thing with T = 1, S = 1 + N*T_clip, causal = 0 on its compacted sequences.  For every sequence g,
+ *       entry i and head h, out[g, i, h, :] = the softmax of query position pos[i] over all S slots, no mask; out f32 [G, nq, heads, S], column 0
+ *       exactly +0.0 when slot 0 takes no part.  lse (NULL = not wanted) f32 [G, nq, heads].  An entry outside [0, S - s0) writes NaN to its own
+ *       rows of out (and lse) and reads nothing -- the bad row of tcow_attn_temporal_step; the other entries are unaffected.
+ * Arithmetic, for every dtype: the stored q and k as they are (the build's 16-bit type, or f32; TCOW_F32X3 stores f32 and takes the f32 kernel),
+ * f32 products and f32 accumulation in a fixed order, maximum, exp and normalisation in f32, no atomics: a fixed function of the inputs.
+ * That is the softmax of the q and k the model computed, NOT a replay of a flash kernel's own score rounding: the 16-bit streaming forward rounds a
+ * pre-scaled Q once, the x3 kernels drop lo x lo -- out @ v therefore agrees with tcow_attn_*_fwd to those kernels' own tolerance, not bit for bit.
+ * Refused before anything is launched (TCOW_ERR_INVALID_ARG, the message names the field): NULL args, qkv or out; B, T, heads < 1, S < 2;
+ * D != heads * 64; an unknown dtype or form; temporal: T > TCOW_STREAM_MAX_FRAMES, nq != 0, pos != NULL; rows: nq < 1, pos == NULL. */
+#define TCOW_PROBS_TEMPORAL 0
+#define TCOW_PROBS_ROWS 1
+typedef struct {
+    tcow_attn_shape shape;
+    int form;                   /* TCOW_PROBS_TEMPORAL / TCOW_PROBS_ROWS */
+    int nq;                     /* rows form: entries of pos; temporal form: 0 */
+    const int* pos;             /* rows form: device int32 [nq]; temporal form: NULL */
+    const void* qkv;
+    float* out;
+    float* lse;                 /* may be NULL */
+} tcow_attn_probs_args;
+int tcow_attn_probs(void* stream, const tcow_attn_probs_args* args);
+
 /* ------------------------------------------------------------------------------------------- streaming inference (attention_stream.hip)
  * A stream feeds the model c >= 1 new frames at a time (tcow_amd/stream.py).  With causal_attention 1 or 2 frame t depends on frames 0..t only
  * (tril() of vit.py:93-99, frame-0 cls of vit.py:192-198), so each step runs the block schedule on its own rows and takes the temporal keys /

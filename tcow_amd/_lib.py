@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get('TCOW_LIB') or os.path.join(_HERE, 'libtcow_hip.so')  
 LIB_PATH_FP16 = os.path.join(_HERE, 'libtcow_hip_fp16.so')                          # the binary16 build of the same sources (precision='fp16')
 
 TCOW_F32, TCOW_BF16, TCOW_F32X3 = 0, 1, 2
+PROBS_TEMPORAL, PROBS_ROWS = 0, 1     # form of tcow_attn_probs
 TCOW_FP8E4M3 = 3          # cache_dtype of tcow_attn_temporal_step only (one OCP e4m3fn byte per element)
 ACT_NONE, ACT_GELU, ACT_DGELU, ACT_GELU_DSAVE, ACT_MUL_AUX = 0, 1, 2, 3, 4
 
@@ -30,6 +31,11 @@ class StreamAttnArgs(ctypes.Structure):
                 ('t0_rows', ctypes.c_void_p), ('slot_rows', ctypes.c_void_p), ('first_rows', ctypes.c_void_p), ('c_rows', ctypes.c_void_p),
                 ('row_of_frame', ctypes.c_void_p), ('page_rows', ctypes.c_void_p),
                 ('qkv', ctypes.c_void_p), ('k_cache', ctypes.c_void_p), ('v_cache', ctypes.c_void_p), ('out', ctypes.c_void_p)]
+
+
+class AttnProbsArgs(ctypes.Structure):
+    _fields_ = [('shape', AttnShape), ('form', ctypes.c_int), ('nq', ctypes.c_int), ('pos', ctypes.c_void_p), ('qkv', ctypes.c_void_p),
+                ('out', ctypes.c_void_p), ('lse', ctypes.c_void_p)]
 
 
 class StreamClsArgs(ctypes.Structure):
@@ -123,6 +129,7 @@ SIGNATURES = {
     'tcow_attn_bwd_workspace_bytes': (_l, [_ash]),
     'tcow_attn_temporal_bwd': (_i, [_vp, _ash, _vp, _vp, _vp, _vp, _vp, _vp, _l]),
     'tcow_attn_spatial_bwd': (_i, [_vp, _ash, _vp, _vp, _vp, _vp, _vp, _vp, _l]),
+    'tcow_attn_probs': (_i, [_vp, ctypes.POINTER(AttnProbsArgs)]),
     'tcow_attn_temporal_step': (_i, [_vp, ctypes.POINTER(StreamAttnArgs)]),
     'tcow_cls_step': (_i, [_vp, ctypes.POINTER(StreamClsArgs)]),
     'tcow_requery_mask': (_i, [_vp, _i, _l, _vp, _l, _vp, _f, _vp, _vp, _i, _vp]),

@@ -210,8 +210,9 @@ class _Ctx:
     in bf16x3, csrc/attention_x3.hip), the geometry g, the attention shapes, the parameter layout, and `save`: whether activations are kept
     for a backward (the forward of a training step, and the backward itself)."""
 
-    def __init__(self, module, g, dev, save, stream=None):
+    def __init__(self, module, g, dev, save, stream=None, probe=None):
         self.module, self.g, self.dev, self.save, self.stream = module, g, dev, save, stream
+        self.probe = probe                  # attention_maps only (attn_probe.MapProbe); None: nothing is called
         self.mode, self.gmode = module.mode, module.gemm_mode
         self.amode = self.gmode if self.gmode == ops.F32X3 else self.mode
         self.dt = ops.tdtype(self.mode)
@@ -320,6 +321,8 @@ def _block_forward_joint(c, i, q, R0, dp, mask0, st):
     QKV2 = c.E(M, 3 * D)
     ops.gemm_nt(c.gmode, V, c.W(q[ix['qkv']]), QKV2, bias=q[ix['qkv'] + 1].detach(), **c.sk)
     QJ = QKV2.index_select(0, c.jrows)                                # compact (cls, patches) sequences: the kernels take contiguous ones
+    if c.probe is not None:
+        c.probe.spatial(i, c, QJ)
     OJ = c.E(B * c.Lj, D); lse_s = c.E(B * c.Lj, heads, dtype=f32) if c.save else None
     ops.attn_fwd(c.shape_joint, True, QJ, OJ, lse_s)
     O2 = torch.zeros(M, D, dtype=c.dt, device=c.dev)
@@ -341,6 +344,8 @@ def _block_forward_divided(c, i, q, R0, dp, mask0, st):
     U, mu0, rs0 = c.ln_fwd(R0, P_('tn'), P_('tn', 1))
     QKV = E(M, 3 * D)
     ops.gemm_nt(gmode, U, W(q[ix['tqkv']]), QKV, bias=P_('tqkv', 1), **sk)
+    if c.probe is not None:
+        c.probe.temporal(i, c, QKV)
     O = E(M, D); lse_t = E(M, heads, dtype=f32) if save else None
     if stream is None:
         ops.attn_fwd(c.shape_attn, False, QKV, O, lse_t)
@@ -361,6 +366,8 @@ def _block_forward_divided(c, i, q, R0, dp, mask0, st):
     V, mu1, rs1 = c.ln_fwd(R1, P_('n1'), P_('n1', 1))
     QKV2 = E(M, 3 * D)
     ops.gemm_nt(gmode, V, W(q[ix['qkv']]), QKV2, bias=P_('qkv', 1), **sk)
+    if c.probe is not None:
+        c.probe.spatial(i, c, QKV2)
     O2 = E(M, D); lse_s = E(M, heads, dtype=f32) if save else None
     ops.attn_fwd(c.shape_attn, True, QKV2, O2, lse_s)
     rs_s = dp['s']
@@ -429,7 +436,7 @@ def lowest_block(lay, frozen, want_inputs):
     return lay.depth
 
 
-def run_forward(module, rgb, qm, params, save, stream=None, frozen=frozenset(), want_inputs=(False, False)):
+def run_forward(module, rgb, qm, params, save, stream=None, frozen=frozenset(), want_inputs=(False, False), probe=None):
     """-> (mask logits, flags, saved activations or None).
     frozen, want_inputs (training): the indices of the parameters whose gradient is NOT wanted and which input gradients (frames, query mask) are,
     as SeekerFunction.forward reads them; they hold for this forward's backward (sv['frozen'], sv['want_inputs'], sv['k'] = lowest_block()) and
@@ -438,10 +445,13 @@ def run_forward(module, rgb, qm, params, save, stream=None, frozen=frozenset(), 
     per row, and the schedule differs in three places: the embeddings (stream.pos, and stream.time_rows [B*T, D], one row of the time table per
     (row, frame)), the temporal attention (stream.attn_temporal: against the block's K / V cache, which it extends) and, for
     causal_attention == 1, the cls row (stream.cls_row: frame 0's, kept per block).  A fifth thing is asked of the step: stream.skinny, whether its
-    GEMMs may take the skinny-M entry point (ops.gemm_nt(..., skinny=)); the clip path never passes the keyword."""
+    GEMMs may take the skinny-M entry point (ops.gemm_nt(..., skinny=)); the clip path never passes the keyword.
+    probe (Seeker.attention_maps; None: nothing changes): every block calls probe.temporal(i, c, QKV) right after its temporal qkv GEMM and
+    probe.spatial(i, c, QKV2 -- joint: the compacted QJ) right after its spatial one; the probe launches ops.attn_probs on the same stream into
+    tensors of its own and decides which blocks it serves.  It reads the tensor during the call only: no activation is kept alive for it."""
     B = qm.shape[0]                          # query rows (== clips unless the rgb frames are shared between a clip's queries)
     g = module.geometry(B) if stream is None else module.geometry(B, T=rgb.shape[2])
-    c = _Ctx(module, g, rgb.device, save, stream)
+    c = _Ctx(module, g, rgb.device, save, stream, probe)
     mask0, dps = _row_vectors(module, g, module.training, stream_step=stream is not None)
     sv = {'g': g, 'blocks': [], 'mask0': mask0, 'dps': dps} if save else None
     k = lowest_block(c.lay, frozen, want_inputs) if save else 0
@@ -450,7 +460,7 @@ def run_forward(module, rgb, qm, params, save, stream=None, frozen=frozenset(), 
     X = _patch_embed(c, rgb, qm, params, sv if save and (c.lay.patch_w not in frozen or any(want_inputs)) else None)
     _embed(c, X, params, sv)
     block_forward = _block_forward_joint if c.joint else _block_forward_divided
-    below = _Ctx(module, g, rgb.device, False, stream) if k > 0 else None      # the blocks under the lowest wanted parameter run as in inference
+    below = _Ctx(module, g, rgb.device, False, stream, probe) if k > 0 else None      # the blocks under the lowest wanted parameter run as in inference
     for i in range(module.network_depth):
         keep = save and i >= k
         st = {} if keep else None

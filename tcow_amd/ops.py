@@ -346,6 +346,30 @@ def attn_bwd(shape, spatial, qkv, out, dout, lse, dqkv):
     return dqkv
 
 
+def attn_probs(shape, spatial_rows, qkv, out, lse=None, pos=None):
+    """The attention maps of one block from its qkv GEMM output [rows, 3D] (tcow_attn_probs), f32.  spatial_rows False: the temporal form,
+    out [B, S-1, heads, T, T], lse [B*T*S, heads] as attn_fwd writes it.  True: the rows form -- pos, a device int32 table of nq query positions
+    of the sequences attn_fwd(shape, True, ...) runs over; out [B*T, nq, heads, S], lse [B*T, nq, heads]."""
+    _need_cuda(qkv, out, lse, pos)
+    lib = shape.tcow_lib
+    if pos is not None and (pos.dtype != torch.int32 or pos.dim() != 1 or not pos.is_contiguous()):
+        raise L.TcowError(f'attn_probs: pos must be a contiguous int32 vector, got {pos.dtype} {tuple(pos.shape)}')
+    if out.dtype != torch.float32 or not out.is_contiguous() or (lse is not None and (lse.dtype != torch.float32 or not lse.is_contiguous())):
+        raise L.TcowError('attn_probs: out and lse must be contiguous float32 tensors')
+    nq = pos.numel() if pos is not None else 0
+    want = shape.B * shape.T * nq * shape.heads * shape.S if spatial_rows else shape.B * (shape.S - 1) * shape.heads * shape.T * shape.T
+    if out.numel() != want or qkv.shape[0] != shape.B * shape.T * shape.S:
+        raise L.TcowError(f'attn_probs: out must hold {want} floats and qkv {shape.B * shape.T * shape.S} rows, got {out.numel()} / {qkv.shape[0]}')
+    if qkv.dim() != 2 or qkv.shape[1] != 3 * shape.D or not qkv.is_contiguous() or qkv.element_size() != (2 if shape.dtype == BF16 else 4):
+        raise L.TcowError(f'attn_probs: qkv must be a contiguous [rows, {3 * shape.D}] tensor of the shape\'s storage type, got {qkv.dtype} {tuple(qkv.shape)}')
+    want = shape.B * shape.T * (nq if spatial_rows else shape.S) * shape.heads
+    if lse is not None and lse.numel() != want:
+        raise L.TcowError(f'attn_probs: lse must hold {want} floats, got {lse.numel()}')
+    args = L.AttnProbsArgs(shape, L.PROBS_ROWS if spatial_rows else L.PROBS_TEMPORAL, nq, _p(pos), qkv.data_ptr(), out.data_ptr(), _p(lse))
+    L.check(lib.tcow_attn_probs(_stream(), ctypes.byref(args)), 'tcow_attn_probs', lib)
+    return out
+
+
 FP8 = L.TCOW_FP8E4M3      # cache_dtype of the attn_temporal_* wrappers only: a K / V cache of torch.float8_e4m3fn elements
 
 

@@ -359,6 +359,44 @@ class QueryMaskTracker(nn.Module):
             out_flags = None
         return (out_mask, out_flags)
 
+    def attention_maps(self, input_frames, query_mask, blocks=None, temporal=True, spatial_queries=None, max_bytes=None):
+        """forward() that also returns attention weights: (output_mask, output_flags, maps), the two outputs with the bits of forward() on the
+        same inputs, maps an attn_probe.AttentionMaps:
+          maps.temporal[i] (B, N, heads, T, T): block i, which earlier frames a patch pulls from (temporal=True; divided_space_time only);
+          maps.spatial[i]  (B, nq, heads, S):   block i, which slots the tokens of spatial_queries look at -- None: no spatial maps, 'cls', or a
+                                                list of (frame, slot), slot 0 = cls, 1 + n = patch n; joint_space_time: (B, nq, heads, 1 + N*T)
+                                                over the clip's tokens in the reference's order (cls, 1 + n*T + t);
+          maps.queries: the normalised (frame, slot) list.  B counts query rows (clips x queries per clip).
+        blocks: None = all, or block indices (negative from the top).  max_bytes: budget of the maps (default 4 GiB); what is asked for is
+        computed and refused, in bytes, before anything runs (tcow_amd/attn_maps.py has every rule).
+        The maps are the f32 softmax of the q and k the model computed and stored (include/tcow_hip.h, tcow_attn_probs), not a replay of the
+        flash kernels' own score rounding.  Eval mode only (DropPath draws would make a map a sample), no forced_drop_masks, under
+        torch.no_grad(), the clip path only: maps of a live stream or pool session against its cache are out of scope."""
+        from .attn_maps import DEFAULT_MAX_BYTES, MapPlan
+        from .attn_probe import MapProbe
+        from .engine import run_forward
+        if self.training:
+            raise TcowError('attention_maps: the module is in training mode: DropPath draws would make a map a sample (call .eval())')
+        if self.forced_drop_masks is not None:
+            raise TcowError('attention_maps: forced_drop_masks is set: the maps are defined for the eval forward only')
+        if not input_frames.is_cuda or not query_mask.is_cuda or not self.vit.pos_embed.is_cuda:
+            raise TcowError('attention_maps: Seeker (tcow_amd) runs on the GPU only: move inputs and module to cuda')
+        if query_mask.device != input_frames.device or self.vit.pos_embed.device != input_frames.device:
+            raise TcowError(f'attention_maps: inputs ({input_frames.device}, {query_mask.device}) and parameters ({self.vit.pos_embed.device}) must share one device')
+        (B, _, T, Hf, Wf) = input_frames.shape
+        assert query_mask.shape[1] == 1 and query_mask.shape[0] % B == 0 and query_mask.shape[2:] == input_frames.shape[2:]
+        assert T == self.num_total_frames and Hf == self.frame_height and Wf == self.frame_width
+        assert self.attention_type == 'divided_space_time' or self.causal_attention == 0
+        g = self.geometry(query_mask.shape[0])
+        plan = MapPlan(self.network_depth, g['B'], g['T'], g['S'], g['heads'], self.causal_attention, self.attention_type != 'divided_space_time',
+                       blocks, temporal, spatial_queries, DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
+        rgb = input_frames.to(torch.float32).contiguous()
+        qm = query_mask.to(torch.float32).contiguous()
+        with torch.no_grad(), torch.cuda.device(input_frames.device):
+            probe = MapProbe(plan, input_frames.device)
+            out_mask, out_flags, _ = run_forward(self, rgb, qm, self.param_list(), save=False, probe=probe)
+        return (out_mask, out_flags if self.flag_channels > 0 else None, probe.maps)
+
 
 class Seeker(nn.Module):
     """model/seeker.py:17-25."""
@@ -373,6 +411,10 @@ class Seeker(nn.Module):
 
     def forward(self, *args):
         return self.seeker(*args)
+
+    def attention_maps(self, input_frames, query_mask, blocks=None, temporal=True, spatial_queries=None, max_bytes=None):
+        """See QueryMaskTracker.attention_maps."""
+        return self.seeker.attention_maps(input_frames, query_mask, blocks, temporal, spatial_queries, max_bytes)
 
     def stream(self, batch_size=1, queries_per_clip=1, graph=False, skinny_gemm=None, cache_dtype=None):
         """See QueryMaskTracker.stream."""

@@ -65,6 +65,13 @@ static inline SeqDesc spatial_desc(const tcow_attn_shape* s) {
     return d;
 }
 
+// Hand-off through wave-private LDS (some lanes write, other lanes of the SAME wave read; no workgroup barrier): a wave's LDS operations execute in
+// order, so the hardware needs nothing -- a compiler barrier that emits no instruction would do.  What the hand-off does need is that hipcc keeps
+// the reads after the writes, which it may not know to alias (accesses through different pointer types): TCOW_WAVE_LDS_ORDER.  TCOW_WAVE_LDS_FENCE also
+// waits; it is what the exact-f32 one-tile kernels were measured with, and their code stays as it is.
+#define TCOW_WAVE_LDS_ORDER() asm volatile("" ::: "memory")
+#define TCOW_WAVE_LDS_FENCE() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
+
 // ---- the attention back ends behind attention_api.hip's dispatch (host)
 // 16-bit storage: MFMA flash attention (attention_bf16.hip)
 bool tcow_attn_mfma_zeroes_slot0(const SeqDesc& d, bool shared, bool backward);

@@ -302,7 +302,6 @@ __device__ __forceinline__ void frag_from_tile(const float* __restrict__ tile, i
 #pragma unroll
     for (int s = 0; s < 32; ++s) f[s] = tile[l31 * TP + 2 * s + hi] * scale;
 }
-#define TCOW_WAVE_LDS_FENCE() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")     /* a wave's LDS operations execute in order; this keeps hipcc from reordering them */
 
 __global__ __launch_bounds__(256, 2) void attn_f32_fwd_solo(SeqDesc sd, const float* __restrict__ qkv, float* __restrict__ out, float* __restrict__ lse) {
     extern __shared__ __attribute__((aligned(16))) float smem[];

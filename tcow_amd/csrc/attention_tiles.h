@@ -1,5 +1,5 @@
-// Tile helpers shared by the 16-bit MFMA attention kernels (attention_bf16.hip and its three family files) and
-// the micro-benchmark tools/ubench_valu.hip: the [32 rows][64 x 16-bit] LDS tile with its universal swizzle, direct-to-LDS tile loads, MFMA operand
+// Tile helpers shared by the 16-bit MFMA attention kernels (attention_bf16.hip and its three family files), the split-bf16 kernels of
+// attention_x3.hip (the SplitOp policy below) and the micro-benchmark tools/ubench_valu.hip: the [32 rows][64 x 16-bit] LDS tile with its universal swizzle, direct-to-LDS tile loads, MFMA operand
 // fragments (row fragments / transpose reads), the half-wave exchange, the forward and backward tile steps that more than one kernel family uses,
 // and the stores of a transposed accumulator pair (a row per lane, or whole rows through LDS).  Everything lives in an anonymous namespace: each
 // translation unit gets its own copy.
@@ -78,10 +78,31 @@ __device__ __forceinline__ void load_chunk2(const bf16_t* a, long psa, const bf1
     }
 }
 
+// How a tile step holds an MFMA operand and multiplies two of them (defined below pack8): PlainOp, the default, is one fragment in the library's
+// 16-bit format and one MFMA; SplitOp is a (hi, lo) pair of bfloat16 fragments and three MFMAs (attention_x3.hip).  frag_row, frag_tr and the forward
+// tile step are written once over the policy: P::Tile finds a tile (SplitOp: in both planes), P::Frag is an operand.  (dq_tile / dkv_tile are the 16-bit
+// kernels' alone: attention_x3.hip says why its backward steps differ.)
+struct PlainOp;
+struct SplitOp;
+
+// the two LDS reads behind the fragments: 16 bytes of a row, and two transpose reads joined (V = the 8 x 16-bit operand type).
+// (The row read goes through HIP's uint4 whoever wrote the tile -- attention_x3.hip stages through the vector type xu4 --, so no reader may count on
+// type-based ordering against the writes: a workgroup barrier, or for wave-private tiles the compiler barrier that ends x_stage_wave, stands between them.)
+template <typename V>
+__device__ __forceinline__ V tile_read(const char* tile, int row_off, int off) { return __builtin_bit_cast(V, *reinterpret_cast<const uint4*>(tile + row_off + off)); }
+template <typename V>
+__device__ __forceinline__ V tile_read_tr(const char* tile, int o0, int o1) {
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(tile + o0));
+    const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(tile + o1));
+    typedef __attribute__((ext_vector_type(8))) short s16x8;
+    return __builtin_bit_cast(V, (s16x8)__builtin_shufflevector(lo, hi4, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
 // A/B fragment of a row-major tile for a contraction over d: lane (row = lane&31, hi) gets d = 16*ks + 8*hi .. +7
-__device__ __forceinline__ bf16x8 frag_row(const char* tile, int row, int ks, int hi) {
+template <class P = PlainOp>
+__device__ __forceinline__ typename P::Frag frag_row(typename P::Tile tile, int row, int ks, int hi) {
     const int c = (2 * ks + hi) ^ swz_g(row);
-    return __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(tile + row * 128 + (c << 4)));
+    return P::read(tile, row * 128, c << 4);
 }
 // the same fragment straight from global memory (rows at stride pse elements)
 __device__ __forceinline__ bf16x8 frag_row_global(const bf16_t* src, long pse, int pos, int ks, int hi) {
@@ -89,16 +110,14 @@ __device__ __forceinline__ bf16x8 frag_row_global(const bf16_t* src, long pse, i
 }
 // fragment for a contraction over the tile's ROWS: lane (col = 32*dt + (lane&31), hi) gets rows crow32(8*s + j, hi), j = 0..7,
 // i.e. rows {16s + 4hi + 0..3} and {16s + 8 + 4hi + 0..3}: two transpose reads of [4 rows][16 cols] blocks.
-__device__ __forceinline__ bf16x8 frag_tr(const char* tile, int s, int dt, int lane) {
+template <class P = PlainOp>
+__device__ __forceinline__ typename P::Frag frag_tr(typename P::Tile tile, int s, int dt, int lane) {
     const int q16 = lane & 15, g16 = (lane >> 4) & 1, hi = lane >> 5;
     const int chunk = 4 * dt + 2 * g16 + ((q16 & 3) >> 1);
     const int r0 = 16 * s + 4 * hi + (q16 >> 2), r1 = r0 + 8;
     const int o0 = r0 * 128 + ((chunk ^ swz_g(r0)) << 4) + (q16 & 1) * 8;
     const int o1 = r1 * 128 + ((chunk ^ swz_g(r1)) << 4) + (q16 & 1) * 8;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(tile + o0));
-    const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(tile + o1));
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-    return __builtin_bit_cast(bf16x8, (s16x8)__builtin_shufflevector(lo, hi4, 0, 1, 2, 3, 4, 5, 6, 7));
+    return P::read_tr(tile, o0, o1);
 }
 // registers 8s..8s+7 of a C-layout accumulator as a bf16 operand (contraction slot j <-> row crow32(8s+j, hi))
 __device__ __forceinline__ bf16x8 pack8(const float* v) {
@@ -106,6 +125,51 @@ __device__ __forceinline__ bf16x8 pack8(const float* v) {
     f32x8 t = {v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]};
     return __builtin_convertvector(t, bf16x8);
 }
+
+struct PlainOp {
+    typedef bf16x8 Frag;
+    typedef const char* Tile;
+    static __device__ __forceinline__ Frag read(Tile t, int row_off, int off) { return tile_read<bf16x8>(t, row_off, off); }
+    static __device__ __forceinline__ Frag read_tr(Tile t, int o0, int o1) { return tile_read_tr<bf16x8>(t, o0, o1); }
+    static __device__ __forceinline__ Frag pack(const float* v) { return pack8(v); }
+    static __device__ __forceinline__ f32x16 mm(const Frag& a, const Frag& b, f32x16 acc) { return TCOW_MFMA_32x32x16_H16(a, b, acc, 0, 0, 0); }
+};
+
+// Split operands: x = hi + lo, hi = bf16(x) (round to nearest even), lo = bf16(x - hi), |x - hi - lo| <= 2^-18 |x|;
+// a.b ~ a_lo*b_hi + a_hi*b_lo + a_hi*b_hi (f32 accumulate, small terms first).
+typedef __attribute__((ext_vector_type(8))) __bf16 xb8;       // (always bfloat16, whatever 16-bit format the library is built for: bf16 keeps the f32 exponent range)
+typedef uint32_t xu4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ uint32_t xpack(float a, float b) {
+    typedef __attribute__((ext_vector_type(2))) __bf16 xb2;
+    f32x2 v = {a, b};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, xb2));
+}
+__device__ __forceinline__ void xsplit2(float x0, float x1, uint32_t& h, uint32_t& l) {
+    h = xpack(x0, x1);
+    l = xpack(x0 - __builtin_bit_cast(float, h << 16), x1 - __builtin_bit_cast(float, h & 0xffff0000u));     // exact differences (hi shares the leading bits of x)
+}
+// eight f32 -> the hi and lo halves of an operand, as stored in a tile's two planes
+__device__ __forceinline__ void xsplit8u(const float* v, xu4& hh, xu4& ll) {
+    uint32_t h0, h1, h2, h3, l0, l1, l2, l3;
+    xsplit2(v[0], v[1], h0, l0); xsplit2(v[2], v[3], h1, l1); xsplit2(v[4], v[5], h2, l2); xsplit2(v[6], v[7], h3, l3);
+    hh = (xu4){h0, h1, h2, h3}; ll = (xu4){l0, l1, l2, l3};
+}
+struct SplitOp {
+    struct Frag { xb8 hi, lo; };
+    struct Tile { const char* hi; const char* lo; };           // the same tile in the hi plane and in the lo plane
+    static __device__ __forceinline__ Frag read(Tile t, int row_off, int off) { return {tile_read<xb8>(t.hi, row_off, off), tile_read<xb8>(t.lo, row_off, off)}; }
+    static __device__ __forceinline__ Frag read_tr(Tile t, int o0, int o1) { return {tile_read_tr<xb8>(t.hi, o0, o1), tile_read_tr<xb8>(t.lo, o0, o1)}; }
+    static __device__ __forceinline__ Frag pack(const float* v) {
+        xu4 hh, ll;
+        xsplit8u(v, hh, ll);
+        return {__builtin_bit_cast(xb8, hh), __builtin_bit_cast(xb8, ll)};
+    }
+    static __device__ __forceinline__ f32x16 mm(const Frag& a, const Frag& b, f32x16 acc) {
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.lo, b.hi, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.hi, b.lo, acc, 0, 0, 0);
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.hi, b.hi, acc, 0, 0, 0);
+    }
+};
 
 // wave-private kernels: four waves of a workgroup own four consecutive (sequence, head) pairs
 struct WorkId { int item, head; bool valid; };
@@ -122,14 +186,15 @@ __device__ __forceinline__ WorkId work_id(const SeqDesc& sd, int wave) {
 // elements rely on exp2 underflow (no select), and the running maximum is LAZY: accumulators are rescaled only when some row's
 // maximum grew by more than 2^8 since the reference maximum was set (probabilities then stay <= 256, harmless in bf16 / f32, and
 // the final O / l and log-sum-exp are independent of the reference) -- after the first key tile that almost never happens.
-__device__ __forceinline__ void fwd_tile(const SeqDesc& sd, const char* ktile, const char* vtile, const bf16x8 (&qf)[4], int j, int qt, int q, int l31, int hi, int lane,
-                                         float& m, float& l, f32x16& o0, f32x16& o1) {
+template <class P = PlainOp>
+__device__ __forceinline__ void fwd_tile(const SeqDesc& sd, typename P::Tile ktile, typename P::Tile vtile, const typename P::Frag (&qf)[4], int j, int qt, int q, int l31, int hi,
+                                         int lane, float& m, float& l, f32x16& o0, f32x16& o1) {
     const float sc = kScale * kLog2e;
     f32x16 s;
 #pragma unroll
     for (int r = 0; r < 16; ++r) s[r] = 0.f;
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) s = TCOW_MFMA_32x32x16_H16(frag_row(ktile, l31, ks, hi), qf[ks], s, 0, 0, 0);
+    for (int ks = 0; ks < 4; ++ks) s = P::mm(frag_row<P>(ktile, l31, ks, hi), qf[ks], s);
     const bool need_mask = (32 * j + 31 >= sd.L) || ((long)32 * j + 31 > (long)32 * qt + sd.diag);
     if (need_mask) {
         TCOW_NO_IFCVT();
@@ -162,11 +227,11 @@ __device__ __forceinline__ void fwd_tile(const SeqDesc& sd, const char* ktile, c
         for (int r = 0; r < 16; ++r) { if (s[r] <= -1e29f) p[r] = 0.f; ps += p[r]; }
     }
     l += ps;
-    const bf16x8 pb0 = pack8(p), pb1 = pack8(p + 8);
-    o0 = TCOW_MFMA_32x32x16_H16(frag_tr(vtile, 0, 0, lane), pb0, o0, 0, 0, 0);
-    o0 = TCOW_MFMA_32x32x16_H16(frag_tr(vtile, 1, 0, lane), pb1, o0, 0, 0, 0);
-    o1 = TCOW_MFMA_32x32x16_H16(frag_tr(vtile, 0, 1, lane), pb0, o1, 0, 0, 0);
-    o1 = TCOW_MFMA_32x32x16_H16(frag_tr(vtile, 1, 1, lane), pb1, o1, 0, 0, 0);
+    const typename P::Frag pb0 = P::pack(p), pb1 = P::pack(p + 8);
+    o0 = P::mm(frag_tr<P>(vtile, 0, 0, lane), pb0, o0);
+    o0 = P::mm(frag_tr<P>(vtile, 1, 0, lane), pb1, o0);
+    o1 = P::mm(frag_tr<P>(vtile, 0, 1, lane), pb0, o1);
+    o1 = P::mm(frag_tr<P>(vtile, 1, 1, lane), pb1, o1);
 }
 
 // The P V and gradient MFMAs are issued as (transposed-read fragment, P or dS), i.e. they accumulate O^T / dV^T / dK^T / dQ^T: lane (l31, hi)
@@ -177,6 +242,14 @@ __device__ __forceinline__ void store_rowT(bf16_t* drow, int hi, const f32x16& a
     for (int gq = 0; gq < 4; ++gq) {
         st4(drow + 8 * gq + 4 * hi, make_float4(a0[4 * gq], a0[4 * gq + 1], a0[4 * gq + 2], a0[4 * gq + 3]));
         st4(drow + 32 + 8 * gq + 4 * hi, make_float4(a1[4 * gq], a1[4 * gq + 1], a1[4 * gq + 2], a1[4 * gq + 3]));
+    }
+}
+// the same row in f32 storage, times `mul` (attention_x3.hip)
+__device__ __forceinline__ void store_rowT(float* __restrict__ drow, int hi, const f32x16& a0, const f32x16& a1, float mul) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        st4(drow + 8 * g + 4 * hi, make_float4(a0[4 * g] * mul, a0[4 * g + 1] * mul, a0[4 * g + 2] * mul, a0[4 * g + 3] * mul));
+        st4(drow + 32 + 8 * g + 4 * hi, make_float4(a1[4 * g] * mul, a1[4 * g + 1] * mul, a1[4 * g + 2] * mul, a1[4 * g + 3] * mul));
     }
 }
 

@@ -1,65 +1,32 @@
 // Flash attention of the f32-storage mode precision='bf16x3' on the bf16 matrix cores: softmax(q k^T * d^-0.5 [causal mask]) v (vit.py:88-109) with every
-// matrix product formed as THREE bf16 MFMAs on hi / lo operand splits, exactly as gemm_x3.hip does for the Linear layers:
-//   x = hi + lo, hi = bf16(x) (round to nearest even), lo = bf16(x - hi), |x - hi - lo| <= 2^-18 |x|;   a.b ~ a_lo*b_hi + a_hi*b_lo + a_hi*b_hi (f32 accumulate).
+// matrix product formed as THREE bf16 MFMAs on hi / lo operand splits, exactly as gemm_x3.hip does for the Linear layers (attention_tiles.h, SplitOp).
 // Until round 6 the mode ran its attention on the exact-f32 MFMA (attention_f32.hip: 1/16 of the bf16 rate): 1 499 us per spatial forward at configs[1], a fifth
 // of that mode's step.  Same contract as attention_f32.hip (f32 qkv [rows, 3D] in, f32 out / dqkv, natural-log LSE, delta workspace in the lse layout).
 //
 // Structure = the kernels of attention_bf16_chunked.inc: a 256-thread workgroup owns 4 query (forward, dQ) or 4 key (dK / dV) tiles of one (sequence, head),
-// one per wave, and walks the other side in chunks of CH tiles.  A chunk is read as f32 by all 256 threads (one 8-element piece of a row per thread and
-// tile: two 16-byte loads), split ONCE in registers and stored as two [32][64] bf16 LDS tiles (hi, lo) in the layout of attention_tiles.h (16-byte chunk c of row
-// r at c ^ g(r): conflict-free ds_read_b128 row fragments and ds_read_b64_tr_b16 transpose reads).  The wave's own rows (Q, dO or K, V) are split when
-// their fragments are loaded; probabilities / dS are split in registers before they become MFMA B operands.  Softmax statistics, masks, the lazy running
-// maximum and the accumulation order are those of attention_tiles.h's fwd_tile / dq_tile / dkv_tile.
+// one per wave, and walks the other side in chunks of CH tiles.  The forward step of one tile against another IS attention_tiles.h's fwd_tile, called with
+// the split operand policy: softmax statistics, masks, the lazy running maximum and the accumulation order are stated there, once.  The two backward
+// steps stand here, written on that header's helpers (fragments, split, product, half-wave exchange, row store): see the comment above attn_x3_bwd_dkv.
+// What this file holds is what the f32 storage needs around those steps:
+//   staging     a chunk is read as f32 by all 256 threads (one 8-element piece of a row per thread and tile: two 16-byte loads), split ONCE in registers and
+//               stored as two [32][64] bf16 LDS tiles (hi, lo) in the layout of attention_tiles.h; arrays [a hi][a lo][b hi][b lo], CH tiles each (x_stage),
+//               or one such set per wave in the one-tile SOLO kernels (x_stage_wave)
+//   xfrag_global  the wave's own rows (Q, dO or K, V), split when their fragments are loaded
+//   delta       rowsum(dO * O) in f32, from the unsplit dO
+//   the launchers with the CH / SOLO choices and what they measured.
 // MFMAs per (query tile, key tile) pair: forward 24, dQ 36, dK / dV 48 (bf16 mode: 8 / 12 / 16).
 #include <stdlib.h>
 
-#include "attention_common.h"
+#include "attention_tiles.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 xb8;       // (always bfloat16, whatever 16-bit format the library is built for: bf16 keeps the f32 exponent range)
-typedef __attribute__((ext_vector_type(2))) __bf16 xb2;
-typedef uint32_t xu4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((ext_vector_type(4))) short xs4;
-typedef __attribute__((ext_vector_type(8))) short xs8;
+constexpr float kLn2 = 0.6931471805599453f;
+typedef SplitOp P;          // the operand policy of every kernel here
 
-constexpr int XTILE = 4096;                  // [32 rows][64 bf16]
-constexpr float xScale = 0.125f;             // head_dim^-0.5 (vit.py:70)
-constexpr float xLog2e = 1.4426950408889634f;
-constexpr float xLn2 = 0.6931471805599453f;
-
-#define X3_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-#define X3_NO_IFCVT() asm volatile("" ::: "memory")
-
-__device__ __forceinline__ int xswz(int r) { return (((r >> 1) & 1) << 2) | ((r >> 2) & 3); }
-__device__ __forceinline__ uint32_t xpack(float a, float b) {
-    f32x2 v = {a, b};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, xb2));
-}
-__device__ __forceinline__ void xsplit2(float x0, float x1, uint32_t& h, uint32_t& l) {
-    h = xpack(x0, x1);
-    l = xpack(x0 - __builtin_bit_cast(float, h << 16), x1 - __builtin_bit_cast(float, h & 0xffff0000u));     // exact differences (hi shares the leading bits of x)
-}
-// eight f32 -> the hi and lo bf16x8 operands
-__device__ __forceinline__ void xsplit8u(const float* v, xu4& hh, xu4& ll) {
-    uint32_t h0, h1, h2, h3, l0, l1, l2, l3;
-    xsplit2(v[0], v[1], h0, l0); xsplit2(v[2], v[3], h1, l1); xsplit2(v[4], v[5], h2, l2); xsplit2(v[6], v[7], h3, l3);
-    hh = (xu4){h0, h1, h2, h3}; ll = (xu4){l0, l1, l2, l3};
-}
-__device__ __forceinline__ void xsplit8(const float* v, xb8& h, xb8& l) {
-    xu4 hh, ll;
-    xsplit8u(v, hh, ll);
-    h = __builtin_bit_cast(xb8, hh); l = __builtin_bit_cast(xb8, ll);
-}
-__device__ __forceinline__ float xhalf_sum(float v) { return v + __shfl_xor(v, 32, 64); }
-__device__ __forceinline__ float xhalf_max(float v) { return fmaxf(v, __shfl_xor(v, 32, 64)); }
-
-// acc += a . b with both operands split: small terms first
-__device__ __forceinline__ f32x16 x3_mm(const xb8& ah, const xb8& al, const xb8& bh, const xb8& bl, f32x16 acc) {
-    acc = X3_MFMA(al, bh, acc);
-    acc = X3_MFMA(ah, bl, acc);
-    return X3_MFMA(ah, bh, acc);
-}
+// tile t of a staged source whose hi plane starts at `hi_plane`; the lo plane follows CH tiles later
+template <int CH>
+__device__ __forceinline__ SplitOp::Tile x_tile(const char* hi_plane, int t) { return {hi_plane + t * TILE_B, hi_plane + (CH + t) * TILE_B}; }
 
 // ---- staging: tile = rows p0 .. p0+31 (clamped to L-1: padding rows hold finite data, masks / zero probabilities keep them out) of a 64-column f32 block.
 // Thread t of the 256: row t >> 3, columns 8 (t & 7) .. + 7.
@@ -76,7 +43,7 @@ __device__ __forceinline__ void x_store_rc(const XItem& it, char* hi_tile, char*
     xu4 h, l;
     const float v[8] = {it.a[0], it.a[1], it.a[2], it.a[3], it.b[0], it.b[1], it.b[2], it.b[3]};
     xsplit8u(v, h, l);
-    const int off = r * 128 + ((c ^ xswz(r)) << 4);
+    const int off = r * 128 + ((c ^ swz_g(r)) << 4);
     *reinterpret_cast<xu4*>(hi_tile + off) = h;
     *reinterpret_cast<xu4*>(lo_tile + off) = l;
 }
@@ -91,8 +58,8 @@ __device__ __forceinline__ void x_stage(const float* __restrict__ a, long sa, co
 #pragma unroll
     for (int t = 0; t < CH; ++t)
         if (c0 + t < nt_end) {
-            x_store(ia[t], smem + t * XTILE, smem + (CH + t) * XTILE, tid);
-            x_store(ib[t], smem + (2 * CH + t) * XTILE, smem + (3 * CH + t) * XTILE, tid);
+            x_store(ia[t], smem + t * TILE_B, smem + (CH + t) * TILE_B, tid);
+            x_store(ib[t], smem + (2 * CH + t) * TILE_B, smem + (3 * CH + t) * TILE_B, tid);
         }
 }
 
@@ -106,49 +73,24 @@ __device__ __forceinline__ void x_stage_wave(const float* __restrict__ a, long s
         for (int ps = 0; ps < 2; ++ps) { ia[ps] = x_load(a, sa, 16 * half + 8 * ps, L, lane); ib[ps] = x_load(b, sb, 16 * half + 8 * ps, L, lane); }
 #pragma unroll
         for (int ps = 0; ps < 2; ++ps) {
-            x_store_rc(ia[ps], wsm, wsm + XTILE, 16 * half + 8 * ps + (lane >> 3), lane & 7);
-            x_store_rc(ib[ps], wsm + 2 * XTILE, wsm + 3 * XTILE, 16 * half + 8 * ps + (lane >> 3), lane & 7);
+            x_store_rc(ia[ps], wsm, wsm + TILE_B, 16 * half + 8 * ps + (lane >> 3), lane & 7);
+            x_store_rc(ib[ps], wsm + 2 * TILE_B, wsm + 3 * TILE_B, 16 * half + 8 * ps + (lane >> 3), lane & 7);
         }
         asm volatile("" ::: "memory");                   // (keeps hipcc from issuing the second round's loads with the first)
     }
 }
 
-// A/B fragment of a row-major tile for a contraction over d: lane (row, hi) gets d = 16 ks + 8 hi .. + 7
-__device__ __forceinline__ xb8 xfrag_row(const char* tile, int row, int ks, int hi) {
-    const int c = (2 * ks + hi) ^ xswz(row);
-    return __builtin_bit_cast(xb8, *reinterpret_cast<const xu4*>(tile + row * 128 + (c << 4)));
-}
-// fragment for a contraction over the tile's ROWS: lane (col = 32 dt + (lane & 31), hi) gets rows crow32(8 s + j, hi), j = 0..7 (two transpose reads)
-__device__ __forceinline__ xb8 xfrag_tr(const char* tile, int s, int dt, int lane) {
-    const int q16 = lane & 15, g16 = (lane >> 4) & 1, hi = lane >> 5;
-    const int chunk = 4 * dt + 2 * g16 + ((q16 & 3) >> 1);
-    const int r0 = 16 * s + 4 * hi + (q16 >> 2), r1 = r0 + 8;
-    const int o0 = r0 * 128 + ((chunk ^ xswz(r0)) << 4) + (q16 & 1) * 8;
-    const int o1 = r1 * 128 + ((chunk ^ xswz(r1)) << 4) + (q16 & 1) * 8;
-    const xs4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(xs4))(tile + o0));
-    const xs4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(xs4))(tile + o1));
-    return __builtin_bit_cast(xb8, (xs8)__builtin_shufflevector(lo, hi4, 0, 1, 2, 3, 4, 5, 6, 7));
-}
 // the wave's own row (position pos of a 64-column f32 block), split: fragment ks = columns 16 ks + 8 hi .. + 7
-__device__ __forceinline__ void xfrag_global(const float* __restrict__ row, int hi, xb8 (&h)[4], xb8 (&l)[4], float* keep = nullptr) {
+__device__ __forceinline__ void xfrag_global(const float* __restrict__ row, int hi, SplitOp::Frag (&f)[4], float* keep = nullptr) {
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
         const f32x4 a = *reinterpret_cast<const f32x4*>(row + 16 * ks + 8 * hi), b = *reinterpret_cast<const f32x4*>(row + 16 * ks + 8 * hi + 4);
         const float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-        xsplit8(v, h[ks], l[ks]);
+        f[ks] = SplitOp::pack(v);
         if (keep) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) keep[8 * ks + e] = v[e];
         }
-    }
-}
-
-// f32 row store of a transposed accumulator pair: lane (row l31, hi) owns channels 32 dt + 8 g + 4 hi + 0..3 of register quad g
-__device__ __forceinline__ void x_store_row(float* __restrict__ drow, int hi, const f32x16& a0, const f32x16& a1, float mul) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        st4(drow + 8 * g + 4 * hi, make_float4(a0[4 * g] * mul, a0[4 * g + 1] * mul, a0[4 * g + 2] * mul, a0[4 * g + 3] * mul));
-        st4(drow + 32 + 8 * g + 4 * hi, make_float4(a1[4 * g] * mul, a1[4 * g + 1] * mul, a1[4 * g + 2] * mul, a1[4 * g + 3] * mul));
     }
 }
 
@@ -162,7 +104,7 @@ __global__ __launch_bounds__(256, 2) void attn_x3_fwd(SeqDesc sd, int nt, const 
     StreamWork w = stream_work(sd.n_outer * sd.n_inner * sd.heads, (nt + 3) / 4);
     if (SOLO) { w.pair = blockIdx.x * 4 + wave; w.chunk = 0; w.valid = w.pair < sd.n_outer * sd.n_inner * sd.heads; }
     if (!w.valid) return;
-    char* smem = SOLO ? smem_ + wave * (4 * XTILE) : smem_;
+    char* smem = SOLO ? smem_ + wave * (4 * TILE_B) : smem_;
     const int item = w.pair / sd.heads, head = w.pair - item * sd.heads;
     const long base = seq_base(sd, item);
     const long ld3 = 3L * sd.D, pse = sd.pos_stride * ld3;
@@ -171,13 +113,12 @@ __global__ __launch_bounds__(256, 2) void attn_x3_fwd(SeqDesc sd, int nt, const 
     const bool active = qt < nt;
     const int q = 32 * qt + l31, qc = q < sd.L ? q : sd.L - 1;
     if (SOLO) x_stage_wave(qh + sd.D, pse, qh + 2 * sd.D, pse, sd.L, smem, lane);      // (before the wave's own fragments are loaded: the staging registers are dead by then)
-    xb8 qfh[4], qfl[4];
-    xfrag_global(qh + (size_t)qc * pse, hi, qfh, qfl);
+    SplitOp::Frag qf[4];
+    xfrag_global(qh + (size_t)qc * pse, hi, qf);
     f32x16 o0, o1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
     float m = -1e30f, l = 0.f;
-    const float sc = xScale * xLog2e;
     const int kt_end = (!active) ? 0 : causal_key_tiles(sd, nt, qt);
     const int kt_end_wg = causal_key_tiles(sd, nt, w.chunk * 4 + 3);          // key tiles any wave of this workgroup needs
     for (int c0 = 0; c0 < kt_end_wg; c0 += CH) {
@@ -187,60 +128,15 @@ __global__ __launch_bounds__(256, 2) void attn_x3_fwd(SeqDesc sd, int nt, const 
             __syncthreads();
         }
         const int jend = (c0 + CH < kt_end) ? c0 + CH : kt_end;
-        for (int j = c0; j < jend; ++j) {
-            const char* kh = smem + (j - c0) * XTILE; const char* kl = kh + CH * XTILE;
-            const char* vh = kh + 2 * CH * XTILE; const char* vl = kh + 3 * CH * XTILE;
-            f32x16 s;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[r] = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) s = x3_mm(xfrag_row(kh, l31, ks, hi), xfrag_row(kl, l31, ks, hi), qfh[ks], qfl[ks], s);
-            const bool need_mask = (32 * j + 31 >= sd.L) || ((long)32 * j + 31 > (long)32 * qt + sd.diag);
-            if (need_mask) {
-                X3_NO_IFCVT();
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = 32 * j + crow32(r, hi);
-                    if (key >= sd.L || (long)key > (long)q + sd.diag) s[r] = -1e30f;
-                }
-            }
-            float mx = s[0];
-#pragma unroll
-            for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[r]);
-            mx = xhalf_max(mx) * sc;                                       // (sc > 0: the maximum commutes with the scale)
-            if (__any(mx > m + 8.0f)) {                                    // lazy running maximum (attention_tiles.h fwd_tile)
-                const float mn = fmaxf(m, mx);
-                const float alpha = exp2f(m - mn);
-                l *= alpha;
-                m = mn;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; }
-            }
-            float p[16];
-            float ps = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { p[r] = __builtin_amdgcn_exp2f(fmaf(s[r], sc, -m)); ps += p[r]; }
-            if (need_mask) {                                               // a fully masked row (m still at its start value) must contribute nothing
-                X3_NO_IFCVT();
-                ps = 0.f;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { if (s[r] <= -1e29f) p[r] = 0.f; ps += p[r]; }
-            }
-            l += ps;
-            xb8 ph0, pl0, ph1, pl1;
-            xsplit8(p, ph0, pl0); xsplit8(p + 8, ph1, pl1);
-            o0 = x3_mm(xfrag_tr(vh, 0, 0, lane), xfrag_tr(vl, 0, 0, lane), ph0, pl0, o0);
-            o1 = x3_mm(xfrag_tr(vh, 0, 1, lane), xfrag_tr(vl, 0, 1, lane), ph0, pl0, o1);
-            o0 = x3_mm(xfrag_tr(vh, 1, 0, lane), xfrag_tr(vl, 1, 0, lane), ph1, pl1, o0);
-            o1 = x3_mm(xfrag_tr(vh, 1, 1, lane), xfrag_tr(vl, 1, 1, lane), ph1, pl1, o1);
-        }
+        for (int j = c0; j < jend; ++j)
+            fwd_tile<SplitOp>(sd, x_tile<CH>(smem, j - c0), x_tile<CH>(smem + 2 * CH * TILE_B, j - c0), qf, j, qt, q, l31, hi, lane, m, l, o0, o1);
     }
     if (!active) return;
-    l = xhalf_sum(l);
+    l = half_sum(l);
     if (q < sd.L) {
         const long row = base + (long)q * sd.pos_stride;
-        x_store_row(out + row * sd.D + head * ATT_HD, hi, o0, o1, 1.0f / l);
-        if (lse && hi == 0) lse[row * sd.heads + head] = (m + log2f(l)) * xLn2;          // natural-log LSE of the scaled scores
+        store_rowT(out + row * sd.D + head * ATT_HD, hi, o0, o1, 1.0f / l);
+        if (lse && hi == 0) lse[row * sd.heads + head] = (m + log2f(l)) * kLn2;          // natural-log LSE of the scaled scores
     }
 }
 
@@ -255,7 +151,7 @@ __global__ __launch_bounds__(256, 2) void attn_x3_bwd_dq(SeqDesc sd, int nt, con
     StreamWork w = stream_work(sd.n_outer * sd.n_inner * sd.heads, (nt + 3) / 4);
     if (SOLO) { w.pair = blockIdx.x * 4 + wave; w.chunk = 0; w.valid = w.pair < sd.n_outer * sd.n_inner * sd.heads; }
     if (!w.valid) return;
-    char* smem = SOLO ? smem_ + wave * (4 * XTILE) : smem_;
+    char* smem = SOLO ? smem_ + wave * (4 * TILE_B) : smem_;
     const int item = w.pair / sd.heads, head = w.pair - item * sd.heads;
     const long base = seq_base(sd, item);
     const long ld3 = 3L * sd.D, pse = sd.pos_stride * ld3;
@@ -265,13 +161,13 @@ __global__ __launch_bounds__(256, 2) void attn_x3_bwd_dq(SeqDesc sd, int nt, con
     const int q = 32 * qt + l31, qc = q < sd.L ? q : sd.L - 1;
     const long row = base + (long)qc * sd.pos_stride;
     if (SOLO) x_stage_wave(qh + sd.D, pse, qh + 2 * sd.D, pse, sd.L, smem, lane);
-    xb8 qfh[4], qfl[4], dfh[4], dfl[4];
-    xfrag_global(qh + (size_t)qc * pse, hi, qfh, qfl);
+    SplitOp::Frag qf[4], dof[4];
+    xfrag_global(qh + (size_t)qc * pse, hi, qf);
     // delta = rowsum(dO * O) of this lane's query in f32 (this half-wave's 32 channels + the other's): published for the dK / dV kernel, which runs after this one
     float dl;
     {
         float dov[32];
-        xfrag_global(dout + row * sd.D + head * ATT_HD, hi, dfh, dfl, dov);
+        xfrag_global(dout + row * sd.D + head * ATT_HD, hi, dof, dov);
         const float* orow = o + row * sd.D + head * ATT_HD;
         float part = 0.f;
 #pragma unroll
@@ -280,11 +176,11 @@ __global__ __launch_bounds__(256, 2) void attn_x3_bwd_dq(SeqDesc sd, int nt, con
 #pragma unroll
             for (int e = 0; e < 4; ++e) { part = fmaf(dov[8 * ks + e], a[e], part); part = fmaf(dov[8 * ks + 4 + e], b[e], part); }
         }
-        dl = xhalf_sum(part);
+        dl = half_sum(part);
         if (active && q < sd.L && hi == 0) delta[row * sd.heads + head] = dl;
     }
-    const float ls = lse[row * sd.heads + head] * xLog2e;
-    const float sc = xScale * xLog2e;
+    const float ls = lse[row * sd.heads + head] * kLog2e;
+    const float sc = kScale * kLog2e;
     f32x16 dq0, dq1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { dq0[r] = 0.f; dq1[r] = 0.f; }
@@ -298,15 +194,15 @@ __global__ __launch_bounds__(256, 2) void attn_x3_bwd_dq(SeqDesc sd, int nt, con
         }
         const int jend = (c0 + CH < kt_end) ? c0 + CH : kt_end;
         for (int j = c0; j < jend; ++j) {
-            const char* kh = smem + (j - c0) * XTILE; const char* kl = kh + CH * XTILE;
-            const char* vh = kh + 2 * CH * XTILE; const char* vl = kh + 3 * CH * XTILE;
+            // dq_tile on its helpers, written out (see the comment above attn_x3_bwd_dkv)
+            const P::Tile kt = x_tile<CH>(smem, j - c0), vt = x_tile<CH>(smem + 2 * CH * TILE_B, j - c0);
             f32x16 s, dp;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
-                s = x3_mm(xfrag_row(kh, l31, ks, hi), xfrag_row(kl, l31, ks, hi), qfh[ks], qfl[ks], s);            // S^T[key][query]
-                dp = x3_mm(xfrag_row(vh, l31, ks, hi), xfrag_row(vl, l31, ks, hi), dfh[ks], dfl[ks], dp);          // dP^T[key][query] = V dO^T
+                s = P::mm(frag_row<P>(kt, l31, ks, hi), qf[ks], s);                 // S^T[key][query]
+                dp = P::mm(frag_row<P>(vt, l31, ks, hi), dof[ks], dp);              // dP^T[key][query] = V dO^T
             }
             const bool need_mask = (32 * j + 31 >= sd.L) || (q - l31 + 31 >= sd.L) || ((long)32 * j + 31 > (long)(q - l31) + sd.diag);
             float dsv[16];
@@ -316,26 +212,31 @@ __global__ __launch_bounds__(256, 2) void attn_x3_bwd_dq(SeqDesc sd, int nt, con
                 dsv[r] = p * (dp[r] - dl);
             }
             if (need_mask) {
-                X3_NO_IFCVT();
+                TCOW_NO_IFCVT();
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int key = 32 * j + crow32(r, hi);
                     if (!(q < sd.L && key < sd.L && (long)key <= (long)q + sd.diag)) dsv[r] = 0.f;
                 }
             }
-            xb8 dh0, dl0, dh1, dl1;
-            xsplit8(dsv, dh0, dl0); xsplit8(dsv + 8, dh1, dl1);
-            dq0 = x3_mm(xfrag_tr(kh, 0, 0, lane), xfrag_tr(kl, 0, 0, lane), dh0, dl0, dq0);                        // dQ^T += K^T dS^T
-            dq1 = x3_mm(xfrag_tr(kh, 0, 1, lane), xfrag_tr(kl, 0, 1, lane), dh0, dl0, dq1);
-            dq0 = x3_mm(xfrag_tr(kh, 1, 0, lane), xfrag_tr(kl, 1, 0, lane), dh1, dl1, dq0);
-            dq1 = x3_mm(xfrag_tr(kh, 1, 1, lane), xfrag_tr(kl, 1, 1, lane), dh1, dl1, dq1);
+            const P::Frag d0 = P::pack(dsv), d1 = P::pack(dsv + 8);
+            dq0 = P::mm(frag_tr<P>(kt, 0, 0, lane), d0, dq0);                       // dQ^T += K^T dS^T
+            dq1 = P::mm(frag_tr<P>(kt, 0, 1, lane), d0, dq1);
+            dq0 = P::mm(frag_tr<P>(kt, 1, 0, lane), d1, dq0);
+            dq1 = P::mm(frag_tr<P>(kt, 1, 1, lane), d1, dq1);
         }
     }
     if (!active || q >= sd.L) return;
-    x_store_row(dqkv + row * ld3 + head * ATT_HD, hi, dq0, dq1, xScale);        // dS was accumulated without its 1/sqrt(d) factor
+    store_rowT(dqkv + row * ld3 + head * ATT_HD, hi, dq0, dq1, kScale);        // dS was accumulated without its 1/sqrt(d) factor
 }
 
 // ------------------------------------------------------------------------------------------------ backward: dK, dV
+// The steps of the two backward kernels are dq_tile / dkv_tile of attention_tiles.h written out on that header's helpers (P = SplitOp), not calls of them, for
+// two measured reasons.  (1) dkv_tile pushes masked scores to -1e30 before the exp2; in the code hipcc generates that keeps a second copy of the 16 score
+// registers across the mask branch, and with split operands (64 registers of K / V fragments, 64 of accumulators) the chunked dK / dV kernel then needs 256
+// registers plus 64 bytes of scratch.  (2) Through dq_tile (and through a dK / dV step in the header's MFMA order) the chunked kernels ran 1.7 % and 3 % slower than
+// with the loops below, more than the run-to-run spread (profiles/attn_tile_policy_ab.json).  So here P and dS are zeroed AFTER the exp2, the accumulators
+// alternate (dq0, dq1, dq0, dq1), and dkv_tile's key-padding fast path is not taken.  Same values: a masked score gives P = 0 there, P is set to 0 here.
 template <int CH, bool SOLO = false>
 __global__ __launch_bounds__(256, 2) void attn_x3_bwd_dkv(SeqDesc sd, int nt, const float* __restrict__ qkv, const float* __restrict__ dout, const float* __restrict__ lse,
                                                           const float* __restrict__ delta, float* __restrict__ dqkv) {
@@ -346,8 +247,8 @@ __global__ __launch_bounds__(256, 2) void attn_x3_bwd_dkv(SeqDesc sd, int nt, co
     StreamWork w = stream_work(sd.n_outer * sd.n_inner * sd.heads, (nt + 3) / 4);
     if (SOLO) { w.pair = blockIdx.x * 4 + wave; w.chunk = 0; w.valid = w.pair < sd.n_outer * sd.n_inner * sd.heads; }
     if (!w.valid) return;
-    char* smem = SOLO ? smem_ + wave * (4 * XTILE + 256) : smem_;
-    float2* tab = reinterpret_cast<float2*>(smem + 4 * CH * XTILE);
+    char* smem = SOLO ? smem_ + wave * (4 * TILE_B + 256) : smem_;
+    float2* tab = reinterpret_cast<float2*>(smem + 4 * CH * TILE_B);
     const int item = w.pair / sd.heads, head = w.pair - item * sd.heads;
     const long base = seq_base(sd, item);
     const long ld3 = 3L * sd.D, pse = sd.pos_stride * ld3, pso = sd.pos_stride * sd.D;
@@ -360,19 +261,22 @@ __global__ __launch_bounds__(256, 2) void attn_x3_bwd_dkv(SeqDesc sd, int nt, co
         x_stage_wave(qh, pse, doh, pso, sd.L, smem, lane);
         if (lane < 32) {
             const long row = base + (long)(lane < sd.L ? lane : sd.L - 1) * sd.pos_stride;
-            tab[lane] = make_float2(lse[row * sd.heads + head] * xLog2e, delta[row * sd.heads + head]);
+            tab[lane] = make_float2(lse[row * sd.heads + head] * kLog2e, delta[row * sd.heads + head]);
         }
     }
-    xb8 kfh[4], kfl[4], vfh[4], vfl[4];
-    xfrag_global(qh + (size_t)kc * pse + sd.D, hi, kfh, kfl);
-    xfrag_global(qh + (size_t)kc * pse + 2 * sd.D, hi, vfh, vfl);
+    SplitOp::Frag kf[4], vf[4];
+    xfrag_global(qh + (size_t)kc * pse + sd.D, hi, kf);
+    xfrag_global(qh + (size_t)kc * pse + 2 * sd.D, hi, vf);
+    // lanes 0..31 wrote the table through a float2*, the tile step reads it in every lane through a float4*: keep hipcc from moving those reads up
+    // (placed after the K / V loads are issued, so that they still go out together with the table's lse / delta loads)
+    if (SOLO) TCOW_WAVE_LDS_ORDER();
     f32x16 dk0, dk1, dv0, dv1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { dk0[r] = 0.f; dk1[r] = 0.f; dv0[r] = 0.f; dv1[r] = 0.f; }
-    const float sc = xScale * xLog2e;
+    const float sc = kScale * kLog2e;
     // first query tile that can see any key of this wave / of this workgroup
     // (i0 = causal_first_query_tile(sd, jt), written out: with jt = 0 in the SOLO instantiation hipcc folds this form to a 32-bit value that it knows
-    // to be non-negative and drops the max(c0, i0) of the loop below; through the function that kernel needs 234 registers instead of 226)
+    // to be non-negative and drops the max(c0, i0) of the loop below; through the function that kernel needed 8 registers more)
     const long qlo = (long)32 * jt - sd.diag;
     const int i0 = qlo > 0 ? (int)(qlo / 32) : 0;
     const int c_start = (causal_first_query_tile(sd, w.chunk * 4) / CH) * CH;
@@ -383,22 +287,21 @@ __global__ __launch_bounds__(256, 2) void attn_x3_bwd_dkv(SeqDesc sd, int nt, co
             if (tid < CH * 32) {
                 const int qi = 32 * c0 + tid;
                 const long row = base + (long)(qi < sd.L ? qi : sd.L - 1) * sd.pos_stride;
-                tab[tid] = make_float2(lse[row * sd.heads + head] * xLog2e, delta[row * sd.heads + head]);
+                tab[tid] = make_float2(lse[row * sd.heads + head] * kLog2e, delta[row * sd.heads + head]);
             }
             __syncthreads();
         }
         if (!active) continue;
         const int ib = c0 > i0 ? c0 : i0, ie = c0 + CH < nt ? c0 + CH : nt;
         for (int i = ib; i < ie; ++i) {
-            const char* qth = smem + (i - c0) * XTILE; const char* qtl = qth + CH * XTILE;
-            const char* doth = qth + 2 * CH * XTILE; const char* dotl = qth + 3 * CH * XTILE;
+            const P::Tile qt_ = x_tile<CH>(smem, i - c0), dot_ = x_tile<CH>(smem + 2 * CH * TILE_B, i - c0);
             f32x16 s, dp;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
-                s = x3_mm(xfrag_row(qth, l31, ks, hi), xfrag_row(qtl, l31, ks, hi), kfh[ks], kfl[ks], s);          // S[query crow32(r, hi)][key l31]
-                dp = x3_mm(xfrag_row(doth, l31, ks, hi), xfrag_row(dotl, l31, ks, hi), vfh[ks], vfl[ks], dp);      // dP[query][key] = dO V^T
+                s = P::mm(frag_row<P>(qt_, l31, ks, hi), kf[ks], s);                // S[query crow32(r, hi)][key l31]
+                dp = P::mm(frag_row<P>(dot_, l31, ks, hi), vf[ks], dp);             // dP[query][key] = dO V^T
             }
             const bool need_mask = (32 * i + 31 >= sd.L) || (key - l31 + 31 >= sd.L) || ((long)(key - l31) + 31 > (long)32 * i + sd.diag);
             float pv[16], dsv[16];
@@ -416,34 +319,33 @@ __global__ __launch_bounds__(256, 2) void attn_x3_bwd_dkv(SeqDesc sd, int nt, co
                 }
             }
             if (need_mask) {
-                X3_NO_IFCVT();
+                TCOW_NO_IFCVT();
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int qi = 32 * i + crow32(r, hi);
                     if (!(qi < sd.L && key < sd.L && (long)key <= (long)qi + sd.diag)) { pv[r] = 0.f; dsv[r] = 0.f; }
                 }
             }
-            xb8 ph0, pl0, ph1, pl1, dh0, dl0, dh1, dl1;
-            xsplit8(pv, ph0, pl0); xsplit8(pv + 8, ph1, pl1); xsplit8(dsv, dh0, dl0); xsplit8(dsv + 8, dh1, dl1);
-            dv0 = x3_mm(xfrag_tr(doth, 0, 0, lane), xfrag_tr(dotl, 0, 0, lane), ph0, pl0, dv0);                    // dV^T += dO^T P
-            dv1 = x3_mm(xfrag_tr(doth, 0, 1, lane), xfrag_tr(dotl, 0, 1, lane), ph0, pl0, dv1);
-            dv0 = x3_mm(xfrag_tr(doth, 1, 0, lane), xfrag_tr(dotl, 1, 0, lane), ph1, pl1, dv0);
-            dv1 = x3_mm(xfrag_tr(doth, 1, 1, lane), xfrag_tr(dotl, 1, 1, lane), ph1, pl1, dv1);
-            dk0 = x3_mm(xfrag_tr(qth, 0, 0, lane), xfrag_tr(qtl, 0, 0, lane), dh0, dl0, dk0);                      // dK^T += Q^T dS
-            dk1 = x3_mm(xfrag_tr(qth, 0, 1, lane), xfrag_tr(qtl, 0, 1, lane), dh0, dl0, dk1);
-            dk0 = x3_mm(xfrag_tr(qth, 1, 0, lane), xfrag_tr(qtl, 1, 0, lane), dh1, dl1, dk0);
-            dk1 = x3_mm(xfrag_tr(qth, 1, 1, lane), xfrag_tr(qtl, 1, 1, lane), dh1, dl1, dk1);
+            const P::Frag p0 = P::pack(pv), p1 = P::pack(pv + 8), d0 = P::pack(dsv), d1 = P::pack(dsv + 8);
+            dv0 = P::mm(frag_tr<P>(dot_, 0, 0, lane), p0, dv0);                     // dV^T += dO^T P
+            dv1 = P::mm(frag_tr<P>(dot_, 0, 1, lane), p0, dv1);
+            dv0 = P::mm(frag_tr<P>(dot_, 1, 0, lane), p1, dv0);
+            dv1 = P::mm(frag_tr<P>(dot_, 1, 1, lane), p1, dv1);
+            dk0 = P::mm(frag_tr<P>(qt_, 0, 0, lane), d0, dk0);                      // dK^T += Q^T dS
+            dk1 = P::mm(frag_tr<P>(qt_, 0, 1, lane), d0, dk1);
+            dk0 = P::mm(frag_tr<P>(qt_, 1, 0, lane), d1, dk0);
+            dk1 = P::mm(frag_tr<P>(qt_, 1, 1, lane), d1, dk1);
         }
     }
     if (!active || key >= sd.L) return;
     const long row = base + (long)key * sd.pos_stride;
-    x_store_row(dqkv + row * ld3 + sd.D + head * ATT_HD, hi, dk0, dk1, xScale);
-    x_store_row(dqkv + row * ld3 + 2 * sd.D + head * ATT_HD, hi, dv0, dv1, 1.0f);
+    store_rowT(dqkv + row * ld3 + sd.D + head * ATT_HD, hi, dk0, dk1, kScale);
+    store_rowT(dqkv + row * ld3 + 2 * sd.D + head * ATT_HD, hi, dv0, dv1, 1.0f);
 }
 
 constexpr int X3_CH = 4;
-template <int CH> constexpr int x3_lds() { return 4 * CH * XTILE; }
-template <int CH> constexpr int x3_lds_dkv() { return 4 * CH * XTILE + CH * 32 * 8; }
+template <int CH> constexpr int x3_lds() { return 4 * CH * TILE_B; }
+template <int CH> constexpr int x3_lds_dkv() { return 4 * CH * TILE_B + CH * 32 * 8; }
 
 template <int CH>
 int x3_fwd_launch(hipStream_t st, const SeqDesc& d, int nt, int grid, const void* qkv, void* out, float* lse) {
@@ -471,7 +373,7 @@ int x3_bwd_launch(hipStream_t st, const SeqDesc& d, int nt, int grid, const void
 int tcow_attn_x3_fwd(hipStream_t st, const SeqDesc& d, const void* qkv, void* out, float* lse) {
     const int nt = cdiv(d.L, 32), pairs = d.n_outer * d.n_inner * d.heads, grid = stream_grid(pairs, cdiv(nt, 4));
     if (nt == 1) {                       // one-tile sequences: a wave per (sequence, head), wave-private 16 KiB
-        constexpr int lds = 4 * 4 * XTILE;
+        constexpr int lds = 4 * 4 * TILE_B;
         tcow_ensure_lds((const void*)attn_x3_fwd<1, true>, lds);
         hipLaunchKernelGGL((attn_x3_fwd<1, true>), dim3(cdiv(pairs, 4)), dim3(256), lds, st, d, nt, (const float*)qkv, (float*)out, lse);
         TCOW_CHECK_LAUNCH();
@@ -484,7 +386,7 @@ int tcow_attn_x3_fwd(hipStream_t st, const SeqDesc& d, const void* qkv, void* ou
 int tcow_attn_x3_bwd(hipStream_t st, const SeqDesc& d, const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv) {
     const int nt = cdiv(d.L, 32), pairs = d.n_outer * d.n_inner * d.heads, grid = stream_grid(pairs, cdiv(nt, 4));
     if (nt == 1) {
-        constexpr int lds = 4 * 4 * XTILE, lds_dkv = 4 * (4 * XTILE + 256);
+        constexpr int lds = 4 * 4 * TILE_B, lds_dkv = 4 * (4 * TILE_B + 256);
         tcow_ensure_lds((const void*)attn_x3_bwd_dq<1, true>, lds);
         tcow_ensure_lds((const void*)attn_x3_bwd_dkv<1, true>, lds_dkv);
         hipLaunchKernelGGL((attn_x3_bwd_dq<1, true>), dim3(cdiv(pairs, 4)), dim3(256), lds, st, d, nt, (const float*)qkv, (const float*)out, (const float*)dout, lse, delta, (float*)dqkv);

@@ -347,6 +347,27 @@ typedef struct {
     void* out;
 } tcow_stream_attn_args;
 int tcow_attn_temporal_step(void* stream, const tcow_stream_attn_args* args);
+/* Attention maps of a live session (attention_stream_probs.hip; a new entry point, no signature changed: the ABI version stays): the softmax rows
+ * of a step against the sessions' K caches, which tcow_attn_temporal_step (an online softmax that stores no lse) never forms.
+ *   The record is that of tcow_attn_temporal_step, every field with the same meaning: the same forms (rows, the stream, ragged), layouts
+ *   (contiguous, paged) and cache types (the storage type, TCOW_BF16 under TCOW_F32, TCOW_FP8E4M3 under either), and the same refusals, reported
+ *   under this symbol's name; probs == NULL is refused too, before any launch.  args->out is neither read nor written and may be NULL.  The
+ *   caches are only read: nothing is appended.
+ *   probs f32 [F, S-1, heads, T_total], F = shape.B * shape.T flat frames in the step's row order.  For flat frame f of session r at
+ *   t = t0_r + j, slot s >= 1 and head h:
+ *       probs[f, s-1, h, k] = softmax_{k' <= t}(q_t . K_k' / 8)[k]   for k <= t
+ *                           = +0.0 exactly                            for t < k < T_total
+ *   K_k for k < t0 is the session's cached line, decoded from C when the cache is compact; for k >= t0 the step's own qkv row, rounded through
+ *   C when the cache is compact (rnd_C of the step: a key has one value wherever it is read from).  q is never rounded.
+ *   Arithmetic.  The score of a key is computed exactly as the step computes it (the lane group's fused multiply-adds in channel order, the
+ *   xor-shuffle tree over the group, d * 0.125f; a key's group and batch follow from its index alone); maximum, exp(s - max), the sum in a fixed
+ *   order and the division are f32, nothing is atomic.  A row is therefore a fixed function of (q_t, K_0 .. K_t): it depends neither on how the
+ *   frames were split into steps, nor on the form, nor on the layout -- those agree bit for bit.
+ *   Bad rows are those tcow_attn_temporal_step defines (t0 or slot out of range, a ragged frame outside its session, a page entry among
+ *   page_rows[r][0 .. t / P] outside the heap): NaN to the frame's own rows of probs, no cache byte read, other sessions unaffected.
+ *   Ordering.  A wave reads cache positions < t0 only and the step writes positions >= t0: the call gives the same bits whether it is enqueued
+ *   before or after tcow_attn_temporal_step of the same record on the same stream. */
+int tcow_attn_temporal_step_probs(void* stream, const tcow_stream_attn_args* args, float* probs);
 typedef struct {
     int n;                      /* rows (rows form) or sessions (ragged form) */
     int c;                      /* rows form: frames per row */

@@ -131,6 +131,7 @@ SIGNATURES = {
     'tcow_attn_spatial_bwd': (_i, [_vp, _ash, _vp, _vp, _vp, _vp, _vp, _vp, _l]),
     'tcow_attn_probs': (_i, [_vp, ctypes.POINTER(AttnProbsArgs)]),
     'tcow_attn_temporal_step': (_i, [_vp, ctypes.POINTER(StreamAttnArgs)]),
+    'tcow_attn_temporal_step_probs': (_i, [_vp, ctypes.POINTER(StreamAttnArgs), _vp]),
     'tcow_cls_step': (_i, [_vp, ctypes.POINTER(StreamClsArgs)]),
     'tcow_requery_mask': (_i, [_vp, _i, _l, _vp, _l, _vp, _f, _vp, _vp, _i, _vp]),
     'tcow_im2col': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),

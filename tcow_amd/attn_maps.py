@@ -1,6 +1,7 @@
 """Host arithmetic of Seeker.attention_maps: what the arguments mean, where a (frame, slot) query sits in the sequences the attention kernels run
 over, the shapes and bytes of the maps, and every refusal -- all of it before a launch.  No device, module or tensor in here (the probe that
-launches ops.attn_probs is tcow_amd/attn_probe.py); tests/test_attn_maps_plan_host.py pins it on the CPU.
+launches ops.attn_probs is tcow_amd/attn_probe.py); tests/test_attn_maps_plan_host.py pins it on the CPU.  The same for the maps of a live
+stream or pool step against its cache (StepMapPlan, at the end; tests/test_step_map_plan_host.py).
 
 A query is (frame, slot): slot 0 is the cls token, slot 1 + n patch n = h' * W' + w' of that frame.
   divided_space_time: the spatial sequences are those of tcow_attn_spatial_fwd, one per (clip, frame) over slots s0 .. S-1, s0 = 0 when
@@ -135,3 +136,79 @@ class MapPlan:
         if self.bytes > max_bytes:
             raise TcowError(f'attention_maps: the maps asked for take {self.bytes} bytes ({len(self.blocks)} block(s) x {per_block}), over '
                             f'max_bytes = {max_bytes}: name fewer blocks or queries, or raise the budget')
+
+
+# ---------------------------------------------------------------------------------------------------------------------------- live sessions
+
+def normalise_slots(spatial_slots, S, causal, who='step_maps'):
+    """The spatial queries of a step: every frame of a step asks the same slots, so a query is a slot.  None -> []; 'cls' -> [0], where slot 0
+    takes part in spatial attention (a stream has causal_attention 1 or 2: with 1 only); a list of slots in 0 .. S-1, slot 0 under the same
+    rule, a slot named twice refused."""
+    if spatial_slots is None:
+        return []
+    if isinstance(spatial_slots, str):
+        if spatial_slots != 'cls':
+            raise TcowError(f"{who}: spatial_slots={spatial_slots!r} must be None, 'cls' or a list of slots")
+        if not cls_takes_part(causal):
+            raise TcowError(f"{who}: spatial_slots='cls' but slot 0 takes no part in spatial attention with causal_attention={causal}")
+        return [0]
+    if isinstance(spatial_slots, int) and not isinstance(spatial_slots, bool):
+        spatial_slots = [spatial_slots]
+    out = []
+    for s in spatial_slots:
+        if isinstance(s, bool) or not isinstance(s, int):
+            raise TcowError(f'{who}: a spatial slot must be an integer, got {s!r}')
+        if not 0 <= s < S:
+            raise TcowError(f'{who}: slot {s} is out of range 0 .. {S - 1}')
+        if s == 0 and not cls_takes_part(causal):
+            raise TcowError(f'{who}: slot 0 takes no part in spatial attention with causal_attention={causal}')
+        if s in out:
+            raise TcowError(f'{who}: slot {s} is named twice in spatial_slots={list(spatial_slots)!r}')
+        out.append(s)
+    return out
+
+
+class StepMapPlan:
+    """What one step_maps / step_ragged_maps call of a live stream or pool computes, beside the step.  rows_or_chunks: a tuple (rows, c) -- a
+    stream or pool step of `rows` query rows with c frames each -- or a list of chunk lengths, one per session of a ragged step.
+    blocks, temporal, slots: the normalised arguments; s0 and positions (slot - s0, the table of ops.attn_probs' rows form) as in MapPlan.
+    F: flat frames of the step; first: every session's first flat frame (rows form: r * c); chunks: its frames.
+    temporal_launch (F, S-1, heads, T_total): tcow_attn_temporal_step_probs' output; temporal_shape: the public layout -- (rows, N, heads, c, T),
+        ragged a list of (1, N, heads, c_k, T) -- or None.
+    spatial_launch (F, nq, heads, S): the rows form's output, of which the public maps are views -- (rows, c, nq, heads, S), ragged a list of
+        (1, c_k, nq, heads, S) -- or None.
+    bytes: everything the call allocates for maps: per block the temporal launch output and its permuted copy, and the spatial launch output."""
+
+    def __init__(self, depth, rows_or_chunks, T_total, S, heads, causal, blocks=None, temporal=True, spatial_slots=None, max_bytes=DEFAULT_MAX_BYTES,
+                 who='step_maps'):
+        self.ragged = not isinstance(rows_or_chunks, tuple)
+        if self.ragged:
+            self.chunks = [int(c) for c in rows_or_chunks]
+        else:
+            rows, c = rows_or_chunks
+            self.chunks = [int(c)] * int(rows)
+        if not self.chunks or min(self.chunks) < 1:
+            raise TcowError(f'{who}: a step has at least one row and every row at least one frame, got {rows_or_chunks!r}')
+        self.first = [sum(self.chunks[:k]) for k in range(len(self.chunks))]
+        self.F = F = sum(self.chunks)
+        self.blocks = normalise_blocks(blocks, depth)
+        self.temporal = bool(temporal)
+        self.slots = normalise_slots(spatial_slots, S, causal, who)
+        self.s0 = 0 if cls_takes_part(causal) else 1
+        self.positions = [s - self.s0 for s in self.slots]
+        N, nq, n = S - 1, len(self.slots), len(self.chunks)
+        self.temporal_launch = (F, N, heads, T_total) if self.temporal else None
+        self.spatial_launch = (F, nq, heads, S) if nq else None
+        if self.ragged:
+            self.temporal_shape = [(1, N, heads, c, T_total) for c in self.chunks] if self.temporal else None
+            self.spatial_shape = [(1, c, nq, heads, S) for c in self.chunks] if nq else None
+        else:
+            self.temporal_shape = (n, N, heads, self.chunks[0], T_total) if self.temporal else None
+            self.spatial_shape = (n, self.chunks[0], nq, heads, S) if nq else None
+        per_block = (2 * 4 * F * N * heads * T_total if self.temporal else 0) + (4 * F * nq * heads * S if nq else 0)
+        self.bytes_per_block, self.bytes = per_block, per_block * len(self.blocks)
+        if isinstance(max_bytes, bool) or not isinstance(max_bytes, int) or max_bytes < 0:
+            raise TcowError(f'{who}: max_bytes ({max_bytes!r}) must be a non-negative integer')
+        if self.bytes > max_bytes:
+            raise TcowError(f'{who}: the maps asked for take {self.bytes} bytes ({len(self.blocks)} block(s) x {per_block}), over '
+                            f'max_bytes = {max_bytes}: name fewer blocks or slots, or raise the budget')

@@ -28,11 +28,9 @@
 #include <math.h>
 
 #include "attention_stream_cache.h"
+#include "internal.h"
 
 namespace {
-
-constexpr int ST_WAVES = 4;     // waves (items) per workgroup
-constexpr int ST_U = 4;         // batches of G key rows loaded before they are used
 
 // One query frame of a temporal stream step, shared by every kernel of this file so that they agree bit for bit: chunk frame j (flat frame
 // fb + j of the step's rows, fb = the chunk's first flat frame) stands at t = t0 + j and attends to keys 0 .. t, keys < t0 from the cache at
@@ -368,55 +366,59 @@ __global__ void cls_ragged_kernel(int n, int F, int S, int D, float* __restrict_
     cls_session(slot, n_slots, t0_rows[r], x + (size_t)first * S * D + ch, c, (size_t)S * D, cls_cache, (size_t)slot * D + ch);
 }
 
-// Calls f(T{}, C{}) with the storage type T of `dtype` and the cache element type C of `cq` (both checked by tcow_attn_temporal_step).
-template <typename F> void with_cache_types(int dtype, int cq, F f) {
-    if (dtype == TCOW_BF16) {
-        if (cq == TCOW_FP8E4M3) f(bf16_t{}, fp8_t{}); else f(bf16_t{}, bf16_t{});
-    } else {
-        if (cq == TCOW_FP8E4M3) f(float{}, fp8_t{}); else if (cq == TCOW_BF16) f(float{}, bf16_t{}); else f(float{}, float{});
-    }
-}
-
 }  // namespace
-
-extern "C" {
 
 // What it asks of every step: a shape of s.T >= 1 frames per row, head_dim 64, a causal mask, a stream of T_min .. TCOW_STREAM_MAX_FRAMES frames
 // (a chunk of s.B rows must fit into the cache: T_min = s.T; the F frames of a ragged step belong to several sessions and may exceed T_total:
 // T_min = 1), a storage type of this file, at least one cache slot (the stream: a slot per row; a paged cache has pages, checked below), and a
 // cache element type that is one of the three and no wider than the storage; of a ragged step of n sessions also its one row of F frames, of
-// a paged cache its geometry; then the pointers of the form.  One wave per item: (row, slot, head), ragged (flat frame, slot, head).
-int tcow_attn_temporal_step(void* stream, const tcow_stream_attn_args* args) {
-    TCOW_CHECK_ARG(args != nullptr, "tcow_attn_temporal_step: null args");
+// a paged cache its geometry; then the pointers of the form.  `who` is the entry point the refusal is reported under: tcow_attn_temporal_step, and
+// tcow_attn_temporal_step_probs (attention_stream_probs.hip), which takes the same record and neither reads nor writes `out` (needs_out false).
+int tcow_stream_attn_check(const char* who, const tcow_stream_attn_args* args, bool needs_out) {
+    TCOW_CHECK_ARG(args != nullptr, "%s: null args", who);
     const tcow_stream_attn_args& a = *args;
     const tcow_attn_shape& s = a.shape;
     const bool ragged = a.n_sessions != 0, paged = a.page_frames != 0;
     const int n = a.n_sessions, cq = a.cache_dtype, T_total = a.T_total;
-    TCOW_CHECK_ARG(ragged || !paged, "tcow_attn_temporal_step: a paged cache (page_frames=%d) serves ragged steps only (n_sessions=0 is the rows form)",
+    TCOW_CHECK_ARG(ragged || !paged, "%s: a paged cache (page_frames=%d) serves ragged steps only (n_sessions=0 is the rows form)", who,
                    a.page_frames);
-    TCOW_CHECK_ARG(s.B > 0 && s.T > 0 && s.S > 1 && s.heads > 0, "tcow_attn_temporal_step: bad step shape B=%d T=%d S=%d heads=%d", s.B, s.T, s.S, s.heads);
-    TCOW_CHECK_ARG(s.D == s.heads * ATT_HD, "tcow_attn_temporal_step: head_dim must be 64 (D=%d heads=%d)", s.D, s.heads);
-    TCOW_CHECK_ARG(s.causal == 1 || s.causal == 2, "tcow_attn_temporal_step: causal must be 1 or 2 (got %d): other masks let a frame see later frames", s.causal);
+    TCOW_CHECK_ARG(s.B > 0 && s.T > 0 && s.S > 1 && s.heads > 0, "%s: bad step shape B=%d T=%d S=%d heads=%d", who, s.B, s.T, s.S, s.heads);
+    TCOW_CHECK_ARG(s.D == s.heads * ATT_HD, "%s: head_dim must be 64 (D=%d heads=%d)", who, s.D, s.heads);
+    TCOW_CHECK_ARG(s.causal == 1 || s.causal == 2, "%s: causal must be 1 or 2 (got %d): other masks let a frame see later frames", who, s.causal);
     const int T_min = ragged ? 1 : s.T;
-    TCOW_CHECK_ARG(T_total >= T_min && T_total <= TCOW_STREAM_MAX_FRAMES, "tcow_attn_temporal_step: T_total=%d must be in [%d, %d]", T_total, T_min,
+    TCOW_CHECK_ARG(T_total >= T_min && T_total <= TCOW_STREAM_MAX_FRAMES, "%s: T_total=%d must be in [%d, %d]", who, T_total, T_min,
                    TCOW_STREAM_MAX_FRAMES);
-    TCOW_CHECK_ARG(s.dtype == TCOW_F32 || s.dtype == TCOW_BF16, "tcow_attn_temporal_step: dtype must be TCOW_F32 or TCOW_BF16 (got %d)", s.dtype);
+    TCOW_CHECK_ARG(s.dtype == TCOW_F32 || s.dtype == TCOW_BF16, "%s: dtype must be TCOW_F32 or TCOW_BF16 (got %d)", who, s.dtype);
     const int n_slots = !ragged && !a.slot_rows ? s.B : a.n_slots;
-    TCOW_CHECK_ARG(paged || n_slots >= 1, "tcow_attn_temporal_step: n_slots=%d must be >= 1", n_slots);
+    TCOW_CHECK_ARG(paged || n_slots >= 1, "%s: n_slots=%d must be >= 1", who, n_slots);
     TCOW_CHECK_ARG(cq == TCOW_F32 || cq == TCOW_BF16 || cq == TCOW_FP8E4M3,
-                   "tcow_attn_temporal_step: cache_dtype must be TCOW_F32, TCOW_BF16 or TCOW_FP8E4M3 (got %d)", cq);
-    TCOW_CHECK_ARG(!(s.dtype == TCOW_BF16 && cq == TCOW_F32), "tcow_attn_temporal_step: cache_dtype TCOW_F32 is wider than the 16-bit storage (dtype TCOW_BF16)");
+                   "%s: cache_dtype must be TCOW_F32, TCOW_BF16 or TCOW_FP8E4M3 (got %d)", who, cq);
+    TCOW_CHECK_ARG(!(s.dtype == TCOW_BF16 && cq == TCOW_F32), "%s: cache_dtype TCOW_F32 is wider than the 16-bit storage (dtype TCOW_BF16)", who);
     TCOW_CHECK_ARG(!ragged || (s.B == 1 && n > 0 && n <= s.T),
-                   "tcow_attn_temporal_step: a ragged step is one row of F frames of 1 <= n <= F sessions (B=%d F=%d n=%d)", s.B, s.T, n);
+                   "%s: a ragged step is one row of F frames of 1 <= n <= F sessions (B=%d F=%d n=%d)", who, s.B, s.T, n);
     if (paged) {
         TCOW_CHECK_ARG(a.page_frames >= 1 && a.page_frames <= TCOW_STREAM_MAX_FRAMES && (a.page_frames & (a.page_frames - 1)) == 0,
-                       "tcow_attn_temporal_step: page_frames=%d must be a power of two in [1, %d]", a.page_frames, TCOW_STREAM_MAX_FRAMES);
-        TCOW_CHECK_ARG(a.n_pages >= 1, "tcow_attn_temporal_step: n_pages=%d must be >= 1", a.n_pages);
+                       "%s: page_frames=%d must be a power of two in [1, %d]", who, a.page_frames, TCOW_STREAM_MAX_FRAMES);
+        TCOW_CHECK_ARG(a.n_pages >= 1, "%s: n_pages=%d must be >= 1", who, a.n_pages);
         TCOW_CHECK_ARG(a.pages_per_session >= 1 && (long)a.pages_per_session * a.page_frames >= T_total,
-                       "tcow_attn_temporal_step: pages_per_session=%d x page_frames=%d does not cover T_total=%d", a.pages_per_session, a.page_frames, T_total);
+                       "%s: pages_per_session=%d x page_frames=%d does not cover T_total=%d", who, a.pages_per_session, a.page_frames, T_total);
     }
-    TCOW_CHECK_ARG(a.t0_rows && a.qkv && a.k_cache && a.v_cache && a.out &&
-                   (!ragged || (a.first_rows && a.c_rows && a.row_of_frame && (paged ? a.page_rows : a.slot_rows))), "tcow_attn_temporal_step: null pointer");
+    TCOW_CHECK_ARG(a.t0_rows && a.qkv && a.k_cache && a.v_cache && (a.out || !needs_out) &&
+                   (!ragged || (a.first_rows && a.c_rows && a.row_of_frame && (paged ? a.page_rows : a.slot_rows))), "%s: null pointer", who);
+    return TCOW_OK;
+}
+
+extern "C" {
+
+// One wave per item: (row, slot, head), ragged (flat frame, slot, head).
+int tcow_attn_temporal_step(void* stream, const tcow_stream_attn_args* args) {
+    const int status = tcow_stream_attn_check("tcow_attn_temporal_step", args, true);
+    if (status != TCOW_OK) return status;
+    const tcow_stream_attn_args& a = *args;
+    const tcow_attn_shape& s = a.shape;
+    const bool ragged = a.n_sessions != 0, paged = a.page_frames != 0;
+    const int n = a.n_sessions, cq = a.cache_dtype, T_total = a.T_total;
+    const int n_slots = !ragged && !a.slot_rows ? s.B : a.n_slots;
     const long items = (long)(ragged ? s.T : s.B) * s.S * s.heads;
     const dim3 grid((unsigned)cdiv(items, ST_WAVES)), block(64 * ST_WAVES);
     const hipStream_t st = (hipStream_t)stream;

@@ -1,6 +1,6 @@
-// What the stream attention kernels (attention_stream.hip) know about a cache element and about where a key lives: a lane's slice of a line
+// What the stream attention kernels (attention_stream.hip, attention_stream_probs.hip) know about a cache element and about where a key lives: a lane's slice of a line
 // in the storage type (StreamVec), in the cache type (CacheVec, fp8_t), the append of a line, and the two cache layouts (ContiguousKeys /
-// PagedKeys).  Everything else in attention_stream.hip is written against these.
+// PagedKeys), the wave and batch counts and the switch over (storage, cache) types.  Everything else in the two sources is written against these.
 //
 // Lines.  The head's 64 channels of a K / V row are one 128-byte (16-bit) or 256-byte (f32) line: LPR lanes read it with one 16-byte load each,
 // so a wave covers G = 64 / LPR key rows per load (16-bit: 8 lanes x 8 elements, 8 rows; f32: 16 lanes x 4, 4 rows).
@@ -16,6 +16,9 @@
 #include "attention_common.h"
 
 namespace {
+
+constexpr int ST_WAVES = 4;     // waves (items) per workgroup
+constexpr int ST_U = 4;         // batches of G key rows loaded before they are used
 
 template <typename T> struct StreamVec;
 template <> struct StreamVec<bf16_t> {
@@ -130,5 +133,14 @@ struct PagedKeys {                  // [n_pages, S-1, heads, P, 64], P = 1 << lg
         return base + ((size_t)pg * page_stride + line + (size_t)(kt & ((1 << lgP) - 1)) * ATT_HD);
     }
 };
+
+// Calls f(T{}, C{}) with the storage type T of `dtype` and the cache element type C of `cq` (both checked by tcow_stream_attn_check).
+template <typename F> void with_cache_types(int dtype, int cq, F f) {
+    if (dtype == TCOW_BF16) {
+        if (cq == TCOW_FP8E4M3) f(bf16_t{}, fp8_t{}); else f(bf16_t{}, bf16_t{});
+    } else {
+        if (cq == TCOW_FP8E4M3) f(float{}, fp8_t{}); else if (cq == TCOW_BF16) f(float{}, bf16_t{}); else f(float{}, float{});
+    }
+}
 
 }  // namespace

@@ -24,6 +24,10 @@ int tcow_gemm_tn_bf16_group(hipStream_t stream, const TnGroupPlan& pl, int n, co
 int tcow_gemm_tn_f32(hipStream_t stream, const TnPlan& pl, int M, int N, int K, const float* dY, long ldy, const float* X, long ldx, float* slab);      // gemm_f32.hip
 int tcow_gemm_tn_x3(hipStream_t stream, const TnPlan& pl, int M, int N, int K, const float* dY, long ldy, const float* X, long ldx, float* slab);       // gemm_x3.hip
 
+// ---- the checks of a stream attention record (attention_stream.hip), reported under the entry point `who`: tcow_attn_temporal_step, and
+// tcow_attn_temporal_step_probs (attention_stream_probs.hip), which does not ask for `out` (needs_out false)
+int tcow_stream_attn_check(const char* who, const tcow_stream_attn_args* args, bool needs_out);
+
 // ---- hand-off of a rollover stream pool (stream_requery.hip); tcow_requery_mask checks the arguments
 int tcow_launch_requery_mask(hipStream_t stream, int n, long plane, const float* logits, long logits_len, const long* src_off, float threshold, float* mask,
                              const int* dst_rows, int n_dst, int* pixels);

@@ -373,10 +373,15 @@ def attn_probs(shape, spatial_rows, qkv, out, lse=None, pos=None):
 FP8 = L.TCOW_FP8E4M3      # cache_dtype of the attn_temporal_* wrappers only: a K / V cache of torch.float8_e4m3fn elements
 
 
+STEP, STEP_PROBS = 'tcow_attn_temporal_step', 'tcow_attn_temporal_step_probs'        # the two entry points that take a tcow_stream_attn_args record
+
+
 def _stream_attn(who, mode, B, T, S, D, heads, causal, cache_dtype, T_total, t0_rows, qkv, k_cache, v_cache, out, n_sessions=0, n_slots=0, slot_rows=None,
-                 first_rows=None, c_rows=None, row_of_frame=None, page_frames=0, n_pages=0, pages_per_session=0, page_rows=None):
+                 first_rows=None, c_rows=None, row_of_frame=None, page_frames=0, n_pages=0, pages_per_session=0, page_rows=None, symbol=STEP):
     """The call of the four attn_temporal_* wrappers (`who`): fills tcow_stream_attn_args (include/tcow_hip.h: which fields a form leaves 0 / None;
     the keywords are those) and calls tcow_attn_temporal_step of the mode's build.  `mode` is the attention mode: F32X3 (precision='bf16x3') stores f32 and runs as F32.
+    symbol=STEP_PROBS: the same record to tcow_attn_temporal_step_probs -- `out` is then the maps, a contiguous f32 tensor of exactly
+    F * (S-1) * heads * T_total elements (F = B * T flat frames), and the record's own out stays NULL.
     cache_dtype None = the storage type.  F32, BF16 (= the 16-bit type) or FP8: the caches must have the torch dtype it names -- torch.float8_e4m3fn;
     for BF16 the mode's 16-bit type, torch.bfloat16 under f32 storage (the main build serves it); torch.float32 -- and that refusal carries the
     wrapper's name.  A value or pair the library refuses (unknown, wider than the storage) is passed on for it to refuse, under its symbol."""
@@ -388,10 +393,17 @@ def _stream_attn(who, mode, B, T, S, D, heads, causal, cache_dtype, T_total, t0_
             torch.float32 if cq == F32 and not is16(mode) else None
         if want is not None and (k_cache.dtype != want or v_cache.dtype != want):
             raise L.TcowError(f'{who}: cache_dtype={cq} needs {want} caches, got {k_cache.dtype} / {v_cache.dtype}')
+    probs = symbol == STEP_PROBS
+    if probs:
+        want = B * T * (S - 1) * heads * int(T_total)
+        if not torch.is_tensor(out) or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != want:
+            raise L.TcowError(f'{who}: probs must be a contiguous float32 tensor of F * (S-1) * heads * T_total = {want} elements, got '
+                              f'{(out.dtype, tuple(out.shape), "contiguous" if out.is_contiguous() else "strided") if torch.is_tensor(out) else type(out).__name__}')
     args = L.StreamAttnArgs(L.AttnShape(B, T, S, D, heads, int(causal), dm), cq, int(T_total), int(n_sessions), int(n_slots), int(page_frames), int(n_pages),
                             int(pages_per_session), t0_rows.data_ptr(), _p(slot_rows), _p(first_rows), _p(c_rows), _p(row_of_frame), _p(page_rows),
-                            qkv.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr())
-    L.check(lib.tcow_attn_temporal_step(_stream(), ctypes.byref(args)), 'tcow_attn_temporal_step', lib)
+                            qkv.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), None if probs else out.data_ptr())
+    fn = getattr(lib, symbol)
+    L.check(fn(_stream(), ctypes.byref(args), out.data_ptr()) if probs else fn(_stream(), ctypes.byref(args)), symbol, lib)
     return out
 
 
@@ -403,13 +415,13 @@ def _stream_cls(x, n, c, F, S, cls_cache, n_slots, t0_rows, slot_rows=None, firs
     return x
 
 
-def attn_temporal_cached(mode, B, c, S, D, heads, causal, T_total, t0_dev, qkv, k_cache, v_cache, out, cache_dtype=None):
+def attn_temporal_cached(mode, B, c, S, D, heads, causal, T_total, t0_dev, qkv, k_cache, v_cache, out, cache_dtype=None, who='attn_temporal_cached', symbol=STEP):
     """Temporal attention of a c-frame chunk (qkv [B*c*S, 3D] -> out [B*c*S, D]) against the K / V cache [B, S-1, heads, T_total, 64] of the
     frames before t0 = t0_dev[0] (int32 device scalar); appends the chunk's K / V at t0 (tcow_attn_temporal_step, the stream of the rows form).
     cache_dtype (here and in the three wrappers below): None = caches in the storage type; F32 / BF16 / FP8 = caches of that element type, every
     key and value taken at its value rounded to it (the compact cache of tcow_attn_temporal_step)."""
     _need_cuda(qkv, k_cache, v_cache, out, t0_dev)
-    return _stream_attn('attn_temporal_cached', mode, B, c, S, D, heads, causal, cache_dtype, T_total, t0_dev, qkv, k_cache, v_cache, out)
+    return _stream_attn(who, mode, B, c, S, D, heads, causal, cache_dtype, T_total, t0_dev, qkv, k_cache, v_cache, out, symbol=symbol)
 
 
 def cls_stream(x, B, c, S, cls_cache, t0_dev):
@@ -417,12 +429,13 @@ def cls_stream(x, B, c, S, cls_cache, t0_dev):
     return _stream_cls(x, B, c, 0, S, cls_cache, 0, t0_dev)
 
 
-def attn_temporal_pool(mode, n, c, S, D, heads, causal, T_total, n_slots, t0_rows, slot_rows, qkv, k_cache, v_cache, out, cache_dtype=None):
+def attn_temporal_pool(mode, n, c, S, D, heads, causal, T_total, n_slots, t0_rows, slot_rows, qkv, k_cache, v_cache, out, cache_dtype=None, who='attn_temporal_pool',
+                       symbol=STEP):
     """attn_temporal_cached for n rows that stand at different frames: row r attends at t0_rows[r] against block slot_rows[r] of the caches
     [n_slots, S-1, heads, T_total, 64] and appends there (int32 device tensors [n]; distinct slots -- the rows form of tcow_attn_temporal_step)."""
     _need_cuda(qkv, k_cache, v_cache, out, t0_rows, slot_rows)
-    return _stream_attn('attn_temporal_pool', mode, n, c, S, D, heads, causal, cache_dtype, T_total, t0_rows, qkv, k_cache, v_cache, out, n_slots=n_slots,
-                        slot_rows=slot_rows)
+    return _stream_attn(who, mode, n, c, S, D, heads, causal, cache_dtype, T_total, t0_rows, qkv, k_cache, v_cache, out, n_slots=n_slots,
+                        slot_rows=slot_rows, symbol=symbol)
 
 
 def cls_pool(x, n, c, S, cls_cache, n_slots, t0_rows, slot_rows):
@@ -446,39 +459,55 @@ def _ragged_tables(who, n, F, t0_rows, slot_rows, first_rows, c_rows, row_of_fra
 
 
 def _ragged_rows(who, F, S, qkv, out):
-    """The rows of a ragged attention step: all F frames of all sessions, flat."""
-    if qkv.shape[0] != F * S or out.shape[0] != F * S:
+    """The rows of a ragged attention step: all F frames of all sessions, flat (out None: the maps, whose size _stream_attn checks)."""
+    if out is None:
+        if qkv.shape[0] != F * S:
+            raise L.TcowError(f'{who}: qkv must have F * S = {F * S} rows, got {qkv.shape[0]}')
+    elif qkv.shape[0] != F * S or out.shape[0] != F * S:
         raise L.TcowError(f'{who}: qkv / out must have F * S = {F * S} rows, got {qkv.shape[0]} / {out.shape[0]}')
 
 
 def attn_temporal_ragged(mode, n, F, S, D, heads, causal, T_total, n_slots, t0_rows, slot_rows, first_rows, c_rows, row_of_frame, qkv, k_cache, v_cache,
-                         out, cache_dtype=None):
+                         out, cache_dtype=None, who='attn_temporal_ragged', symbol=STEP):
     """attn_temporal_pool for n sessions that bring different numbers of frames: session r owns the flat frames first_rows[r] .. + c_rows[r] - 1 of
     the step's F frames (qkv [F*S, 3D] -> out [F*S, D]), row_of_frame[f] names the session of frame f (int32 device tensors [n] / [F]); one wave per
     frame, bit-identical per session to attn_temporal_pool (the ragged form of tcow_attn_temporal_step)."""
     _need_cuda(qkv, k_cache, v_cache, out)
-    _ragged_tables('attn_temporal_ragged', n, F, t0_rows, slot_rows, first_rows, c_rows, row_of_frame)
-    _ragged_rows('attn_temporal_ragged', F, S, qkv, out)
-    return _stream_attn('attn_temporal_ragged', mode, 1, F, S, D, heads, causal, cache_dtype, T_total, t0_rows, qkv, k_cache, v_cache, out, n_sessions=n,
-                        n_slots=n_slots, slot_rows=slot_rows, first_rows=first_rows, c_rows=c_rows, row_of_frame=row_of_frame)
+    _ragged_tables(who, n, F, t0_rows, slot_rows, first_rows, c_rows, row_of_frame)
+    _ragged_rows(who, F, S, qkv, out if symbol == STEP else None)
+    return _stream_attn(who, mode, 1, F, S, D, heads, causal, cache_dtype, T_total, t0_rows, qkv, k_cache, v_cache, out, n_sessions=n,
+                        n_slots=n_slots, slot_rows=slot_rows, first_rows=first_rows, c_rows=c_rows, row_of_frame=row_of_frame, symbol=symbol)
 
 
 def attn_temporal_ragged_paged(mode, n, F, S, D, heads, causal, T_total, n_pages, page_frames, t0_rows, page_rows, first_rows, c_rows, row_of_frame, qkv,
-                               k_pages, v_pages, out, cache_dtype=None):
+                               k_pages, v_pages, out, cache_dtype=None, who='attn_temporal_ragged_paged', symbol=STEP):
     """attn_temporal_ragged on a paged cache: k_pages / v_pages [n_pages, S-1, heads, page_frames, 64], and instead of a slot session r brings row r
     of page_rows (int32 device tensor [n, pages_per_session]): entry q is the page of its frames q * page_frames .. + page_frames - 1.
     Bit-identical to attn_temporal_ragged on contiguous caches of the same contents (the paged layout of tcow_attn_temporal_step)."""
     _need_cuda(qkv, k_pages, v_pages, out, page_rows)
-    _ragged_tables('attn_temporal_ragged_paged', n, F, t0_rows, None, first_rows, c_rows, row_of_frame)
+    _ragged_tables(who, n, F, t0_rows, None, first_rows, c_rows, row_of_frame)
     if page_rows.dtype != torch.int32 or page_rows.dim() != 2 or page_rows.shape[0] != n or page_rows.shape[1] < 1 or not page_rows.is_contiguous():
-        raise L.TcowError(f'attn_temporal_ragged_paged: page_rows must be a contiguous int32 tensor of n = {n} rows of pages_per_session entries, got '
+        raise L.TcowError(f'{who}: page_rows must be a contiguous int32 tensor of n = {n} rows of pages_per_session entries, got '
                           f'{page_rows.dtype} {tuple(page_rows.shape)}')
-    _ragged_rows('attn_temporal_ragged_paged', F, S, qkv, out)
+    _ragged_rows(who, F, S, qkv, out if symbol == STEP else None)
     if not page_frames:         # (0 in the record says "contiguous": refused here, in the words the library has for every other bad page size)
-        raise L.TcowError('attn_temporal_ragged_paged: page_frames=0 must be a power of two in [1, 1024]')
-    return _stream_attn('attn_temporal_ragged_paged', mode, 1, F, S, D, heads, causal, cache_dtype, T_total, t0_rows, qkv, k_pages, v_pages, out, n_sessions=n,
+        raise L.TcowError(f'{who}: page_frames=0 must be a power of two in [1, 1024]')
+    return _stream_attn(who, mode, 1, F, S, D, heads, causal, cache_dtype, T_total, t0_rows, qkv, k_pages, v_pages, out, n_sessions=n,
                         first_rows=first_rows, c_rows=c_rows, row_of_frame=row_of_frame, page_frames=page_frames, n_pages=n_pages,
-                        pages_per_session=page_rows.shape[1], page_rows=page_rows)
+                        pages_per_session=page_rows.shape[1], page_rows=page_rows, symbol=symbol)
+
+
+STEP_FORMS = {'stream': attn_temporal_cached, 'pool': attn_temporal_pool, 'ragged': attn_temporal_ragged, 'paged': attn_temporal_ragged_paged}
+
+
+def attn_temporal_step_probs(form, *args, cache_dtype=None):
+    """The attention maps of one stream step against its K cache (tcow_attn_temporal_step_probs): `form` names the wrapper whose record this is --
+    'stream' (attn_temporal_cached), 'pool', 'ragged', 'paged' -- and the arguments are that wrapper's, with the maps `probs`, a contiguous f32
+    tensor of exactly F * (S-1) * heads * T_total elements ([F, S-1, heads, T_total], F flat frames in the step's row order), in the place of
+    `out`.  The same host checks of tables and cache dtypes apply; the caches are only read, nothing is appended."""
+    if form not in STEP_FORMS:
+        raise L.TcowError(f'attn_temporal_step_probs: form={form!r} must be one of {sorted(STEP_FORMS)}')
+    return STEP_FORMS[form](*args, cache_dtype=cache_dtype, who='attn_temporal_step_probs', symbol=STEP_PROBS)
 
 
 def cls_ragged(x, n, F, S, cls_cache, n_slots, t0_rows, slot_rows, first_rows, c_rows):

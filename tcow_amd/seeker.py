@@ -371,7 +371,8 @@ class QueryMaskTracker(nn.Module):
         computed and refused, in bytes, before anything runs (tcow_amd/attn_maps.py has every rule).
         The maps are the f32 softmax of the q and k the model computed and stored (include/tcow_hip.h, tcow_attn_probs), not a replay of the
         flash kernels' own score rounding.  Eval mode only (DropPath draws would make a map a sample), no forced_drop_masks, under
-        torch.no_grad(), the clip path only: maps of a live stream or pool session against its cache are out of scope."""
+        torch.no_grad().  This is the clip path; a live stream or pool session serves the maps of a step against its cache through
+        SeekerStream.step_maps / SeekerStreamPool.step_maps / step_ragged_maps."""
         from .attn_maps import DEFAULT_MAX_BYTES, MapPlan
         from .attn_probe import MapProbe
         from .engine import run_forward

@@ -61,6 +61,11 @@ only fill its cache, and the reported outputs are forward() of every window buil
 Seeker step unless a chunk goes on after a hand-off frame (then two), and the steps are the ragged forms above, unchanged.  Without the keyword
 a pool is what it was.
 
+Attention maps (step_maps of a stream or pool, step_ragged_maps): the step, run eagerly with a probe (attn_probe.StepMapProbe; attn_maps.StepMapPlan
+has the host rules and refusals) that asks the step object for probs_temporal(i, ...) right before attn_temporal -- the softmax rows of the
+step's frames against the block's K cache (ops.attn_temporal_step_probs: the caches are only read) -- and launches ops.attn_probs on the
+step's own spatial qkv.  The outputs are step()'s, bit for bit; a rollover pool refuses.
+
 graph=True (SeekerStream): the first step of each chunk length c runs eagerly and captures the step as a torch.cuda.CUDAGraph; later steps copy
 their inputs into the graph's static buffers, write t0 and the time rows (the stream keeps one _StreamStep with static time rows per chunk
 length, and one t0 scalar: the graph points into both) and replay.  No step synchronises the host except the one capture per chunk length.  A
@@ -73,6 +78,8 @@ import torch
 
 from . import engine, ops
 from ._lib import TcowError
+from .attn_maps import DEFAULT_MAX_BYTES, StepMapPlan
+from .attn_probe import StepMapProbe
 from .stream_plan import (MAX_FRAMES, PageAllocator, RolloverCall, RolloverPlan, cache_plan, check_range, check_sessions, page_plan,  # noqa: F401
                           ragged_tables, rollover_capacity, rollover_page_moves, rollover_pages, rollover_threshold)
 
@@ -132,7 +139,8 @@ class _PagedState(_State):
 
 class _Step:
     """What engine.run_forward asks of one stream step: pos, time_rows [B*T, D] (one row of the time table per (row, chunk frame)) and the two
-    substitutions of block i, attn_temporal and cls_row.  A form is its tables and its two ops entry points; it is chosen by constructing one of
+    substitutions of block i, attn_temporal and cls_row; a step_maps call also asks probs_temporal, the attention maps of the step's frames
+    against the same tables and caches (right before attn_temporal: the caches are only read).  A form is its tables and its ops entry points; it is chosen by constructing one of
     the three classes below, where the tables are built, and nowhere else."""
 
     def __init__(self, state, time_rows, *tables):
@@ -147,6 +155,10 @@ class _StreamStep(_Step):
         st = self.state
         ops.attn_temporal_cached(amode, B, T, S, D, heads, ca, st.T_total, *self.tables, QKV, st.k_cache[i], st.v_cache[i], O, st.cq)
 
+    def probs_temporal(self, i, amode, B, T, S, D, heads, ca, QKV, probs):
+        st = self.state
+        ops.attn_temporal_step_probs('stream', amode, B, T, S, D, heads, ca, st.T_total, *self.tables, QKV, st.k_cache[i], st.v_cache[i], probs, cache_dtype=st.cq)
+
     def cls_row(self, i, R2, B, T, S):
         ops.cls_stream(R2, B, T, S, self.state.cls_cache[i], *self.tables)
 
@@ -157,6 +169,11 @@ class _PoolStep(_Step):
     def attn_temporal(self, i, amode, B, T, S, D, heads, ca, QKV, O):
         st = self.state
         ops.attn_temporal_pool(amode, B, T, S, D, heads, ca, st.T_total, st.n_slots, *self.tables, QKV, st.k_cache[i], st.v_cache[i], O, st.cq)
+
+    def probs_temporal(self, i, amode, B, T, S, D, heads, ca, QKV, probs):
+        st = self.state
+        ops.attn_temporal_step_probs('pool', amode, B, T, S, D, heads, ca, st.T_total, st.n_slots, *self.tables, QKV, st.k_cache[i], st.v_cache[i], probs,
+                                     cache_dtype=st.cq)
 
     def cls_row(self, i, R2, B, T, S):
         ops.cls_pool(R2, B, T, S, self.state.cls_cache[i], self.state.n_slots, *self.tables)
@@ -171,6 +188,11 @@ class _RaggedStep(_Step):
         ops.attn_temporal_ragged(amode, self.tables[0].numel(), T, S, D, heads, ca, st.T_total, st.n_slots, *self.tables, QKV, st.k_cache[i],
                                  st.v_cache[i], O, st.cq)
 
+    def probs_temporal(self, i, amode, B, T, S, D, heads, ca, QKV, probs):
+        st = self.state
+        ops.attn_temporal_step_probs('ragged', amode, self.tables[0].numel(), T, S, D, heads, ca, st.T_total, st.n_slots, *self.tables, QKV, st.k_cache[i],
+                                     st.v_cache[i], probs, cache_dtype=st.cq)
+
     def cls_row(self, i, R2, B, T, S):
         ops.cls_ragged(R2, self.tables[0].numel(), T, S, self.state.cls_cache[i], self.state.n_slots, *self.tables[:4])
 
@@ -184,6 +206,12 @@ class _PagedRaggedStep(_RaggedStep):
         t0_rows, _, first_rows, c_rows, row_of_frame, page_rows = self.tables
         ops.attn_temporal_ragged_paged(amode, t0_rows.numel(), T, S, D, heads, ca, st.T_total, st.n_pages, st.P, t0_rows, page_rows, first_rows, c_rows,
                                        row_of_frame, QKV, st.k_cache[i], st.v_cache[i], O, st.cq)
+
+    def probs_temporal(self, i, amode, B, T, S, D, heads, ca, QKV, probs):
+        st = self.state
+        t0_rows, _, first_rows, c_rows, row_of_frame, page_rows = self.tables
+        ops.attn_temporal_step_probs('paged', amode, t0_rows.numel(), T, S, D, heads, ca, st.T_total, st.n_pages, st.P, t0_rows, page_rows, first_rows, c_rows,
+                                     row_of_frame, QKV, st.k_cache[i], st.v_cache[i], probs, cache_dtype=st.cq)
 
 
 def check_streamable(module):
@@ -246,10 +274,19 @@ def _cat_f32(chunks):
     return _f32(chunks[0]) if len(chunks) == 1 else torch.cat([x.to(torch.float32) for x in chunks], 2)
 
 
-def _seeker_step(module, step, rgb, qm, rows):
-    """One Seeker step of `rows` query rows (qm None: all zeros) -> (mask logits, flags or None)."""
-    out_mask, flags, _ = engine.run_forward(module, rgb, _zero_mask(rows, rgb) if qm is None else qm, module.param_list(), save=False, stream=step)
+def _seeker_step(module, step, rgb, qm, rows, probe=None):
+    """One Seeker step of `rows` query rows (qm None: all zeros) -> (mask logits, flags or None).  probe: the StepMapProbe of a step_maps call."""
+    kw = {} if probe is None else {'probe': probe}
+    out_mask, flags, _ = engine.run_forward(module, rgb, _zero_mask(rows, rgb) if qm is None else qm, module.param_list(), save=False, stream=step, **kw)
     return out_mask, (flags if module.flag_channels > 0 else None)
+
+
+def _map_plan(who, module, rows_or_chunks, maps):
+    """The StepMapPlan of a step_maps call (`maps`: its blocks, temporal, spatial_slots, max_bytes): every refusal of those arguments, on the host."""
+    g = module.geometry(1, T=1)
+    blocks, temporal, spatial_slots, max_bytes = maps
+    return StepMapPlan(module.network_depth, rows_or_chunks, module.num_total_frames, g['S'], g['heads'], module.causal_attention, blocks, temporal,
+                       spatial_slots, DEFAULT_MAX_BYTES if max_bytes is None else max_bytes, who)
 
 
 class SeekerStream:
@@ -288,12 +325,30 @@ class SeekerStream:
     def step(self, rgb, query_mask=None):
         """rgb (Bc, 3, c, H, W), query_mask (Bc*Qs, 1, c, H, W) or None (all zeros) for the next c >= 1 frames ->
         (mask logits (Bc*Qs, Co, c, H, W) f32, flags (Bc*Qs, c, F) or None) of exactly those frames, owned by the caller."""
+        return self._step('stream.step', rgb, query_mask, None)[:2]
+
+    def step_maps(self, rgb, query_mask=None, blocks=None, temporal=True, spatial_slots=None, max_bytes=None):
+        """step() that also returns what the step's frames look at: (mask logits, flags, maps), the two outputs with the bits of step() on the
+        same frames, maps an attn_probe.StepAttentionMaps of this step:
+          maps.temporal[i] (rows, N, heads, c, T): block i, how much frame t0 + j of a patch pulls from every frame 0 .. t0 + j of the stream,
+                                                   the earlier ones as the K cache holds them (a compact cache: the rounded keys the model attends
+                                                   to); later frames +0.0.  Concatenated along dim 3 over the steps: the clip's causal map;
+          maps.spatial[i]  (rows, c, nq, heads, S): block i, which slots of its own frame each of spatial_slots looks at -- None: no spatial maps,
+                                                   'cls' (causal_attention == 1 only), or a list of slots, 0 = cls, 1 + n = patch n;
+          maps.slots, maps.t0: the normalised slots, the step's first frame.
+        blocks: None = all, or block indices (negative from the top); max_bytes: budget of the maps (default 4 GiB); tcow_amd/attn_maps.py,
+        StepMapPlan, has every rule, and a refused call moves nothing.  On a graph=True stream the call runs eagerly and leaves the captured
+        graphs alone: later step() calls replay as before."""
+        return self._step('stream.step_maps', rgb, query_mask, (blocks, temporal, spatial_slots, max_bytes))
+
+    def _step(self, who, rgb, query_mask, maps):
         _check_module(self.module, self._sig)
-        c = _check_inputs('stream.step', self.module, self.device, self.Bc, self.B, rgb, query_mask)
+        c = _check_inputs(who, self.module, self.device, self.Bc, self.B, rgb, query_mask)
         t0 = self.frames_done
         if t0 + c > self.T:
-            raise TcowError(f'stream.step: frames {t0}..{t0 + c - 1} run past the last frame {self.T - 1} of the stream (num_total_frames = {self.T}); '
+            raise TcowError(f'{who}: frames {t0}..{t0 + c - 1} run past the last frame {self.T - 1} of the stream (num_total_frames = {self.T}); '
                             'reset() to start again, or run the camera on net.stream_pool(capacity, rollover=k), whose sessions have no last frame')
+        plan = None if maps is None else _map_plan(who, self.module, (self.B, c), maps)
         with torch.no_grad(), torch.cuda.device(self.device):
             step = self._steps.get(c)
             if step is None:
@@ -301,7 +356,11 @@ class SeekerStream:
             step.time_rows.view(self.B, c, -1).copy_(self._st.time[t0:t0 + c])      # row b*c + j = time row t0 + j, for every b
             self._t0_dev.fill_(t0)
             rgb32, qm32 = _f32(rgb), _f32(query_mask)
-            out = self._graph_step(step, rgb32, qm32) if self.graph else _seeker_step(self.module, step, rgb32, qm32, self.B)
+            if plan is not None:                    # (eager also on a graph stream: the graphs hold no probe launches and stay as they are)
+                probe = StepMapProbe(plan, self.device, t0)
+                out = _seeker_step(self.module, step, rgb32, qm32, self.B, probe) + (probe.maps,)
+            else:
+                out = self._graph_step(step, rgb32, qm32) if self.graph else _seeker_step(self.module, step, rgb32, qm32, self.B)
         self.frames_done = t0 + c
         return out
 
@@ -433,15 +492,17 @@ class SeekerStreamPool:
         if self._alloc is not None:
             self._alloc.release(sid)
 
-    def _checked(self, who, ids, rgbs, qms, per):
+    def _checked(self, who, ids, rgbs, qms, per, maps=None):
         """Every check of a step (`who`), before anything is launched or any counter moves.  rgbs / qms: one tensor of all sessions, or (per) a list
-        with an entry per session.  Returns (ids, the frame every session stands at, the chunk length of every session, and in a paged pool the pages
-        of every session, grown to hold the step's frames; else None)."""
+        with an entry per session.  Returns (ids, the frame every session stands at, the chunk length of every session, in a paged pool the pages
+        of every session, grown to hold the step's frames; else None, and the StepMapProbe of a step_maps call -- `maps`: its arguments -- or None)."""
         ids, cs = self._prologue(who, ids, rgbs, qms, per)
         t0s = [self._done[sid] for sid in ids]
         check_range(who, ids, t0s, cs, self.T)
+        plan = None if maps is None else _map_plan(who, self.module, list(cs) if per else (len(ids), cs[0]), maps)
         # the last check, and the only thing of a refused step that could have moved: the pages of frames up to t0 + c_i - 1 (all or nothing)
-        return ids, t0s, cs, (None if self._alloc is None else self._alloc.grow(ids, [t0 + c for t0, c in zip(t0s, cs)]))
+        pages = None if self._alloc is None else self._alloc.grow(ids, [t0 + c for t0, c in zip(t0s, cs)])
+        return ids, t0s, cs, pages, (None if plan is None else StepMapProbe(plan, self.device, list(t0s)))
 
     def _prologue(self, who, ids, rgbs, qms, per):
         """What every pool call (`who`) checks first, in this order: the sessions, the module, the inputs.  Returns (ids, every session's chunk length)."""
@@ -452,9 +513,9 @@ class SeekerStreamPool:
             return ids, [_check_inputs(f'{who}: session {sid}', m, self.device, 1, 1, rgbs[k], None if qms is None else qms[k]) for k, sid in enumerate(ids)]
         return ids, [_check_inputs(who, m, self.device, len(ids), len(ids), rgbs, qms)] * len(ids)
 
-    def _run(self, step, ids, cs, rgb, qm):
+    def _run(self, step, ids, cs, rgb, qm, probe=None):
         """One Seeker step, after which every session has moved on by its chunk length."""
-        out = _seeker_step(self.module, step, rgb, qm, rgb.shape[0])
+        out = _seeker_step(self.module, step, rgb, qm, rgb.shape[0], probe)
         for sid, c in zip(ids, cs):
             self._done[sid] += c
         return out
@@ -463,16 +524,26 @@ class SeekerStreamPool:
         """ids: n distinct open sessions, at any phases; rgb (n, 3, c, H, W), query_mask (n, 1, c, H, W) or None (all zeros): the next c >= 1
         frames of each -> (mask logits (n, Co, c, H, W) f32, flags (n, c, F) or None) in the order of `ids`, owned by the caller.  Every check
         runs before anything is launched: a refused step leaves every session where it was."""
-        ids, t0s, cs, pages = self._checked('stream_pool.step', ids, rgb, query_mask, False)
+        return self._step('stream_pool.step', ids, rgb, query_mask, None)
+
+    def step_maps(self, ids, rgb, query_mask=None, blocks=None, temporal=True, spatial_slots=None, max_bytes=None):
+        """step() that also returns the attention maps of the step's frames against the sessions' caches: (mask logits, flags, maps) -- the
+        keywords, shapes and rules of SeekerStream.step_maps, rows in the order of `ids`, maps.t0 the frame every session stood at.  A paged pool
+        and any cache_dtype are served alike; a refused call moves no counter and allocates no page."""
+        return self._step('stream_pool.step_maps', ids, rgb, query_mask, (blocks, temporal, spatial_slots, max_bytes))
+
+    def _step(self, who, ids, rgb, query_mask, maps):
+        ids, t0s, cs, pages, probe = self._checked(who, ids, rgb, query_mask, False, maps)
+        more = () if probe is None else (probe.maps,)
         if pages is not None:
-            return self._step_paged(ids, t0s, cs, pages, rgb, query_mask)
+            return self._step_paged(ids, t0s, cs, pages, rgb, query_mask, probe) + more
         st, c = self._st, cs[0]
         with torch.no_grad(), torch.cuda.device(self.device):
             t0_rows = torch.tensor(t0s, dtype=torch.int32, device=self.device)
             slot_rows = torch.tensor([self._slot[sid] for sid in ids], dtype=torch.int32, device=self.device)
             frames = (t0_rows[:, None] + torch.arange(c, dtype=torch.int32, device=self.device)[None, :]).reshape(-1)
             step = _PoolStep(st, st.time.index_select(0, frames), t0_rows, slot_rows)         # [n*c, D]: row r*c + j = time row t0_rows[r] + j
-            return self._run(step, ids, cs, _f32(rgb), _f32(query_mask))
+            return self._run(step, ids, cs, _f32(rgb), _f32(query_mask), probe) + more
 
     def _ragged_form(self, t0s, slots, cs, pages):
         """The step object of a ragged step (inside no_grad on the pool's device) and every row's first flat frame.  pages: None, or in a paged
@@ -491,14 +562,14 @@ class SeekerStreamPool:
             return _RaggedStep(st, time_rows, *tables), tab['first']
         return _PagedRaggedStep(st, time_rows, *tables, dev[4 * n + 2 * F:].view(n, st.pps)), tab['first']
 
-    def _step_paged(self, ids, t0s, cs, pages, rgb, query_mask):
+    def _step_paged(self, ids, t0s, cs, pages, rgb, query_mask, probe=None):
         """step() of a paged pool: the ragged form with equal chunk lengths (bit-equal to the pool form), in and out in step()'s shapes."""
         n, c = len(ids), cs[0]
         # (n, C, c, H, W) -> (1, C, n*c, H, W): the frames flat in session order
         flat = lambda x: x.to(torch.float32).transpose(0, 1).reshape(1, x.shape[1], n * c, *x.shape[3:]).contiguous()
         with torch.no_grad(), torch.cuda.device(self.device):
             step, _ = self._ragged_form(t0s, [self._slot[sid] for sid in ids], cs, pages)
-            out_mask, flags = self._run(step, ids, cs, flat(rgb), None if query_mask is None else flat(query_mask))
+            out_mask, flags = self._run(step, ids, cs, flat(rgb), None if query_mask is None else flat(query_mask), probe)
             out_mask = out_mask.view(out_mask.shape[1], n, c, *out_mask.shape[3:]).transpose(0, 1).contiguous()
         return out_mask, (None if flags is None else flags.reshape(n, c, -1))
 
@@ -508,9 +579,17 @@ class SeekerStreamPool:
         (1, Co, c_i, H, W) f32, a list of n flag tensors (1, c_i, F) or None), in the order of `ids`.  The outputs are slices of buffers allocated
         for this step and owned by the caller.  The whole step is ONE Seeker step over the sum of the c_i frames.  Every check runs before anything
         is launched: a refused step leaves every session where it was."""
+        return self._step_ragged('stream_pool.step_ragged', ids, rgbs, query_masks, None)
+
+    def step_ragged_maps(self, ids, rgbs, query_masks=None, blocks=None, temporal=True, spatial_slots=None, max_bytes=None):
+        """step_ragged() that also returns the attention maps, per session: (masks, flags, maps) with maps.temporal[i][k] (1, N, heads, c_k, T)
+        and maps.spatial[i][k] (1, c_k, nq, heads, S) of session ids[k]; the keywords and rules of SeekerStream.step_maps."""
+        return self._step_ragged('stream_pool.step_ragged_maps', ids, rgbs, query_masks, (blocks, temporal, spatial_slots, max_bytes))
+
+    def _step_ragged(self, who, ids, rgbs, query_masks, maps):
         rgbs = list(rgbs)
         qms = None if query_masks is None else list(query_masks)
-        ids, t0s, cs, pages = self._checked('stream_pool.step_ragged', ids, rgbs, qms, True)
+        ids, t0s, cs, pages, probe = self._checked(who, ids, rgbs, qms, True, maps)
         with torch.no_grad(), torch.cuda.device(self.device):
             step, first = self._ragged_form(t0s, [self._slot[sid] for sid in ids], cs, pages)
             rgb32 = _cat_f32(rgbs)
@@ -521,9 +600,9 @@ class SeekerStreamPool:
                 for q, f0, c in zip(qms or (), first, cs):
                     if q is not None:
                         qm32[:, :, f0:f0 + c] = q
-            out_mask, flags = self._run(step, ids, cs, rgb32, qm32)
+            out_mask, flags = self._run(step, ids, cs, rgb32, qm32, probe)
         masks = [out_mask[:, :, f0:f0 + c] for f0, c in zip(first, cs)]
-        return masks, (None if flags is None else [flags[:, f0:f0 + c] for f0, c in zip(first, cs)])
+        return (masks, (None if flags is None else [flags[:, f0:f0 + c] for f0, c in zip(first, cs)])) + (() if probe is None else (probe.maps,))
 
 
 class SeekerRolloverPool(SeekerStreamPool):
@@ -666,6 +745,16 @@ class SeekerRolloverPool(SeekerStreamPool):
         res = self._roll('stream_pool.step', ids, rgb, query_mask, False)
         masks = torch.cat([r[0] for r in res], 0) if len(res) > 1 else res[0][0].contiguous()
         return masks, (None if res[0][1] is None else torch.cat([r[1] for r in res], 0))
+
+    def step_maps(self, *args, **kwargs):
+        """Refused: a rollover session's frames are window-relative and a hand-off step runs two windows; maps of it need a design of their own."""
+        raise TcowError('stream_pool.step_maps: a rollover pool (rollover=k) serves no attention maps: frame indices are relative to a window and a '
+                        'hand-off frame belongs to two; use a pool without rollover')
+
+    def step_ragged_maps(self, *args, **kwargs):
+        """Refused, as step_maps."""
+        raise TcowError('stream_pool.step_ragged_maps: a rollover pool (rollover=k) serves no attention maps: frame indices are relative to a window '
+                        'and a hand-off frame belongs to two; use a pool without rollover')
 
     def step_ragged(self, ids, rgbs, query_masks=None):
         """SeekerStreamPool.step_ragged with c_i <= T - rollover frames of session i, at any global frame."""
